@@ -1,7 +1,11 @@
 """bench.py — images/s of Mask R-CNN R50-FPN inference on synthetic 1024x1024 micrographs (BASELINE.json configs[1]).
 
 python bench.py --gpus N --steps K --warmup W       (N > 1: one rank per GPU -- started by torch.distributed.run, or by bench.py itself when RANK is not set)
+python bench.py ... --full                          (also the secondary measurements: roofline, fp32-MFMA reference, host-inclusive, two pipelines,
+                                                     training, X-101, CPU baseline -- each may be switched off with its own --no-* / --*-steps 0 option)
+python bench.py ... --dump-outputs DIR              (what the last timed step returned, as DIR/<name>.npy: see dump_outputs)
 
+A plain run sets up, runs W untimed and K timed steps of the headline workload and prints the line; nothing else.
 A step = one pass of the hot path (amp_model_infer: preprocess -> backbone -> FPN -> RPN -> proposals -> box head ->
 detections -> mask head -> paste -> RLE counts strings on the host) over one batch of 8 images that is already resident in HBM.
 Image-parallel replicas: every rank runs the same per-GPU batch, no data-path collective ("weak" scaling); RCCL (through the C ABI) is only
@@ -24,6 +28,8 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true", help="also run the secondary measurements (the options below); off: the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned as DIR/<name>.npy (rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-power-probe", action="store_true", help="skip roofline.power_probe (the dominant layer on random and on all-zero operands)")
     ap.add_argument("--cpu-images", type=int, default=10)
@@ -34,7 +40,10 @@ def parse_args():
     ap.add_argument("--no-two-pipelines", action="store_true", help="skip the secondary `two_pipelines` object")
     ap.add_argument("--no-host-inclusive", action="store_true", help="skip the secondary `host_inclusive` object")
     ap.add_argument("--train-timeout", type=float, default=420.0, help="watchdog for the secondary legs, seconds")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def self_launch(args):
@@ -493,6 +502,33 @@ def x101_leg(ctx, dev, rank, world, steps, ranks):
             "conv_useful_tflops": round((prof["flops"][0] + prof["flops"][1]) / (conv_ms * 1e-3) / 1e12, 2) if conv_ms > 0 else None}
 
 
+def dump_outputs(path, dets):
+    """--dump-outputs DIR: what the caller of the timed path receives from its last timed step (MaskRCNN.unpack of the Dets view: per image
+    boxes, scores, classes and every mask as a COCO counts string), as fixed-shape arrays, slot i of image b = detection i, zeros past
+    num_detections[b]: boxes [B,D,4] / scores [B,D] / classes [B,D] float32, num_detections [B] and mask_areas [B,D] (pixels) float64,
+    and a seeded sample of whole masks decoded to pixels: mask_sample [B,H,W] float32 = detection mask_sample_index[b] of image b."""
+    from ampis_amd import rle
+    res = MaskRCNN.unpack(dets)
+    B, D = dets.B, dets.D
+    H, W = res[0]["image_size"]
+    a = {"num_detections": np.zeros(B, np.float64), "boxes": np.zeros((B, D, 4), np.float32), "scores": np.zeros((B, D), np.float32),
+         "classes": np.zeros((B, D), np.float32), "mask_areas": np.zeros((B, D), np.float64),
+         "mask_sample": np.zeros((B, H, W), np.float32), "mask_sample_index": np.zeros((B, 2), np.float64)}
+    pick = np.random.default_rng(0).integers(0, D, size=B)
+    for b, r in enumerate(res):
+        n = len(r["scores"])
+        a["num_detections"][b] = n
+        a["boxes"][b, :n], a["scores"][b, :n], a["classes"][b, :n] = r["boxes"], r["scores"], r["classes"]
+        a["mask_areas"][b, :n] = [rle.area(m) for m in r["masks"]]
+        a["mask_sample_index"][b] = (b, pick[b])
+        if pick[b] < n:
+            a["mask_sample"][b] = rle.decode(r["masks"][pick[b]])
+    os.makedirs(path, exist_ok=True)
+    for k, v in a.items():
+        np.save(os.path.join(path, f"{k}.npy"), v)
+    log(f"outputs of the last timed step: {len(a)} arrays, {sum(v.nbytes for v in a.values()) / 2**20:.1f} MiB in {path}")
+
+
 def main(args):
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -556,8 +592,9 @@ def main(args):
     def step():
         return model.infer_raw(None, device_ptr=d_imgs, shape=(BATCH, SIZE, SIZE))
 
-    def timed(mode, warmup, steps):
-        """W untimed + exactly K timed steps in one conv arithmetic, bracketed by barrier + synchronize; max over ranks."""
+    def timed(mode, warmup, steps, sample):
+        """W untimed + exactly K timed steps in one conv arithmetic, bracketed by barrier + synchronize; max over ranks.  sample: per-launch
+        HIP events on every PROF_EVERY-th timed step, for the roofline of --full (prof is None without).  Also returns the last step's Dets."""
         ctx.conv_mode = mode
         for i in range(warmup):
             t = time.perf_counter()
@@ -566,30 +603,36 @@ def main(args):
         ranks.barrier()
         # per-launch HIP events on every PROF_EVERY-th timed step: they cost ~8 us of idle GPU per launch (0.8 ms
         # = 4.7 % of a step when every step carries them)
-        ctx.prof_begin(max_launches=(steps // PROF_EVERY + 1) * 96)
+        if sample:
+            ctx.prof_begin(max_launches=(steps // PROF_EVERY + 1) * 96)
         t0 = time.perf_counter()
         ndet = 0
         prof_steps = 0
         for i in range(steps):
-            sampled = i % PROF_EVERY == 0
-            ctx.prof_pause(not sampled)
-            prof_steps += int(sampled)
+            if sample:
+                sampled = i % PROF_EVERY == 0
+                ctx.prof_pause(not sampled)
+                prof_steps += int(sampled)
             d = step()
             ndet += sum(d.n[b] for b in range(BATCH))
         torch.cuda.synchronize(dev)
         el = time.perf_counter() - t0
-        prof = ctx.prof_end()
-        prof["steps"] = prof_steps
-        prof["by_bound"] = by_bound(ctx.prof_launches(), mode, prof_steps)
+        prof = None
+        if sample:
+            prof = ctx.prof_end()
+            prof["steps"] = prof_steps
+            prof["by_bound"] = by_bound(ctx.prof_launches(), mode, prof_steps)
         log(f"[{mode}] timed {steps} steps in {el:.3f} s")
         ranks.barrier()
-        return ranks.max(el), prof, ndet
+        return ranks.max(el), prof, ndet, d
 
     mode = "f32" if os.environ.get("AMP_CONV_MODE") == "f32" else "f16x3"
-    elapsed, prof, ndet = timed(mode, args.warmup, args.steps)
+    elapsed, prof, ndet, last = timed(mode, args.warmup, args.steps, sample=args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)       # before any other call of the model: `last` views its result buffers
     strict = None
-    if mode == "f16x3" and not args.no_strict:      # the same workload on the fp32-MFMA kernels, for reference
-        s_el, s_prof, _ = timed("f32", 2, args.steps)
+    if args.full and mode == "f16x3" and not args.no_strict:      # the same workload on the fp32-MFMA kernels, for reference
+        s_el, s_prof, _, _ = timed("f32", 2, args.steps, sample=True)
         ctx.conv_mode = "f16x3"
         s_ach = s_prof["flops"][0] / (s_prof["ms"][0] * 1e-3) / 1e12 if s_prof["ms"][0] > 0 else 0.0
         strict = {"what": "same workload with AMP_CONV_MODE=f32: every conv on v_mfma_f32_32x32x2_f32",
@@ -600,14 +643,8 @@ def main(args):
 
     out = None
     if rank == 0:
-        keys = ["conv_split_kernel<128x256>", "conv_glds_kernel<256>[f16x3, both operands pre-split]", "conv_f16x3_kernel<256>"] if mode == "f16x3" else ["conv_glds_kernel<128>"]
-        traffic, traffic_src, traffic_key = pmc_traffic(keys)   # HBM bytes per launch of the dominant kernel, from the committed PMC passes (profiles/)
         ms_per_step = elapsed / args.steps * 1e3
         value = world * BATCH * args.steps / elapsed
-        ach = prof["flops"][0] / (prof["ms"][0] * 1e-3) / 1e12 if prof["ms"][0] > 0 else 0.0
-        peak = PEAK_F16X3_TFLOPS if mode == "f16x3" else PEAK_F32_MFMA_TFLOPS
-        conv_all = (prof["flops"][0] + prof["flops"][1]) / ((prof["ms"][0] + prof["ms"][1]) * 1e-3) / 1e12
-        all_conv_ms = (prof["ms"][0] + prof["ms"][1]) / prof["steps"]
         out = {
             "metric": "images/sec Mask R-CNN R50-FPN @1024x1024 inference", "value": round(value, 3), "unit": "images/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
@@ -622,31 +659,38 @@ def main(args):
                        "parallelism": f"image-parallel replicas x{world}, no data-path collective"
                                       + (f"; barrier / max-over-ranks on RCCL {rccl[2]} through the C ABI" if rccl else "")
                                       + (f"; RCCL COMMUNICATOR NOT CREATED ({rccl_error}): barrier / max-over-ranks on gloo" if rccl_error else "")},
-            "roofline": {"bound": "mfma",
-                         "kernel": ("conv_split_kernel<128x256> -- every launch of it and nothing else (tagged where it is launched: the 3x3 256->256 layers "
-                                    "of FPN / RPN / mask head / res4, fc1, the fused RPN tail; the fused mask-head tail is mask_tail_kernel since round 4 and not counted here): implicit-GEMM conv on "
-                                    "v_mfma_f32_16x16x32_f16, 3 MFMAs per product, both operands pre-split and staged by LDS-DMA through a ring of "
-                                    "three 48-KB tiles, the two waves of a SIMD ping-pong between loading and multiplying") if mode == "f16x3" else
-                                   "conv_glds_kernel<128> (fp32 MFMA implicit-GEMM conv, 128x128x32 tiles, LDS-DMA staging)",
-                         "achieved": round(ach, 2), "peak": round(peak, 1), "unit": "TFLOP/s", "frac": round(ach / peak, 4),
-                         "peak_is": ("f16 dense MFMA peak 2500 / 3 MFMAs per algorithmic product" if mode == "f16x3" else "fp32 dense MFMA peak"),
-                         "achieved_over_fp32_mfma_peak": round(ach / PEAK_F32_MFMA_TFLOPS, 3),
-                         **({"sustained_peak_random_operands": round(SUSTAINED_F16_MFMA_RANDOM_TFLOPS / 3.0, 1),
-                             "frac_of_sustained": round(ach / (SUSTAINED_F16_MFMA_RANDOM_TFLOPS / 3.0), 4),
-                             "sustained_is": "measured on this chip: MFMA-only loop on random f16 operands 1655 TFLOP/s (clock drops under "
-                                             "toggling inputs; 2475 on constants), / 3 (profiles/r01/mfma_peak.json)"} if mode == "f16x3" else {}),
-                         "traffic": traffic,
-                         "traffic_unit": f"HBM bytes per launch of {traffic_key} (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, {traffic_src})",
-                         "launches_per_step": prof["launches"][0] / prof["steps"],
-                         "kernel_ms_per_step": round(prof["ms"][0] / prof["steps"], 3),
-                         "all_conv_ms_per_step": round(all_conv_ms, 3),
-                         "non_conv_ms_per_step": round(ms_per_step - all_conv_ms, 3),
-                         "events_on": f"every {PROF_EVERY}th timed step ({prof['steps']} of {args.steps} steps, {prof['launches'][0]} launches of the dominant kernel)",
-                         "all_conv_tflops": round(conv_all, 2), "by_bound": prof["by_bound"], "truncated": prof["truncated"]},
         }
-        rp = rocprof_reported("infer") if mode == "f16x3" else None
-        if rp:
-            out["rocprof_reported"] = rp
+        if prof is not None:      # --full: the dominant kernel's roofline from the HIP events of the sampled timed steps
+            keys = ["conv_split_kernel<128x256>", "conv_glds_kernel<256>[f16x3, both operands pre-split]", "conv_f16x3_kernel<256>"] if mode == "f16x3" else ["conv_glds_kernel<128>"]
+            traffic, traffic_src, traffic_key = pmc_traffic(keys)   # HBM bytes per launch of the dominant kernel, from the committed PMC passes (profiles/)
+            ach = prof["flops"][0] / (prof["ms"][0] * 1e-3) / 1e12 if prof["ms"][0] > 0 else 0.0
+            peak = PEAK_F16X3_TFLOPS if mode == "f16x3" else PEAK_F32_MFMA_TFLOPS
+            conv_all = (prof["flops"][0] + prof["flops"][1]) / ((prof["ms"][0] + prof["ms"][1]) * 1e-3) / 1e12
+            all_conv_ms = (prof["ms"][0] + prof["ms"][1]) / prof["steps"]
+            out["roofline"] = {"bound": "mfma",
+                               "kernel": ("conv_split_kernel<128x256> -- every launch of it and nothing else (tagged where it is launched: the 3x3 256->256 layers "
+                                          "of FPN / RPN / mask head / res4, fc1, the fused RPN tail; the fused mask-head tail is mask_tail_kernel since round 4 and not counted here): implicit-GEMM conv on "
+                                          "v_mfma_f32_16x16x32_f16, 3 MFMAs per product, both operands pre-split and staged by LDS-DMA through a ring of "
+                                          "three 48-KB tiles, the two waves of a SIMD ping-pong between loading and multiplying") if mode == "f16x3" else
+                                         "conv_glds_kernel<128> (fp32 MFMA implicit-GEMM conv, 128x128x32 tiles, LDS-DMA staging)",
+                               "achieved": round(ach, 2), "peak": round(peak, 1), "unit": "TFLOP/s", "frac": round(ach / peak, 4),
+                               "peak_is": ("f16 dense MFMA peak 2500 / 3 MFMAs per algorithmic product" if mode == "f16x3" else "fp32 dense MFMA peak"),
+                               "achieved_over_fp32_mfma_peak": round(ach / PEAK_F32_MFMA_TFLOPS, 3),
+                               **({"sustained_peak_random_operands": round(SUSTAINED_F16_MFMA_RANDOM_TFLOPS / 3.0, 1),
+                                   "frac_of_sustained": round(ach / (SUSTAINED_F16_MFMA_RANDOM_TFLOPS / 3.0), 4),
+                                   "sustained_is": "measured on this chip: MFMA-only loop on random f16 operands 1655 TFLOP/s (clock drops under "
+                                                   "toggling inputs; 2475 on constants), / 3 (profiles/r01/mfma_peak.json)"} if mode == "f16x3" else {}),
+                               "traffic": traffic,
+                               "traffic_unit": f"HBM bytes per launch of {traffic_key} (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, {traffic_src})",
+                               "launches_per_step": prof["launches"][0] / prof["steps"],
+                               "kernel_ms_per_step": round(prof["ms"][0] / prof["steps"], 3),
+                               "all_conv_ms_per_step": round(all_conv_ms, 3),
+                               "non_conv_ms_per_step": round(ms_per_step - all_conv_ms, 3),
+                               "events_on": f"every {PROF_EVERY}th timed step ({prof['steps']} of {args.steps} steps, {prof['launches'][0]} launches of the dominant kernel)",
+                               "all_conv_tflops": round(conv_all, 2), "by_bound": prof["by_bound"], "truncated": prof["truncated"]}
+            rp = rocprof_reported("infer") if mode == "f16x3" else None
+            if rp:
+                out["rocprof_reported"] = rp
 
     emitted = threading.Lock()
 
@@ -663,7 +707,7 @@ def main(args):
             out["f32_mfma_reference"] = strict
         if train_obj is not None:
             out["train"] = train_obj
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_images)
         print(json.dumps(out), flush=True)
 
@@ -671,7 +715,7 @@ def main(args):
     # collective that does not return (a rank died) is cut off by a watchdog that prints the headline and exits NON-ZERO, naming the leg.
     train_obj = None
     leg = {"name": None}
-    if args.train_steps > 0 or args.x101_steps > 0 or not args.no_two_pipelines or not args.no_host_inclusive or not args.no_power_probe:
+    if args.full and (args.train_steps > 0 or args.x101_steps > 0 or not args.no_two_pipelines or not args.no_host_inclusive or not args.no_power_probe):
         def on_stall():
             msg = f"secondary leg '{leg['name']}' did not finish within {args.train_timeout} s"
             log(f"rank {rank}: {msg}; emitting the inference line without it and exiting with code 3")

@@ -3,7 +3,7 @@
 # alternations of the bench, the per-launch table of both, per-dispatch traffic of the variant, then the full-size gate and smoke.
 set -o pipefail
 O=gpurun_out/c2; mkdir -p $O
-BQ="--steps 30 --warmup 5 --no-cpu-baseline --train-steps 0 --x101-steps 0 --no-strict --no-two-pipelines --no-host-inclusive"
+BQ="--full --steps 30 --warmup 5 --no-cpu-baseline --train-steps 0 --x101-steps 0 --no-strict --no-two-pipelines --no-host-inclusive"
 timeout -k 10 200 python tools/exp_korder.py > $O/exp_korder.log 2>&1 || { tail -20 $O/exp_korder.log; exit 1; }
 tail -3 $O/exp_korder.log
 for ko in 0 1 0 1 0 1; do

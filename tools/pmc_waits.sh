@@ -7,7 +7,7 @@ OUT=$ROOT/gpurun_out/pmc_waits_$MODE
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 if [ "$MODE" = train ]; then
-  BENCH="python3 $ROOT/bench.py --steps 1 --warmup 1 --no-cpu-baseline --train-steps 3 --train-warmup 1 --x101-steps 0 --no-two-pipelines --no-host-inclusive --no-strict"
+  BENCH="python3 $ROOT/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --train-steps 3 --train-warmup 1 --x101-steps 0 --no-two-pipelines --no-host-inclusive --no-strict"
 else
   BENCH="python3 $ROOT/bench.py --steps 4 --warmup 1 --no-cpu-baseline --train-steps 0 --x101-steps 0 --no-two-pipelines --no-host-inclusive --no-strict"
 fi

@@ -46,7 +46,7 @@ for d in glob.glob(os.path.join(src, "pmc_*")):
         for r in csv.DictReader(open(f)):
             k = short(r["Kernel_Name"]); c = r["Counter_Name"]
             ctr[k][c] += float(r["Counter_Value"]); n[k][c] += 1
-out = {"command": "rocprofv3 --pmc <set> --kernel-trace --output-format csv -- python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline "
+out = {"command": "rocprofv3 --pmc <set> --kernel-trace --output-format csv -- python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline "
                   "--train-steps 0 --x101-steps 0 --no-strict  (one set per pass: FETCH_SIZE | WRITE_SIZE | SQ_VALU_MFMA_BUSY_CYCLES "
                   "SQ_BUSY_CYCLES | GRBM_GUI_ACTIVE)",
        "corrections": "FETCH_SIZE / WRITE_SIZE are KiB; FETCH_SIZE is doubled (gfx950 reports half the bytes of 16-B/lane streaming reads, "
