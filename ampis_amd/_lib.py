@@ -42,6 +42,36 @@ class ModelCfg(C.Structure):
                 ("resnet_depth", C.c_int), ("num_groups", C.c_int), ("width_per_group", C.c_int), ("stride_in_1x1", C.c_int)]
 
 
+class SgdOpts(C.Structure):
+    """amp_sgd_opts (include/ampis_hip.h): the general SGD step."""
+    _fields_ = [("lr", C.c_float), ("momentum", C.c_float), ("weight_decay", C.c_float), ("grad_scale", C.c_float),
+                ("nesterov", C.c_int), ("bias_lr_factor", C.c_float), ("weight_decay_bias", C.c_float),
+                ("clip_type", C.c_int), ("clip_value", C.c_float), ("norm_type", C.c_float)]
+
+
+CLIP_NONE, CLIP_VALUE, CLIP_NORM = 0, 1, 2
+
+
+def sgd_opts(lr, momentum=0.9, weight_decay=1e-4, grad_scale=1.0, nesterov=False, bias_lr_factor=1.0, weight_decay_bias=None, clip=None):
+    """SgdOpts from the keyword arguments of MaskRCNN.sgd_step / ops.sgd_step_tensors.  clip: None, ("value", c) or ("norm", c, norm_type);
+    weight_decay_bias None = weight_decay."""
+    o = SgdOpts()
+    check(lib().amp_sgd_opts_default(C.byref(o)), "amp_sgd_opts_default")
+    o.lr, o.momentum, o.weight_decay, o.grad_scale = float(lr), float(momentum), float(weight_decay), float(grad_scale)
+    o.nesterov = int(bool(nesterov))
+    o.bias_lr_factor = float(bias_lr_factor)
+    o.weight_decay_bias = float(weight_decay if weight_decay_bias is None else weight_decay_bias)
+    if clip is not None:
+        kind = str(clip[0]).lower()
+        if kind == "value" and len(clip) == 2:
+            o.clip_type, o.clip_value = CLIP_VALUE, float(clip[1])
+        elif kind == "norm" and len(clip) in (2, 3):
+            o.clip_type, o.clip_value, o.norm_type = CLIP_NORM, float(clip[1]), float(clip[2] if len(clip) == 3 else 2.0)
+        else:
+            raise ValueError(f"clip must be None, ('value', c) or ('norm', c, norm_type), got {clip!r}")
+    return o
+
+
 class Gt(C.Structure):
     _fields_ = [("B", C.c_int), ("gt_off", C.POINTER(C.c_int)), ("boxes", C.POINTER(C.c_float)),
                 ("classes", C.POINTER(C.c_int)), ("poly_off", C.POINTER(C.c_int)), ("poly_xy", C.POINTER(C.c_double)),
@@ -194,6 +224,11 @@ def _declare(L):
         "amp_small_k_dgrad": ([vp, vp, i, i, vp, i, vp, vp, C.c_size_t], i),
         "amp_deconv_grad_transpose": ([vp, vp, vp, i, i, i, i], i),
         "amp_sgd_update": ([vp, vp, vp, vp, C.c_size_t, f, f, f, f], i),
+        "amp_sgd_opts_default": ([C.POINTER(SgdOpts)], i),
+        "amp_sgd_step_tensors": ([vp, vp, vp, vp, vp, vp, vp, i, C.POINTER(SgdOpts), vp, vp], i),
+        "amp_model_sgd_step_ex": ([vp, C.POINTER(SgdOpts)], i),
+        "amp_model_clip_stats": ([vp, vp, vp, i, C.POINTER(i)], i),
+        "amp_debug_last_sgd_path": ([vp], i),
         "amp_pipeline_create": ([vp, i, C.POINTER(vp)], i),
         "amp_pipeline_submit": ([vp, vp, i, i, i, i, vp, vp, C.POINTER(C.c_longlong)], i),
         "amp_pipeline_wait": ([vp, C.c_longlong, C.POINTER(Dets)], i),

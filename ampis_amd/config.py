@@ -96,7 +96,11 @@ _DEFAULTS = {
     "DATALOADER": {"NUM_WORKERS": 4},
     "SOLVER": {"IMS_PER_BATCH": 16, "BASE_LR": 0.001, "MOMENTUM": 0.9, "WEIGHT_DECAY": 0.0001, "WEIGHT_DECAY_NORM": 0.0,
                "MAX_ITER": 40000, "STEPS": (30000,), "GAMMA": 0.1, "WARMUP_ITERS": 1000, "WARMUP_FACTOR": 0.001,
-               "CHECKPOINT_PERIOD": 5000},
+               "CHECKPOINT_PERIOD": 5000,
+               # detectron2's defaults; engine/defaults.py solver_kwargs maps them to the native optimizer step
+               "NESTEROV": False, "BIAS_LR_FACTOR": 1.0, "WEIGHT_DECAY_BIAS": None,
+               "LR_SCHEDULER_NAME": "WarmupMultiStepLR", "WARMUP_METHOD": "linear",
+               "CLIP_GRADIENTS": {"ENABLED": False, "CLIP_TYPE": "value", "CLIP_VALUE": 1.0, "NORM_TYPE": 2.0}},
     "TEST": {"DETECTIONS_PER_IMAGE": 100, "EVAL_PERIOD": 0},
     "OUTPUT_DIR": "./output",
     "SEED": -1,

@@ -226,6 +226,23 @@ int weight_jobs_run(amp_ctx* ctx, const WeightJob* jobs_dev, const void* chunks_
 // train_bwd.hip: amp_sgd_update over a device table of chunks (low 32 bits: offset in floats, a multiple of 4; high 32: length) of the arenas p / g / v
 int sgd_chunks_run(amp_ctx* ctx, const unsigned long long* chunks_dev, int nchunks, float* p, const float* g, float* v, float lr,
                    float momentum, float weight_decay, float grad_scale);
+// train_bwd.hip: the general step (per-tensor learning rate / weight decay, Nesterov, gradient clipping): gradient statistics, finish and
+// update launches over one plan.  Tensor t is floats [off[t], off[t] + n[t]) of the arenas; its first nstat[t] floats count for its norm
+// (null: all of them -- the rest are replicated copies or zero padding of the stored layout).
+struct SgdPlan {
+    void* chunks = nullptr;       // uint4 per chunk of <= 16384 floats
+    void* tinfo = nullptr;        // int4 per tensor
+    double* partials = nullptr;   // one per chunk
+    void* ttab = nullptr;         // float4 {lr_t, wd_t, k, N} per tensor, written by the finish launch of every step
+    int nchunks = 0, ntensors = 0;
+};
+int sgd_plan_build(const unsigned long long* off, const unsigned long long* n, const unsigned long long* nstat, const unsigned char* is_bias,
+                   int ntensors, SgdPlan* plan);
+void sgd_plan_free(SgdPlan* plan);
+int sgd_opts_check(const amp_sgd_opts* o, const char* fn);
+bool sgd_opts_plain(const amp_sgd_opts* o);     // what sgd_chunks_run computes: no clipping, no Nesterov, one learning rate and one decay
+int sgd_general_run(amp_ctx* ctx, const SgdPlan& plan, float* p, const float* g, float* v, const amp_sgd_opts& o);
+int sgd_plan_read_stats(amp_ctx* ctx, const SgdPlan& plan, float* norms_h, float* coefs_h);     // synchronises
 // wgrad.hip: slab reductions on a second stream.  begin(scratch1): every amp_conv2d_wgrad* call from here on launches its reduction on
 // ctx->side (alternating between the scratch it is given and scratch1); join: `stream` waits for every reduction issued so far (before
 // anything on it reads or adds to a gradient); end: join + off.

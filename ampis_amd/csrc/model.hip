@@ -117,6 +117,10 @@ struct amp_model {
     std::vector<Trainable> trainable;
     unsigned long long* sgd_chunks = nullptr;   // device table for amp::sgd_chunks_run, built at the first amp_model_sgd_step
     int sgd_nchunks = 0;
+    amp::SgdPlan sgd_plan;                      // the general step (amp_model_sgd_step_ex): built at its first call, one tensor per state_dict entry
+    bool sgd_plan_built = false;
+    bool clip_stats_valid = false;              // sgd_plan.ttab holds N / k of a norm-clipped step
+    int last_sgd_path = 0;                      // amp_debug_last_sgd_path: 1 sgd_chunks_kernel, 2 the general kernels
     struct JobTable { amp::WeightJob* jobs = nullptr; void* chunks = nullptr; int nchunks = 0; };
     JobTable fwd_jobs, dgrad_jobs;              // refresh_split_weights / refresh_dgrad_weights: every layer's split copy in one launch
     bool fwd_jobs_dirty = true, dgrad_jobs_dirty = true;
@@ -1777,6 +1781,7 @@ void amp_model_destroy(amp_model* m) {
     (void)hipFree(m->garena);
     (void)hipFree(m->varena);
     (void)hipFree(m->sgd_chunks);
+    amp::sgd_plan_free(&m->sgd_plan);
     (void)hipFree(m->fwd_jobs.jobs); (void)hipFree(m->fwd_jobs.chunks); (void)hipFree(m->dgrad_jobs.jobs); (void)hipFree(m->dgrad_jobs.chunks);
     (void)hipFree(m->dgrad_arena);
     (void)hipFree(m->split_arena);
@@ -2099,6 +2104,7 @@ int amp_model_finalize(amp_model* m) {
     // trainable tensors: every conv / fc weight and true bias outside the frozen stem + res2 (FREEZE_AT = 2); FrozenBN has none
     m->trainable.clear();
     if (m->sgd_chunks) { (void)hipFree(m->sgd_chunks); m->sgd_chunks = nullptr; m->sgd_nchunks = 0; }   // rebuilt by the next amp_model_sgd_step
+    amp::sgd_plan_free(&m->sgd_plan); m->sgd_plan_built = false; m->clip_stats_valid = false;
     for (auto& kv : m->conv) {
         const std::string& key = kv.first;
         if (key.rfind("backbone.bottom_up.stem", 0) == 0 || key.rfind("backbone.bottom_up.res2", 0) == 0) continue;
@@ -2269,8 +2275,101 @@ int amp_model_sgd_step(amp_model* m, float lr, float momentum, float weight_deca
     AMP_TRY(amp::sgd_chunks_run(m->ctx, m->sgd_chunks, m->sgd_nchunks, m->parena, m->garena, m->varena, lr, momentum, weight_decay, grad_scale));
     m->grads_valid = false;
     m->split_stale = true;               // the f16x3 operand copies no longer match the weights
+    m->last_sgd_path = 1;
     return AMP_OK;
 }
+
+// Where the state_dict entry `name` lives in the parameter arena: floats [*off, *off + *n) are updated with it, the first *nstat of them are
+// the entry itself (behind them: the zero rows a fused / padded matrix ends with, the three extra copies of the deconvolution's bias).
+// The arithmetic of the step is per element, so the stored layout (xfer_tensor) does not matter.
+static int sgd_locate(amp_model* m, const std::string& name, unsigned long long* off, unsigned long long* n, unsigned long long* nstat) {
+    const std::string prefix = name.substr(0, name.rfind('.'));
+    const bool is_w = ends_with(name, ".weight");
+    const int K = m->cfg.num_classes;
+    std::string key = prefix;
+    int row0 = 0, rows = -1;
+    bool last = false;            // the second half of a fused matrix also owns the padding rows
+    if (prefix == "roi_heads.box_predictor.cls_score") { key = "roi_heads.box_predictor"; rows = K + 1; }
+    else if (prefix == "roi_heads.box_predictor.bbox_pred") { key = "roi_heads.box_predictor"; row0 = K + 1; rows = 4 * K; last = true; }
+    else if (prefix == "proposal_generator.rpn_head.objectness_logits") { key = "proposal_generator.rpn_head.pred"; rows = 3; }
+    else if (prefix == "proposal_generator.rpn_head.anchor_deltas") { key = "proposal_generator.rpn_head.pred"; row0 = 3; rows = 12; last = true; }
+    else if (prefix == "roi_heads.mask_head.predictor") { rows = K; last = true; }
+    auto it = m->conv.find(key);
+    AMP_REQUIRE(it != m->conv.end(), "amp_model_sgd_step_ex: no stored tensor for '%s'", name.c_str());
+    const ConvW& cw = it->second;
+    const unsigned long long cols = is_w ? (unsigned long long)cw.kh * cw.kw * (cw.groups > 1 ? 64 : cw.cin) : 1;
+    const float* base = is_w ? cw.w : cw.shift;
+    AMP_REQUIRE(base, "amp_model_sgd_step_ex: '%s' is not stored", name.c_str());
+    if (rows < 0) {
+        *off = (unsigned long long)(base - m->parena); *n = (unsigned long long)cw.cout * cols;
+        *nstat = (!is_w && prefix == "roi_heads.mask_head.deconv") ? 256 : *n;      // the bias is stored once per tap, its gradient too
+        return AMP_OK;
+    }
+    AMP_REQUIRE(row0 + rows <= cw.cout, "amp_model_sgd_step_ex: '%s' does not fit its fused tensor", name.c_str());
+    *off = (unsigned long long)(base - m->parena) + (unsigned long long)row0 * cols;
+    *nstat = (unsigned long long)rows * cols;
+    *n = (unsigned long long)((last ? cw.cout : row0 + rows) - row0) * cols;
+    return AMP_OK;
+}
+
+static int sgd_plan_of_model(amp_model* m) {
+    if (m->sgd_plan_built) return AMP_OK;
+    std::vector<unsigned long long> off, n, ns;
+    std::vector<unsigned char> bias;
+    unsigned long long total = 0;
+    for (auto& name : m->expected) {
+        if (name.find(".norm.") != std::string::npos || name.rfind("backbone.bottom_up.stem", 0) == 0 || name.rfind("backbone.bottom_up.res2", 0) == 0) continue;
+        unsigned long long o = 0, c = 0, s = 0;
+        AMP_TRY(sgd_locate(m, name, &o, &c, &s));
+        off.push_back(o); n.push_back(c); ns.push_back(s); bias.push_back(ends_with(name, ".bias") ? 1 : 0);
+        total += c;
+    }
+    // the same floats amp_model_sgd_step updates, each exactly once: every entry inside one stored tensor, the sizes adding up
+    unsigned long long stored = 0;
+    for (auto& t : m->trainable) stored += t.n;
+    AMP_REQUIRE(total == stored, "amp_model_sgd_step_ex: the state_dict entries cover %llu floats, the stored trainable tensors %llu", total, stored);
+    for (size_t i = 0; i < off.size(); ++i) {
+        bool inside = false;
+        for (auto& t : m->trainable) {
+            const unsigned long long t0 = (unsigned long long)(t.p - m->parena);
+            if (off[i] >= t0 && off[i] + n[i] <= t0 + t.n) { inside = true; break; }
+        }
+        AMP_REQUIRE(inside, "amp_model_sgd_step_ex: entry %zu lies outside the stored trainable tensors", i);
+        for (size_t j = 0; j < i; ++j)
+            AMP_REQUIRE(off[i] + n[i] <= off[j] || off[j] + n[j] <= off[i], "amp_model_sgd_step_ex: entries %zu and %zu overlap", j, i);
+    }
+    AMP_TRY(amp::sgd_plan_build(off.data(), n.data(), ns.data(), bias.data(), (int)off.size(), &m->sgd_plan));
+    m->sgd_plan_built = true;
+    return AMP_OK;
+}
+
+int amp_model_sgd_step_ex(amp_model* m, const amp_sgd_opts* o) {
+    AMP_REQUIRE(m && m->garena && m->varena, "amp_model_sgd_step_ex: the model was created without cfg.train_enable");
+    AMP_TRY(amp::sgd_opts_check(o, "amp_model_sgd_step_ex"));
+    if (amp::sgd_opts_plain(o)) return amp_model_sgd_step(m, o->lr, o->momentum, o->weight_decay, o->grad_scale);
+    AMP_REQUIRE(m->grads_valid, "amp_model_sgd_step_ex: no gradients (call amp_model_forward_backward first)");
+    AMP_TRY(sgd_plan_of_model(m));
+    AMP_TRY(amp::comm_wait_done(m->ctx));    // the statistics are those of the summed gradients: after the exchange, on the device
+    AMP_TRY(amp::sgd_general_run(m->ctx, m->sgd_plan, m->parena, m->garena, m->varena, *o));
+    m->clip_stats_valid = o->clip_type == AMP_CLIP_NORM;
+    m->grads_valid = false;
+    m->split_stale = true;
+    m->last_sgd_path = 2;
+    return AMP_OK;
+}
+
+int amp_model_clip_stats(amp_model* m, float* norms_h, float* coefs_h, int cap, int* n_out) {
+    AMP_REQUIRE(m && n_out && m->finalized && m->garena, "amp_model_clip_stats: null argument, or a model that does not train");
+    AMP_TRY(sgd_plan_of_model(m));
+    *n_out = m->sgd_plan.ntensors;
+    if (!norms_h && !coefs_h) return AMP_OK;
+    AMP_REQUIRE(m->clip_stats_valid, "amp_model_clip_stats: the last step was not an amp_model_sgd_step_ex with AMP_CLIP_NORM");
+    AMP_REQUIRE(cap >= m->sgd_plan.ntensors, "amp_model_clip_stats: %d tensors, capacity %d", m->sgd_plan.ntensors, cap);
+    return amp::sgd_plan_read_stats(m->ctx, m->sgd_plan, norms_h, coefs_h);
+}
+
+/* tests: which kernels the last step of this model ran (0 none yet, 1 sgd_chunks_kernel, 2 the general step) */
+int amp_debug_last_sgd_path(amp_model* m) { return m ? m->last_sgd_path : 0; }
 
 int amp_model_grad_arena(amp_model* m, float** grads, size_t* nfloats) {
     AMP_REQUIRE(m && grads && nfloats && m->garena, "amp_model_grad_arena: the model was created without cfg.train_enable");

@@ -609,6 +609,122 @@ __global__ __launch_bounds__(256) void sgd_chunks_kernel(const unsigned long lon
     }
 }
 
+// ---- The general step (amp_model_sgd_step_ex / amp_sgd_step_tensors): per-tensor learning rate, weight decay and gradient clipping ----
+// Three launches over one plan (amp::SgdPlan).  A chunk is uint4 {offset in floats, length <= 16384, tensor index, leading floats that
+// count for the tensor's norm}; a tensor is int4 {first chunk, chunks, is_bias, 0}; the per-tensor table the update reads is float4
+// {lr_t, wd_t, k, N}.  Nothing is handed from one workgroup to another inside a launch and no float atomic is used: every sum has one
+// fixed order (lane tree, waves in index order, chunks in index order), so the step is bitwise reproducible.
+template <int NORM>
+__device__ __forceinline__ double stat_op(double a, double b) {
+    if (NORM == 0) return (b > a || b != b) ? b : a;      // max; a NaN sticks, as in torch's norm
+    return a + b;
+}
+
+// Pass 1: one fp64 partial per chunk of gs = fl32(g * grad_scale): sum gs^2 (NORM 2), sum |gs| (NORM 1) or max |gs| (NORM 0 = infinity).
+template <int NORM>
+__global__ __launch_bounds__(256) void sgd_stats_kernel(const uint4* __restrict__ chunks, const float* __restrict__ g, float gscale,
+                                                        double* __restrict__ partials) {
+    __shared__ double wave_part[4];
+    const uint4 ch = chunks[blockIdx.x];
+    const size_t off = (size_t)ch.x;
+    const int n = (int)(ch.w < ch.y ? ch.w : ch.y);       // floats of this chunk that belong to the tensor's norm (copies / padding behind them do not)
+    double acc = 0.0;
+    auto take = [&](float x) {
+        const double a = (double)fabsf(__fmul_rn(x, gscale));
+        acc = stat_op<NORM>(acc, NORM == 2 ? a * a : a);   // a * a is exact in fp64
+    };
+    if ((off & 3) == 0) {
+        const int n4 = n >> 2;
+        const f32x4* g4 = reinterpret_cast<const f32x4*>(g + off);
+        for (int i = threadIdx.x; i < n4; i += 256) {
+            const f32x4 gi = g4[i];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) take(gi[e]);
+        }
+        const int i = 4 * n4 + (int)threadIdx.x;
+        if (i < n) take(g[off + i]);
+    } else {                                              // a slice of a fused tensor that does not start on 16 bytes (a few floats)
+        for (int i = threadIdx.x; i < n; i += 256) take(g[off + i]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc = stat_op<NORM>(acc, __shfl_down(acc, o, 64));
+    if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        partials[blockIdx.x] = stat_op<NORM>(stat_op<NORM>(stat_op<NORM>(wave_part[0], wave_part[1]), wave_part[2]), wave_part[3]);
+}
+
+// Pass 2: one workgroup per tensor.  With norm clipping: the tensor's chunk partials combined in chunk order, N = fl32(sqrt(sum)) (fl32(sum),
+// max), k = min(c / (N + 1e-6), 1) in fp32 (torch.nn.utils.clip_grad_norm_).  Always: the tensor's learning rate and weight decay.
+__global__ __launch_bounds__(256) void sgd_finish_kernel(const int4* __restrict__ tinfo, const double* __restrict__ partials, float4* __restrict__ ttab,
+                                                         int norm_clip, int norm, float c, float lr_w, float lr_b, float wd_w, float wd_b) {
+    __shared__ double tile[256];
+    const int4 ti = tinfo[blockIdx.x];
+    float N = 0.f, k = 1.f;
+    if (norm_clip) {
+        double s = 0.0;
+        for (int base = 0; base < ti.y; base += 256) {
+            if (base + (int)threadIdx.x < ti.y) tile[threadIdx.x] = partials[ti.x + base + threadIdx.x];
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                const int m = ti.y - base < 256 ? ti.y - base : 256;
+                if (norm == 0) { for (int j = 0; j < m; ++j) s = stat_op<0>(s, tile[j]); }
+                else { for (int j = 0; j < m; ++j) s = s + tile[j]; }
+            }
+            __syncthreads();
+        }
+        N = norm == 2 ? (float)sqrt(s) : (float)s;
+        k = __fdiv_rn(c, __fadd_rn(N, 1e-6f));
+        k = k > 1.0f ? 1.0f : k;                          // a NaN norm gives a NaN factor, as torch's clamp does
+    }
+    if (threadIdx.x == 0) ttab[blockIdx.x] = make_float4(ti.z ? lr_b : lr_w, ti.z ? wd_b : wd_w, k, N);
+}
+
+// gs = g*grad_scale; gc = gs | clamp(gs, -c, c) | gs*k; g' = gc + wd*p; v = mu*v + g'; u = nesterov ? g' + mu*v : v; p -= lr*u -- every
+// operation rounded on its own
+template <int CLIP, int NESTEROV>
+__device__ __forceinline__ void sgd_elem(float& p, float& v, float g, float lr, float wd, float k, float mu, float gscale, float c) {
+    float gs = __fmul_rn(g, gscale);
+    if (CLIP == AMP_CLIP_VALUE) gs = gs < -c ? -c : (gs > c ? c : gs);
+    if (CLIP == AMP_CLIP_NORM) gs = __fmul_rn(gs, k);
+    const float ge = __fadd_rn(gs, __fmul_rn(wd, p));
+    v = __fadd_rn(__fmul_rn(mu, v), ge);
+    const float u = NESTEROV ? __fadd_rn(ge, __fmul_rn(mu, v)) : v;
+    p = __fsub_rn(p, __fmul_rn(lr, u));
+}
+
+// Pass 3: the update over the same chunk table; lr_t / wd_t / k of the chunk's tensor come from the table pass 2 wrote.
+template <int CLIP, int NESTEROV>
+__global__ __launch_bounds__(256) void sgd_general_kernel(const uint4* __restrict__ chunks, const float4* __restrict__ ttab, float* __restrict__ p,
+                                                          const float* __restrict__ g, float* __restrict__ v, float mu, float gscale, float c) {
+    const uint4 ch = chunks[blockIdx.x];
+    const float4 tt = ttab[ch.z];
+    const float lr = tt.x, wd = tt.y, k = tt.z;
+    const size_t off = (size_t)ch.x;
+    const int n = (int)ch.y;
+    if ((off & 3) == 0) {
+        const int n4 = n >> 2;
+        f32x4* p4 = reinterpret_cast<f32x4*>(p + off);
+        const f32x4* g4 = reinterpret_cast<const f32x4*>(g + off);
+        f32x4* v4 = reinterpret_cast<f32x4*>(v + off);
+        for (int i = threadIdx.x; i < n4; i += 256) {
+            f32x4 pi = p4[i], vi = v4[i];
+            const f32x4 gi = g4[i];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float pe = pi[e], ve = vi[e];
+                sgd_elem<CLIP, NESTEROV>(pe, ve, gi[e], lr, wd, k, mu, gscale, c);
+                pi[e] = pe; vi[e] = ve;
+            }
+            v4[i] = vi; p4[i] = pi;
+        }
+        const int i = 4 * n4 + (int)threadIdx.x;
+        if (i < n) sgd_elem<CLIP, NESTEROV>(p[off + i], v[off + i], g[off + i], lr, wd, k, mu, gscale, c);
+    } else {
+        for (int i = threadIdx.x; i < n; i += 256) sgd_elem<CLIP, NESTEROV>(p[off + i], v[off + i], g[off + i], lr, wd, k, mu, gscale, c);
+    }
+}
+
 inline unsigned grid_for(size_t total) { return (unsigned)std::min<size_t>(std::max<size_t>((total + 255) / 256, 1), 4096); }
 
 }  // namespace
@@ -618,6 +734,103 @@ int amp::sgd_chunks_run(amp_ctx* ctx, const unsigned long long* chunks_dev, int 
     if (nchunks <= 0) return AMP_OK;
     hipLaunchKernelGGL(sgd_chunks_kernel, dim3((unsigned)nchunks), dim3(256), 0, ctx->stream, chunks_dev, p, g, v, lr, momentum, weight_decay, grad_scale);
     AMP_HIP_CHECK(hipGetLastError());
+    return AMP_OK;
+}
+
+int amp::sgd_opts_check(const amp_sgd_opts* o, const char* fn) {
+    AMP_REQUIRE(o, "%s: null options", fn);
+    const struct { const char* name; float v; } scalars[] = {{"lr", o->lr}, {"momentum", o->momentum}, {"weight_decay", o->weight_decay},
+        {"grad_scale", o->grad_scale}, {"bias_lr_factor", o->bias_lr_factor}, {"weight_decay_bias", o->weight_decay_bias}, {"clip_value", o->clip_value}};
+    for (auto& s : scalars) AMP_REQUIRE(std::isfinite(s.v), "%s: amp_sgd_opts.%s is not finite", fn, s.name);
+    AMP_REQUIRE(o->clip_type == AMP_CLIP_NONE || o->clip_type == AMP_CLIP_VALUE || o->clip_type == AMP_CLIP_NORM,
+                "%s: amp_sgd_opts.clip_type %d (AMP_CLIP_NONE, AMP_CLIP_VALUE or AMP_CLIP_NORM)", fn, o->clip_type);
+    if (o->clip_type != AMP_CLIP_NONE) AMP_REQUIRE(o->clip_value > 0.f, "%s: amp_sgd_opts.clip_value %g must be positive", fn, (double)o->clip_value);
+    if (o->clip_type == AMP_CLIP_NORM)
+        AMP_REQUIRE(o->norm_type == 1.f || o->norm_type == 2.f || (std::isinf(o->norm_type) && o->norm_type > 0.f),
+                    "%s: amp_sgd_opts.norm_type %g (1, 2 or INFINITY)", fn, (double)o->norm_type);
+    return AMP_OK;
+}
+
+bool amp::sgd_opts_plain(const amp_sgd_opts* o) {
+    return o->clip_type == AMP_CLIP_NONE && o->nesterov == 0 && o->bias_lr_factor == 1.f && o->weight_decay_bias == o->weight_decay;
+}
+
+void amp::sgd_plan_free(SgdPlan* pl) {
+    (void)hipFree(pl->chunks); (void)hipFree(pl->tinfo); (void)hipFree(pl->partials); (void)hipFree(pl->ttab);
+    *pl = SgdPlan();
+}
+
+int amp::sgd_plan_build(const unsigned long long* off, const unsigned long long* n, const unsigned long long* nstat, const unsigned char* is_bias,
+                        int ntensors, SgdPlan* pl) {
+    std::vector<uint4> ch;
+    std::vector<int4> ti((size_t)std::max(ntensors, 0));
+    for (int t = 0; t < ntensors; ++t) {
+        const unsigned long long ns = nstat ? nstat[t] : n[t];
+        AMP_REQUIRE(n[t] >= 1 && ns >= 1 && ns <= n[t] && off[t] + n[t] <= (1ull << 32), "sgd plan: tensor %d: offset %llu, %llu floats out of range", t, off[t], n[t]);
+        ti[t] = make_int4((int)ch.size(), (int)((n[t] + 16383) / 16384), is_bias[t] ? 1 : 0, 0);
+        for (unsigned long long o = 0; o < n[t]; o += 16384)
+            ch.push_back(make_uint4((unsigned)(off[t] + o), (unsigned)std::min<unsigned long long>(16384, n[t] - o), (unsigned)t,
+                                    (unsigned)(ns > o ? std::min<unsigned long long>(16384, ns - o) : 0)));
+    }
+    sgd_plan_free(pl);
+    if (ch.empty()) return AMP_OK;
+    AMP_REQUIRE(ch.size() < (1u << 30), "sgd plan: too many chunks");
+    AMP_HIP_CHECK(hipMalloc(&pl->chunks, ch.size() * sizeof(uint4)));
+    AMP_HIP_CHECK(hipMalloc(&pl->tinfo, ti.size() * sizeof(int4)));
+    AMP_HIP_CHECK(hipMalloc(&pl->partials, ch.size() * sizeof(double)));
+    AMP_HIP_CHECK(hipMalloc(&pl->ttab, ti.size() * sizeof(float4)));
+    AMP_HIP_CHECK(hipMemcpy(pl->chunks, ch.data(), ch.size() * sizeof(uint4), hipMemcpyHostToDevice));
+    AMP_HIP_CHECK(hipMemcpy(pl->tinfo, ti.data(), ti.size() * sizeof(int4), hipMemcpyHostToDevice));
+    AMP_HIP_CHECK(hipMemset(pl->partials, 0, ch.size() * sizeof(double)));
+    AMP_HIP_CHECK(hipMemset(pl->ttab, 0, ti.size() * sizeof(float4)));
+    pl->nchunks = (int)ch.size();
+    pl->ntensors = ntensors;
+    return AMP_OK;
+}
+
+int amp::sgd_general_run(amp_ctx* ctx, const SgdPlan& pl, float* p, const float* g, float* v, const amp_sgd_opts& o) {
+    if (pl.nchunks <= 0) return AMP_OK;
+    const uint4* chunks = static_cast<const uint4*>(pl.chunks);
+    float4* ttab = static_cast<float4*>(pl.ttab);
+    const dim3 grid((unsigned)pl.nchunks), block(256);
+    const bool norm_clip = o.clip_type == AMP_CLIP_NORM;
+    const int norm = !norm_clip ? 2 : o.norm_type == 1.f ? 1 : o.norm_type == 2.f ? 2 : 0;
+    if (norm_clip) {
+        if (norm == 2) hipLaunchKernelGGL(sgd_stats_kernel<2>, grid, block, 0, ctx->stream, chunks, g, o.grad_scale, pl.partials);
+        else if (norm == 1) hipLaunchKernelGGL(sgd_stats_kernel<1>, grid, block, 0, ctx->stream, chunks, g, o.grad_scale, pl.partials);
+        else hipLaunchKernelGGL(sgd_stats_kernel<0>, grid, block, 0, ctx->stream, chunks, g, o.grad_scale, pl.partials);
+        AMP_HIP_CHECK(hipGetLastError());
+    }
+    // the bias group's learning rate and the two decays: each product formed in double, narrowed once
+    const float lr_b = (float)((double)o.lr * (double)o.bias_lr_factor);
+    hipLaunchKernelGGL(sgd_finish_kernel, dim3((unsigned)pl.ntensors), block, 0, ctx->stream, static_cast<const int4*>(pl.tinfo), pl.partials, ttab,
+                       norm_clip ? 1 : 0, norm, o.clip_value, o.lr, lr_b, o.weight_decay, o.weight_decay_bias);
+    AMP_HIP_CHECK(hipGetLastError());
+#define AMP_SGD_LAUNCH(CLIP, NEST) \
+    hipLaunchKernelGGL((sgd_general_kernel<CLIP, NEST>), grid, block, 0, ctx->stream, chunks, ttab, p, g, v, o.momentum, o.grad_scale, o.clip_value)
+    if (o.nesterov) {
+        if (o.clip_type == AMP_CLIP_NONE) AMP_SGD_LAUNCH(AMP_CLIP_NONE, 1);
+        else if (o.clip_type == AMP_CLIP_VALUE) AMP_SGD_LAUNCH(AMP_CLIP_VALUE, 1);
+        else AMP_SGD_LAUNCH(AMP_CLIP_NORM, 1);
+    } else {
+        if (o.clip_type == AMP_CLIP_NONE) AMP_SGD_LAUNCH(AMP_CLIP_NONE, 0);
+        else if (o.clip_type == AMP_CLIP_VALUE) AMP_SGD_LAUNCH(AMP_CLIP_VALUE, 0);
+        else AMP_SGD_LAUNCH(AMP_CLIP_NORM, 0);
+    }
+#undef AMP_SGD_LAUNCH
+    AMP_HIP_CHECK(hipGetLastError());
+    return AMP_OK;
+}
+
+int amp::sgd_plan_read_stats(amp_ctx* ctx, const SgdPlan& pl, float* norms_h, float* coefs_h) {
+    if (pl.ntensors <= 0 || (!norms_h && !coefs_h)) return AMP_OK;
+    std::vector<float4> tt((size_t)pl.ntensors);
+    AMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    AMP_HIP_CHECK(hipMemcpy(tt.data(), pl.ttab, tt.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    for (int t = 0; t < pl.ntensors; ++t) {
+        if (norms_h) norms_h[t] = tt[t].w;
+        if (coefs_h) coefs_h[t] = tt[t].z;
+    }
     return AMP_OK;
 }
 
@@ -836,6 +1049,30 @@ int amp_sgd_update(amp_ctx* ctx, float* p, const float* g, float* v, size_t n, f
     hipLaunchKernelGGL(sgd_kernel, dim3(grid_for(n)), dim3(256), 0, ctx->stream, p, g, v, n, lr, momentum, weight_decay, grad_scale);
     AMP_HIP_CHECK(hipGetLastError());
     return AMP_OK;
+}
+
+int amp_sgd_opts_default(amp_sgd_opts* o) {
+    AMP_REQUIRE(o, "amp_sgd_opts_default: null argument");
+    o->lr = 0.f; o->momentum = 0.9f; o->weight_decay = 1e-4f; o->grad_scale = 1.f;
+    o->nesterov = 0;
+    o->bias_lr_factor = 1.f; o->weight_decay_bias = 1e-4f;
+    o->clip_type = AMP_CLIP_NONE; o->clip_value = 1.f; o->norm_type = 2.f;
+    return AMP_OK;
+}
+
+int amp_sgd_step_tensors(amp_ctx* ctx, float* p, const float* g, float* v, const unsigned long long* off_h, const unsigned long long* n_h,
+                         const unsigned char* is_bias_h, int ntensors, const amp_sgd_opts* opts, float* norms_h, float* coefs_h) {
+    AMP_REQUIRE(ctx && p && g && v && off_h && n_h && is_bias_h && ntensors >= 1, "amp_sgd_step_tensors: null argument or no tensors");
+    AMP_TRY_STATUS(amp::sgd_opts_check(opts, "amp_sgd_step_tensors"));
+    for (int t = 0; t < ntensors; ++t)
+        AMP_REQUIRE(off_h[t] % 4 == 0 && n_h[t] >= 1, "amp_sgd_step_tensors: tensor %d: offset %llu (a multiple of 4), %llu floats (>= 1)", t, off_h[t], n_h[t]);
+    amp::SgdPlan pl;
+    int st = amp::sgd_plan_build(off_h, n_h, nullptr, is_bias_h, ntensors, &pl);
+    if (st == AMP_OK) st = amp::sgd_general_run(ctx, pl, p, g, v, *opts);
+    if (st == AMP_OK) st = amp::sgd_plan_read_stats(ctx, pl, norms_h, coefs_h);
+    if (st == AMP_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) { amp::set_error("amp_sgd_step_tensors: the stream failed"); st = AMP_ERR_HIP; }
+    amp::sgd_plan_free(&pl);      // after the synchronisation: the launches read the plan
+    return st;
 }
 
 }  // extern "C"

@@ -34,6 +34,64 @@ def train_model_kwargs(cfg, per_rank):
     return kw
 
 
+_SOLVER_DEFAULTS = {"NESTEROV": False, "BIAS_LR_FACTOR": 1.0, "WEIGHT_DECAY_BIAS": None, "LR_SCHEDULER_NAME": "WarmupMultiStepLR",
+                    "WARMUP_METHOD": "linear"}
+_CLIP_DEFAULTS = {"ENABLED": False, "CLIP_TYPE": "value", "CLIP_VALUE": 1.0, "NORM_TYPE": 2.0}
+
+
+def _number(v, key):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+        raise ValueError(f"{key} = {v!r}: a finite number is required")
+    return float(v)
+
+
+def _positive(v, key):
+    v = _number(v, key)
+    if v <= 0:
+        raise ValueError(f"{key} = {v!r}: must be positive")
+    return v
+
+
+def solver_kwargs(cfg):
+    """The keyword arguments MaskRCNN.sgd_step takes from cfg.SOLVER beyond lr / MOMENTUM / WEIGHT_DECAY, as detectron2's build_optimizer
+    reads them: NESTEROV, BIAS_LR_FACTOR and WEIGHT_DECAY_BIAS (None = WEIGHT_DECAY) for the tensors named *.bias, and CLIP_GRADIENTS
+    (ENABLED, CLIP_TYPE "value" | "norm", CLIP_VALUE, NORM_TYPE 1 | 2 | inf; clipping is per parameter tensor, as in detectron2).  A
+    cfg without these keys (a hand-built CfgNode) gets detectron2's defaults.  WEIGHT_DECAY_NORM is accepted and has no effect: every norm
+    layer here is FrozenBN and has no trainable parameter.  Raises ValueError naming the cfg key for what the native step cannot
+    represent, before any device work."""
+    s = cfg.SOLVER
+    get = lambda k: s.get(k, _SOLVER_DEFAULTS[k])
+    nesterov = get("NESTEROV")
+    if not isinstance(nesterov, (bool, np.bool_)):
+        raise ValueError(f"SOLVER.NESTEROV = {nesterov!r}: True or False is required")
+    blf = _number(get("BIAS_LR_FACTOR"), "SOLVER.BIAS_LR_FACTOR")
+    if blf < 0:
+        raise ValueError(f"SOLVER.BIAS_LR_FACTOR = {blf!r}: must not be negative")
+    wdb = get("WEIGHT_DECAY_BIAS")
+    wdb = None if wdb is None else _number(wdb, "SOLVER.WEIGHT_DECAY_BIAS")
+    kw = dict(nesterov=bool(nesterov), bias_lr_factor=blf, weight_decay_bias=wdb, clip=None)
+    c = s.get("CLIP_GRADIENTS", None) or {}
+    cget = lambda k: c.get(k, _CLIP_DEFAULTS[k])
+    enabled = cget("ENABLED")
+    if not isinstance(enabled, (bool, np.bool_)):
+        raise ValueError(f"SOLVER.CLIP_GRADIENTS.ENABLED = {enabled!r}: True or False is required")
+    if enabled:
+        kind = cget("CLIP_TYPE")
+        if not isinstance(kind, str) or kind.lower() not in ("value", "norm"):
+            raise ValueError(f"SOLVER.CLIP_GRADIENTS.CLIP_TYPE = {kind!r}: 'value' or 'norm' (per-parameter clipping, as detectron2 core)")
+        value = _positive(cget("CLIP_VALUE"), "SOLVER.CLIP_GRADIENTS.CLIP_VALUE")
+        if kind.lower() == "value":
+            kw["clip"] = ("value", value)
+        else:
+            nt = cget("NORM_TYPE")
+            if isinstance(nt, str) and nt.lower() in ("inf", "+inf", "infinity"):
+                nt = float("inf")
+            if isinstance(nt, bool) or not isinstance(nt, (int, float, np.integer, np.floating)) or float(nt) not in (1.0, 2.0, float("inf")):
+                raise ValueError(f"SOLVER.CLIP_GRADIENTS.NORM_TYPE = {nt!r}: 1, 2 or inf")
+            kw["clip"] = ("norm", value, float(nt))
+    return kw
+
+
 def read_image_bgr(path):
     """cv2.imread stand-in (notebook cells 26/28): 8-bit image -> HxWx3 BGR uint8 (grayscale replicated)."""
     from PIL import Image
@@ -406,6 +464,8 @@ class DefaultTrainer:
         self._cap = self._capacity_from_cfg()              # one allocation for everything the loaders can produce
         self._per_rank = int(cfg.SOLVER.IMS_PER_BATCH) // self.world_size
         train_model_kwargs(cfg, self._per_rank)            # a sampling setting the native path cannot represent fails here, naming its key
+        self._solver_kw = solver_kwargs(cfg)               # ... and so does an optimizer setting
+        self.lr_at(0)                                      # ... and an unknown LR_SCHEDULER_NAME / WARMUP_METHOD
         from ..data import PREFETCH_DEPTH
         workers = int(cfg.DATALOADER.get("NUM_WORKERS", 0)) if "DATALOADER" in cfg else 0
         self._dev, self._workers, self._loader_epoch = dev, workers, 0
@@ -574,9 +634,18 @@ class DefaultTrainer:
 
     # ---- loop ----
     def lr_at(self, it):
-        from .train_loop import warmup_multistep_lr
+        """The learning rate of iteration `it`: SOLVER.LR_SCHEDULER_NAME = WarmupMultiStepLR (STEPS, GAMMA) or WarmupCosineLR (MAX_ITER), with
+        the WARMUP_METHOD ("linear" | "constant") warm-up of WARMUP_ITERS iterations starting at WARMUP_FACTOR."""
+        from .train_loop import warmup_cosine_lr, warmup_multistep_lr
         s = self.cfg.SOLVER
-        return warmup_multistep_lr(it, float(s.BASE_LR), tuple(s.STEPS), float(s.GAMMA), int(s.WARMUP_ITERS), float(s.WARMUP_FACTOR))
+        name = s.get("LR_SCHEDULER_NAME", _SOLVER_DEFAULTS["LR_SCHEDULER_NAME"])
+        method = s.get("WARMUP_METHOD", _SOLVER_DEFAULTS["WARMUP_METHOD"])
+        iters, factor = int(s.WARMUP_ITERS), float(s.WARMUP_FACTOR)
+        if name == "WarmupMultiStepLR":
+            return warmup_multistep_lr(it, float(s.BASE_LR), tuple(s.STEPS), float(s.GAMMA), iters, factor, method)
+        if name == "WarmupCosineLR":
+            return warmup_cosine_lr(it, float(s.BASE_LR), int(s.MAX_ITER), iters, factor, method)
+        raise ValueError(f"Unknown LR scheduler: {name}")
 
     def run_step(self):
         from ..utils import comm
@@ -591,7 +660,7 @@ class DefaultTrainer:
         scale = comm.all_reduce_gradients(self._net, self.ctx)
         lr = self.lr_at(self.iter)
         s = self.cfg.SOLVER
-        self._net.sgd_step(lr, float(s.MOMENTUM), float(s.WEIGHT_DECAY), grad_scale=scale)
+        self._net.sgd_step(lr, float(s.MOMENTUM), float(s.WEIGHT_DECAY), grad_scale=scale, **self._solver_kw)
         total = sum(losses.values())
         if not np.isfinite(total):
             raise FloatingPointError(f"Loss became infinite or NaN at iteration={self.iter}!\nloss_dict = {losses}")

@@ -4,6 +4,7 @@ DefaultTrainer.build_hooks returns (the writer is LAST: AmpisTrainer inserts its
 import bisect
 import json
 import logging
+import math
 import os
 import time
 from collections import defaultdict
@@ -41,14 +42,33 @@ class EventStorage:
         self.iter += 1
 
 
-def warmup_multistep_lr(it, base_lr, steps, gamma, warmup_iters, warmup_factor):
-    """detectron2 solver/lr_scheduler.py WarmupMultiStepLR (linear warm-up)."""
-    if it < warmup_iters:
-        alpha = it / warmup_iters
-        w = warmup_factor * (1 - alpha) + alpha
-    else:
-        w = 1.0
+def warmup_factor_at(it, method, warmup_iters, warmup_factor):
+    """detectron2 solver/lr_scheduler.py _get_warmup_factor_at_iter: the factor the schedule's value is MULTIPLIED by while
+    it < warmup_iters -- warmup_factor ("constant") or warmup_factor * (1 - it / warmup_iters) + it / warmup_iters ("linear") -- and 1 after."""
+    if method not in ("constant", "linear"):
+        raise ValueError(f"Unknown warmup method: {method}")
+    if it >= warmup_iters:
+        return 1.0
+    if method == "constant":
+        return float(warmup_factor)
+    alpha = it / warmup_iters
+    return warmup_factor * (1 - alpha) + alpha
+
+
+def warmup_multistep_lr(it, base_lr, steps, gamma, warmup_iters, warmup_factor, warmup_method="linear"):
+    """detectron2 solver/lr_scheduler.py WarmupMultiStepLR."""
+    w = warmup_factor_at(it, warmup_method, warmup_iters, warmup_factor)
     return base_lr * w * gamma ** bisect.bisect_right(list(steps), it)
+
+
+def warmup_cosine_lr(it, base_lr, max_iter, warmup_iters, warmup_factor, warmup_method="linear"):
+    """detectron2 solver/lr_scheduler.py WarmupCosineLR: base_lr * warm(it) * 0.5 * (1 + cos(pi * it / max_iter)).
+    The multiplicative form of that class, the lineage warmup_multistep_lr follows: the warm-up factor multiplies the cosine value.
+    detectron2 >= 0.4 (fvcore's WarmupParamScheduler) instead interpolates from warmup_factor * base_lr towards the schedule's value at
+    the end of the warm-up; for WarmupMultiStepLR the two agree whenever no step falls inside the warm-up, for the cosine they differ
+    slightly during it."""
+    w = warmup_factor_at(it, warmup_method, warmup_iters, warmup_factor)
+    return base_lr * w * 0.5 * (1.0 + math.cos(math.pi * it / max_iter))
 
 
 class PeriodicCheckpointer(HookBase):

@@ -383,8 +383,32 @@ class MaskRCNN:
             a = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32).reshape(-1, 2))
             check(lib().amp_model_set_image_sizes(self._h, a.ctypes.data_as(C.c_void_p), len(a)), "amp_model_set_image_sizes")
 
-    def sgd_step(self, lr, momentum=0.9, weight_decay=1e-4, grad_scale=1.0):
-        check(lib().amp_model_sgd_step(self._h, float(lr), float(momentum), float(weight_decay), float(grad_scale)), "amp_model_sgd_step")
+    def sgd_step(self, lr, momentum=0.9, weight_decay=1e-4, grad_scale=1.0, *, nesterov=False, bias_lr_factor=1.0, weight_decay_bias=None,
+                 clip=None):
+        """One optimizer step on every trainable tensor, what detectron2's build_optimizer makes of torch.optim.SGD:
+        gs = g * grad_scale; gc = gs, clamp(gs, -c, c) for clip=("value", c), or gs * k for clip=("norm", c, norm_type) with
+        k = min(c / (||gs|| + 1e-6), 1) per tensor (the norm summed in fp64); g' = gc + wd_t * p; v = mu * v + g';
+        p -= lr_t * (g' + mu * v if nesterov else v).  Tensors named *.bias take lr * bias_lr_factor and weight_decay_bias (None =
+        weight_decay).  With the keyword arguments at their defaults this is amp_model_sgd_step: the same kernel, the same bits."""
+        if not nesterov and bias_lr_factor == 1.0 and weight_decay_bias is None and clip is None:
+            check(lib().amp_model_sgd_step(self._h, float(lr), float(momentum), float(weight_decay), float(grad_scale)), "amp_model_sgd_step")
+            return
+        o = _lib.sgd_opts(lr, momentum, weight_decay, grad_scale, nesterov, bias_lr_factor, weight_decay_bias, clip)
+        check(lib().amp_model_sgd_step_ex(self._h, C.byref(o)), "amp_model_sgd_step_ex")
+
+    def clip_stats(self):
+        """{name: (N, k)} of the last sgd_step with clip=("norm", ...): each trainable tensor's gradient norm and the factor applied."""
+        names = [lib().amp_model_tensor_name(self._h, i).decode() for i in range(lib().amp_model_num_tensors(self._h))]
+        frozen = set(names) - set(self.trainable_names())
+        names = [k for k in names if k not in frozen]          # the library's order of the trainable tensors
+        n = C.c_int()
+        check(lib().amp_model_clip_stats(self._h, None, None, 0, C.byref(n)), "amp_model_clip_stats")
+        if n.value != len(names):
+            raise _lib.AmpError(f"amp_model_clip_stats reports {n.value} tensors, the model trains {len(names)}")
+        norms, coefs = np.empty(n.value, np.float32), np.empty(n.value, np.float32)
+        check(lib().amp_model_clip_stats(self._h, norms.ctypes.data_as(C.c_void_p), coefs.ctypes.data_as(C.c_void_p), n.value, C.byref(n)),
+              "amp_model_clip_stats")
+        return {k: (norms[i], coefs[i]) for i, k in enumerate(names)}
 
     def grad_arena(self):
         """(device pointer, number of floats) of the flat gradient arena (for the RCCL all-reduce)."""

@@ -282,6 +282,29 @@ def roi_align_bwd(ctx, dfeats, strides, rois, batch_idx, P, dout, B=0):
                                           ptr(_f32c(dout)), int(B)), "amp_roi_align_bwd_batched")
 
 
+def sgd_step_tensors(ctx, p, g, v, offsets, sizes, is_bias, lr, momentum=0.9, weight_decay=1e-4, grad_scale=1.0, *, nesterov=False,
+                     bias_lr_factor=1.0, weight_decay_bias=None, clip=None):
+    """The general SGD step (amp_sgd_step_tensors; MaskRCNN.sgd_step documents the arithmetic and the keyword arguments) on three flat
+    float32 device arenas p / g / v: tensor t is floats [offsets[t], offsets[t] + sizes[t]) (offset % 4 == 0), is_bias[t] puts it in the
+    bias group.  p and v are updated in place.  Returns (norms, coefs): float32 arrays [ntensors], N and k of every tensor (0 and 1
+    unless clip=("norm", ...))."""
+    import numpy as np
+    for t in (p, g, v):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 1 and t.numel() == p.numel()
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = np.ascontiguousarray(sizes, dtype=np.uint64)
+    bias = np.ascontiguousarray(is_bias, dtype=np.uint8)
+    assert off.shape == n.shape == bias.shape and off.ndim == 1
+    if len(off) and int((off + n).max()) > p.numel():
+        raise ValueError("sgd_step_tensors: a tensor ends beyond the arena")
+    o = _lib.sgd_opts(lr, momentum, weight_decay, grad_scale, nesterov, bias_lr_factor, weight_decay_bias, clip)
+    norms, coefs = np.empty(len(off), np.float32), np.empty(len(off), np.float32)
+    torch.cuda.synchronize()       # the arenas were written on torch's stream
+    check(lib().amp_sgd_step_tensors(ctx.handle, ptr(p), ptr(g), ptr(v), ptr(off), ptr(n), ptr(bias), len(off), C.byref(o), ptr(norms), ptr(coefs)),
+          "amp_sgd_step_tensors")
+    return norms, coefs
+
+
 def box_candidates(ctx, pred, proposals, prop_count, K, score_thresh, img_h, img_w, weights=(10., 10., 5., 5.), ccap=8192):
     B, Rcap, _ = proposals.shape
     dev = pred.device

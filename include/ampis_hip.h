@@ -237,6 +237,30 @@ int amp_colsum_finish(amp_ctx* ctx, const float* partial, int parts, int N, floa
 int amp_deconv_grad_transpose(amp_ctx* ctx, const float* in, float* out, int Cin, int T, int C2, int accumulate);
 /* torch.optim.SGD: g' = grad_scale*g + wd*p; v = mu*v + g'; p -= lr*v */
 int amp_sgd_update(amp_ctx* ctx, float* p, const float* g, float* v, size_t n, float lr, float momentum, float weight_decay, float grad_scale);
+/* The general step: what detectron2's build_optimizer adds to torch.optim.SGD (SOLVER.NESTEROV, BIAS_LR_FACTOR, WEIGHT_DECAY_BIAS,
+ * CLIP_GRADIENTS).  Per element, every operation rounded on its own:
+ *   gs = g * grad_scale
+ *   gc = gs | min(max(gs, -c), c) (AMP_CLIP_VALUE) | gs * k (AMP_CLIP_NORM, per tensor: N = ||gs||_norm_type accumulated in fp64 and
+ *        narrowed to fp32, k = min(c / (N + 1e-6), 1) in fp32 -- torch.nn.utils.clip_grad_norm_ on that tensor alone)
+ *   g' = gc + wd_t * p;  v = mu * v + g';  u = nesterov ? g' + mu * v : v;  p -= lr_t * u
+ * lr_t = lr * bias_lr_factor and wd_t = weight_decay_bias for bias tensors, lr and weight_decay for the others. */
+enum { AMP_CLIP_NONE = 0, AMP_CLIP_VALUE = 1, AMP_CLIP_NORM = 2 };
+typedef struct amp_sgd_opts {
+    float lr, momentum, weight_decay, grad_scale;
+    int nesterov;
+    float bias_lr_factor, weight_decay_bias;
+    int clip_type;
+    float clip_value;
+    float norm_type;                 /* 1, 2 or INFINITY (AMP_CLIP_NORM only) */
+} amp_sgd_opts;
+/* lr 0, momentum 0.9, weight_decay = weight_decay_bias = 1e-4, grad_scale 1, bias_lr_factor 1, no Nesterov, AMP_CLIP_NONE (clip_value 1, norm_type 2) */
+int amp_sgd_opts_default(amp_sgd_opts* opts);
+/* The step on a caller's arenas (device) and tensor table (host: offset in floats, a multiple of 4; n >= 1 floats; is_bias), so that the
+ * stage can be tested without a model.  norms_h / coefs_h (host, [ntensors], or NULL): N and k of every tensor (0 and 1 without
+ * AMP_CLIP_NORM).  Synchronises.  Refuses (AMP_ERR_ARG, naming the field) a norm_type other than 1, 2, INFINITY, clip_value <= 0 and
+ * non-finite scalars. */
+int amp_sgd_step_tensors(amp_ctx* ctx, float* p, const float* g, float* v, const unsigned long long* off_h, const unsigned long long* n_h,
+                         const unsigned char* is_bias_h, int ntensors, const amp_sgd_opts* opts, float* norms_h, float* coefs_h);
 
 
 /* Stage a8 / a9 / a10: memory-bound NHWC helpers --------------------------------------------- */
@@ -443,7 +467,7 @@ typedef struct amp_model_cfg {
     float roi_iou;                   /* MODEL.ROI_HEADS.IOU_THRESHOLDS (0.5): one threshold */
     int max_gt;                      /* capacity: ground-truth instances per batch */
     int max_poly_doubles;            /* capacity: polygon coordinates (doubles) per batch */
-    /* backbone variant (inference; training a grouped backbone is not built): MODEL.RESNETS.{DEPTH, NUM_GROUPS, WIDTH_PER_GROUP,
+    /* backbone variant (both train): MODEL.RESNETS.{DEPTH, NUM_GROUPS, WIDTH_PER_GROUP,
      * STRIDE_IN_1X1}.  R50-FPN = 50/1/64/1 (default, also when resnet_depth == 0); X101-32x8d-FPN = 101/32/8/0. */
     int resnet_depth, num_groups, width_per_group, stride_in_1x1;
 } amp_model_cfg;
@@ -513,6 +537,15 @@ int  amp_model_grad_arena(amp_model* m, float** grads_dev, size_t* nfloats);
 int  amp_model_momentum_arena(amp_model* m, float** vel_dev, size_t* nfloats);
 /* torch.optim.SGD step on every trainable tensor: g' = grad_scale*g + wd*p; v = mu*v + g'; p -= lr*v */
 int  amp_model_sgd_step(amp_model* m, float lr, float momentum, float weight_decay, float grad_scale);
+/* The general step (amp_sgd_opts above) on every trainable tensor; a tensor is an entry of detectron2's state_dict (the two halves of a
+ * fused predictor clip separately) and a bias is a name ending in ".bias".  Options that ask for nothing beyond amp_model_sgd_step --
+ * AMP_CLIP_NONE, no Nesterov, bias_lr_factor == 1, weight_decay_bias == weight_decay -- run amp_model_sgd_step's own kernel: the same
+ * bits at the same cost.  Otherwise three launches (gradient statistics with AMP_CLIP_NORM only, the per-tensor table, the update), no
+ * host round trip, bitwise reproducible.  With a communicator it runs after the exchange, on the summed gradients times grad_scale. */
+int  amp_model_sgd_step_ex(amp_model* m, const amp_sgd_opts* opts);
+/* N and k of the last amp_model_sgd_step_ex with AMP_CLIP_NORM, one per trainable tensor in amp_model_tensor_name order (host arrays of
+ * capacity cap; synchronises).  Both arrays NULL: only *n_out, the number of trainable tensors. */
+int  amp_model_clip_stats(amp_model* m, float* norms_h, float* coefs_h, int cap, int* n_out);
 /* Current value (kind 0) / gradient (1) / SGD momentum (2) of one tensor, converted back to the torch layout of detectron2's
  * state_dict entry `name` (host). */
 int  amp_model_get_tensor(amp_model* m, const char* name, int kind, float* out_h, size_t capacity_floats);
