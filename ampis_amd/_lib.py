@@ -20,7 +20,24 @@ class ConvDesc(C.Structure):
 
 class RpnLevels(C.Structure):
     _fields_ = [("nlevels", C.c_int), ("A", C.c_int), ("ld", C.c_int), ("pred", C.c_void_p * 5),
-                ("h", C.c_int * 5), ("w", C.c_int * 5), ("stride", C.c_int * 5), ("anchor_size", C.c_int * 5)]
+                ("h", C.c_int * 5), ("w", C.c_int * 5), ("stride", C.c_int * 5), ("anchor_size", C.c_int * 5),
+                ("n_sizes", C.c_int * 5), ("n_ratios", C.c_int * 5), ("sizes", (C.c_double * 9) * 5), ("ratios", (C.c_double * 9) * 5)]
+
+
+class AnchorCfg(C.Structure):
+    """amp_anchor_cfg: MODEL.ANCHOR_GENERATOR.{SIZES, ASPECT_RATIOS} of p2..p6; all zero = the default anchors."""
+    _fields_ = [("n_sizes", C.c_int * 5), ("n_ratios", C.c_int * 5), ("sizes", (C.c_double * 9) * 5), ("ratios", (C.c_double * 9) * 5)]
+
+
+def fill_anchors(st, sizes, ratios):
+    """Write per-level size / ratio lists (5 lists each) into an RpnLevels or AnchorCfg."""
+    for l in range(5):
+        st.n_sizes[l], st.n_ratios[l] = len(sizes[l]), len(ratios[l])
+        for i, v in enumerate(sizes[l]):
+            st.sizes[l][i] = float(v)
+        for i, v in enumerate(ratios[l]):
+            st.ratios[l][i] = float(v)
+    return st
 
 
 class FpnFeats(C.Structure):
@@ -190,6 +207,9 @@ def _declare(L):
         "amp_rle_from_polygon": ([vp, i, i, i, vp, i, C.POINTER(i)], i),
         "amp_model_cfg_default": ([C.POINTER(ModelCfg)], i),
         "amp_model_create": ([vp, C.POINTER(ModelCfg), C.POINTER(vp)], i),
+        "amp_model_create_anchors": ([vp, C.POINTER(ModelCfg), C.POINTER(AnchorCfg), C.POINTER(vp)], i),
+        "amp_cell_anchors": ([C.POINTER(RpnLevels), i, vp, i, C.POINTER(i)], i),
+        "amp_rpn_head_fused_ld": ([vp, vp, i, i, i, vp, vp, vp, vp, i, vp], i),
         "amp_model_destroy": ([vp], None),
         "amp_model_workspace_bytes": ([vp], C.c_size_t),
         "amp_model_num_tensors": ([vp], i),

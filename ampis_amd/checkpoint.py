@@ -101,12 +101,12 @@ def frozen_bn_defaults(name, shape):
     return np.zeros(shape, np.float32)
 
 
-def load_checkpoint(path, num_classes, arch="R50", init=None, strict=False, seed=0, with_report=False):
+def load_checkpoint(path, num_classes, arch="R50", init=None, strict=False, seed=0, with_report=False, num_anchors=P.NUM_ANCHORS):
     """-> OrderedDict name -> ndarray for amp_model_load_tensor (and the LoadReport when with_report).  See the module docstring."""
     state, source, renamed = read_state(path)
-    want = P.param_shapes(num_classes, arch)
+    want = P.param_shapes(num_classes, arch, num_anchors)
     if init is None:
-        init = P.init_params(num_classes, seed=seed, style="d2", arch=arch)
+        init = P.init_params(num_classes, seed=seed, style="d2", arch=arch, num_anchors=num_anchors)
     # caffe2 names carry no module prefix: match by suffix, as detectron2's align_and_update_state_dicts does (longest suffix wins)
     if source in ("caffe2", "d2-suffix"):
         by_suffix = {}

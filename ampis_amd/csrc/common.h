@@ -4,6 +4,7 @@
 #ifdef __HIPCC__
 #include <hip/hip_ext.h>      // hipExtLaunchKernelGGL (AMP_TIMED_LAUNCH); not a header for the host-only sanitizer build (tests/test_sanitize.py)
 #endif
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <algorithm>
@@ -167,13 +168,38 @@ struct PredictFuse {              // the mask head's tail fused into the deconv'
     float* prob;                  // [N][28][28]
 };
 struct RpnFuse {                  // the RPN head's 1x1 predictors fused into the 3x3 conv's epilogue (conv.hip conv_epilogue_rpn)
-    const float* w_split;         // [16][256] objectness + anchor-delta rows (+ a zero row) in the split row format
-    const float* bias;            // [16]
-    float* pred;                  // [M][16]
+    const float* w_split;         // [ld][256] objectness + anchor-delta rows (+ zero rows) in the split row format
+    const float* bias;            // [ld]
+    float* pred;                  // [M][ld]
+    int ld = 16;                  // predictor rows: 16, 32 or 48 (amp::rpn_ld)
 };
+// Predictor row layout of the RPN head for A anchors per location: A logits, 4 A deltas, zero rows up to a multiple of 16
+inline int rpn_ld(int A) { return 16 * ((5 * A + 15) / 16); }
+constexpr int RPN_MAX_A = 9;      // anchors per location (ld <= 48)
+// Cell anchors of pyramid level l (detectron2 DefaultAnchorGenerator.generate_cell_anchors, offset 0): for size in sizes, for ratio in ratios,
+// python-float math, stored fp32.  The lists of amp_rpn_levels when n_sizes[l] > 0, otherwise anchor_size[l] x (0.5, 1, 2).  Returns A of the
+// level (0: more than RPN_MAX_A, or a list longer than the struct holds).
+inline int cell_anchors(const amp_rpn_levels* lv, int l, float cell[RPN_MAX_A][4]) {
+    static const double def_ratios[3] = {0.5, 1.0, 2.0};
+    const bool custom = lv->n_sizes[l] > 0;
+    const int ns = custom ? lv->n_sizes[l] : 1, nr = custom ? lv->n_ratios[l] : 3;
+    if (ns < 1 || nr < 1 || ns > RPN_MAX_A || nr > RPN_MAX_A || ns * nr > RPN_MAX_A) return 0;
+    int a = 0;
+    for (int s = 0; s < ns; ++s)
+        for (int r = 0; r < nr; ++r, ++a) {
+            const double size = custom ? lv->sizes[l][s] : (double)lv->anchor_size[l];
+            const double ratio = custom ? lv->ratios[l][r] : def_ratios[r];
+            const double area = size * size;
+            const double w = sqrt(area / ratio), h = ratio * w;
+            cell[a][0] = (float)(-w / 2.0); cell[a][1] = (float)(-h / 2.0);
+            cell[a][2] = (float)(w / 2.0);  cell[a][3] = (float)(h / 2.0);
+        }
+    return a;
+}
 // rpn_sparse.hip: the RPN head's backward pass over the sampled anchors' pixels only (every other entry of the predictor gradients is an exact zero)
 struct RpnSparseArgs {
-    int B, batch, ld, K, C;                    // images, RPN.BATCH_SIZE_PER_IMAGE, predictor row length (16) and real rows, hidden channels (256)
+    int B, batch, ld, K, C;                    // images, RPN.BATCH_SIZE_PER_IMAGE, predictor row length (16 / 32 / 48) and real rows (5 A), hidden channels (256)
+    int A;                                     // anchors per location
     int fh[5], fw[5];
     const int* sampled;                        // [B][batch] sampled anchor indices (amp_rpn_sample_loss)
     const int* counts;                         // [B][2] positives, negatives
@@ -190,12 +216,13 @@ struct RpnSparseArgs {
     float* gw_pred; float* gb_pred; float* gw_conv; float* gb_conv;      // gradients (written, not accumulated)
     float* dfeat[5];                           // gradient maps of the FPN features (accumulated in place)
     unsigned int* rows; int* nrows;            // workspace: [B * batch], [B]
-    float* dpred_rows; float* act_rows; float* dt_rows;                  // [B * batch][16], [..][C], [..][C]
+    float* dpred_rows; float* act_rows; float* dt_rows;                  // [B * batch][ld], [..][C], [..][C]
     float* xg; float* G; float* wt;            // [B * batch][9 C], [G_floats], [9 C][C]
     size_t G_floats;                           // >= max(B * batch * 9 C, RPN_SPARSE_SUMS_FLOATS): G holds the head sums' partials first
     float* wg_scratch; size_t wg_scratch_floats;
 };
-constexpr size_t RPN_SPARSE_SUMS_FLOATS = (size_t)18 * 32 * 256;      // partial sums of rpn_head_sums_kernel: 18 sums x 32 row slices x 256
+constexpr size_t rpn_sparse_sums_floats(int ld) { return (size_t)(ld + 2) * 32 * 256; }      // partial sums of rpn_head_sums_kernel: ld + 2 sums x 32 row slices x 256
+constexpr size_t RPN_SPARSE_SUMS_FLOATS = rpn_sparse_sums_floats(16);
 int rpn_sparse_backward(amp_ctx* ctx, const RpnSparseArgs& a);
 int conv_run(amp_ctx* ctx, const amp_conv_desc* d, int groups, const float* x, const float* w, const float* w_split, int force_f32,
              const float* scale, const float* shift, const float* res, const float* mask, float* y, int in_shift = 0, int fmt = 0,

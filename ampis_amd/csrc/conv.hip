@@ -56,7 +56,7 @@ struct ConvArgs {
     // second f16x3 product in the epilogue (conv_epilogue_rpn); the 256-channel hidden tensor is never written
     const float* rpn_w;     // [16][Cout] split rows
     const float* rpn_b;     // [16]
-    float* rpn_pred;        // [M][16]
+    float* rpn_pred;        // [M][16 NBP], NBP = 1, 2, 3 blocks of 16 predictor rows (the epilogue's template argument; amp::rpn_ld)
     float* prob;            // [B][2Ho][2Wo] mask probabilities
     int res_split;          // 1: res is in that format too (decoded in the epilogue: hi + lo' * 2^-11, exact in fp32)
     int mask_split;         // 1: the ReLU mask tensor (training: the forward activation) is in that format (AMP_FMT_MASK_SPLIT)
@@ -1228,13 +1228,15 @@ __device__ __forceinline__ void conv_epilogue_predict(const ConvArgs& a, f32x4 (
 // N-waves' partial sums added through LDS in wave order, + bias -> pred [M][16].  Same operands as the separate 1x1 launch read from the
 // stored hidden tensor (the halves are identical), another summation order.  Replaces a 537 MB write + read at p2 and a launch per level.
 // row_of(i, r): the GEMM row (pixel) of row r (0..15) of the wave tile's 16-row block i, or a.M (or more) for a row outside the image
-template <class RowOf>
+// NBP blocks of 16 predictor rows (A <= 3, 6, 9 anchors per location): lane l15 of block j owns predictor row 16 j + l15; per block the same three MFMAs per
+// 32-channel group and the same wave-order reduction, the 32 KB reduction buffer re-used behind a barrier, the block's weight fragments loaded inside the
+// loop (16 registers, not 16 NBP).  NBP = 1 is the 16-row head as it always was.
+template <int NBP, class RowOf>
 __device__ __forceinline__ void conv_epilogue_rpn_rows(const ConvArgs& a, f32x4 (&acc)[4][4], float* lds, int wave, int lane, int n0, RowOf row_of) {
     const int wm = wave >> 2, wn = wave & 3;
     const int l15 = lane & 15, lq = lane >> 4;
     const int nw0 = n0 + wn * 64;
     f32x2 sc[2][4], sh[2][4];
-    f16x8 wh[2], wl[2];
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
         const int n = nw0 + 32 * g + 8 * lq;
@@ -1243,64 +1245,74 @@ __device__ __forceinline__ void conv_epilogue_rpn_rows(const ConvArgs& a, f32x4 
             sc[g][p] = a.scale ? f32x2{a.scale[n + 2 * p], a.scale[n + 2 * p + 1]} : f32x2{1.f, 1.f};
             sh[g][p] = a.shift ? f32x2{a.shift[n + 2 * p], a.shift[n + 2 * p + 1]} : f32x2{0.f, 0.f};
         }
-        const char* wb = reinterpret_cast<const char*>(a.rpn_w + (size_t)l15 * a.Cout) + (size_t)(n >> 5) * 128 + (size_t)(n & 31) * 2;
-        wh[g] = *reinterpret_cast<const f16x8*>(wb);
-        wl[g] = *reinterpret_cast<const f16x8*>(wb + 64);
     }
     f32x4* red = reinterpret_cast<f32x4*>(lds);                     // [wm][wn][i][lane]
-    f32x2 chk = {0.f, 0.f};
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        f32x4 d = {0.f, 0.f, 0.f, 0.f}, dx = {0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < NBP; ++j) {
+        if (j > 0) __syncthreads();                                 // the previous block's sums have been read
+        f16x8 wh[2], wl[2];
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
-            f16x8 hi, lo;
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                const f32x4& blk = acc[i][2 * g + (p >> 1)];
-                const f32x2 v = {blk[2 * (p & 1)], blk[2 * (p & 1) + 1]};
-                chk = __builtin_elementwise_fma(v, f32x2{0.f, 0.f}, chk);
-                f32x2 o = v * sc[g][p] + sh[g][p];
-                o[0] = fmaxf(o[0], 0.f); o[1] = fmaxf(o[1], 0.f);
-                const f16x2 h = __builtin_convertvector(o, f16x2);
-                const f32x2 hf = {(float)h[0], (float)h[1]};
-                const f32x2 l = __builtin_elementwise_fma(hf, f32x2{-LO_SCALE, -LO_SCALE}, o * LO_SCALE);
-                const f16x2 lh = __builtin_convertvector(l, f16x2);
-                hi[2 * p] = h[0]; hi[2 * p + 1] = h[1];
-                lo[2 * p] = lh[0]; lo[2 * p + 1] = lh[1];
-            }
-            dx = __builtin_amdgcn_mfma_f32_16x16x32_f16(lo, wh[g], dx, 0, 0, 0);
-            dx = __builtin_amdgcn_mfma_f32_16x16x32_f16(hi, wl[g], dx, 0, 0, 0);
-            d = __builtin_amdgcn_mfma_f32_16x16x32_f16(hi, wh[g], d, 0, 0, 0);
+            const int n = nw0 + 32 * g + 8 * lq;
+            const char* wb = reinterpret_cast<const char*>(a.rpn_w + (size_t)(16 * j + l15) * a.Cout) + (size_t)(n >> 5) * 128 + (size_t)(n & 31) * 2;
+            wh[g] = *reinterpret_cast<const f16x8*>(wb);
+            wl[g] = *reinterpret_cast<const f16x8*>(wb + 64);
         }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) d[e] = __fadd_rn(d[e], __fmul_rn(dx[e], 1.0f / LO_SCALE));
-        red[((wm * 4 + wn) * 4 + i) * 64 + lane] = d;
-    }
-    if (!(chk[0] == 0.f) || !(chk[1] == 0.f)) atomicOr(a.range_flag, 1);
-    __syncthreads();
-    if (wn == 0) {                                                  // lane = (output l15, pixels 4 lq .. 4 lq + 3 of block i)
-        const float bias = a.rpn_b[l15];
+        f32x2 chk = {0.f, 0.f};
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            f32x4 s = red[((wm * 4 + 0) * 4 + i) * 64 + lane];
+            f32x4 d = {0.f, 0.f, 0.f, 0.f}, dx = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int w = 1; w < 4; ++w) {
-                const f32x4 t = red[((wm * 4 + w) * 4 + i) * 64 + lane];
+            for (int g = 0; g < 2; ++g) {
+                f16x8 hi, lo;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) s[e] = __fadd_rn(s[e], t[e]);
+                for (int p = 0; p < 4; ++p) {
+                    const f32x4& blk = acc[i][2 * g + (p >> 1)];
+                    const f32x2 v = {blk[2 * (p & 1)], blk[2 * (p & 1) + 1]};
+                    if (j == 0) chk = __builtin_elementwise_fma(v, f32x2{0.f, 0.f}, chk);
+                    f32x2 o = v * sc[g][p] + sh[g][p];
+                    o[0] = fmaxf(o[0], 0.f); o[1] = fmaxf(o[1], 0.f);
+                    const f16x2 h = __builtin_convertvector(o, f16x2);
+                    const f32x2 hf = {(float)h[0], (float)h[1]};
+                    const f32x2 l = __builtin_elementwise_fma(hf, f32x2{-LO_SCALE, -LO_SCALE}, o * LO_SCALE);
+                    const f16x2 lh = __builtin_convertvector(l, f16x2);
+                    hi[2 * p] = h[0]; hi[2 * p + 1] = h[1];
+                    lo[2 * p] = lh[0]; lo[2 * p + 1] = lh[1];
+                }
+                dx = __builtin_amdgcn_mfma_f32_16x16x32_f16(lo, wh[g], dx, 0, 0, 0);
+                dx = __builtin_amdgcn_mfma_f32_16x16x32_f16(hi, wl[g], dx, 0, 0, 0);
+                d = __builtin_amdgcn_mfma_f32_16x16x32_f16(hi, wh[g], d, 0, 0, 0);
             }
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int m = row_of(i, 4 * lq + e);
-                if (m < a.M) a.rpn_pred[(size_t)m * 16 + l15] = __fadd_rn(s[e], bias);
+            for (int e = 0; e < 4; ++e) d[e] = __fadd_rn(d[e], __fmul_rn(dx[e], 1.0f / LO_SCALE));
+            red[((wm * 4 + wn) * 4 + i) * 64 + lane] = d;
+        }
+        if (j == 0) { if (!(chk[0] == 0.f) || !(chk[1] == 0.f)) atomicOr(a.range_flag, 1); }
+        __syncthreads();
+        if (wn == 0) {                                              // lane = (output 16 j + l15, pixels 4 lq .. 4 lq + 3 of block i)
+            const float bias = a.rpn_b[16 * j + l15];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                f32x4 s = red[((wm * 4 + 0) * 4 + i) * 64 + lane];
+#pragma unroll
+                for (int w = 1; w < 4; ++w) {
+                    const f32x4 t = red[((wm * 4 + w) * 4 + i) * 64 + lane];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) s[e] = __fadd_rn(s[e], t[e]);
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int m = row_of(i, 4 * lq + e);
+                    if (m < a.M) a.rpn_pred[(size_t)m * (16 * NBP) + 16 * j + l15] = __fadd_rn(s[e], bias);
+                }
             }
         }
     }
 }
+template <int NBP>
 __device__ __forceinline__ void conv_epilogue_rpn(const ConvArgs& a, f32x4 (&acc)[4][4], float* lds, int wave, int lane, int m0, int n0) {
     const int mw0 = m0 + (wave >> 2) * 64;
-    conv_epilogue_rpn_rows(a, acc, lds, wave, lane, n0, [mw0](int i, int r) { return mw0 + i * 16 + r; });
+    conv_epilogue_rpn_rows<NBP>(a, acc, lds, wave, lane, n0, [mw0](int i, int r) { return mw0 + i * 16 + r; });
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1327,7 +1339,8 @@ __device__ unsigned long long g_stamp_clk[2];
 #define STAMP_T(var)
 #define STAMP_ADD(slot, t0, t1)
 #endif
-template <int BM, int BN, int EPI, int NSTAGE = 3, bool CHAN = false>
+// NBP (EPI 3, the fused RPN tail only): blocks of 16 predictor rows -- 1, 2 or 3 (conv_epilogue_rpn_rows)
+template <int BM, int BN, int EPI, int NSTAGE = 3, bool CHAN = false, int NBP = 1>
 __global__ __launch_bounds__((BM / 64) * (BN / 64) * 64, NSTAGE == 2 ? 2 : 1) void conv_split_kernel(const ConvArgs a, const unsigned int x_bytes,
                                                                                                      const unsigned int w_bytes) {
     constexpr int WTM = 64, WTN = 64;
@@ -1450,7 +1463,7 @@ __global__ __launch_bounds__((BM / 64) * (BN / 64) * 64, NSTAGE == 2 ? 2 : 1) vo
     // wait for must not delay the staging; younger loads in the queue only make the ring's counted vmcnt waits stricter, never looser)
     PredictPrefetch ppf;
     if constexpr (BM == 128 && BN == 256 && EPI == 3) {
-        if (a.out_mode == 3) ppf = predict_prefetch(a, wave, lane, m0);
+        if (NBP == 1 && a.out_mode == 3) ppf = predict_prefetch(a, wave, lane, m0);
     }
     int cur = 0, nxt = 2;                      // ring positions of the tile being computed / staged
     auto open_step = [&](int step) {
@@ -1564,8 +1577,8 @@ __global__ __launch_bounds__((BM / 64) * (BN / 64) * 64, NSTAGE == 2 ? 2 : 1) vo
                 if (scaled_in) acc[i][j][e] *= a.out_scale;      // x arrived as split rows of x * 2^shift (a scaled loss gradient): exact power of two
             }
     if constexpr (BM == 128 && BN == 256 && EPI == 3) {          // the fused tails have an instantiation of their own: no row epilogue, no spills
-        if (a.out_mode == 3) conv_epilogue_predict(a, acc, lds, wave, lane, m0, n0, ppf);
-        else conv_epilogue_rpn(a, acc, lds, wave, lane, m0, n0);
+        if (NBP == 1 && a.out_mode == 3) conv_epilogue_predict(a, acc, lds, wave, lane, m0, n0, ppf);
+        else conv_epilogue_rpn<NBP>(a, acc, lds, wave, lane, m0, n0);
         return;
     }
     if (a.y_split && (!a.mask || a.mask_split) && (a.out_mode == 0 || (EPI == 2 && a.out_mode == 1 && !a.mask && a.res_mode == 0)) && (a.res_mode == 0 || a.res_split) && a.direct_epi)
@@ -1947,7 +1960,7 @@ __global__ __launch_bounds__(512, 1) void conv1x1_nloop_kernel(const ConvArgs a,
 // behind the step's weight requests; the counted vmcnt in front of a step allows for them).
 // Same exact products as every AMP_CONV_F16X3 kernel, summed in conv_split_kernel<.., CHAN = true>'s order (bit-identical to it: AMP_KORDER=1).
 // ------------------------------------------------------------------------------------------------------------------
-template <int EPI>      // 1: split rows through conv_epilogue_direct_rows; 3: the fused RPN tail (conv_epilogue_rpn_rows)
+template <int EPI>      // 1: split rows through conv_epilogue_direct_rows; 3 / 4 / 5: the fused RPN tail with 16 / 32 / 48 predictor rows (conv_epilogue_rpn_rows)
 __global__ __launch_bounds__(512, 1) void conv3x3_patch_kernel(const ConvArgs a, const unsigned int x_bytes, const unsigned int w_bytes, const int tiles_x, const int tiles_y) {
     constexpr int TH = 8, TW = 16, PW = TW + 2, NPIX = (TH + 2) * PW;            // 180 patch pixels
     constexpr int NPIECE = 24;                                                      // DMA pieces of 8 rows x 128 B: 3 per wave (the last 12 rows are zero-filled padding: every wave issues the same number of requests)
@@ -2151,9 +2164,9 @@ __global__ __launch_bounds__(512, 1) void conv3x3_patch_kernel(const ConvArgs a,
                 if (scaled_in) acc[i][j][e] *= a.out_scale;
             }
     const int oyw = oy0 + 4 * wm;
-    if constexpr (EPI == 3) {
+    if constexpr (EPI >= 3) {
         const int Ho = a.Ho, Wo = a.Wo, M = a.M;
-        conv_epilogue_rpn_rows(a, acc, lds, wave, lane, n0, [=](int i, int r) {
+        conv_epilogue_rpn_rows<EPI - 2>(a, acc, lds, wave, lane, n0, [=](int i, int r) {
             const int oy = oyw + i, ox = ox0 + r;
             return (oy < Ho && ox < Wo) ? (b * Ho + oy) * Wo + ox : M;
         });
@@ -2931,6 +2944,8 @@ void launch_split(const ConvArgs& a, int epi, hipStream_t st, unsigned int xb, u
             return;
         }
         if (epi == 3) { AMP_TIMED_LAUNCH((conv_split_kernel<128, 256, 3>), dim3(a.nblk), dim3(NT_), 0, st, a, xb, wb); return; }
+        if (epi == 4) { AMP_TIMED_LAUNCH((conv_split_kernel<128, 256, 3, 3, false, 2>), dim3(a.nblk), dim3(NT_), 0, st, a, xb, wb); return; }      // the RPN tail with 32 ...
+        if (epi == 5) { AMP_TIMED_LAUNCH((conv_split_kernel<128, 256, 3, 3, false, 3>), dim3(a.nblk), dim3(NT_), 0, st, a, xb, wb); return; }      // ... and 48 predictor rows
     }
     if (epi == 2) AMP_TIMED_LAUNCH((conv_split_kernel<BM, BN, 2>), dim3(a.nblk), dim3(NT_), 0, st, a, xb, wb);
     else AMP_TIMED_LAUNCH((conv_split_kernel<BM, BN, 1>), dim3(a.nblk), dim3(NT_), 0, st, a, xb, wb);
@@ -3125,15 +3140,21 @@ extern "C" int amp_conv2d_nhwc_fmt(amp_ctx* ctx, const amp_conv_desc* d, const f
 // The predictor rows are split here per call (the model keeps its own split copy); B*H*W >= 24576 so that the 128 x 256 tiles fill the chip.
 extern "C" int amp_rpn_head_fused(amp_ctx* ctx, const float* x_split, int B, int H, int W, const float* w_conv, const float* b_conv, const float* w_pred,
                                   const float* b_pred, float* pred) {
+    return amp_rpn_head_fused_ld(ctx, x_split, B, H, W, w_conv, b_conv, w_pred, b_pred, 16, pred);
+}
+// ... with ld = 16, 32 or 48 predictor rows (A logits, 4 A deltas, zero rows): w_pred [ld][256], b_pred [ld] -> pred [B*H*W][ld]
+extern "C" int amp_rpn_head_fused_ld(amp_ctx* ctx, const float* x_split, int B, int H, int W, const float* w_conv, const float* b_conv, const float* w_pred,
+                                     const float* b_pred, int ld, float* pred) {
     AMP_REQUIRE(ctx && x_split && w_conv && b_conv && w_pred && b_pred && pred && B > 0 && H > 0 && W > 0, "amp_rpn_head_fused: bad argument");
+    AMP_REQUIRE(ld == 16 || ld == 32 || ld == 48, "amp_rpn_head_fused: ld = %d, must be 16, 32 or 48", ld);
     AMP_REQUIRE(ctx->conv_mode == AMP_CONV_F16X3, "amp_rpn_head_fused: AMP_CONV_F16X3 only (the fp32 path runs the two convolutions)");
     AMP_REQUIRE((long long)B * H * W >= 24576, "amp_rpn_head_fused: fewer than 24576 pixels: run the two convolutions (amp_conv2d_nhwc_fmt)");
     float* wps = nullptr;
-    AMP_HIP_CHECK(hipMalloc(&wps, 16 * 256 * sizeof(float)));
-    hipLaunchKernelGGL(split_weights_kernel, dim3(8), dim3(256), 0, ctx->stream, w_pred, (size_t)16, 256, reinterpret_cast<unsigned int*>(wps));
+    AMP_HIP_CHECK(hipMalloc(&wps, (size_t)ld * 256 * sizeof(float)));
+    hipLaunchKernelGGL(split_weights_kernel, dim3(8), dim3(256), 0, ctx->stream, w_pred, (size_t)ld, 256, reinterpret_cast<unsigned int*>(wps));
     amp_conv_desc d;
     d.B = B; d.H = H; d.W = W; d.Cin = 256; d.Cout = 256; d.KH = 3; d.KW = 3; d.stride = 1; d.pad = 1; d.relu = 1; d.res_mode = 0; d.out_mode = 0;
-    amp::RpnFuse rf{wps, b_pred, pred};
+    amp::RpnFuse rf{wps, b_pred, pred, ld};
     const int st = amp::conv_run(ctx, &d, 1, x_split, w_conv, nullptr, 0, nullptr, b_conv, nullptr, nullptr, pred, 0, 1, nullptr, &rf);
     (void)hipStreamSynchronize(ctx->stream);
     (void)hipFree(wps);
@@ -3575,17 +3596,20 @@ int amp::conv_run(amp_ctx* ctx, const amp_conv_desc* d, int groups, const float*
         a.pred_w = fuse->pred_w; a.pred_b = fuse->pred_b; a.pred_cls = fuse->cls; a.pred_K = fuse->K; a.prob = fuse->prob;
     }
     a.rpn_w = a.rpn_b = nullptr; a.rpn_pred = nullptr;
+    int rpn_nbp = 1;
     if (rpn) {      // the RPN head's predictors in the 3x3 conv's epilogue (conv_epilogue_rpn): one 128 x 256 tile = all hidden channels of 128 pixels
         AMP_REQUIRE(!fuse && x_is_split && d->out_mode == 0 && a.Cout == 256 && a.relu && !res && !mask && g_split_ring && in_shift == 0,
                     "conv: the fused RPN epilogue needs a split input, Cout = 256, ReLU and the ring kernel");
         AMP_REQUIRE(rpn->w_split && rpn->bias && rpn->pred, "conv: incomplete RpnFuse");
+        AMP_REQUIRE(rpn->ld == 16 || ((rpn->ld == 32 || rpn->ld == 48) && !a.korder), "conv: the fused RPN epilogue writes 16, 32 or 48 predictor rows (16 with AMP_KORDER), not %d", rpn->ld);
+        rpn_nbp = rpn->ld / 16;
         a.out_mode = 4;
         a.y_split = 0;
         a.rpn_w = rpn->w_split; a.rpn_b = rpn->bias; a.rpn_pred = rpn->pred;
     }
     if (rec) {      // algorithmic bytes of this launch: every operand once (amp_prof_launches; a 1x1 conv reads only the pixels its stride samples)
         const double in_rows = (a.KH == 1 && a.KW == 1) ? (double)a.M : (double)a.B * a.H * a.W;
-        const double out_vals = a.out_mode == 3 ? (double)a.M * 4.0 : a.out_mode == 4 ? (double)a.M * 16.0 : (double)a.M * a.Cout;
+        const double out_vals = a.out_mode == 3 ? (double)a.M * 4.0 : a.out_mode == 4 ? (double)a.M * 16.0 * rpn_nbp : (double)a.M * a.Cout;
         const double res_vals = !res ? 0.0 : (a.res_mode == 2 ? (double)a.M * a.Cout / 4.0 : (double)a.M * a.Cout);
         rec->bytes = 4.0 * (in_rows * a.Cin + (double)a.Cout * a.K + out_vals + res_vals + (mask ? (double)a.M * a.Cout : 0.0));
         rec->M = a.M; rec->N = a.Cout; rec->K = d->KH * d->KW * cpg;
@@ -3652,7 +3676,9 @@ int amp::conv_run(amp_ctx* ctx, const amp_conv_desc* d, int groups, const float*
             a.ntn = a.Cout / 256; a.nblk = (int)p256_tiles;
             if (rec) rec->variant = 0;
             const int tiles_x = amp::cdiv(a.Wo, 16), tiles_y = amp::cdiv(a.Ho, 8);
-            if (a.out_mode == 4) AMP_TIMED_LAUNCH(conv3x3_patch_kernel<3>, dim3(a.nblk), dim3(512), 0, ctx->stream, a, (unsigned int)x_bytes, (unsigned int)w_bytes, tiles_x, tiles_y);
+            if (a.out_mode == 4 && rpn_nbp == 3) AMP_TIMED_LAUNCH(conv3x3_patch_kernel<5>, dim3(a.nblk), dim3(512), 0, ctx->stream, a, (unsigned int)x_bytes, (unsigned int)w_bytes, tiles_x, tiles_y);
+            else if (a.out_mode == 4 && rpn_nbp == 2) AMP_TIMED_LAUNCH(conv3x3_patch_kernel<4>, dim3(a.nblk), dim3(512), 0, ctx->stream, a, (unsigned int)x_bytes, (unsigned int)w_bytes, tiles_x, tiles_y);
+            else if (a.out_mode == 4) AMP_TIMED_LAUNCH(conv3x3_patch_kernel<3>, dim3(a.nblk), dim3(512), 0, ctx->stream, a, (unsigned int)x_bytes, (unsigned int)w_bytes, tiles_x, tiles_y);
             else AMP_TIMED_LAUNCH(conv3x3_patch_kernel<1>, dim3(a.nblk), dim3(512), 0, ctx->stream, a, (unsigned int)x_bytes, (unsigned int)w_bytes, tiles_x, tiles_y);
         } else
         if (a.out_mode == 3 && g_mask_tail_loop && a.Cin % BK == 0 && !a.korder && a.Ho * a.Wo >= 128 /* a 128-pixel block spans at most two RoIs */) {     // fused mask-head tail: the four taps of a pixel block in one workgroup
@@ -3665,7 +3691,7 @@ int amp::conv_run(amp_ctx* ctx, const amp_conv_desc* d, int groups, const float*
         } else if (a.out_mode == 4) {                                        // fused RPN tail: one N tile
             a.ntn = 1; a.nblk = ntm;
             if (rec) rec->variant = 0;
-            launch_split<128, 256>(a, 3, ctx->stream, (unsigned int)x_bytes, (unsigned int)w_bytes);
+            launch_split<128, 256>(a, 2 + rpn_nbp, ctx->stream, (unsigned int)x_bytes, (unsigned int)w_bytes);
         } else if (x_is_split && g_split_ring && g_short_k && epi != 0 && !a.grouped && a.nsteps <= g_short_k_steps && res && a.res_mode == 1 && a.res_split && a.y_split && !mask &&
                    a.Cout % 128 == 0 && ntm * (a.Cout / 128) >= 1024) {
             // the trunk's conv3 + residual (K = 64 ... 256 into 4 K channels: byte-bound): 128 x 128 tiles on TWO buffers -- tile s + 2 goes into

@@ -59,6 +59,8 @@ const int kStride[4] = {1, 2, 2, 2};
 struct amp_model {
     amp_ctx* ctx = nullptr;
     amp_model_cfg cfg;
+    amp_anchor_cfg anchors;              // MODEL.ANCHOR_GENERATOR.{SIZES, ASPECT_RATIOS}; n_sizes 0 = the sizes 32 .. 512 with the ratios 0.5, 1, 2
+    int rpn_A = 3;                       // anchors per location; the predictor tensor holds A logit rows, 4 A delta rows and zero rows up to amp::rpn_ld(A)
     int nblk[4] = {3, 4, 6, 3};          // RESNETS.DEPTH 50 / 101
     int mid[4] = {64, 128, 256, 512};     // NUM_GROUPS * WIDTH_PER_GROUP * 2^stage
     // ---- parameters ----
@@ -458,10 +460,13 @@ int run_trunk(amp_model* m, const uint8_t* imgs_d, int B, int H, int W, Trunk& T
     }
 
     // ---------------- RPN head ----------------
-    const int ld_rpn = 16;   // 3 logits + 12 deltas + 1 zero pad column
+    const int rpn_A = m->rpn_A;
+    const int ld_rpn = amp::rpn_ld(rpn_A);   // A logits + 4 A deltas + zero pad columns (16 for the default 3 + 12 + 1)
     amp_rpn_levels lv;
     memset(&lv, 0, sizeof(lv));
-    lv.nlevels = 5; lv.A = 3; lv.ld = ld_rpn;
+    lv.nlevels = 5; lv.A = rpn_A; lv.ld = ld_rpn;
+    memcpy(lv.n_sizes, m->anchors.n_sizes, sizeof(lv.n_sizes)); memcpy(lv.n_ratios, m->anchors.n_ratios, sizeof(lv.n_ratios));
+    memcpy(lv.sizes, m->anchors.sizes, sizeof(lv.sizes)); memcpy(lv.ratios, m->anchors.ratios, sizeof(lv.ratios));
     const int asz[5] = {32, 64, 128, 256, 512};
     int max_n = 0;
     for (int l = 0; l < 5; ++l) {
@@ -475,13 +480,13 @@ int run_trunk(amp_model* m, const uint8_t* imgs_d, int B, int H, int W, Trunk& T
             const ConvW& rp = CONV("proposal_generator.rpn_head.pred");
             static const bool no_rpn_fuse = getenv("AMP_NO_RPN_FUSE") != nullptr;      // EXPERIMENT switch
             const long long Ml = (long long)B * fh[l] * fw[l];
-            if (native_all && (!m->saving || m->rpn_train_fused) && !m->split_stale && !no_rpn_fuse && rc.cout == 256 && rc.w_split && rp.w_split && rp.cout == 16 && rp.cin == 256 && Ml >= 24576) {
+            if (native_all && (!m->saving || m->rpn_train_fused) && !m->split_stale && !no_rpn_fuse && rc.cout == 256 && rc.w_split && rp.w_split && rp.cout == ld_rpn && rp.cin == 256 && Ml >= 24576) {
                 // inference on the native trunk -- and a training step whose backward pass takes the sparse route (it recomputes the hidden rows it needs):
                 // the predictors run in the 3x3 conv's epilogue, the hidden tensor is never written
                 fused_rpn = true;
                 amp_conv_desc d;
                 d.B = B; d.H = fh[l]; d.W = fw[l]; d.Cin = rc.cin; d.Cout = rc.cout; d.KH = rc.kh; d.KW = rc.kw; d.stride = 1; d.pad = 1; d.relu = 1; d.res_mode = 0; d.out_mode = 0;
-                amp::RpnFuse rf{rp.w_split, rp.shift, pred};
+                amp::RpnFuse rf{rp.w_split, rp.shift, pred, ld_rpn};
                 AMP_TRY(amp::conv_run(ctx, &d, 1, feat[l], rc.w, rc.w_split, 0, rc.scale, rc.shift, nullptr, nullptr, t, 0, 1, nullptr, &rf));
             } else {
                 AMP_TRY(launch_conv(m, rc, feat[l], B, fh[l], fw[l], 1, 1, true, 0, nullptr, 0, t, FMT(native_all, native_all, false)));
@@ -492,7 +497,7 @@ int run_trunk(amp_model* m, const uint8_t* imgs_d, int B, int H, int W, Trunk& T
         if (m->saving && !fused_rpn) m->rpn_t[l] = t;
         else { if (m->saving) m->rpn_t[l] = nullptr; if (!m->saving) ws.off = keep; }
         lv.pred[l] = pred; lv.h[l] = fh[l]; lv.w[l] = fw[l]; lv.stride[l] = fstride[l]; lv.anchor_size[l] = asz[l];
-        max_n = std::max(max_n, fh[l] * fw[l] * 3);
+        max_n = std::max(max_n, fh[l] * fw[l] * rpn_A);
         if (!dry) {
             const char* pn[5] = {"rpn_pred2", "rpn_pred3", "rpn_pred4", "rpn_pred5", "rpn_pred6"};
             tap(m, pn[l], pred, 0, {B, fh[l] * fw[l], ld_rpn});
@@ -892,7 +897,8 @@ int run_train(amp_model* m, const uint8_t* imgs_d, int B, int H, int W, const am
         static const bool no_rpn_train_fuse = getenv("AMP_NO_RPN_TRAIN_FUSE") != nullptr;  // EXPERIMENT switch: the head's hidden tensor saved by the forward pass
         const ConvW& cpred = CONV("proposal_generator.rpn_head.pred");
         const ConvW& cconv = CONV("proposal_generator.rpn_head.conv");
-        sr_ok = backward && (g_rpn_sparse < 0 ? !no_rpn_sparse : g_rpn_sparse != 0) && cpred.cout <= 16 && cpred.cin == 256 && cpred.scale == nullptr && c.rpn_batch <= 512 &&
+        const int T_ld = amp::rpn_ld(m->rpn_A);
+        sr_ok = backward && (g_rpn_sparse < 0 ? !no_rpn_sparse : g_rpn_sparse != 0) && cpred.cout == T_ld && cpred.cin == 256 && cpred.scale == nullptr && c.rpn_batch <= 512 &&
                 cconv.cout == 256 && cconv.cin == 256 && cconv.kh == 3 && cconv.kw == 3;
         m->rpn_train_fused = !dry && sr_ok && (g_rpn_train_fuse < 0 ? !no_rpn_train_fuse : g_rpn_train_fuse != 0) && m->ctx->conv_mode == AMP_CONV_F16X3;
     }
@@ -904,7 +910,7 @@ int run_train(amp_model* m, const uint8_t* imgs_d, int B, int H, int W, const am
     const int npoly = dry ? c.max_poly_doubles : gt->poly_off[gt->inst_poly_off ? gt->inst_poly_off[total_gt] : total_gt];
     AMP_REQUIRE(total_gt <= c.max_gt && npoly <= c.max_poly_doubles, "amp_model_forward_losses: %d instances / %d polygon doubles exceed cfg.max_gt / max_poly_doubles", total_gt, npoly);
     int A = 0;
-    for (int l = 0; l < 5; ++l) A += T.fh[l] * T.fw[l] * 3;
+    for (int l = 0; l < 5; ++l) A += T.fh[l] * T.fw[l] * m->rpn_A;
 
     AMP_ALLOC(d_gt_boxes, float, (size_t)std::max(total_gt, 1) * 4);
     AMP_ALLOC(d_gt_cls, int, (size_t)std::max(total_gt, 1));
@@ -1335,24 +1341,24 @@ int run_train(amp_model* m, const uint8_t* imgs_d, int B, int H, int W, const am
     const int SRR = B * c.rpn_batch;
     AMP_ALLOC(sr_rows, unsigned int, (size_t)SRR);
     AMP_ALLOC(sr_nrows, int, (size_t)B);
-    AMP_ALLOC(sr_dpred, float, (size_t)SRR * 16);
+    AMP_ALLOC(sr_dpred, float, (size_t)SRR * amp::rpn_ld(m->rpn_A));
     AMP_ALLOC(sr_act, float, (size_t)SRR * 256);
     AMP_ALLOC(sr_dt, float, (size_t)SRR * 256);
     AMP_ALLOC(sr_xg, float, (size_t)SRR * 2304);
-    const size_t sr_G_floats = std::max((size_t)SRR * 2304, amp::RPN_SPARSE_SUMS_FLOATS);      // G, and the head sums' partials before it
+    const size_t sr_G_floats = std::max((size_t)SRR * 2304, amp::rpn_sparse_sums_floats(amp::rpn_ld(m->rpn_A)));      // G, and the head sums' partials before it
     AMP_ALLOC(sr_G, float, sr_G_floats);
     AMP_ALLOC(sr_wt, float, (size_t)2304 * 256);
     bool SR = false;
     if (!dry) {
         const ConvW& cpred = CONV("proposal_generator.rpn_head.pred");
         const ConvW& cconv = CONV("proposal_generator.rpn_head.conv");
-        SR = sr_ok && T.lv.ld == 16;
+        SR = sr_ok && T.lv.ld == cpred.cout;
         bool rpn_fused_lvl = false;
         for (int l = 0; l < 5; ++l) rpn_fused_lvl = rpn_fused_lvl || m->rpn_t[l] == nullptr;
         AMP_REQUIRE(SR || !rpn_fused_lvl, "%s", "backward: the RPN head's hidden tensor was not saved and the sparse backward pass does not apply");
         if (SR) {
             amp::RpnSparseArgs sa;
-            sa.B = B; sa.batch = c.rpn_batch; sa.ld = T.lv.ld; sa.K = cpred.cout; sa.C = 256;
+            sa.B = B; sa.batch = c.rpn_batch; sa.ld = T.lv.ld; sa.K = cpred.cout; sa.C = 256; sa.A = T.lv.A;
             for (int l = 0; l < 5; ++l) {
                 sa.fh[l] = T.fh[l]; sa.fw[l] = T.fw[l];
                 sa.dpred[l] = d_rpn_pred[l]; sa.t[l] = m->rpn_t[l]; sa.feat[l] = T.feat[l]; sa.dfeat[l] = d_feat[l];
@@ -1673,8 +1679,26 @@ int amp_model_cfg_default(amp_model_cfg* c) {
     return AMP_OK;
 }
 
-int amp_model_create(amp_ctx* ctx, const amp_model_cfg* cfg, amp_model** out) {
+int amp_model_create(amp_ctx* ctx, const amp_model_cfg* cfg, amp_model** out) { return amp_model_create_anchors(ctx, cfg, nullptr, out); }
+
+int amp_model_create_anchors(amp_ctx* ctx, const amp_model_cfg* cfg, const amp_anchor_cfg* anchors, amp_model** out) {
     AMP_REQUIRE(ctx && cfg && out, "amp_model_create: null argument");
+    int rpn_A = 3;
+    if (anchors) {
+        bool any = false;
+        for (int l = 0; l < 5; ++l) any = any || anchors->n_sizes[l] != 0 || anchors->n_ratios[l] != 0;
+        if (any) {
+            rpn_A = anchors->n_sizes[0] * anchors->n_ratios[0];
+            for (int l = 0; l < 5; ++l) {
+                const int ns = anchors->n_sizes[l], nr = anchors->n_ratios[l];
+                AMP_REQUIRE(ns >= 1 && ns <= 9 && nr >= 1 && nr <= 9, "amp_model_create_anchors: level %d has %d sizes x %d ratios (1..9 each)", l, ns, nr);
+                AMP_REQUIRE(ns * nr == rpn_A && rpn_A <= amp::RPN_MAX_A, "amp_model_create_anchors: %d anchors per location on level %d, %d on level 0; need the same 1..%d on every level",
+                            ns * nr, l, rpn_A, amp::RPN_MAX_A);
+                for (int i = 0; i < ns; ++i) AMP_REQUIRE(std::isfinite(anchors->sizes[l][i]) && anchors->sizes[l][i] > 0.0, "amp_model_create_anchors: sizes[%d][%d] must be positive and finite", l, i);
+                for (int i = 0; i < nr; ++i) AMP_REQUIRE(std::isfinite(anchors->ratios[l][i]) && anchors->ratios[l][i] > 0.0, "amp_model_create_anchors: ratios[%d][%d] must be positive and finite", l, i);
+            }
+        } else anchors = nullptr;
+    }
     AMP_REQUIRE(cfg->num_classes >= 1 && cfg->num_classes <= 255, "amp_model_create: num_classes out of range");
     AMP_REQUIRE(cfg->pre_nms_topk >= 1 && cfg->pre_nms_topk <= 2048, "amp_model_create: pre_nms_topk must be in [1,2048]");
     AMP_REQUIRE(cfg->post_nms_topk >= 1 && cfg->detections_per_image >= 1, "amp_model_create: bad topk");
@@ -1687,6 +1711,9 @@ int amp_model_create(amp_ctx* ctx, const amp_model_cfg* cfg, amp_model** out) {
     amp_model* m = new amp_model();
     m->ctx = ctx;
     m->cfg = *cfg;
+    memset(&m->anchors, 0, sizeof(m->anchors));
+    if (anchors) m->anchors = *anchors;
+    m->rpn_A = rpn_A;
     if (m->cfg.rle_pool_counts == 0)
         m->cfg.rle_pool_counts = (size_t)m->cfg.max_batch * m->cfg.detections_per_image * 16384;
     const int K = cfg->num_classes;
@@ -1882,7 +1909,7 @@ int amp_model_load_tensor(amp_model* m, const char* name_c, const float* data, c
                prefix == "proposal_generator.rpn_head.objectness_logits" || prefix == "proposal_generator.rpn_head.anchor_deltas") {
         const bool first = prefix.find("cls_score") != std::string::npos || prefix.find("objectness") != std::string::npos;
         const bool box = prefix.find("box_predictor") != std::string::npos;
-        const size_t rows = box ? (first ? K + 1 : 4 * K) : (first ? 3 : 12);
+        const size_t rows = box ? (first ? K + 1 : 4 * K) : (first ? m->rpn_A : 4 * m->rpn_A);
         const size_t cols = box ? 1024 : 256;
         AMP_REQUIRE(numel == rows * (is_w ? cols : 1), "%s: unexpected size %zu", name_c, numel);
         m->host_raw[name].assign(data, data + numel);           // fused at finalize
@@ -2076,8 +2103,8 @@ int amp_model_finalize(amp_model* m) {
         AMP_TRY(upload(m, cw.scale, sc));
         AMP_TRY(upload(m, cw.shift, sh));
     }
-    auto fuse = [&](const char* key, const char* a, const char* b, int ra, int rb, int cols) -> int {
-        const int rp = (ra + rb + 3) / 4 * 4;   // rows padded to a multiple of 4 (zero rows): 16-byte output rows
+    auto fuse = [&](const char* key, const char* a, const char* b, int ra, int rb, int cols, int rows_padded = 0) -> int {
+        const int rp = rows_padded ? rows_padded : (ra + rb + 3) / 4 * 4;   // rows padded to a multiple of 4 (zero rows): 16-byte output rows
         std::vector<float> w((size_t)rp * cols, 0.f), bias(rp, 0.f);
         const auto& wa = m->host_raw.at(std::string(a) + ".weight");
         const auto& wb = m->host_raw.at(std::string(b) + ".weight");
@@ -2097,7 +2124,7 @@ int amp_model_finalize(amp_model* m) {
         return upload(m, cw.shift, bias);
     };
     AMP_TRY(fuse("proposal_generator.rpn_head.pred", "proposal_generator.rpn_head.objectness_logits",
-                 "proposal_generator.rpn_head.anchor_deltas", 3, 12, 256));
+                 "proposal_generator.rpn_head.anchor_deltas", m->rpn_A, 4 * m->rpn_A, 256, amp::rpn_ld(m->rpn_A)));
     AMP_TRY(fuse("roi_heads.box_predictor", "roi_heads.box_predictor.cls_score", "roi_heads.box_predictor.bbox_pred", K + 1, 4 * K, 1024));
     m->fwd_jobs_dirty = m->dgrad_jobs_dirty = true;      // eligibility (w_absmax) and the FrozenBN scale pointers are settled here
     AMP_TRY(refresh_split_weights(m));
@@ -2291,8 +2318,8 @@ static int sgd_locate(amp_model* m, const std::string& name, unsigned long long*
     bool last = false;            // the second half of a fused matrix also owns the padding rows
     if (prefix == "roi_heads.box_predictor.cls_score") { key = "roi_heads.box_predictor"; rows = K + 1; }
     else if (prefix == "roi_heads.box_predictor.bbox_pred") { key = "roi_heads.box_predictor"; row0 = K + 1; rows = 4 * K; last = true; }
-    else if (prefix == "proposal_generator.rpn_head.objectness_logits") { key = "proposal_generator.rpn_head.pred"; rows = 3; }
-    else if (prefix == "proposal_generator.rpn_head.anchor_deltas") { key = "proposal_generator.rpn_head.pred"; row0 = 3; rows = 12; last = true; }
+    else if (prefix == "proposal_generator.rpn_head.objectness_logits") { key = "proposal_generator.rpn_head.pred"; rows = m->rpn_A; }
+    else if (prefix == "proposal_generator.rpn_head.anchor_deltas") { key = "proposal_generator.rpn_head.pred"; row0 = m->rpn_A; rows = 4 * m->rpn_A; last = true; }
     else if (prefix == "roi_heads.mask_head.predictor") { rows = K; last = true; }
     auto it = m->conv.find(key);
     AMP_REQUIRE(it != m->conv.end(), "amp_model_sgd_step_ex: no stored tensor for '%s'", name.c_str());
@@ -2515,8 +2542,8 @@ static int xfer_tensor(amp_model* m, const char* name_c, int kind, float* out, s
     int row0 = 0, rows = -1;   // row slice of a fused tensor
     if (prefix == "roi_heads.box_predictor.cls_score") { key = "roi_heads.box_predictor"; row0 = 0; rows = K + 1; }
     else if (prefix == "roi_heads.box_predictor.bbox_pred") { key = "roi_heads.box_predictor"; row0 = K + 1; rows = 4 * K; }
-    else if (prefix == "proposal_generator.rpn_head.objectness_logits") { key = "proposal_generator.rpn_head.pred"; row0 = 0; rows = 3; }
-    else if (prefix == "proposal_generator.rpn_head.anchor_deltas") { key = "proposal_generator.rpn_head.pred"; row0 = 3; rows = 12; }
+    else if (prefix == "proposal_generator.rpn_head.objectness_logits") { key = "proposal_generator.rpn_head.pred"; row0 = 0; rows = m->rpn_A; }
+    else if (prefix == "proposal_generator.rpn_head.anchor_deltas") { key = "proposal_generator.rpn_head.pred"; row0 = m->rpn_A; rows = 4 * m->rpn_A; }
     else if (prefix == "roi_heads.mask_head.predictor") { row0 = 0; rows = K; }
     auto it = m->conv.find(key);
     AMP_REQUIRE(it != m->conv.end(), "%s: unknown tensor '%s'", fn, name_c);

@@ -129,7 +129,7 @@ __global__ __launch_bounds__(TOPK_THREADS) void topk_merge_kernel(const TopkArgs
 struct DecodeArgs {
     const float* pred[MAX_LEVELS];
     int hw[MAX_LEVELS], fw[MAX_LEVELS], stride[MAX_LEVELS];
-    float cell[MAX_LEVELS][3][4];    // cell anchors per level (A = 3)
+    float cell[MAX_LEVELS][amp::RPN_MAX_A][4];    // cell anchors per level (amp::cell_anchors)
     int nlevels, A, ld, k;
     const int* sel_idx;
     const float* sel_logit;
@@ -251,7 +251,8 @@ extern "C" {
 int amp_rpn_topk(amp_ctx* ctx, const amp_rpn_levels* lv, int B, int k, uint32_t* keys_scratch, int max_n, int* sel_idx,
                  float* sel_logit, int* sel_count) {
     AMP_REQUIRE(ctx && lv && keys_scratch && sel_idx && sel_logit && sel_count, "amp_rpn_topk: null argument");
-    AMP_REQUIRE(lv->nlevels >= 1 && lv->nlevels <= MAX_LEVELS && lv->A == 3, "amp_rpn_topk: need 1..5 levels, A == 3");
+    AMP_REQUIRE(lv->nlevels >= 1 && lv->nlevels <= MAX_LEVELS && lv->A >= 1 && lv->A <= amp::RPN_MAX_A && lv->ld >= lv->A,
+                "amp_rpn_topk: need 1..5 levels, 1 <= A <= %d, ld >= A", amp::RPN_MAX_A);
     AMP_REQUIRE(k >= 1 && k <= amp::SELECT_MAX_K, "amp_rpn_topk: k=%d out of range [1,%d]", k, amp::SELECT_MAX_K);
     TopkArgs a;
     for (int l = 0; l < lv->nlevels; ++l) {
@@ -312,7 +313,8 @@ int amp_rpn_decode_sized(amp_ctx* ctx, const amp_rpn_levels* lv, int B, int k, c
                          const int* sel_count, int img_h, int img_w, const int* img_hw, int cap, float* boxes,
                          unsigned long long* sortkey, int* anchor_id) {
     AMP_REQUIRE(ctx && lv && sel_idx && sel_logit && sel_count && boxes && sortkey, "amp_rpn_decode: null argument");
-    AMP_REQUIRE(lv->nlevels >= 1 && lv->nlevels <= MAX_LEVELS && lv->A == 3, "amp_rpn_decode: need 1..5 levels, A == 3");
+    AMP_REQUIRE(lv->nlevels >= 1 && lv->nlevels <= MAX_LEVELS && lv->A >= 1 && lv->A <= amp::RPN_MAX_A && lv->ld >= 5 * lv->A,
+                "amp_rpn_decode: need 1..5 levels, 1 <= A <= %d, ld >= 5 A", amp::RPN_MAX_A);
     AMP_REQUIRE(cap >= lv->nlevels * k, "amp_rpn_decode: cap=%d < nlevels*k", cap);
     DecodeArgs a;
     for (int l = 0; l < lv->nlevels; ++l) {
@@ -320,14 +322,7 @@ int amp_rpn_decode_sized(amp_ctx* ctx, const amp_rpn_levels* lv, int B, int k, c
         a.hw[l] = lv->h[l] * lv->w[l];
         a.fw[l] = lv->w[l];
         a.stride[l] = lv->stride[l];
-        for (int r = 0; r < 3; ++r) {
-            // detectron2 generate_cell_anchors: python-float math, stored fp32
-            const double ratio = (r == 0) ? 0.5 : (r == 1 ? 1.0 : 2.0);
-            const double area = (double)lv->anchor_size[l] * (double)lv->anchor_size[l];
-            const double w = sqrt(area / ratio), h = ratio * w;
-            a.cell[l][r][0] = (float)(-w / 2.0); a.cell[l][r][1] = (float)(-h / 2.0);
-            a.cell[l][r][2] = (float)(w / 2.0);  a.cell[l][r][3] = (float)(h / 2.0);
-        }
+        AMP_REQUIRE(amp::cell_anchors(lv, l, a.cell[l]) == lv->A, "amp_rpn_decode: level %d: sizes x ratios do not give A = %d anchors", l, lv->A);
     }
     a.nlevels = lv->nlevels; a.A = lv->A; a.ld = lv->ld; a.k = k;
     a.sel_idx = sel_idx; a.sel_logit = sel_logit; a.sel_count = sel_count;
@@ -339,6 +334,17 @@ int amp_rpn_decode_sized(amp_ctx* ctx, const amp_rpn_levels* lv, int B, int k, c
     const int total = B * cap;
     hipLaunchKernelGGL(rpn_decode_kernel, dim3(amp::cdiv(total, 256)), dim3(256), 0, ctx->stream, a, B);
     AMP_HIP_CHECK(hipGetLastError());
+    return AMP_OK;
+}
+
+int amp_cell_anchors(const amp_rpn_levels* lv, int level, float* cell, int cap, int* A_out) {
+    AMP_REQUIRE(lv && cell && A_out && level >= 0 && level < MAX_LEVELS, "amp_cell_anchors: bad argument");
+    float c[amp::RPN_MAX_A][4];
+    const int A = amp::cell_anchors(lv, level, c);
+    AMP_REQUIRE(A >= 1, "amp_cell_anchors: level %d: sizes x ratios must give 1..%d anchors", level, amp::RPN_MAX_A);
+    AMP_REQUIRE(cap >= A, "amp_cell_anchors: cap=%d < A=%d", cap, A);
+    for (int a = 0; a < A; ++a) for (int q = 0; q < 4; ++q) cell[a * 4 + q] = c[a][q];
+    *A_out = A;
     return AMP_OK;
 }
 

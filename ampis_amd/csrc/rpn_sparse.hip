@@ -26,7 +26,8 @@ constexpr int NLV = 5;
 constexpr unsigned int NOROW = 0xffffffffu;
 
 struct SparseGeom {
-    int hw[NLV], fh[NLV], fw[NLV], off[NLV + 1];      // off: first anchor index of a level (3 anchors per pixel)
+    int hw[NLV], fh[NLV], fw[NLV], off[NLV + 1];      // off: first anchor index of a level (A anchors per pixel)
+    int A;
 };
 
 // one workgroup per image: the sampled anchors' pixels, sorted by (level, pixel), duplicates removed -> rows[b * batch + i], NOROW beyond the count
@@ -42,7 +43,7 @@ __global__ __launch_bounds__(512) void rpn_nz_rows_kernel(const SparseGeom g, co
         if (an >= 0 && an < g.off[NLV]) {
             int lvl = 0;
             while (lvl + 1 < NLV && an >= g.off[lvl + 1]) ++lvl;
-            key = ((unsigned int)lvl << 26) | (unsigned int)((an - g.off[lvl]) / 3);
+            key = ((unsigned int)lvl << 26) | (unsigned int)((an - g.off[lvl]) / g.A);
         }
     }
     keys[tid] = key;
@@ -83,7 +84,7 @@ struct RowArgs {
     int t_split;
     const float* t_rows;                       // the rows' hidden activations recomputed ([R][256] fp32) or null: read from t
     const float* w_pred;                       // [K][256]
-    float* dpred_rows;                         // [R][16]
+    float* dpred_rows;                         // [R][ld]
     float* act_rows;                           // [R][256]
     float* dt_rows;                            // [R][256]
 };
@@ -112,34 +113,34 @@ __global__ __launch_bounds__(256) void rpn_dt_rows_kernel(const RowArgs a) {
     }
     a.dt_rows[(size_t)r * 256 + c] = dt;
     a.act_rows[(size_t)r * 256 + c] = act;
-    if (c < 16) a.dpred_rows[(size_t)r * 16 + c] = dp;
+    if (c < a.ld) a.dpred_rows[(size_t)r * a.ld + c] = dp;
 }
 
 // the predictor's gradients and the conv's bias gradient: sums over the rows in ascending order -- 32 row slices in parallel (8 workgroups x 4 quarter
-// slices each), added in slice order by rpn_head_sums_final_kernel.  blockIdx.x 0 .. 15: dW_pred[k][c]; 16: db_conv[c]; 17: db_pred[k]
+// slices each), added in slice order by rpn_head_sums_final_kernel.  blockIdx.x 0 .. ld - 1: dW_pred[k][c]; ld: db_conv[c]; ld + 1: db_pred[k]
 constexpr int SUM_SLICES = 8;
 __global__ __launch_bounds__(1024) void rpn_head_sums_kernel(const float* __restrict__ dpred_rows, const float* __restrict__ act_rows, const float* __restrict__ dt_rows,
-                                                             int R, int K, float* __restrict__ partial) {      // partial [18][SUM_SLICES * 4][256]
+                                                             int R, int K, int ld, float* __restrict__ partial) {      // partial [ld + 2][SUM_SLICES * 4][256]
     const int c = threadIdx.x & 255, q = threadIdx.x >> 8;
     const int blk = blockIdx.x, s = blockIdx.y * 4 + q, ns = SUM_SLICES * 4;
     const int r0 = (int)((long long)R * s / ns), r1 = (int)((long long)R * (s + 1) / ns);
     float acc = 0.f;
-    if (blk < 16) {
-        if (blk < K) for (int r = r0; r < r1; ++r) acc = __fadd_rn(acc, __fmul_rn(dpred_rows[(size_t)r * 16 + blk], act_rows[(size_t)r * 256 + c]));
-    } else if (blk == 16) {
+    if (blk < ld) {
+        if (blk < K) for (int r = r0; r < r1; ++r) acc = __fadd_rn(acc, __fmul_rn(dpred_rows[(size_t)r * ld + blk], act_rows[(size_t)r * 256 + c]));
+    } else if (blk == ld) {
         for (int r = r0; r < r1; ++r) acc = __fadd_rn(acc, dt_rows[(size_t)r * 256 + c]);
     } else {
-        if (c < K) for (int r = r0; r < r1; ++r) acc = __fadd_rn(acc, dpred_rows[(size_t)r * 16 + c]);
+        if (c < K) for (int r = r0; r < r1; ++r) acc = __fadd_rn(acc, dpred_rows[(size_t)r * ld + c]);
     }
     partial[((size_t)blk * ns + s) * 256 + c] = acc;
 }
-__global__ __launch_bounds__(256) void rpn_head_sums_final_kernel(const float* __restrict__ partial, int K, float* __restrict__ gw_pred, float* __restrict__ gb_pred,
+__global__ __launch_bounds__(256) void rpn_head_sums_final_kernel(const float* __restrict__ partial, int K, int ld, float* __restrict__ gw_pred, float* __restrict__ gb_pred,
                                                                    float* __restrict__ gb_conv) {
     const int c = threadIdx.x, blk = blockIdx.x, ns = SUM_SLICES * 4;
     float t = partial[((size_t)blk * ns) * 256 + c];
     for (int s = 1; s < ns; ++s) t = __fadd_rn(t, partial[((size_t)blk * ns + s) * 256 + c]);
-    if (blk < 16) { if (blk < K) gw_pred[(size_t)blk * 256 + c] = t; }
-    else if (blk == 16) gb_conv[c] = t;
+    if (blk < ld) { if (blk < K) gw_pred[(size_t)blk * 256 + c] = t; }
+    else if (blk == ld) gb_conv[c] = t;
     else if (c < K) gb_pred[c] = t;
 }
 
@@ -201,19 +202,22 @@ __global__ __launch_bounds__(256) void rpn_scatter_tap_kernel(const ScatterArgs 
 namespace amp {
 
 int rpn_sparse_backward(amp_ctx* ctx, const RpnSparseArgs& A) {
-    AMP_REQUIRE(A.B >= 1 && A.batch >= 1 && A.batch <= 512 && A.K >= 1 && A.K <= 16 && A.ld == 16, "rpn_sparse_backward: batch <= 512, K <= 16, ld == 16");
+    AMP_REQUIRE(A.B >= 1 && A.batch >= 1 && A.batch <= 512 && A.K >= 1 && A.K <= A.ld && (A.ld == 16 || A.ld == 32 || A.ld == 48) &&
+                A.A >= 1 && 5 * A.A <= A.K, "rpn_sparse_backward: batch <= 512, 5 A <= K <= ld, ld 16 / 32 / 48");
     SparseGeom g;
     g.off[0] = 0;
+    g.A = A.A;
     for (int l = 0; l < NLV; ++l) {
         g.fh[l] = A.fh[l]; g.fw[l] = A.fw[l]; g.hw[l] = A.fh[l] * A.fw[l];
-        g.off[l + 1] = g.off[l] + g.hw[l] * 3;
+        g.off[l + 1] = g.off[l] + g.hw[l] * g.A;
         AMP_REQUIRE(g.hw[l] < (1 << 26), "rpn_sparse_backward: a level of %d pixels", g.hw[l]);
     }
     const int R = A.B * A.batch;
-    static_assert(RPN_SPARSE_SUMS_FLOATS == (size_t)18 * SUM_SLICES * 4 * 256, "rpn_head_sums_kernel's partials");
-    const size_t g_need = std::max((size_t)R * 9 * A.C, RPN_SPARSE_SUMS_FLOATS);
+    static_assert(rpn_sparse_sums_floats(16) == (size_t)18 * SUM_SLICES * 4 * 256 && rpn_sparse_sums_floats(48) == (size_t)50 * SUM_SLICES * 4 * 256, "rpn_head_sums_kernel's partials");
+    const size_t sums_floats = rpn_sparse_sums_floats(A.ld);
+    const size_t g_need = std::max((size_t)R * 9 * A.C, sums_floats);
     AMP_REQUIRE(A.G_floats >= g_need, "rpn_sparse_backward: G holds %zu floats, needs %zu (max of %d rows x %d and the head sums' %zu partials)",
-                A.G_floats, g_need, R, 9 * A.C, RPN_SPARSE_SUMS_FLOATS);
+                A.G_floats, g_need, R, 9 * A.C, sums_floats);
     hipLaunchKernelGGL(rpn_nz_rows_kernel, dim3(A.B), dim3(512), 0, ctx->stream, g, A.sampled, A.counts, A.batch, A.rows, A.nrows);
     GatherArgs ga;
     ga.g = g; ga.rows = A.rows; ga.batch = A.batch; ga.feat_split = A.feat_split; ga.xg = A.xg;
@@ -235,8 +239,8 @@ int rpn_sparse_backward(amp_ctx* ctx, const RpnSparseArgs& A) {
     for (int l = 0; l < NLV; ++l) { ra.dpred[l] = A.dpred[l]; ra.t[l] = A.t[l]; }
     hipLaunchKernelGGL(rpn_dt_rows_kernel, dim3(R), dim3(256), 0, ctx->stream, ra);
     // (the partial sums live in G, which the data-gradient GEMM overwrites further down: RPN_SPARSE_SUMS_FLOATS, more than R x 2304 when R < 64)
-    hipLaunchKernelGGL(rpn_head_sums_kernel, dim3(18, SUM_SLICES), dim3(1024), 0, ctx->stream, A.dpred_rows, A.act_rows, A.dt_rows, R, A.K, A.G);
-    hipLaunchKernelGGL(rpn_head_sums_final_kernel, dim3(18), dim3(256), 0, ctx->stream, A.G, A.K, A.gw_pred, A.gb_pred, A.gb_conv);
+    hipLaunchKernelGGL(rpn_head_sums_kernel, dim3(A.ld + 2, SUM_SLICES), dim3(1024), 0, ctx->stream, A.dpred_rows, A.act_rows, A.dt_rows, R, A.K, A.ld, A.G);
+    hipLaunchKernelGGL(rpn_head_sums_final_kernel, dim3(A.ld + 2), dim3(256), 0, ctx->stream, A.G, A.K, A.ld, A.gw_pred, A.gb_pred, A.gb_conv);
     // dW_conv[n][tap][c] = sum_r d_t[r][n] * X[r][tap][c]: the weight gradient of a 1x1 layer 2304 -> 256 over a 1 x R image (gradients of 1e-9 .. 1e-4: * 2^16 in front of the f16 split)
     amp_conv_desc dw;
     dw.B = 1; dw.H = 1; dw.W = R; dw.Cin = 9 * A.C; dw.Cout = A.C; dw.KH = 1; dw.KW = 1; dw.stride = 1; dw.pad = 0; dw.relu = 0; dw.res_mode = 0; dw.out_mode = 0;

@@ -26,16 +26,16 @@ __device__ __forceinline__ uint32_t sample_key(uint32_t seed, uint32_t image, ui
 }
 
 struct AnchorGeom {
-    int hw[NL], fw[NL], stride[NL], off[NL + 1];   // off: first anchor index of each level (x3 anchors per location)
-    float cell[NL][3][4];
-    int total;
+    int hw[NL], fw[NL], stride[NL], off[NL + 1];   // off: first anchor index of each level (x A anchors per location)
+    float cell[NL][amp::RPN_MAX_A][4];
+    int total, A;
 };
 
 __device__ __forceinline__ void anchor_box(const AnchorGeom& g, int a, float& x1, float& y1, float& x2, float& y2, int& lvl, int& local) {
     lvl = 0;
     while (lvl + 1 < NL && a >= g.off[lvl + 1]) ++lvl;
     local = a - g.off[lvl];
-    const int pix = local / 3, an = local - pix * 3;
+    const int pix = local / g.A, an = local - pix * g.A;
     const int py = pix / g.fw[lvl], px = pix - py * g.fw[lvl];
     const float sx = (float)(px * g.stride[lvl]), sy = (float)(py * g.stride[lvl]);
     x1 = __fadd_rn(sx, g.cell[lvl][an][0]); y1 = __fadd_rn(sy, g.cell[lvl][an][1]);
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(256) void anchor_label_kernel(const AnchorGeom g, c
 // ---- RPN: sample 256 anchors / image, BCE + L1 losses and their gradients -----------------------------------------------------
 struct RpnLossArgs {
     AnchorGeom g;
-    const float* pred[NL];        // [B, hw, ld]: 3 logits, 12 deltas (+ padding)
+    const float* pred[NL];        // [B, hw, ld]: A logits, 4 A deltas (+ padding)
     int ld;
     float* dpred[NL];             // same shape, zero-filled by the caller; receives d(loss)/d(pred) (may be null)
     const float* gt_boxes;
@@ -273,7 +273,7 @@ __global__ __launch_bounds__(1024) void rpn_sample_loss_kernel(const RpnLossArgs
         float x1, y1, x2, y2;
         int lvl, local;
         anchor_box(a.g, an, x1, y1, x2, y2, lvl, local);
-        const int pix = local / 3, k = local - pix * 3;
+        const int A = a.g.A, pix = local / A, k = local - pix * A;
         const size_t row = ((size_t)b * a.g.hw[lvl] + pix) * a.ld;
         const float* p = a.pred[lvl] + row;
         float* dp = a.dpred[lvl] ? a.dpred[lvl] + row : nullptr;
@@ -292,9 +292,9 @@ __global__ __launch_bounds__(1024) void rpn_sample_loss_kernel(const RpnLossArgs
                                 logf(__fdiv_rn(th, sh))};
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const float d = __fsub_rn(p[3 + 4 * k + q], t[q]);
+                const float d = __fsub_rn(p[A + 4 * k + q], t[q]);
                 l1 = __fadd_rn(l1, fabsf(d));
-                if (dp) dp[3 + 4 * k + q] = (d > 0.f ? a.inv_norm : (d < 0.f ? -a.inv_norm : 0.f));
+                if (dp) dp[A + 4 * k + q] = (d > 0.f ? a.inv_norm : (d < 0.f ? -a.inv_norm : 0.f));
             }
         }
     }
@@ -740,22 +740,18 @@ __global__ void focal_finish_kernel(const float* partial, int n, float scale, fl
     *loss = __fmul_rn(s, scale);
 }
 
-void fill_geom(AnchorGeom& g, const amp_rpn_levels* lv) {
+bool fill_geom(AnchorGeom& g, const amp_rpn_levels* lv) {
     g.off[0] = 0;
+    g.A = lv->A;
     for (int l = 0; l < NL; ++l) {
         g.hw[l] = lv->h[l] * lv->w[l];
         g.fw[l] = lv->w[l];
         g.stride[l] = lv->stride[l];
-        g.off[l + 1] = g.off[l] + g.hw[l] * 3;
-        for (int r = 0; r < 3; ++r) {
-            const double ratio = (r == 0) ? 0.5 : (r == 1 ? 1.0 : 2.0);
-            const double area = (double)lv->anchor_size[l] * (double)lv->anchor_size[l];
-            const double w = sqrt(area / ratio), h = ratio * w;
-            g.cell[l][r][0] = (float)(-w / 2.0); g.cell[l][r][1] = (float)(-h / 2.0);
-            g.cell[l][r][2] = (float)(w / 2.0);  g.cell[l][r][3] = (float)(h / 2.0);
-        }
+        g.off[l + 1] = g.off[l] + g.hw[l] * g.A;
+        if (amp::cell_anchors(lv, l, g.cell[l]) != g.A) return false;
     }
     g.total = g.off[NL];
+    return true;
 }
 
 }  // namespace
@@ -765,9 +761,9 @@ extern "C" {
 int amp_anchor_labels(amp_ctx* ctx, const amp_rpn_levels* lv, int B, const float* gt_boxes, const int* gt_off, int total_gt,
                       float iou_lo, float iou_hi, float* match_val, int* match_idx, unsigned int* gt_best, signed char* label) {
     AMP_REQUIRE(ctx && lv && gt_boxes && gt_off && match_val && match_idx && gt_best && label, "amp_anchor_labels: null argument");
-    AMP_REQUIRE(lv->nlevels == NL && lv->A == 3, "amp_anchor_labels: need 5 levels, 3 anchors");
+    AMP_REQUIRE(lv->nlevels == NL && lv->A >= 1 && lv->A <= amp::RPN_MAX_A, "amp_anchor_labels: need 5 levels, 1..%d anchors", amp::RPN_MAX_A);
     AnchorGeom g;
-    fill_geom(g, lv);
+    AMP_REQUIRE(fill_geom(g, lv), "amp_anchor_labels: sizes x ratios do not give A = %d anchors on every level", lv->A);
     AMP_HIP_CHECK(hipMemsetAsync(gt_best, 0, (size_t)(total_gt > 0 ? total_gt : 1) * sizeof(unsigned int), ctx->stream));
     const dim3 grid(amp::cdiv(g.total, 256), B);
     hipLaunchKernelGGL(anchor_match_kernel, grid, dim3(256), 0, ctx->stream, g, gt_boxes, gt_off, match_val, match_idx, gt_best);
@@ -782,8 +778,9 @@ int amp_rpn_sample_loss(amp_ctx* ctx, const amp_rpn_levels* lv, float* const dpr
     AMP_REQUIRE(ctx && lv && gt_boxes && gt_off && label && match_idx && keys_scratch && sampled && counts && partial, "amp_rpn_sample_loss: null argument");
     AMP_REQUIRE(batch >= 1 && batch <= 512, "amp_rpn_sample_loss: batch must be in [1,512]");
     AMP_REQUIRE(num_pos_max >= 0 && num_pos_max <= batch, "amp_rpn_sample_loss: num_pos_max %d outside [0, batch %d]", num_pos_max, batch);
+    AMP_REQUIRE(lv->nlevels == NL && lv->A >= 1 && lv->A <= amp::RPN_MAX_A && lv->ld >= 5 * lv->A, "amp_rpn_sample_loss: need 5 levels, 1..%d anchors, ld >= 5 A", amp::RPN_MAX_A);
     RpnLossArgs a;
-    fill_geom(a.g, lv);
+    AMP_REQUIRE(fill_geom(a.g, lv), "amp_rpn_sample_loss: sizes x ratios do not give A = %d anchors on every level", lv->A);
     for (int l = 0; l < NL; ++l) { a.pred[l] = lv->pred[l]; a.dpred[l] = dpred ? dpred[l] : nullptr; }
     a.ld = lv->ld;
     a.gt_boxes = gt_boxes; a.gt_off = gt_off; a.label = label; a.match_idx = match_idx; a.keys_scratch = keys_scratch;

@@ -18,6 +18,43 @@ from ..structures import Boxes, Instances, RLEBitMasks
 logger = logging.getLogger("ampis_amd")
 
 
+FPN_RPN_FEATURES = ("p2", "p3", "p4", "p5", "p6")
+_anchor_warned = set()
+
+
+def anchor_kwargs(cfg):
+    """The MaskRCNN keyword arguments for MODEL.ANCHOR_GENERATOR: anchor_sizes / aspect_ratios, five lists each (detectron2's
+    DefaultAnchorGenerator: one inner list is broadcast to p2..p6; offset 0; ANGLES belongs to rotated boxes and is ignored).  The keys
+    are read only when MODEL.RPN.IN_FEATURES names the five FPN levels: a cfg without a zoo merge carries detectron2's C4 defaults (one
+    level, five sizes), which this project has always replaced by the zoo's FPN architecture -- then {} (the FPN zoo anchors), with one
+    logged warning.  Raises ValueError naming the cfg key for what the native path cannot represent, before any device work."""
+    from ..model import anchor_lists
+    feats = tuple(cfg.MODEL.RPN.get("IN_FEATURES", ()))
+    if feats != FPN_RPN_FEATURES:
+        if feats not in _anchor_warned:
+            _anchor_warned.add(feats)
+            logger.warning(f"MODEL.RPN.IN_FEATURES = {list(feats)!r} is not the FPN level set p2..p6: the model is the zoo's R-FPN architecture and "
+                           "MODEL.ANCHOR_GENERATOR is not read (sizes 32..512, aspect ratios 0.5, 1, 2); merge a zoo config to set the anchors")
+        return {}
+    g = cfg.MODEL.get("ANCHOR_GENERATOR", None) or {}
+    name = g.get("NAME", "DefaultAnchorGenerator")
+    if name != "DefaultAnchorGenerator":
+        raise ValueError(f"MODEL.ANCHOR_GENERATOR.NAME = {name!r}: only 'DefaultAnchorGenerator' has a native path")
+    off = g.get("OFFSET", 0.0)
+    if isinstance(off, bool) or not isinstance(off, (int, float, np.integer, np.floating)) or float(off) != 0.0:
+        raise ValueError(f"MODEL.ANCHOR_GENERATOR.OFFSET = {off!r}: the native anchors sit at offset 0")
+    unwrap = lambda v: [list(x) if isinstance(x, (list, tuple)) else x for x in v] if isinstance(v, (list, tuple)) else v
+    sizes, ratios = anchor_lists(unwrap(g.get("SIZES", None)), unwrap(g.get("ASPECT_RATIOS", None)))
+    return dict(anchor_sizes=[list(s) for s in sizes], aspect_ratios=[list(r) for r in ratios])
+
+
+def _num_anchors(anchor_kw):
+    """Anchors per location of anchor_kwargs' result ({} = the default 3)."""
+    if not anchor_kw:
+        return P.NUM_ANCHORS
+    return len(anchor_kw["anchor_sizes"][0]) * len(anchor_kw["aspect_ratios"][0])
+
+
 def train_model_kwargs(cfg, per_rank):
     """The MaskRCNN keyword arguments a training net takes from cfg (the trainer adds classes, capacity and backbone): batch size per
     rank, training top-k, pixel statistics and every sampling setting of MODEL.RPN / MODEL.ROI_HEADS.  Refuses (ValueError naming the
@@ -31,6 +68,7 @@ def train_model_kwargs(cfg, per_rank):
               rpn_batch=r.BATCH_SIZE_PER_IMAGE, rpn_pos_frac=r.POSITIVE_FRACTION, rpn_iou=seq(r.IOU_THRESHOLDS),
               roi_batch=h.BATCH_SIZE_PER_IMAGE, roi_fg_frac=h.POSITIVE_FRACTION, roi_iou=seq(h.IOU_THRESHOLDS))
     sampling_caps(kw["rpn_batch"], kw["rpn_pos_frac"], kw["rpn_iou"], kw["roi_batch"], kw["roi_fg_frac"], kw["roi_iou"])
+    kw.update(anchor_kwargs(cfg))
     return kw
 
 
@@ -170,11 +208,13 @@ class DefaultPredictor:
         self.ctx = _lib.Context(_device_index(cfg.MODEL.DEVICE))
         w = str(cfg.MODEL.WEIGHTS)
         self.arch = P.arch_from_cfg(cfg)
+        self._anchor_kw = anchor_kwargs(cfg)               # an anchor setting the native path cannot represent fails here, naming its key
+        self.num_anchors = _num_anchors(self._anchor_kw)
         if w:
-            self.params = checkpoint.load_checkpoint(w, self.num_classes, self.arch)
+            self.params = checkpoint.load_checkpoint(w, self.num_classes, self.arch, num_anchors=self.num_anchors)
         else:
             logger.warning("cfg.MODEL.WEIGHTS is empty: using seeded random initialisation (like an un-loaded detectron2 model)")
-            self.params = P.init_params(self.num_classes, seed=0, style="d2", arch=self.arch)
+            self.params = P.init_params(self.num_classes, seed=0, style="d2", arch=self.arch, num_anchors=self.num_anchors)
         self._model = None
         self._cap = (0, 0, 0)
 
@@ -190,7 +230,7 @@ class DefaultPredictor:
                                    pre_nms_topk=int(c.MODEL.RPN.PRE_NMS_TOPK_TEST), post_nms_topk=int(c.MODEL.RPN.POST_NMS_TOPK_TEST),
                                    rpn_nms_thresh=float(c.MODEL.RPN.NMS_THRESH), score_thresh=float(c.MODEL.ROI_HEADS.SCORE_THRESH_TEST),
                                    nms_thresh=float(c.MODEL.ROI_HEADS.NMS_THRESH_TEST), pixel_mean=tuple(c.MODEL.PIXEL_MEAN),
-                                   pixel_std=tuple(c.MODEL.PIXEL_STD), arch=self.arch)
+                                   pixel_std=tuple(c.MODEL.PIXEL_STD), arch=self.arch, **self._anchor_kw)
             self._model.load_params(self.params)
             self._cap = cap
         return self._model
@@ -233,7 +273,7 @@ class DefaultPredictor:
         return dict(detections_per_image=int(c.TEST.DETECTIONS_PER_IMAGE), pre_nms_topk=int(c.MODEL.RPN.PRE_NMS_TOPK_TEST),
                     post_nms_topk=int(c.MODEL.RPN.POST_NMS_TOPK_TEST), rpn_nms_thresh=float(c.MODEL.RPN.NMS_THRESH),
                     score_thresh=float(c.MODEL.ROI_HEADS.SCORE_THRESH_TEST), nms_thresh=float(c.MODEL.ROI_HEADS.NMS_THRESH_TEST),
-                    pixel_mean=tuple(c.MODEL.PIXEL_MEAN), pixel_std=tuple(c.MODEL.PIXEL_STD), arch=self.arch)
+                    pixel_mean=tuple(c.MODEL.PIXEL_MEAN), pixel_std=tuple(c.MODEL.PIXEL_STD), arch=self.arch, **self._anchor_kw)
 
     def stream(self, images, depth=2):
         """`predictor(img)` for every image of an iterable, with `depth` images in flight on the GPU (amp_pipeline: the next image's
@@ -457,7 +497,8 @@ class DefaultTrainer:
         if self.world_size > 1 and comm.backend() == "rccl":
             comm.attach_rccl(self.ctx)       # the gradient exchange and synchronize() run on RCCL inside the library from here on
         self.arch = P.arch_from_cfg(cfg)     # a grouped (ResNeXt) backbone is inference-only: amp_model_create refuses to train it
-        self.params = P.init_params(self.num_classes, seed=max(int(cfg.get("SEED", -1)), 0), style="d2", arch=self.arch)
+        self.num_anchors = _num_anchors(anchor_kwargs(cfg))      # an anchor setting the native path cannot represent fails here, naming its key
+        self.params = P.init_params(self.num_classes, seed=max(int(cfg.get("SEED", -1)), 0), style="d2", arch=self.arch, num_anchors=self.num_anchors)
         self._net = None
         self._momentum = None                              # SGD velocity carried over a re-created net / read from a checkpoint
         self.model = TrainModel(None, self.ctx, ensure=self._ensure_net)
@@ -596,7 +637,8 @@ class DefaultTrainer:
                 w = os.path.join(self.cfg.OUTPUT_DIR, open(last).read().strip())
                 resumed = True
         if w and not w.startswith(("detectron2://", "http://", "https://")):
-            self.params, self.load_report = checkpoint.load_checkpoint(w, self.num_classes, self.arch, init=self.params, strict=resumed, with_report=True)
+            self.params, self.load_report = checkpoint.load_checkpoint(w, self.num_classes, self.arch, init=self.params, strict=resumed, with_report=True,
+                                                                           num_anchors=self.num_anchors)
             if resumed:
                 it = checkpoint.checkpoint_iteration(w)
                 self.start_iter = self.iter = (it + 1) if it is not None else 0

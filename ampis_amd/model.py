@@ -229,14 +229,59 @@ def sampling_caps(rpn_batch=256, rpn_pos_frac=0.5, rpn_iou=(0.3, 0.7), roi_batch
     return rb, int(rb * rf), lo, hi, bb, int(bb * bf), ri
 
 
+DEFAULT_ANCHOR_SIZES = ((32,), (64,), (128,), (256,), (512,))      # p2 .. p6 (the model zoo's FPN configs)
+DEFAULT_ASPECT_RATIOS = ((0.5, 1.0, 2.0),) * 5
+MAX_ANCHORS = 9               # anchors per location: 48 predictor rows (amp::rpn_ld)
+
+
+def anchor_lists(sizes=None, ratios=None):
+    """MODEL.ANCHOR_GENERATOR.{SIZES, ASPECT_RATIOS} as the native config holds them: (sizes, ratios), five tuples of floats each (p2 .. p6).
+    detectron2's DefaultAnchorGenerator semantics: a list with one inner list is broadcast to the five levels, otherwise five inner lists;
+    A = len(sizes[l]) * len(ratios[l]) anchors per location, the same on every level (StandardRPNHead), 1 <= A <= 9.  None = the default.
+    Raises ValueError naming the cfg key of a value the native path cannot represent."""
+    def level_lists(key, v, default):
+        if v is None:
+            return tuple(tuple(float(x) for x in lvl) for lvl in default)
+        if isinstance(v, (str, bytes)) or not hasattr(v, "__len__") or len(v) == 0 or \
+                any(isinstance(lvl, (str, bytes)) or not hasattr(lvl, "__len__") for lvl in v):
+            raise ValueError(f"{key} = {v!r}: a list of lists is expected (one inner list, or one per level p2..p6)")
+        if len(v) not in (1, 5):
+            raise ValueError(f"{key} = {v!r}: {len(v)} inner lists; one (broadcast to p2..p6) or five are expected")
+        out = []
+        for lvl in (list(v) * 5 if len(v) == 1 else v):
+            if len(lvl) == 0:
+                raise ValueError(f"{key} = {v!r}: an empty inner list")
+            vals = []
+            for x in lvl:
+                ok = not isinstance(x, bool) and isinstance(x, (int, float, np.integer, np.floating)) and bool(np.isfinite(x)) and x > 0
+                if not ok:
+                    raise ValueError(f"{key} = {v!r}: entry {x!r} is not a positive finite number")
+                vals.append(float(x))
+            out.append(tuple(vals))
+        return tuple(out)
+
+    s = level_lists("MODEL.ANCHOR_GENERATOR.SIZES", sizes, DEFAULT_ANCHOR_SIZES)
+    r = level_lists("MODEL.ANCHOR_GENERATOR.ASPECT_RATIOS", ratios, DEFAULT_ASPECT_RATIOS)
+    counts = [len(a) * len(b) for a, b in zip(s, r)]
+    if len(set(counts)) != 1:
+        raise ValueError(f"MODEL.ANCHOR_GENERATOR.SIZES x ASPECT_RATIOS give {counts} anchors per location on p2..p6: the RPN head needs the same "
+                         "number on every level")
+    if counts[0] > MAX_ANCHORS:
+        raise ValueError(f"MODEL.ANCHOR_GENERATOR.SIZES x ASPECT_RATIOS give {counts[0]} anchors per location: the native RPN head takes at most {MAX_ANCHORS}")
+    return s, r
+
+
 class MaskRCNN:
     def __init__(self, ctx, num_classes, max_batch=1, max_h=1344, max_w=1344, max_out_hw=4096,
                  detections_per_image=100, pre_nms_topk=1000, post_nms_topk=1000, rpn_nms_thresh=0.7,
                  score_thresh=0.05, nms_thresh=0.5, mask_threshold=0.5, pixel_mean=(103.530, 116.280, 123.675),
                  pixel_std=(1.0, 1.0, 1.0), rle_pool_counts=0, train=False, max_gt=16384, max_poly_doubles=16384 * 80,
                  pre_nms_topk_train=2000, post_nms_topk_train=1000, rpn_batch=256, roi_batch=512, arch="R50",
-                 rpn_pos_frac=0.5, rpn_iou=(0.3, 0.7), roi_fg_frac=0.25, roi_iou=0.5):
+                 rpn_pos_frac=0.5, rpn_iou=(0.3, 0.7), roi_fg_frac=0.25, roi_iou=0.5, anchor_sizes=None, aspect_ratios=None):
         caps = sampling_caps(rpn_batch, rpn_pos_frac, rpn_iou, roi_batch, roi_fg_frac, roi_iou)
+        # MODEL.ANCHOR_GENERATOR.{SIZES, ASPECT_RATIOS}: lists of lists (one inner list = every level); None = the zoo's FPN anchors
+        self.anchor_sizes, self.aspect_ratios = anchor_lists(anchor_sizes, aspect_ratios)
+        self.num_anchors = len(self.anchor_sizes[0]) * len(self.aspect_ratios[0])
         self.ctx = ctx
         cfg = ModelCfg()
         check(lib().amp_model_cfg_default(C.byref(cfg)), "amp_model_cfg_default")
@@ -263,7 +308,11 @@ class MaskRCNN:
         self.cfg = cfg
         self.num_classes = int(num_classes)
         self._h = C.c_void_p()
-        check(lib().amp_model_create(ctx.handle, C.byref(cfg), C.byref(self._h)), "amp_model_create")
+        if anchor_sizes is None and aspect_ratios is None:
+            check(lib().amp_model_create(ctx.handle, C.byref(cfg), C.byref(self._h)), "amp_model_create")
+        else:
+            anchors = _lib.fill_anchors(_lib.AnchorCfg(), self.anchor_sizes, self.aspect_ratios)
+            check(lib().amp_model_create_anchors(ctx.handle, C.byref(cfg), C.byref(anchors), C.byref(self._h)), "amp_model_create_anchors")
         self._finalized = False
 
     # ---- parameters ----
@@ -456,7 +505,7 @@ class MaskRCNN:
     def get_tensor(self, name, grad=False, momentum=False):
         """Current value (or gradient, or SGD momentum buffer) of a parameter in detectron2 / torch layout."""
         from . import params as P
-        shape = P.param_shapes(self.num_classes, self.arch)[name]
+        shape = P.param_shapes(self.num_classes, self.arch, self.num_anchors)[name]
         out = np.empty(shape, dtype=np.float32)
         kind = 2 if momentum else int(bool(grad))
         check(lib().amp_model_get_tensor(self._h, name.encode(), kind, out.ctypes.data_as(C.c_void_p), out.size), "amp_model_get_tensor")
@@ -465,7 +514,7 @@ class MaskRCNN:
     def trainable_names(self):
         """Tensors the SGD step updates: everything but FrozenBN statistics and the frozen stem / res2 (FREEZE_AT = 2)."""
         from . import params as P
-        return [k for k in P.param_shapes(self.num_classes, self.arch)
+        return [k for k in P.param_shapes(self.num_classes, self.arch, self.num_anchors)
                 if ".norm." not in k and not k.startswith(("backbone.bottom_up.stem", "backbone.bottom_up.res2"))]
 
     def momentum_dict(self):
@@ -475,7 +524,7 @@ class MaskRCNN:
     def load_momentum_dict(self, bufs):
         """Inverse of momentum_dict.  Sizes are validated; names the model does not train are reported, not loaded."""
         from . import params as P
-        shapes = P.param_shapes(self.num_classes, self.arch)
+        shapes = P.param_shapes(self.num_classes, self.arch, self.num_anchors)
         train = set(self.trainable_names())
         unknown = [k for k in bufs if k not in train]
         for k, v in bufs.items():
@@ -490,7 +539,7 @@ class MaskRCNN:
     def state_dict(self):
         """All trainable tensors + the FrozenBN statistics they were loaded with are not tracked here; returns the trainable part."""
         from . import params as P
-        return {k: self.get_tensor(k) for k in P.param_shapes(self.num_classes, self.arch) if ".norm." not in k}
+        return {k: self.get_tensor(k) for k in P.param_shapes(self.num_classes, self.arch, self.num_anchors) if ".norm." not in k}
 
     def tap(self, name):
         """Copy an intermediate device buffer of the last infer call to the host (parity tests)."""

@@ -5,6 +5,7 @@ Every function launches on the stream of the Context it is given and never falls
 """
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -175,22 +176,49 @@ def _u64(*shape, device="cuda:0"):
     return torch.empty(shape, dtype=torch.int64, device=device)   # same bits; viewed as u64 by the library
 
 
-def make_rpn_levels(preds, shapes, strides=(4, 8, 16, 32, 64), sizes=(32, 64, 128, 256, 512)):
+def make_rpn_levels(preds, shapes, strides=(4, 8, 16, 32, 64), sizes=(32, 64, 128, 256, 512), ratios=None):
+    """sizes: one number per level (with ratios None: the ratios 0.5, 1, 2 -- A = 3) or one list per level; ratios: one list for every level or
+    one list per level (MODEL.ANCHOR_GENERATOR.ASPECT_RATIOS).  preds may hold None (host-only use: amp_cell_anchors)."""
     lv = _lib.RpnLevels()
-    lv.nlevels, lv.A, lv.ld = len(preds), 3, preds[0].shape[-1]
+    per_level = any(hasattr(s, "__len__") for s in sizes)
+    A = 3
+    if per_level or ratios is not None:
+        from .model import anchor_lists
+        sz = [list(s) if hasattr(s, "__len__") else [s] for s in sizes]
+        sz = sz + [sz[-1]] * (5 - len(sz))
+        rt = [[0.5, 1.0, 2.0]] if ratios is None else ([list(ratios)] if not hasattr(ratios[0], "__len__") else [list(r) for r in ratios])
+        s5, r5 = anchor_lists(sz, rt)
+        _lib.fill_anchors(lv, s5, r5)
+        A = len(s5[0]) * len(r5[0])
+    lv.nlevels, lv.A = len(preds), A
+    lv.ld = preds[0].shape[-1] if preds[0] is not None else 16 * ((5 * A + 15) // 16)
     for i, (p, (h, w)) in enumerate(zip(preds, shapes)):
-        _f32c(p)
-        lv.pred[i] = p.data_ptr()
-        lv.h[i], lv.w[i], lv.stride[i], lv.anchor_size[i] = h, w, strides[i], sizes[i]
+        if p is not None:
+            _f32c(p)
+            lv.pred[i] = p.data_ptr()
+        lv.h[i], lv.w[i], lv.stride[i] = h, w, strides[i]
+        lv.anchor_size[i] = 0 if hasattr(sizes[i], "__len__") else int(sizes[i])
     return lv
 
 
-def rpn_topk(ctx, preds, shapes, B, k):
-    """preds: per level [B, h*w, 15]. Returns sel_idx [B,L,k] i32, sel_logit [B,L,k] f32, sel_count [B,L] i32."""
-    lv = make_rpn_levels(preds, shapes)
+def cell_anchors(sizes=(32, 64, 128, 256, 512), ratios=None):
+    """The cell anchors the kernels use (amp_cell_anchors; host only): list of five float32 arrays [A, 4]."""
+    lv = make_rpn_levels([None] * 5, [(1, 1)] * 5, sizes=sizes, ratios=ratios)
+    out = []
+    for l in range(5):
+        buf = np.zeros((9, 4), np.float32)
+        n = C.c_int()
+        check(lib().amp_cell_anchors(C.byref(lv), l, buf.ctypes.data_as(C.c_void_p), 9, C.byref(n)), "amp_cell_anchors")
+        out.append(buf[:n.value].copy())
+    return out
+
+
+def rpn_topk(ctx, preds, shapes, B, k, sizes=(32, 64, 128, 256, 512), ratios=None):
+    """preds: per level [B, h*w, ld]. Returns sel_idx [B,L,k] i32, sel_logit [B,L,k] f32, sel_count [B,L] i32."""
+    lv = make_rpn_levels(preds, shapes, sizes=sizes, ratios=ratios)
     L = len(preds)
     dev = preds[0].device
-    max_n = max(h * w * 3 for h, w in shapes)
+    max_n = max(h * w * lv.A for h, w in shapes)
     scratch = torch.empty((B * L * max_n,), dtype=torch.int32, device=dev)
     sel_idx, sel_logit, sel_count = _i32(B, L, k, device=dev), torch.zeros((B, L, k), device=dev), _i32(B, L, device=dev)
     check(lib().amp_rpn_topk(ctx.handle, C.byref(lv), B, k, ptr(scratch), max_n, ptr(sel_idx), ptr(sel_logit), ptr(sel_count)),
@@ -198,8 +226,8 @@ def rpn_topk(ctx, preds, shapes, B, k):
     return sel_idx, sel_logit, sel_count
 
 
-def rpn_decode(ctx, preds, shapes, B, k, sel_idx, sel_logit, sel_count, img_h, img_w):
-    lv = make_rpn_levels(preds, shapes)
+def rpn_decode(ctx, preds, shapes, B, k, sel_idx, sel_logit, sel_count, img_h, img_w, sizes=(32, 64, 128, 256, 512), ratios=None):
+    lv = make_rpn_levels(preds, shapes, sizes=sizes, ratios=ratios)
     cap = len(preds) * k
     dev = preds[0].device
     boxes, keys = torch.empty((B, cap, 4), device=dev), _u64(B, cap, device=dev)

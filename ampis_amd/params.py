@@ -33,16 +33,21 @@ def res_stages(arch="R50"):
 FPN_LEVELS = (2, 3, 4, 5)
 FPN_IN = {2: 256, 3: 512, 4: 1024, 5: 2048}
 FPN_CH = 256
-NUM_ANCHORS = 3
+NUM_ANCHORS = 3               # anchors per location of the default anchor generator (one size per level x ratios 0.5, 1, 2)
+MAX_ANCHORS = 9               # the native RPN head holds up to 9 (48 predictor rows)
 POOL_BOX = 7
 POOL_MASK = 14
 FC_DIM = 1024
 BN_EPS = 1e-5
 
 
-def param_shapes(num_classes, arch="R50"):
-    """OrderedDict name -> shape in detectron2/torch layout (conv OIHW, ConvTranspose IOHW, linear [out,in])."""
+def param_shapes(num_classes, arch="R50", num_anchors=NUM_ANCHORS):
+    """OrderedDict name -> shape in detectron2/torch layout (conv OIHW, ConvTranspose IOHW, linear [out,in]).  num_anchors: anchors per
+    location (len(sizes) x len(ratios) of MODEL.ANCHOR_GENERATOR), the width of the RPN predictors."""
     K = int(num_classes)
+    A = int(num_anchors)
+    if not 1 <= A <= MAX_ANCHORS:
+        raise ValueError(f"num_anchors = {num_anchors!r}: the RPN head takes 1..{MAX_ANCHORS} anchors per location")
     s = OrderedDict()
 
     def conv_bn(prefix, cout, cin, k):
@@ -69,10 +74,10 @@ def param_shapes(num_classes, arch="R50"):
     r = "proposal_generator.rpn_head."
     s[r + "conv.weight"] = (FPN_CH, FPN_CH, 3, 3)
     s[r + "conv.bias"] = (FPN_CH,)
-    s[r + "objectness_logits.weight"] = (NUM_ANCHORS, FPN_CH, 1, 1)
-    s[r + "objectness_logits.bias"] = (NUM_ANCHORS,)
-    s[r + "anchor_deltas.weight"] = (NUM_ANCHORS * 4, FPN_CH, 1, 1)
-    s[r + "anchor_deltas.bias"] = (NUM_ANCHORS * 4,)
+    s[r + "objectness_logits.weight"] = (A, FPN_CH, 1, 1)
+    s[r + "objectness_logits.bias"] = (A,)
+    s[r + "anchor_deltas.weight"] = (A * 4, FPN_CH, 1, 1)
+    s[r + "anchor_deltas.bias"] = (A * 4,)
     s["roi_heads.box_head.fc1.weight"] = (FC_DIM, FPN_CH * POOL_BOX * POOL_BOX)
     s["roi_heads.box_head.fc1.bias"] = (FC_DIM,)
     s["roi_heads.box_head.fc2.weight"] = (FC_DIM, FC_DIM)
@@ -91,11 +96,11 @@ def param_shapes(num_classes, arch="R50"):
     return s
 
 
-def count_params(num_classes, arch="R50"):
-    return int(sum(int(np.prod(v)) for v in param_shapes(num_classes, arch).values()))
+def count_params(num_classes, arch="R50", num_anchors=NUM_ANCHORS):
+    return int(sum(int(np.prod(v)) for v in param_shapes(num_classes, arch, num_anchors).values()))
 
 
-def init_params(num_classes, seed=0, style="d2", dtype=np.float32, arch="R50"):
+def init_params(num_classes, seed=0, style="d2", dtype=np.float32, arch="R50", num_anchors=NUM_ANCHORS):
     """Seeded random initialisation -> OrderedDict name -> np.ndarray (torch layout).
 
     style="d2":     detectron2's initialisers: c2_msra_fill (Kaiming normal, fan_out) for the
@@ -107,7 +112,7 @@ def init_params(num_classes, seed=0, style="d2", dtype=np.float32, arch="R50"):
                     goal: oracle and HIP path read the same arrays.
     """
     rng = np.random.Generator(np.random.PCG64(seed))
-    shapes = param_shapes(num_classes, arch)
+    shapes = param_shapes(num_classes, arch, num_anchors)
     out = OrderedDict()
     spread = style == "spread"
     assert style in ("d2", "spread")

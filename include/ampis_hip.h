@@ -274,11 +274,19 @@ int amp_subsample2(amp_ctx* ctx, const float* x, int B, int H, int W, int C, flo
 /* Stage a12: RPN candidate selection ----------------------------------------------------------- */
 typedef struct amp_rpn_levels {
     int nlevels;               /* <= 5 */
-    int A;                     /* anchors per location (3) */
-    int ld;                    /* row length of pred: A logits then A*4 deltas (15) */
+    int A;                     /* anchors per location (3), 1..9 */
+    int ld;                    /* row length of pred: A logits, then A*4 deltas, then padding (>= 5 A; the model uses 16 * ceil(5 A / 16)) */
     const float* pred[5];      /* per level [B, h*w, ld] */
     int h[5], w[5], stride[5], anchor_size[5];
+    /* MODEL.ANCHOR_GENERATOR.{SIZES, ASPECT_RATIOS} per level (detectron2 DefaultAnchorGenerator, offset 0): cell anchors in the order
+     * `for size: for ratio:`, n_sizes[l] * n_ratios[l] == A.  n_sizes[l] == 0 (a zero-initialised tail): the one size anchor_size[l]
+     * with the ratios 0.5, 1, 2. */
+    int n_sizes[5], n_ratios[5];
+    double sizes[5][9], ratios[5][9];   /* double: the cell anchors are computed from the cfg's python floats */
 } amp_rpn_levels;
+/* Host only: the cell anchors of level l as the kernels use them, cell[a] = (x1, y1, x2, y2) around the origin, computed in double and
+ * stored fp32 (generate_cell_anchors); *A_out = their number.  cap >= 9 rows is always enough. */
+int amp_cell_anchors(const amp_rpn_levels* lv, int level, float* cell /* [cap][4] */, int cap, int* A_out);
 /* per (image, level) top-k by logit, descending, ties by ascending anchor index. keys_scratch: [B*nlevels*max_n] u32. */
 int amp_rpn_topk(amp_ctx* ctx, const amp_rpn_levels* lv, int B, int k, uint32_t* keys_scratch, int max_n, int* sel_idx,
                  float* sel_logit, int* sel_count);
@@ -355,6 +363,10 @@ int amp_mask_prob(amp_ctx* ctx, const float* logits, const int* classes, int N, 
  * epilogue -> pred [B*H*W][16]; the 256-channel hidden tensor is never written. B*H*W >= 24576. */
 int amp_rpn_head_fused(amp_ctx* ctx, const float* x_split, int B, int H, int W, const float* w_conv, const float* b_conv, const float* w_pred,
                        const float* b_pred, float* pred);
+/* the same for a head of ld = 16, 32 or 48 predictor rows (A <= 3, 6, 9 anchors per location: A logits, 4 A deltas, zero rows up to ld):
+ * w_pred [ld][256], b_pred [ld], pred [B*H*W][ld] */
+int amp_rpn_head_fused_ld(amp_ctx* ctx, const float* x_split, int B, int H, int W, const float* w_conv, const float* b_conv, const float* w_pred,
+                          const float* b_pred, int ld, float* pred);
 /* the tail of the mask head in one kernel (AMP_CONV_F16X3): x_split [N,14,14,256] (split rows) -> ConvTranspose2d 2x2 s2 (w_deconv
  * [(ky,kx,co)][256], bias [1024] = the 256 biases once per tap) -> ReLU -> predictor row of classes[n] (pred_w [K][256], pred_b [K]) ->
  * sigmoid -> prob [N,28,28]; the [N,28,28,256] activation is never written */
@@ -512,6 +524,14 @@ enum { AMP_RLE_COUNTS = 0, AMP_RLE_STRINGS = 1, AMP_RLE_BOTH = 2 };
 int  amp_model_set_rle_output(amp_model* m, int mode);
 int  amp_model_cfg_default(amp_model_cfg* cfg);
 int  amp_model_create(amp_ctx* ctx, const amp_model_cfg* cfg, amp_model** out);
+/* MODEL.ANCHOR_GENERATOR.{SIZES, ASPECT_RATIOS} of p2..p6 (the fields of the same names of amp_rpn_levels): A = n_sizes[l] * n_ratios[l] anchors
+ * per location, the same on every level, 1 <= A <= 9; positive finite entries.  The RPN predictors then are
+ * objectness_logits [A,256,1,1] / anchor_deltas [4A,256,1,1].  A zero-initialised struct = the anchors of amp_model_create. */
+typedef struct amp_anchor_cfg {
+    int n_sizes[5], n_ratios[5];
+    double sizes[5][9], ratios[5][9];   /* double: the cell anchors are computed from the cfg's python floats */
+} amp_anchor_cfg;
+int  amp_model_create_anchors(amp_ctx* ctx, const amp_model_cfg* cfg, const amp_anchor_cfg* anchors /* NULL = amp_model_create */, amp_model** out);
 void amp_model_destroy(amp_model* m);
 size_t amp_model_workspace_bytes(amp_model* m);
 int  amp_model_num_tensors(amp_model* m);
