@@ -227,6 +227,24 @@ int rpn_sparse_backward(amp_ctx* ctx, const RpnSparseArgs& a);
 int conv_run(amp_ctx* ctx, const amp_conv_desc* d, int groups, const float* x, const float* w, const float* w_split, int force_f32,
              const float* scale, const float* shift, const float* res, const float* mask, float* y, int in_shift = 0, int fmt = 0,
              const PredictFuse* fuse = nullptr, const RpnFuse* rpn = nullptr);
+// The launch conv_run gives a layer: kernel family + template choice (conv.hip conv_plan decides, conv_run's switch launches)
+enum class ConvKernel : int {
+    C64_PATCH, C64_PATCH_DIAG,                    // conv3x3_c64_kernel<DIAG>
+    PATCH256,                                     // conv3x3_patch_kernel
+    MASK_TAIL,                                    // mask_tail_kernel
+    SPLIT_128x256, SPLIT_SHORT_128x128, SPLIT_256x128, SPLIT_TALL64,      // conv_split_kernel: 3-buffer ring; 128 x 128, 2 buffers; 256 x 128; 256 x 64, 2 buffers
+    NLOOP, NLOOP_SCATTER,                         // conv1x1_nloop_kernel<SPATIAL>
+    F16X3S_256, F16X3S_128, F16X3S_64, F16X3S_G32,      // conv_glds_kernel<BN, false, EPI, F16 = true (, G32)>: split input
+    F16X3_STEM, F16X3_256, F16X3_128, F16X3_64,   // conv_f16x3_kernel: fp32 input, split in registers
+    GLDS_STEM, GLDS_128, GLDS_64,                 // conv_glds_kernel: fp32 MFMA, LDS-DMA
+    MFMA_128, MFMA_64,                            // conv_mfma_kernel: fp32 MFMA, register-staged (operands of 2 GiB and more, timing variants)
+    COUNT
+};
+// which launch would conv_run give this layer?  Same arguments as conv_run with presence flags for the pointers; host code only, no HIP call.
+// COUNT: conv_run would refuse the combination (amp_last_error says why).
+ConvKernel conv_kernel_for(int conv_mode, const amp_conv_desc& d, int groups, int fmt, int in_shift, bool res, bool mask);
+// the fused RPN head (RpnFuse) is used from this many pixels of a level on: the 128 x 256 tiles fill the chip
+constexpr long long RPN_FUSE_MIN_PIXELS = 24576;
 // comm.hip (all no-ops / errors are explicit when the context has no communicator)
 // grouped in-place SUM, after the compute stream's work so far; slot in [0, AMP_GRAD_BUCKETS): timed for amp_comm_bucket_stats
 int comm_allreduce_ranges(amp_ctx* ctx, float* base, const size_t* off, const size_t* n, int nr, int slot = -1);

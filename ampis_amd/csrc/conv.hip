@@ -60,7 +60,7 @@ struct ConvArgs {
     float* prob;            // [B][2Ho][2Wo] mask probabilities
     int res_split;          // 1: res is in that format too (decoded in the epilogue: hi + lo' * 2^-11, exact in fp32)
     int mask_split;         // 1: the ReLU mask tensor (training: the forward activation) is in that format (AMP_FMT_MASK_SPLIT)
-    int direct_epi;         // conv_split_kernel: split rows written straight from the accumulators (0: staged through LDS; EXPERIMENT switch AMP_DIRECT_EPI)
+    int direct_epi;         // conv_split_kernel: split rows written straight from the accumulators (0: staged through LDS, the form before it; always 1 now)
     int stagger;            // conv_split_kernel: the two halves of the workgroup ping-pong between loading and multiplying (0: lockstep; EXPERIMENT switch AMP_STAGGER)
     int* range_flag;        // f16x3 kernels: set to 1 when an accumulator is not finite (operand beyond fp16 range)
     int cin_win, grouped;   // K runs over KH*KW*cin_win input channels; grouped: the window of N-tile n0 starts at channel n0
@@ -2997,20 +2997,50 @@ void set_fastdiv(unsigned int d, unsigned int* mul, int* shr) {
 
 }  // namespace
 
-static int g_f16x3_bn256 = 1;   // EXPERIMENT switch: 256-wide 8-wave tiles where Cout % 256 == 0
-extern "C" void amp_debug_set_f16x3_bn256(int v) { g_f16x3_bn256 = v; }
-// one round of 128 x 256 tiles (192 ... 511 of them) is taken from this many K-steps on.  Round 4 measured the alternative's bound -- two 128 x 128 workgroups
-// per CU move 64 KB per 1536 MFMA cycles through an L2 -> LDS path that gives a CU ~33 B/clk -- and AMP_WIDE_NSTEPS=16: res4's conv1 (M = 32768, K = 1024)
-// 54 -> 49 us, fc2 55 -> 47 us, res4.0 conv1 32 -> 29 us in the per-launch table (bit-identical), 506.3 / 507.7 against 509.0 / 506.0 images/s for the step:
-// nothing outside the noise, so the rule stays at 64
-static int g_wide_nsteps = getenv("AMP_WIDE_NSTEPS") ? atoi(getenv("AMP_WIDE_NSTEPS")) : 64;
-static int g_short_k_steps = getenv("AMP_SHORT_K_STEPS") ? atoi(getenv("AMP_SHORT_K_STEPS")) : 16;     // K <= 512 (2: K <= 64 only)
-static int g_short_k = getenv("AMP_NO_SHORT_K") ? 0 : 1;      // EXPERIMENT switch: K <= 64 layers on 128 x 128 tiles, two workgroups per CU (0: the 128 x 256 ring tiles)
-extern "C" void amp_debug_set_short_k(int v) { g_short_k = v; }
-static int g_tall64 = getenv("AMP_TALL64") ? atoi(getenv("AMP_TALL64")) : 1;      // Cout = 64 layers on 256 x 64 tiles of conv_split_kernel, two workgroups per CU (0: the 128 x 64 ring tiles of conv_glds_kernel): res2 3x3 160 -> 145 us, 1x1 256 -> 64 148 -> 140 us, bit-identical
-extern "C" void amp_debug_set_tall64(int v) { g_tall64 = v; }
-static int g_split_ring = getenv("AMP_SPLIT_RING") ? atoi(getenv("AMP_SPLIT_RING")) : 1;    // EXPERIMENT switch: the 3-buffer conv_split_kernel for pre-split inputs (0: the 2-buffer conv_glds_kernel<.., F16>)
-extern "C" void amp_debug_set_split_ring(int v) { g_split_ring = v; }
+// The switches conv_plan reads: one instance (g_sw), written by the amp_debug_set_* entries below; the environment gives the initial values.
+struct ConvSwitches {
+    int f16x3_bn256 = 1;   // EXPERIMENT switch: 256-wide 8-wave tiles where Cout % 256 == 0
+    int short_k = getenv("AMP_NO_SHORT_K") ? 0 : 1;      // EXPERIMENT switch: K <= 64 layers on 128 x 128 tiles, two workgroups per CU (0: the 128 x 256 ring tiles)
+    int tall64 = getenv("AMP_TALL64") ? atoi(getenv("AMP_TALL64")) : 1;      // Cout = 64 layers on 256 x 64 tiles of conv_split_kernel, two workgroups per CU (0: the 128 x 64 ring tiles of conv_glds_kernel): res2 3x3 160 -> 145 us, 1x1 256 -> 64 148 -> 140 us, bit-identical
+    int split_ring = getenv("AMP_SPLIT_RING") ? atoi(getenv("AMP_SPLIT_RING")) : 1;    // EXPERIMENT switch: the 3-buffer conv_split_kernel for pre-split inputs (0: the 2-buffer conv_glds_kernel<.., F16>)
+    int korder = getenv("AMP_KORDER") ? atoi(getenv("AMP_KORDER")) : 0;     // EXPERIMENT switch: 1 = channel-major K order in conv_split_kernel (ConvArgs::korder)
+    // EXPERIMENT switch, default OFF: 1 = conv3x3_patch_kernel for the wide 3x3 layers (0: conv_split_kernel<128, 256>); 2 = whatever the grid size (tests).
+    // Measured (round 4, tools/lab/time_conv.py, tools/lab/pmc_p256.sh): FETCH_SIZE per launch of the FPN output conv at p2 1.97 -> 0.44 M KiB, L2 misses
+    // 35.7 -> 11.2 M -- and the SAME wall time on random operands (1410-1420 us either way; the chip holds 1.85 GHz under the ring kernel's loop and
+    // 1.97-2.16 GHz under this one, which needs 2230 cycles per K-step against 1970): the layer is limited by the power the MFMAs draw, not by its
+    // traffic; on all-zero operands (2.4 GHz either way) the ring kernel wins by the cycle ratio, 1049 against 1124 us.  And the channel-major sums move
+    // one box of the full-size gate from 0.9e-3 to 1.01e-3 px off the fp32 oracle (bare tolerance 1e-3): not adopted.
+    int patch256 = getenv("AMP_PATCH256") ? atoi(getenv("AMP_PATCH256")) : 0;
+    // EXPERIMENT switch, default OFF (AMP_NLOOP=1): several N tiles per workgroup for the short-K 1x1 layers (conv1x1_nloop_kernel).  Measured (round 4,
+    // tools/lab/time_nloop.py, A/B in one process, bit-identical): the training step's deconv 930-970 -> 856 us, res3.0's stride-2 shortcut 315 -> 291 us at B = 16
+    // and 154 -> 151 at B = 8, res4.0's shortcut 223 -> 240 us (WORSE), an inference step 16.16 against 16.12 ms: what bounds these layers is not the ring's
+    // cold start (that was the mask tail's case: four taps over the SAME pixels and a store-free epilogue) but their bytes; 0.1 ms of a 74-ms training step
+    // does not pay for a second loop structure on the training path.
+    int nloop = getenv("AMP_NLOOP") ? atoi(getenv("AMP_NLOOP")) : 0;
+    int mask_tail_loop = getenv("AMP_NO_MASK_TAIL_LOOP") ? 0 : 1;      // EXPERIMENT switch: 0 = the fused mask-head tail on conv_split_kernel<128, 256, 3> (one tap per workgroup)
+    int patch_conv = getenv("AMP_NO_PATCH_CONV") ? 0 : 1;      // EXPERIMENT switch: 0 = the implicit-GEMM kernels for the 64-channel-window 3x3 layers; 2 = conv3x3_c64_kernel whatever the grid size (tests)
+    int stagger = getenv("AMP_STAGGER") ? atoi(getenv("AMP_STAGGER")) : 1;      // ConvArgs::stagger (tools/stamp_conv.py)
+    int generic_epi = 0;   // tests: force the generic epilogue
+    int ablate = 0;        // tools/bench_conv_ablate.py: timing variants of the register-staged kernel
+};
+static ConvSwitches g_sw;
+extern "C" void amp_debug_set_f16x3_bn256(int v) { g_sw.f16x3_bn256 = v; }
+extern "C" void amp_debug_set_short_k(int v) { g_sw.short_k = v; }
+extern "C" void amp_debug_set_tall64(int v) { g_sw.tall64 = v; }
+extern "C" void amp_debug_set_split_ring(int v) { g_sw.split_ring = v; }
+extern "C" void amp_debug_set_korder(int v) { g_sw.korder = v; }
+extern "C" void amp_debug_set_patch256(int v) { g_sw.patch256 = v; }
+extern "C" void amp_debug_set_nloop(int v) { g_sw.nloop = v; }
+extern "C" void amp_debug_set_mask_tail_loop(int v) { g_sw.mask_tail_loop = v; }
+extern "C" void amp_debug_set_patch_conv(int v) { g_sw.patch_conv = v; }
+extern "C" void amp_debug_set_conv_generic_epilogue(int on) { g_sw.generic_epi = on; }
+extern "C" void amp_debug_set_conv_ablate(int mode) { g_sw.ablate = mode; }
+// Two thresholds that were switches once.  One round of 128 x 256 tiles (192 ... 511 of them) is taken from WIDE_NSTEPS K-steps on.  Round 4 measured the
+// alternative's bound -- two 128 x 128 workgroups per CU move 64 KB per 1536 MFMA cycles through an L2 -> LDS path that gives a CU ~33 B/clk -- and 16 instead
+// of 64: res4's conv1 (M = 32768, K = 1024) 54 -> 49 us, fc2 55 -> 47 us, res4.0 conv1 32 -> 29 us in the per-launch table (bit-identical), 506.3 / 507.7
+// against 509.0 / 506.0 images/s for the step: nothing outside the noise, so the rule stays at 64
+constexpr int WIDE_NSTEPS = 64;
+constexpr int SHORT_K_STEPS = 16;     // the two-buffer 128 x 128 tiles take K <= 512
 #ifdef AMP_STAMP
 extern "C" int amp_debug_read_stamps(unsigned long long* out) {     // 64 values; zeroes the device counters
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamp), sizeof(unsigned long long) * 64) != hipSuccess) return -1;
@@ -3023,35 +3053,6 @@ extern "C" int amp_debug_read_stamp_clock(unsigned long long* out) {     // 2 va
     return hipMemcpyToSymbol(HIP_SYMBOL(g_stamp_clk), z, sizeof(z)) == hipSuccess ? 0 : -1;
 }
 #endif
-static int g_direct_epi = getenv("AMP_DIRECT_EPI") ? atoi(getenv("AMP_DIRECT_EPI")) : 1;
-extern "C" void amp_debug_set_direct_epi(int v) { g_direct_epi = v; }
-static int g_korder = getenv("AMP_KORDER") ? atoi(getenv("AMP_KORDER")) : 0;     // EXPERIMENT switch: 1 = channel-major K order in conv_split_kernel (ConvArgs::korder)
-extern "C" void amp_debug_set_korder(int v) { g_korder = v; }
-// EXPERIMENT switch, default OFF: 1 = conv3x3_patch_kernel for the wide 3x3 layers (0: conv_split_kernel<128, 256>); 2 = whatever the grid size (tests).
-// Measured (round 4, tools/lab/time_conv.py, tools/lab/pmc_p256.sh): FETCH_SIZE per launch of the FPN output conv at p2 1.97 -> 0.44 M KiB, L2 misses
-// 35.7 -> 11.2 M -- and the SAME wall time on random operands (1410-1420 us either way; the chip holds 1.85 GHz under the ring kernel's loop and
-// 1.97-2.16 GHz under this one, which needs 2230 cycles per K-step against 1970): the layer is limited by the power the MFMAs draw, not by its
-// traffic; on all-zero operands (2.4 GHz either way) the ring kernel wins by the cycle ratio, 1049 against 1124 us.  And the channel-major sums move
-// one box of the full-size gate from 0.9e-3 to 1.01e-3 px off the fp32 oracle (bare tolerance 1e-3): not adopted.
-static int g_patch256 = getenv("AMP_PATCH256") ? atoi(getenv("AMP_PATCH256")) : 0;
-extern "C" void amp_debug_set_patch256(int v) { g_patch256 = v; }
-// EXPERIMENT switch, default OFF (AMP_NLOOP=1): several N tiles per workgroup for the short-K 1x1 layers (conv1x1_nloop_kernel).  Measured (round 4,
-// tools/lab/time_nloop.py, A/B in one process, bit-identical): the training step's deconv 930-970 -> 856 us, res3.0's stride-2 shortcut 315 -> 291 us at B = 16
-// and 154 -> 151 at B = 8, res4.0's shortcut 223 -> 240 us (WORSE), an inference step 16.16 against 16.12 ms: what bounds these layers is not the ring's
-// cold start (that was the mask tail's case: four taps over the SAME pixels and a store-free epilogue) but their bytes; 0.1 ms of a 74-ms training step
-// does not pay for a second loop structure on the training path.
-static int g_nloop = getenv("AMP_NLOOP") ? atoi(getenv("AMP_NLOOP")) : 0;
-extern "C" void amp_debug_set_nloop(int v) { g_nloop = v; }
-static int g_mask_tail_loop = getenv("AMP_NO_MASK_TAIL_LOOP") ? 0 : 1;      // EXPERIMENT switch: 0 = the fused mask-head tail on conv_split_kernel<128, 256, 3> (one tap per workgroup)
-extern "C" void amp_debug_set_mask_tail_loop(int v) { g_mask_tail_loop = v; }
-static int g_patch_conv = getenv("AMP_NO_PATCH_CONV") ? 0 : 1;      // EXPERIMENT switch: 0 = the implicit-GEMM kernels for the 64-channel-window 3x3 layers; 2 = conv3x3_c64_kernel whatever the grid size (tests)
-extern "C" void amp_debug_set_patch_conv(int v) { g_patch_conv = v; }
-static int g_stagger = getenv("AMP_STAGGER") ? atoi(getenv("AMP_STAGGER")) : 1;
-extern "C" void amp_debug_set_stagger(int v) { g_stagger = v; }
-static int g_conv_generic_epi = 0;   // tests: force the generic epilogue
-extern "C" void amp_debug_set_conv_generic_epilogue(int on) { g_conv_generic_epi = on; }
-static int g_conv_ablate = 0;   // tools/bench_conv_ablate.py: timing variants of the register-staged kernel
-extern "C" void amp_debug_set_conv_ablate(int mode) { g_conv_ablate = mode; }
 
 static int conv_impl(amp_ctx* ctx, const amp_conv_desc* d, int groups, const float* x, const float* w, const float* scale,
                      const float* shift, const float* res, const float* mask, float* y) {
@@ -3137,7 +3138,7 @@ extern "C" int amp_conv2d_nhwc_fmt(amp_ctx* ctx, const amp_conv_desc* d, const f
 
 // Stage a11, fused: x [B,H,W,256] (a pyramid level, split rows) -> 3x3 conv 256 -> 256 + bias + ReLU -> the 16 predictor rows (3 objectness
 // logits, 12 anchor deltas, one zero row; w_pred [16][256], b_pred [16]) -> pred [B*H*W][16]; the hidden tensor is never written.
-// The predictor rows are split here per call (the model keeps its own split copy); B*H*W >= 24576 so that the 128 x 256 tiles fill the chip.
+// The predictor rows are split here per call (the model keeps its own split copy); B*H*W >= amp::RPN_FUSE_MIN_PIXELS so that the 128 x 256 tiles fill the chip.
 extern "C" int amp_rpn_head_fused(amp_ctx* ctx, const float* x_split, int B, int H, int W, const float* w_conv, const float* b_conv, const float* w_pred,
                                   const float* b_pred, float* pred) {
     return amp_rpn_head_fused_ld(ctx, x_split, B, H, W, w_conv, b_conv, w_pred, b_pred, 16, pred);
@@ -3148,7 +3149,7 @@ extern "C" int amp_rpn_head_fused_ld(amp_ctx* ctx, const float* x_split, int B, 
     AMP_REQUIRE(ctx && x_split && w_conv && b_conv && w_pred && b_pred && pred && B > 0 && H > 0 && W > 0, "amp_rpn_head_fused: bad argument");
     AMP_REQUIRE(ld == 16 || ld == 32 || ld == 48, "amp_rpn_head_fused: ld = %d, must be 16, 32 or 48", ld);
     AMP_REQUIRE(ctx->conv_mode == AMP_CONV_F16X3, "amp_rpn_head_fused: AMP_CONV_F16X3 only (the fp32 path runs the two convolutions)");
-    AMP_REQUIRE((long long)B * H * W >= 24576, "amp_rpn_head_fused: fewer than 24576 pixels: run the two convolutions (amp_conv2d_nhwc_fmt)");
+    AMP_REQUIRE((long long)B * H * W >= amp::RPN_FUSE_MIN_PIXELS, "amp_rpn_head_fused: fewer than %lld pixels: run the two convolutions (amp_conv2d_nhwc_fmt)", amp::RPN_FUSE_MIN_PIXELS);
     float* wps = nullptr;
     AMP_HIP_CHECK(hipMalloc(&wps, (size_t)ld * 256 * sizeof(float)));
     hipLaunchKernelGGL(split_weights_kernel, dim3(8), dim3(256), 0, ctx->stream, w_pred, (size_t)ld, 256, reinterpret_cast<unsigned int*>(wps));
@@ -3422,11 +3423,19 @@ extern "C" void amp_debug_set_stem_pool(int v) { g_stem_pool = v; }
 // Stem (7x7 stride 2 on the [B,H,W,4] input, weights [64][7][8][4], ReLU) + max-pool 3x3 stride 2 pad 1 in one kernel: AMP_CONV_F16X3 with
 // pre-split weights only.  Returns 1 (nothing launched) when the fused form does not apply -- the caller runs the two kernels.
 bool amp::stem_pool_applies(amp_ctx* ctx, const float* w_split) {
-    return g_stem_pool && ctx->conv_mode == AMP_CONV_F16X3 && w_split && g_conv_ablate == 0;
+    return g_stem_pool && ctx->conv_mode == AMP_CONV_F16X3 && w_split && g_sw.ablate == 0;
 }
-int amp::stem_pool_run(amp_ctx* ctx, int B, int H, int W, const float* x, int x_split, const float* w_split, const float* scale, const float* shift,
-                       float* pool, int pool_split) {
-    if (!amp::stem_pool_applies(ctx, w_split)) return 1;
+// a profiling record for the launch that follows: null outside a profile, or when the pool is used up (the profile is then marked truncated).
+// variant 0 = a launch of the DOMINANT kernel (conv_split_kernel<128x256>, fp32 mode conv_glds_kernel<128>)
+static amp_prof_rec* prof_open(amp_ctx* ctx, double flops, double bytes, int M, int N, int K, int variant = 1) {
+    if (!ctx->prof_on) return nullptr;
+    if (ctx->prof_used >= ctx->prof_pool.size()) { ctx->prof_truncated = true; return nullptr; }
+    amp_prof_rec* rec = &ctx->prof_pool[ctx->prof_used++];
+    rec->flops = flops; rec->variant = variant; rec->bytes = bytes; rec->M = M; rec->N = N; rec->K = K;
+    return rec;
+}
+// the stem as the fused stem + pool kernels see it: 7x7 stride 2 pad 3 over the H x W frame of 4-channel pixels (x: null for the uint8 kernel)
+static ConvArgs stem_args(amp_ctx* ctx, int B, int H, int W, const float* x, const float* w_split, const float* scale, const float* shift) {
     ConvArgs a = ConvArgs();
     a.x = x; a.w = w_split; a.scale = scale; a.shift = shift;
     a.B = B; a.H = H; a.W = W; a.Cin = 4; a.Cout = 64;
@@ -3438,6 +3447,12 @@ int amp::stem_pool_run(amp_ctx* ctx, int B, int H, int W, const float* x, int x_
     a.relu = 1;
     a.in_scale = a.out_scale = 1.0f;
     a.range_flag = ctx->d_conv_flag;
+    return a;
+}
+int amp::stem_pool_run(amp_ctx* ctx, int B, int H, int W, const float* x, int x_split, const float* w_split, const float* scale, const float* shift,
+                       float* pool, int pool_split) {
+    if (!amp::stem_pool_applies(ctx, w_split)) return 1;
+    const ConvArgs a = stem_args(ctx, B, H, W, x, w_split, scale, shift);
     const size_t x_bytes = (size_t)B * H * W * 4 * sizeof(float), w_bytes = (size_t)64 * a.K * sizeof(float);
     if (a.Ho < 1 || a.Wo < 1 || x_bytes >= (size_t)OOB_VOFF || (long long)B * H * W >= (1ll << 27)) {
         AMP_REQUIRE(!x_split, "stem_pool_run: a split input needs the fused kernel, which this size does not fit");
@@ -3447,18 +3462,9 @@ int amp::stem_pool_run(amp_ctx* ctx, int B, int H, int W, const float* x, int x_
     sp.pool = pool; sp.pool_split = pool_split;
     sp.Hq = (a.Ho + 2 - 3) / 2 + 1; sp.Wq = (a.Wo + 2 - 3) / 2 + 1;
     sp.tiles_y = amp::cdiv(sp.Hq, SP_PH); sp.tiles_x = amp::cdiv(sp.Wq, SP_PW);
-    amp_prof_rec* rec = nullptr;
-    if (ctx->prof_on) {
-        if (ctx->prof_used < ctx->prof_pool.size()) {
-            rec = &ctx->prof_pool[ctx->prof_used++];
-            rec->flops = 2.0 * (double)B * a.Ho * a.Wo * 64.0 * 7.0 * 8.0 * 4.0;   // useful work of the stem (as conv_run counts it), not the halo
-            rec->variant = 1;
-            rec->bytes = (double)x_bytes + (double)w_bytes + 4.0 * (double)B * sp.Hq * sp.Wq * 64.0;   // input + weights + the pooled tensor
-            rec->M = B * a.Ho * a.Wo; rec->N = 64; rec->K = 7 * 8 * 4;
-        } else {
-            ctx->prof_truncated = true;
-        }
-    }
+    // flops: useful work of the stem (as conv_run counts it), not the halo; bytes: input + weights + the pooled tensor
+    amp_prof_rec* rec = prof_open(ctx, 2.0 * (double)B * a.Ho * a.Wo * 64.0 * 7.0 * 8.0 * 4.0,
+                                  (double)x_bytes + (double)w_bytes + 4.0 * (double)B * sp.Hq * sp.Wq * 64.0, B * a.Ho * a.Wo, 64, 7 * 8 * 4);
     amp::ProfLaunchScope timed(rec ? rec->e0 : nullptr, rec ? rec->e1 : nullptr);      // attached to the launch below (AMP_TIMED_LAUNCH)
     if (x_split) AMP_TIMED_LAUNCH(stem_pool_f16x3_kernel<true>, dim3((unsigned)(B * sp.tiles_y * sp.tiles_x)), dim3(512), 0, ctx->stream, a, sp,
                                     (unsigned int)x_bytes, (unsigned int)w_bytes);
@@ -3475,17 +3481,7 @@ bool amp::stem_u8_applies(amp_ctx* ctx, const float* w_split) { return g_stem_u8
 int amp::stem_pool_u8_run(amp_ctx* ctx, const uint8_t* img, int B, int H, int W, int Hp, int Wp, const float mean[3], const float std_[3],
                           const int* img_hw, const float* w_split, const float* scale, const float* shift, float* pool, int pool_split) {
     AMP_REQUIRE(amp::stem_u8_applies(ctx, w_split) && img && mean && std_ && pool && B > 0 && Hp >= H && Wp >= W, "stem_pool_u8_run: bad argument");
-    ConvArgs a = ConvArgs();
-    a.w = w_split; a.scale = scale; a.shift = shift;
-    a.B = B; a.H = Hp; a.W = Wp; a.Cin = 4; a.Cout = 64;
-    a.KH = 7; a.KW = 8; a.stride = 2; a.pad = 3;
-    a.Ho = (Hp + 2 * 3 - 7) / 2 + 1;
-    a.Wo = (Wp + 2 * 3 - 7) / 2 + 1;
-    a.cin_win = 4;
-    a.K = 7 * 8 * 4; a.nsteps = 7;
-    a.relu = 1;
-    a.in_scale = a.out_scale = 1.0f;
-    a.range_flag = ctx->d_conv_flag;
+    const ConvArgs a = stem_args(ctx, B, Hp, Wp, nullptr, w_split, scale, shift);
     const size_t w_bytes = (size_t)64 * a.K * sizeof(float);
     StemPoolArgs sp;
     sp.pool = pool; sp.pool_split = pool_split;
@@ -3494,18 +3490,9 @@ int amp::stem_pool_u8_run(amp_ctx* ctx, const uint8_t* img, int B, int H, int W,
     StemU8Args u;
     u.img = img; u.H = H; u.W = W; u.img_hw = img_hw;
     u.m0 = mean[0]; u.m1 = mean[1]; u.m2 = mean[2]; u.s0 = std_[0]; u.s1 = std_[1]; u.s2 = std_[2];
-    amp_prof_rec* rec = nullptr;
-    if (ctx->prof_on) {
-        if (ctx->prof_used < ctx->prof_pool.size()) {
-            rec = &ctx->prof_pool[ctx->prof_used++];
-            rec->flops = 2.0 * (double)B * a.Ho * a.Wo * 64.0 * 7.0 * 8.0 * 4.0;   // useful work of the stem (as conv_run counts it), not the halo
-            rec->variant = 1;
-            rec->bytes = 3.0 * (double)B * H * W + (double)w_bytes + 4.0 * (double)B * sp.Hq * sp.Wq * 64.0;       // uint8 pixels + weights + the pooled tensor
-            rec->M = B * a.Ho * a.Wo; rec->N = 64; rec->K = 7 * 8 * 4;
-        } else {
-            ctx->prof_truncated = true;
-        }
-    }
+    // flops: useful work of the stem (as conv_run counts it), not the halo; bytes: uint8 pixels + weights + the pooled tensor
+    amp_prof_rec* rec = prof_open(ctx, 2.0 * (double)B * a.Ho * a.Wo * 64.0 * 7.0 * 8.0 * 4.0,
+                                  3.0 * (double)B * H * W + (double)w_bytes + 4.0 * (double)B * sp.Hq * sp.Wq * 64.0, B * a.Ho * a.Wo, 64, 7 * 8 * 4);
     amp::ProfLaunchScope timed(rec ? rec->e0 : nullptr, rec ? rec->e1 : nullptr);
     AMP_TIMED_LAUNCH(stem_pool_u8_kernel, dim3((unsigned)(B * sp.tiles_y * sp.tiles_x)), dim3(512), 0, ctx->stream, a, sp, u, (unsigned int)w_bytes);
     AMP_HIP_CHECK(hipGetLastError());
@@ -3517,276 +3504,328 @@ extern "C" int amp_conv2d_nhwc(amp_ctx* ctx, const amp_conv_desc* d, const float
     return amp_conv2d_nhwc_ex(ctx, d, x, w, scale, shift, res, nullptr, y);
 }
 
-int amp::conv_run(amp_ctx* ctx, const amp_conv_desc* d, int groups, const float* x, const float* w, const float* w_split, int force_f32,
-                  const float* scale, const float* shift, const float* res, const float* mask, float* y, int in_shift, int fmt,
-                  const amp::PredictFuse* fuse, const amp::RpnFuse* rpn) {
-    AMP_REQUIRE(ctx && d && x && w && y, "amp_conv2d_nhwc: null argument");
+namespace {
+struct ConvPlanIn {             // what the selection depends on: conv_run's arguments with presence flags for the pointers
+    int mode;                   // amp_ctx::conv_mode
+    amp_conv_desc d;
+    int groups, fmt, in_shift, force_f32;
+    bool res, mask, scale;
+    int fuse;                   // 0: none, 1: PredictFuse, 2: RpnFuse with rpn_ld predictor rows
+    int rpn_ld;
+};
+struct ConvPlan {
+    amp::ConvKernel kernel;
+    int epi;                    // the launch's epilogue template argument (0 generic, 1 rows, 2 scatter / upsampled residual, 3: predict or RPN tail with 16 rows, 4 / 5: 32 / 48 rows)
+    int ntn, nblk, stagger;     // ConvArgs::ntn, ::nblk (the grid), ::stagger
+    int tiles_x, tiles_y;       // the patch kernels' 8 x 16 pixel tiles
+    int nloop_nt;               // N tiles per workgroup of conv1x1_nloop_kernel
+    int rpn_nbp;                // blocks of 16 predictor rows of the fused RPN tail
+    bool dominant;              // a launch of the dominant kernel (amp_prof_rec::variant 0)
+    bool f16x3;                 // the kernel reads the weights in the split layout
+    int Ho, Wo, M, K, nsteps, cin_win, cpg, out_mode, y_split, korder;      // the layer as ConvArgs carries it
+    size_t x_bytes, w_bytes;
+};
+
+// conv3x3_c64_kernel is taken from 512 tiles of 8 x 16 pixels x 64 channels on (patch_conv = 2: whatever the grid size)
+bool c64_patch_fills(const ConvSwitches& sw, long long tiles) { return sw.patch_conv == 2 || tiles >= 512; }
+
+// Which kernel takes the layer, and with which grid: pure host code (no HIP call, nothing of a context but its mode).  AMP_ERR_ARG + amp_last_error
+// on a combination no kernel supports.
+int conv_plan(const ConvPlanIn& in, const ConvSwitches& sw, ConvPlan* plan) {
+    using amp::ConvKernel;
+    const amp_conv_desc* d = &in.d;
+    ConvPlan p = ConvPlan();
     AMP_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0, "amp_conv2d_nhwc: bad shape");
     AMP_REQUIRE(d->Cin % 4 == 0, "amp_conv2d_nhwc: Cin=%d must be a multiple of 4 (pad the input)", d->Cin);
     AMP_REQUIRE(d->KH > 0 && d->KW > 0 && d->stride > 0 && d->pad >= 0, "amp_conv2d_nhwc: bad window");
     AMP_REQUIRE(d->res_mode >= 0 && d->res_mode <= 2 && d->out_mode >= 0 && d->out_mode <= 2,
                 "amp_conv2d_nhwc: bad res_mode/out_mode");
-    AMP_REQUIRE(d->res_mode == 0 || res != nullptr, "amp_conv2d_nhwc: res_mode=%d needs res", d->res_mode);
-    ConvArgs a;
-    a.x = x; a.w = w; a.scale = scale; a.shift = shift; a.res = res; a.mask = mask; a.y = y;
-    a.B = d->B; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Cout = d->Cout;
-    a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad;
-    a.Ho = (d->H + 2 * d->pad - d->KH) / d->stride + 1;
-    a.Wo = (d->W + 2 * d->pad - d->KW) / d->stride + 1;
-    AMP_REQUIRE(a.Ho > 0 && a.Wo > 0, "amp_conv2d_nhwc: empty output");
-    AMP_REQUIRE(d->res_mode != 2 || (a.Ho % 2 == 0 && a.Wo % 2 == 0),
-                "amp_conv2d_nhwc: res_mode=2 needs even output size, got %dx%d", a.Ho, a.Wo);
-    AMP_REQUIRE(d->out_mode != 1 || d->Cout % 4 == 0, "amp_conv2d_nhwc: out_mode=1 needs Cout %% 4 == 0");
-    const long long Mll = (long long)a.B * a.Ho * a.Wo;
-    AMP_REQUIRE(Mll < (1ll << 31) / 4 && (long long)a.B * a.H * a.W < (1ll << 31),
+    AMP_REQUIRE(d->res_mode == 0 || in.res, "amp_conv2d_nhwc: res_mode=%d needs res", d->res_mode);
+    const int Cin = d->Cin, Cout = d->Cout, KH = d->KH, KW = d->KW;
+    p.Ho = (d->H + 2 * d->pad - KH) / d->stride + 1;
+    p.Wo = (d->W + 2 * d->pad - KW) / d->stride + 1;
+    AMP_REQUIRE(p.Ho > 0 && p.Wo > 0, "amp_conv2d_nhwc: empty output");
+    AMP_REQUIRE(d->res_mode != 2 || (p.Ho % 2 == 0 && p.Wo % 2 == 0),
+                "amp_conv2d_nhwc: res_mode=2 needs even output size, got %dx%d", p.Ho, p.Wo);
+    AMP_REQUIRE(d->out_mode != 1 || Cout % 4 == 0, "amp_conv2d_nhwc: out_mode=1 needs Cout %% 4 == 0");
+    const long long Mll = (long long)d->B * p.Ho * p.Wo;
+    AMP_REQUIRE(Mll < (1ll << 31) / 4 && (long long)d->B * d->H * d->W < (1ll << 31),
                 "amp_conv2d_nhwc: tensor too large for 32-bit pixel indices");
-    a.M = (int)Mll;
-    a.grouped = groups > 1;
-    a.cin_win = a.Cin;
-    int cpg = a.Cin;
-    if (a.grouped) {
-        AMP_REQUIRE(d->Cin == d->Cout && d->Cin % groups == 0 && d->Cout % 64 == 0 && d->out_mode == 0,
+    p.M = (int)Mll;
+    const bool grouped = in.groups > 1;
+    p.cin_win = p.cpg = Cin;
+    if (grouped) {
+        AMP_REQUIRE(Cin == Cout && Cin % in.groups == 0 && Cout % 64 == 0 && d->out_mode == 0,
                     "amp_conv2d_grouped_nhwc: needs Cin == Cout, a multiple of 64 and of groups, out_mode 0");
-        cpg = d->Cin / groups;
-        AMP_REQUIRE(cpg == 8 || cpg == 16 || cpg == 32 || cpg == 64, "amp_conv2d_grouped_nhwc: %d channels per group (8/16/32/64 supported)", cpg);
-        a.cin_win = 64;
+        p.cpg = Cin / in.groups;
+        AMP_REQUIRE(p.cpg == 8 || p.cpg == 16 || p.cpg == 32 || p.cpg == 64, "amp_conv2d_grouped_nhwc: %d channels per group (8/16/32/64 supported)", p.cpg);
+        p.cin_win = 64;
     }
-    a.K = a.KH * a.KW * a.cin_win;
-    a.nsteps = amp::cdiv(a.K, BK);
-    a.relu = d->relu; a.res_mode = d->res_mode; a.out_mode = d->out_mode;
-
-    set_fastdiv((unsigned int)(a.Ho * a.Wo), &a.div_howo_mul, &a.div_howo_shr);
-    set_fastdiv((unsigned int)a.Wo, &a.div_wo_mul, &a.div_wo_shr);
-    const int epi = (g_conv_generic_epi || (a.Cout & 3) != 0) ? 0 : ((a.res_mode == 2 || a.out_mode != 0) ? 2 : 1);
-
-    constexpr int BM = 128;
-    const int ntm = amp::cdiv(a.M, BM);
-    amp_prof_rec* rec = nullptr;
-    if (ctx->prof_on) {
-        if (ctx->prof_used < ctx->prof_pool.size()) {
-            rec = &ctx->prof_pool[ctx->prof_used++];
-            rec->flops = 2.0 * (double)a.M * (double)a.Cout * (double)d->KH * (double)d->KW * (double)cpg;   // useful work
-            rec->variant = 1;      // 0 = a launch of the DOMINANT kernel (set where it is launched: conv_split_kernel<128x256>, fp32 mode conv_glds_kernel<128>)
-        } else {
-            ctx->prof_truncated = true;
-        }
-    }
-    amp::ProfLaunchScope timed(rec ? rec->e0 : nullptr, rec ? rec->e1 : nullptr);      // the convolution kernel launched below carries the events
-    const size_t x_bytes = (size_t)a.B * a.H * a.W * a.Cin * sizeof(float);
-    const size_t w_bytes = (size_t)a.Cout * a.K * sizeof(float);
+    p.K = KH * KW * p.cin_win;
+    p.nsteps = amp::cdiv(p.K, BK);
+    const int epi = (sw.generic_epi || (Cout & 3) != 0) ? 0 : ((d->res_mode == 2 || d->out_mode != 0) ? 2 : 1);
+    const int ntm = amp::cdiv(p.M, 128);
+    p.x_bytes = (size_t)d->B * d->H * d->W * Cin * sizeof(float);
+    p.w_bytes = (size_t)Cout * p.K * sizeof(float);
     // LDS-DMA kernel: every layer but the stem (Cin = 4); buffers must stay below the out-of-range marker (2 GiB)
-    const bool small = g_conv_ablate == 0 && x_bytes < (size_t)OOB_VOFF && w_bytes < (size_t)OOB_VOFF;
-    const bool glds = (a.Cin % BK == 0) && small;
-    AMP_REQUIRE(!a.grouped || glds, "amp_conv2d_grouped_nhwc: operands must stay below 2 GiB");
-    const bool stem = a.Cin == 4 && a.KW == 8 && a.Cout <= 64 && small;   // the padded 7x7 stem
-    a.range_flag = ctx->d_conv_flag;
-    const bool x_is_split = (fmt & 1) != 0;
-    a.y_split = (fmt & 2) ? 1 : 0;
-    a.res_split = (fmt & 4) ? 1 : 0;
-    a.mask_split = (fmt & 8) ? 1 : 0;
-    a.stagger = g_stagger;
-    a.korder = (g_korder && a.KH * a.KW > 1) ? 1 : 0;
-    a.direct_epi = g_direct_epi;
-    a.pred_w = a.pred_b = nullptr; a.pred_cls = nullptr; a.pred_K = 0; a.prob = nullptr;
-    if (fuse) {     // the mask head's deconv with ReLU + predictor + sigmoid in its epilogue (conv_epilogue_predict)
-        AMP_REQUIRE(x_is_split && d->out_mode == 1 && a.Cout == 1024 && a.KH == 1 && a.KW == 1 && a.relu && !res && !mask && !scale && g_split_ring,
+    const bool small = sw.ablate == 0 && p.x_bytes < (size_t)OOB_VOFF && p.w_bytes < (size_t)OOB_VOFF;
+    const bool glds = (Cin % BK == 0) && small;
+    AMP_REQUIRE(!grouped || glds, "amp_conv2d_grouped_nhwc: operands must stay below 2 GiB");
+    const bool stem = Cin == 4 && KW == 8 && Cout <= 64 && small;   // the padded 7x7 stem
+    const bool x_is_split = (in.fmt & 1) != 0, res_split = (in.fmt & 4) != 0, mask_split = (in.fmt & 8) != 0;
+    p.y_split = (in.fmt & 2) ? 1 : 0;
+    p.korder = (sw.korder && KH * KW > 1) ? 1 : 0;
+    p.out_mode = d->out_mode;
+    p.rpn_nbp = 1;
+    if (in.fuse == 1) {     // the mask head's deconv with ReLU + predictor + sigmoid in its epilogue (conv_epilogue_predict)
+        AMP_REQUIRE(x_is_split && d->out_mode == 1 && Cout == 1024 && KH == 1 && KW == 1 && d->relu && !in.res && !in.mask && !in.scale && sw.split_ring,
                     "conv: the fused deconv-predict epilogue needs a split input, Cout = 4 x 256, ReLU and the ring kernel");
-        AMP_REQUIRE(fuse->pred_w && fuse->pred_b && fuse->cls && fuse->prob && fuse->K >= 1, "conv: incomplete PredictFuse");
-        a.out_mode = 3;
-        a.pred_w = fuse->pred_w; a.pred_b = fuse->pred_b; a.pred_cls = fuse->cls; a.pred_K = fuse->K; a.prob = fuse->prob;
-    }
-    a.rpn_w = a.rpn_b = nullptr; a.rpn_pred = nullptr;
-    int rpn_nbp = 1;
-    if (rpn) {      // the RPN head's predictors in the 3x3 conv's epilogue (conv_epilogue_rpn): one 128 x 256 tile = all hidden channels of 128 pixels
-        AMP_REQUIRE(!fuse && x_is_split && d->out_mode == 0 && a.Cout == 256 && a.relu && !res && !mask && g_split_ring && in_shift == 0,
+        p.out_mode = 3;
+    } else if (in.fuse == 2) {      // the RPN head's predictors in the 3x3 conv's epilogue (conv_epilogue_rpn): one 128 x 256 tile = all hidden channels of 128 pixels
+        AMP_REQUIRE(x_is_split && d->out_mode == 0 && Cout == 256 && d->relu && !in.res && !in.mask && sw.split_ring && in.in_shift == 0,
                     "conv: the fused RPN epilogue needs a split input, Cout = 256, ReLU and the ring kernel");
-        AMP_REQUIRE(rpn->w_split && rpn->bias && rpn->pred, "conv: incomplete RpnFuse");
-        AMP_REQUIRE(rpn->ld == 16 || ((rpn->ld == 32 || rpn->ld == 48) && !a.korder), "conv: the fused RPN epilogue writes 16, 32 or 48 predictor rows (16 with AMP_KORDER), not %d", rpn->ld);
-        rpn_nbp = rpn->ld / 16;
-        a.out_mode = 4;
-        a.y_split = 0;
-        a.rpn_w = rpn->w_split; a.rpn_b = rpn->bias; a.rpn_pred = rpn->pred;
+        AMP_REQUIRE(in.rpn_ld == 16 || ((in.rpn_ld == 32 || in.rpn_ld == 48) && !p.korder), "conv: the fused RPN epilogue writes 16, 32 or 48 predictor rows (16 with AMP_KORDER), not %d", in.rpn_ld);
+        p.rpn_nbp = in.rpn_ld / 16;
+        p.out_mode = 4;
+        p.y_split = 0;
     }
-    if (rec) {      // algorithmic bytes of this launch: every operand once (amp_prof_launches; a 1x1 conv reads only the pixels its stride samples)
-        const double in_rows = (a.KH == 1 && a.KW == 1) ? (double)a.M : (double)a.B * a.H * a.W;
-        const double out_vals = a.out_mode == 3 ? (double)a.M * 4.0 : a.out_mode == 4 ? (double)a.M * 16.0 * rpn_nbp : (double)a.M * a.Cout;
-        const double res_vals = !res ? 0.0 : (a.res_mode == 2 ? (double)a.M * a.Cout / 4.0 : (double)a.M * a.Cout);
-        rec->bytes = 4.0 * (in_rows * a.Cin + (double)a.Cout * a.K + out_vals + res_vals + (mask ? (double)a.M * a.Cout : 0.0));
-        rec->M = a.M; rec->N = a.Cout; rec->K = d->KH * d->KW * cpg;
-    }
-    AMP_REQUIRE(!a.mask_split || (mask != nullptr && epi != 0 && a.Cout % 32 == 0 && a.out_mode == 0), "conv: a split-format mask needs mask, Cout %% 32 == 0, out_mode 0 and a fast epilogue");
-    AMP_REQUIRE(!a.res_split || (res != nullptr && epi != 0 && a.Cout % 32 == 0), "conv: a split-format residual needs res, Cout %% 32 == 0 and a fast epilogue");
+    AMP_REQUIRE(!mask_split || (in.mask && epi != 0 && Cout % 32 == 0 && p.out_mode == 0), "conv: a split-format mask needs mask, Cout %% 32 == 0, out_mode 0 and a fast epilogue");
+    AMP_REQUIRE(!res_split || (in.res && epi != 0 && Cout % 32 == 0), "conv: a split-format residual needs res, Cout %% 32 == 0 and a fast epilogue");
     // split output: out_mode 0; or the 2x2 deconv scatter (out_mode 1) straight from the ring kernel's accumulators -- checked again where the kernel is chosen
-    const bool deconv_split = a.y_split && a.out_mode == 1;
-    AMP_REQUIRE(!a.y_split || ((a.out_mode == 0 || a.out_mode == 1) && a.Cout % 32 == 0 && epi != 0), "conv: split output needs out_mode 0 (or the deconv scatter) and Cout %% 32 == 0");
-    AMP_REQUIRE(!deconv_split || ((a.Cout / 4) % 64 == 0 && !res && !mask && x_is_split && g_split_ring && g_direct_epi && a.Cout % 256 == 0),
+    const bool deconv_split = p.y_split && p.out_mode == 1;
+    AMP_REQUIRE(!p.y_split || ((p.out_mode == 0 || p.out_mode == 1) && Cout % 32 == 0 && epi != 0), "conv: split output needs out_mode 0 (or the deconv scatter) and Cout %% 32 == 0");
+    AMP_REQUIRE(!deconv_split || ((Cout / 4) % 64 == 0 && !in.res && !in.mask && x_is_split && sw.split_ring && Cout % 256 == 0),
                 "conv: a split deconv output needs Cout / 4 %% 64 == 0, a split input, no residual / mask and the ring kernel's direct epilogue");
-    AMP_REQUIRE(!x_is_split || (ctx->conv_mode == AMP_CONV_F16X3 && !force_f32 && a.Cin % 32 == 0 && glds),
+    AMP_REQUIRE(!x_is_split || (in.mode == AMP_CONV_F16X3 && !in.force_f32 && Cin % 32 == 0 && glds),
                 "conv: a split-format input needs AMP_CONV_F16X3, Cin %% 32 == 0 and operands below 2 GiB");
-    a.in_scale = (in_shift != 0) ? ldexpf(1.0f, in_shift) : 1.0f;
-    a.out_scale = (in_shift != 0) ? ldexpf(1.0f, -in_shift) : 1.0f;
-    if (ctx->conv_mode == AMP_CONV_F16X3 && !force_f32 && g_conv_ablate == 0 && (glds || stem)) {
-        if (!w_split) {   // per-call split into the context's scratch (stream order makes the reuse safe)
-            if (ctx->split_bytes < w_bytes) {
-                AMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-                if (ctx->split_scratch) AMP_HIP_CHECK(hipFree(ctx->split_scratch));
-                ctx->split_scratch = nullptr; ctx->split_bytes = 0;
-                AMP_HIP_CHECK(hipMalloc(&ctx->split_scratch, w_bytes));
-                ctx->split_bytes = w_bytes;
-            }
-            hipLaunchKernelGGL(split_weights_kernel, dim3(2048), dim3(256), 0, ctx->stream, w, (size_t)a.Cout, a.K,
-                               reinterpret_cast<unsigned int*>(ctx->split_scratch));
-            w_split = ctx->split_scratch;
-        }
-        a.w = w_split;
-        const int nblk128 = ntm * amp::cdiv(a.Cout, 128);
+    p.epi = epi;
+    p.stagger = sw.stagger;
+    p.tiles_x = amp::cdiv(p.Wo, 16); p.tiles_y = amp::cdiv(p.Ho, 8);
+    auto take = [&](ConvKernel k, int ntn, long long nblk, bool dominant = false) {
+        p.kernel = k; p.ntn = ntn; p.nblk = (int)nblk; p.dominant = dominant;
+        *plan = p;
+        return AMP_OK;
+    };
+    const int nblk128 = ntm * amp::cdiv(Cout, 128);
+    if (in.mode == AMP_CONV_F16X3 && !in.force_f32 && sw.ablate == 0 && (glds || stem)) {
+        p.f16x3 = true;
         // 256-wide tiles (8 waves, one workgroup per CU) when they fill the chip twice -- or once, if the K loop is long enough to
         // amortise a single round (fc1: M = 8000, K = 12544: 64-wide tiles re-read the 400 MB activation matrix from HBM)
-        const int nblk256 = (a.Cout % 256 == 0) ? ntm * (a.Cout / 256) : 0;
-        const bool wide256 = g_f16x3_bn256 && !a.grouped && !stem && (nblk256 >= 512 || (nblk256 >= 192 && a.nsteps >= g_wide_nsteps));
-        const int ntm256 = amp::cdiv(a.M, 256);
-        // a split input that carries a 2^in_shift (scaled loss gradients): only the ring kernel undoes it (a.out_scale in its fold)
-        AMP_REQUIRE(!(x_is_split && in_shift != 0) || (g_split_ring && epi != 0 && wide256 && a.out_mode != 3),
+        const int nblk256 = (Cout % 256 == 0) ? ntm * (Cout / 256) : 0;
+        const bool wide256 = sw.f16x3_bn256 && !grouped && !stem && (nblk256 >= 512 || (nblk256 >= 192 && p.nsteps >= WIDE_NSTEPS));
+        const int ntm256 = amp::cdiv(p.M, 256);
+        // a split input that carries a 2^in_shift (scaled loss gradients): only the ring kernel undoes it (out_scale in its fold)
+        AMP_REQUIRE(!(x_is_split && in.in_shift != 0) || (sw.split_ring && epi != 0 && wide256 && p.out_mode != 3),
                     "conv: a scaled split input needs a layer the 128 x 256 ring kernel takes (Cout %% 256 == 0, enough tiles)");
         // N tiles per workgroup for the short-K 1x1 layers on the ring kernel (0: not such a layer): as many as leave a full round of workgroups
         int nloop_nt = 0;
-        if (a.KH == 1 && a.KW == 1 && a.pad == 0 && !a.grouped && a.Cout % 256 == 0 && a.Cout >= 512 && a.Cin % BK == 0 && a.nsteps >= 2 && a.nsteps <= 16 && !a.korder &&
-            a.y_split && g_direct_epi && !mask && a.res_mode == 0 && (a.out_mode == 0 || a.out_mode == 1)) {      // (no residual, no mask: see conv_epilogue_direct_rows PLAIN)
-            const int ntn_ = a.Cout / 256;
+        if (KH == 1 && KW == 1 && d->pad == 0 && !grouped && Cout % 256 == 0 && Cout >= 512 && Cin % BK == 0 && p.nsteps >= 2 && p.nsteps <= 16 && !p.korder &&
+            p.y_split && !in.mask && d->res_mode == 0 && (p.out_mode == 0 || p.out_mode == 1)) {      // (no residual, no mask: see conv_epilogue_direct_rows PLAIN)
+            const int ntn_ = Cout / 256;
             nloop_nt = ntn_ < 8 ? ntn_ : 8;
             while (nloop_nt > 1 && (ntn_ % nloop_nt != 0 || (long long)ntm * (ntn_ / nloop_nt) < 256)) --nloop_nt;
         }
-        const long long p256_tiles = (long long)a.B * amp::cdiv(a.Ho, 8) * amp::cdiv(a.Wo, 16) * (a.Cout / 256);
-        const bool patch256_ok = g_patch256 != 0 && x_is_split && g_split_ring && epi != 0 && !a.grouped && a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 &&
-            a.Cin % 32 == 0 && a.Cin >= 64 && a.Cout % 256 == 0 && a.nsteps == 9 * (a.Cin / 32) &&
-            (a.out_mode == 4 || (a.out_mode == 0 && a.y_split && g_direct_epi && (!mask || a.mask_split) && (a.res_mode == 0 || (a.res_mode == 1 && a.res_split)))) &&
-            (g_patch256 == 2 || ((p256_tiles >= 512 || (p256_tiles >= 192 && a.nsteps >= 64)) && p256_tiles * 100 <= (long long)nblk256 * 108));
-        if (g_patch_conv != 0 && x_is_split && a.y_split && a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.cin_win == 64 && (a.grouped || (a.Cin == 64 && a.Cout == 64)) &&
-            a.out_mode == 0 && a.res_mode == 0 && epi != 0 && g_direct_epi && (!mask || a.mask_split) && a.in_scale == 1.0f && a.Cout % 64 == 0 &&
-            (g_patch_conv == 2 || (long long)a.B * amp::cdiv(a.Ho, 8) * amp::cdiv(a.Wo, 16) * (a.Cout / 64) >= 512)) {
+        const long long tiles = (long long)d->B * p.tiles_y * p.tiles_x;      // 8 x 16 pixel tiles of the patch kernels
+        const long long p256_tiles = tiles * (Cout / 256);
+        const bool plain_3x3 = KH == 3 && KW == 3 && d->stride == 1 && d->pad == 1;
+        const bool patch256_ok = sw.patch256 != 0 && x_is_split && sw.split_ring && epi != 0 && !grouped && plain_3x3 &&
+            Cin % 32 == 0 && Cin >= 64 && Cout % 256 == 0 && p.nsteps == 9 * (Cin / 32) &&
+            (p.out_mode == 4 || (p.out_mode == 0 && p.y_split && (!in.mask || mask_split) && (d->res_mode == 0 || (d->res_mode == 1 && res_split)))) &&
+            (sw.patch256 == 2 || ((p256_tiles >= 512 || (p256_tiles >= 192 && p.nsteps >= 64)) && p256_tiles * 100 <= (long long)nblk256 * 108));
+        const bool ring = x_is_split && sw.split_ring && epi != 0;      // conv_split_kernel's precondition
+        if (sw.patch_conv != 0 && x_is_split && p.y_split && plain_3x3 && p.cin_win == 64 && (grouped || (Cin == 64 && Cout == 64)) &&
+            p.out_mode == 0 && d->res_mode == 0 && epi != 0 && (!in.mask || mask_split) && in.in_shift == 0 && Cout % 64 == 0 && c64_patch_fills(sw, tiles * (Cout / 64)))
             // res2's dense 64 -> 64 layers and the ResNeXt conv2: a pixel patch staged once, nine taps read out of it (conv3x3_c64_kernel)
-            const int tiles_x = amp::cdiv(a.Wo, 16), tiles_y = amp::cdiv(a.Ho, 8);
-            a.ntn = a.Cout / 64; a.nblk = a.B * tiles_x * tiles_y * a.ntn;
-            const Fuse3Args nofuse = Fuse3Args();
-            if (a.grouped && cpg <= 32) AMP_TIMED_LAUNCH(conv3x3_c64_kernel<true>, dim3(a.nblk), dim3(256), 0, ctx->stream, a, (unsigned int)x_bytes, (unsigned int)w_bytes, tiles_x, tiles_y, nofuse);
-            else AMP_TIMED_LAUNCH(conv3x3_c64_kernel<false>, dim3(a.nblk), dim3(256), 0, ctx->stream, a, (unsigned int)x_bytes, (unsigned int)w_bytes, tiles_x, tiles_y, nofuse);
-        } else
+            return take(grouped && p.cpg <= 32 ? ConvKernel::C64_PATCH_DIAG : ConvKernel::C64_PATCH, Cout / 64, tiles * (Cout / 64));
         if (patch256_ok) {
             // FPN output / RPN / res4 / res5 3x3: 8 x 16 pixel tiles, the patch of a 32-channel chunk staged once for its nine taps (conv3x3_patch_kernel)
-            a.ntn = a.Cout / 256; a.nblk = (int)p256_tiles;
-            if (rec) rec->variant = 0;
-            const int tiles_x = amp::cdiv(a.Wo, 16), tiles_y = amp::cdiv(a.Ho, 8);
-            if (a.out_mode == 4 && rpn_nbp == 3) AMP_TIMED_LAUNCH(conv3x3_patch_kernel<5>, dim3(a.nblk), dim3(512), 0, ctx->stream, a, (unsigned int)x_bytes, (unsigned int)w_bytes, tiles_x, tiles_y);
-            else if (a.out_mode == 4 && rpn_nbp == 2) AMP_TIMED_LAUNCH(conv3x3_patch_kernel<4>, dim3(a.nblk), dim3(512), 0, ctx->stream, a, (unsigned int)x_bytes, (unsigned int)w_bytes, tiles_x, tiles_y);
-            else if (a.out_mode == 4) AMP_TIMED_LAUNCH(conv3x3_patch_kernel<3>, dim3(a.nblk), dim3(512), 0, ctx->stream, a, (unsigned int)x_bytes, (unsigned int)w_bytes, tiles_x, tiles_y);
-            else AMP_TIMED_LAUNCH(conv3x3_patch_kernel<1>, dim3(a.nblk), dim3(512), 0, ctx->stream, a, (unsigned int)x_bytes, (unsigned int)w_bytes, tiles_x, tiles_y);
-        } else
-        if (a.out_mode == 3 && g_mask_tail_loop && a.Cin % BK == 0 && !a.korder && a.Ho * a.Wo >= 128 /* a 128-pixel block spans at most two RoIs */) {     // fused mask-head tail: the four taps of a pixel block in one workgroup
-            a.ntn = 1; a.nblk = ntm;      // (a kernel of its own: not tagged as a launch of the dominant kernel)
-            AMP_TIMED_LAUNCH(mask_tail_kernel, dim3(a.nblk), dim3(512), 0, ctx->stream, a, (unsigned int)x_bytes, (unsigned int)w_bytes);
-        } else if (a.out_mode == 3) {                                        // ... one (pixel block, tap) tile per workgroup on the 128 x 256 ring kernel
-            a.ntn = 4; a.nblk = ntm * 4;
-            if (rec) rec->variant = 0;
-            launch_split<128, 256>(a, 3, ctx->stream, (unsigned int)x_bytes, (unsigned int)w_bytes);
-        } else if (a.out_mode == 4) {                                        // fused RPN tail: one N tile
-            a.ntn = 1; a.nblk = ntm;
-            if (rec) rec->variant = 0;
-            launch_split<128, 256>(a, 2 + rpn_nbp, ctx->stream, (unsigned int)x_bytes, (unsigned int)w_bytes);
-        } else if (x_is_split && g_split_ring && g_short_k && epi != 0 && !a.grouped && a.nsteps <= g_short_k_steps && res && a.res_mode == 1 && a.res_split && a.y_split && !mask &&
-                   a.Cout % 128 == 0 && ntm * (a.Cout / 128) >= 1024) {
+            p.epi = p.out_mode == 4 ? 2 + p.rpn_nbp : 1;
+            return take(ConvKernel::PATCH256, Cout / 256, p256_tiles, true);
+        }
+        if (p.out_mode == 3 && sw.mask_tail_loop && Cin % BK == 0 && !p.korder && p.Ho * p.Wo >= 128 /* a 128-pixel block spans at most two RoIs */)
+            return take(ConvKernel::MASK_TAIL, 1, ntm);      // fused mask-head tail: the four taps of a pixel block in one workgroup (a kernel of its own: not the dominant one)
+        if (p.out_mode == 3) {                                // ... one (pixel block, tap) tile per workgroup on the 128 x 256 ring kernel
+            p.epi = 3;
+            return take(ConvKernel::SPLIT_128x256, 4, ntm * 4, true);
+        }
+        if (p.out_mode == 4) {                                // fused RPN tail: one N tile
+            p.epi = 2 + p.rpn_nbp;
+            return take(ConvKernel::SPLIT_128x256, 1, ntm, true);
+        }
+        if (ring && sw.short_k && !grouped && p.nsteps <= SHORT_K_STEPS && in.res && d->res_mode == 1 && res_split && p.y_split && !in.mask &&
+            Cout % 128 == 0 && ntm * (Cout / 128) >= 1024) {
             // the trunk's conv3 + residual (K = 64 ... 256 into 4 K channels: byte-bound): 128 x 128 tiles on TWO buffers -- tile s + 2 goes into
             // the buffer of tile s once every wave holds its fragments, same prefetch distance as the three-buffer ring -- so that TWO
             // workgroups fit a CU and one's residual loads and stores overlap the other's staging: res2 -5 %, res3 -8 %, res4 -3 % on these
             // launches (A/B in one call; bit-identical); without a residual it is 4 % slower
-            a.ntn = a.Cout / 128; a.nblk = ntm * a.ntn;
-            a.stagger = 0;
-            launch_split_short(a, epi, ctx->stream, (unsigned int)x_bytes, (unsigned int)w_bytes);
-        } else if (g_nloop && nloop_nt >= 2 && x_is_split && g_split_ring && epi != 0 && (wide256 || deconv_split)) {
+            p.stagger = 0;
+            return take(ConvKernel::SPLIT_SHORT_128x128, Cout / 128, ntm * (Cout / 128));
+        }
+        if (sw.nloop && nloop_nt >= 2 && ring && (wide256 || deconv_split)) {
             // short-K 1x1 layers: several N tiles of a pixel block in one workgroup, the ring carried across them (conv1x1_nloop_kernel)
-            a.ntn = a.Cout / 256; a.nblk = ntm * (a.ntn / nloop_nt);
-            if (a.out_mode == 1) AMP_TIMED_LAUNCH(conv1x1_nloop_kernel<true>, dim3(a.nblk), dim3(512), 0, ctx->stream, a, (unsigned int)x_bytes, (unsigned int)w_bytes, nloop_nt);
-            else AMP_TIMED_LAUNCH(conv1x1_nloop_kernel<false>, dim3(a.nblk), dim3(512), 0, ctx->stream, a, (unsigned int)x_bytes, (unsigned int)w_bytes, nloop_nt);
-        } else if (x_is_split && g_split_ring && epi != 0 && (wide256 || deconv_split)) {            // 128 x 256 tiles, 3-buffer ring
+            p.nloop_nt = nloop_nt;
+            return take(p.out_mode == 1 ? ConvKernel::NLOOP_SCATTER : ConvKernel::NLOOP, Cout / 256, ntm * (Cout / 256 / nloop_nt));
+        }
+        if (ring && (wide256 || deconv_split))                // 128 x 256 tiles, 3-buffer ring
             // (the K = 256 deconv with its scatter epilogue on two-buffer 128 x 128 tiles, two workgroups per CU: 1009 against 931 us -- measured, not kept)
-            a.ntn = a.Cout / 256; a.nblk = ntm * a.ntn;
-            if (rec) rec->variant = 0;
-            launch_split<128, 256>(a, epi, ctx->stream, (unsigned int)x_bytes, (unsigned int)w_bytes);
-        } else if (x_is_split && g_split_ring && epi != 0 && !a.grouped && a.Cout % 128 == 0 && (ntm256 * (a.Cout / 128) >= 512 || (ntm256 * (a.Cout / 128) >= 192 && a.nsteps >= 64))) {
-            a.ntn = a.Cout / 128; a.nblk = ntm256 * a.ntn;                  // Cout = 128 (or 384, ...): 256 x 128 tiles
-            launch_split<256, 128>(a, epi, ctx->stream, (unsigned int)x_bytes, (unsigned int)w_bytes);
-        } else if (x_is_split && g_split_ring && g_tall64 && epi == 1 && !a.grouped && a.Cout == 64 && in_shift == 0 && amp::cdiv(a.M, 256) >= 1024) {
-            a.ntn = 1; a.nblk = amp::cdiv(a.M, 256);
-            a.stagger = 0;
-            launch_split_tall64(a, ctx->stream, (unsigned int)x_bytes, (unsigned int)w_bytes);
-        } else if (x_is_split) {      // both operands by LDS-DMA
-            if (wide256) {
-                a.ntn = a.Cout / 256; a.nblk = ntm * a.ntn;
-                launch_f16x3s<256>(a, epi, ctx->stream, (unsigned int)x_bytes, (unsigned int)w_bytes);
-            } else if (!a.grouped && a.Cout > 64 && nblk128 >= 512) {
-                a.ntn = amp::cdiv(a.Cout, 128); a.nblk = ntm * a.ntn;
-                launch_f16x3s<128>(a, epi, ctx->stream, (unsigned int)x_bytes, (unsigned int)w_bytes);
-            } else {    // (grouped: the window of a 64-wide N tile is the tile's own 64 input channels = 256 B of a split row too)
-                a.ntn = amp::cdiv(a.Cout, 64); a.nblk = ntm * a.ntn;
-                static const bool no_g32 = getenv("AMP_NO_G32") != nullptr;      // EXPERIMENT switch: two K-steps per tap for every grouped layer
-                if (a.grouped && cpg <= 32 && !no_g32) launch_f16x3s_g32(a, epi, ctx->stream, (unsigned int)x_bytes, (unsigned int)w_bytes);
-                else launch_f16x3s<64>(a, epi, ctx->stream, (unsigned int)x_bytes, (unsigned int)w_bytes);
-            }
-        } else if (stem) {
-            a.ntn = 1;
-            a.nblk = ntm;
-            launch_f16x3_stem(a, epi == 2 ? 0 : epi, ctx->stream, (unsigned int)x_bytes, (unsigned int)w_bytes);
-        } else if (a.grouped) {     // the window of a 64-wide N tile is the tile's own 64 input channels
-            a.ntn = a.Cout / 64;
-            a.nblk = ntm * a.ntn;
-            launch_f16x3<64>(a, epi, ctx->stream, (unsigned int)x_bytes, (unsigned int)w_bytes);
-        } else if (wide256) {
-            a.ntn = a.Cout / 256;
-            a.nblk = ntm * a.ntn;
-            launch_f16x3<256>(a, epi, ctx->stream, (unsigned int)x_bytes, (unsigned int)w_bytes);
-        } else if (a.Cout > 64 && nblk128 >= 512) {
-            a.ntn = amp::cdiv(a.Cout, 128);
-            a.nblk = ntm * a.ntn;
-            launch_f16x3<128>(a, epi, ctx->stream, (unsigned int)x_bytes, (unsigned int)w_bytes);
-        } else {
-            a.ntn = amp::cdiv(a.Cout, 64);
-            a.nblk = ntm * a.ntn;
-            launch_f16x3<64>(a, epi, ctx->stream, (unsigned int)x_bytes, (unsigned int)w_bytes);
+            return take(ConvKernel::SPLIT_128x256, Cout / 256, ntm * (Cout / 256), true);
+        if (ring && !grouped && Cout % 128 == 0 && (ntm256 * (Cout / 128) >= 512 || (ntm256 * (Cout / 128) >= 192 && p.nsteps >= 64)))
+            return take(ConvKernel::SPLIT_256x128, Cout / 128, ntm256 * (Cout / 128));      // Cout = 128 (or 384, ...): 256 x 128 tiles
+        if (ring && sw.tall64 && epi == 1 && !grouped && Cout == 64 && in.in_shift == 0 && ntm256 >= 1024) {
+            p.stagger = 0;
+            return take(ConvKernel::SPLIT_TALL64, 1, ntm256);
         }
-    } else if (stem) {
-        a.ntn = 1;
-        a.nblk = ntm;
-        launch_glds<64, true>(a, epi, ctx->stream, (unsigned int)x_bytes, (unsigned int)w_bytes);
-    } else if (glds) {
-        const int nblk128 = ntm * amp::cdiv(a.Cout, 128);
-        // BN = 64 also for wide layers whose 128-wide grid would leave CUs idle (2 workgroups fit per CU)
-        if (!a.grouped && a.Cout > 64 && nblk128 >= 512) {
-            a.ntn = amp::cdiv(a.Cout, 128);
-            a.nblk = ntm * a.ntn;
-            if (rec) rec->variant = 0;
-            launch_glds<128, false>(a, epi, ctx->stream, (unsigned int)x_bytes, (unsigned int)w_bytes);
-        } else {
-            a.ntn = amp::cdiv(a.Cout, 64);
-            a.nblk = ntm * a.ntn;
-            launch_glds<64, false>(a, epi, ctx->stream, (unsigned int)x_bytes, (unsigned int)w_bytes);
+        if (x_is_split) {      // both operands by LDS-DMA
+            if (wide256) return take(ConvKernel::F16X3S_256, Cout / 256, ntm * (Cout / 256));
+            if (!grouped && Cout > 64 && nblk128 >= 512) return take(ConvKernel::F16X3S_128, amp::cdiv(Cout, 128), nblk128);
+            // (grouped: the window of a 64-wide N tile is the tile's own 64 input channels = 256 B of a split row too; <= 32 channels per group: one K-step per tap)
+            return take(grouped && p.cpg <= 32 ? ConvKernel::F16X3S_G32 : ConvKernel::F16X3S_64, amp::cdiv(Cout, 64), ntm * amp::cdiv(Cout, 64));
         }
-    } else if (a.Cout > 64) {
-        a.ntn = amp::cdiv(a.Cout, 128);
-        a.nblk = ntm * a.ntn;
-        switch (g_conv_ablate) {
-            case 1: AMP_TIMED_LAUNCH((conv_mfma_kernel<BM, 128, 1>), dim3(a.nblk), dim3(256), 0, ctx->stream, a); break;
-            case 2: AMP_TIMED_LAUNCH((conv_mfma_kernel<BM, 128, 2>), dim3(a.nblk), dim3(256), 0, ctx->stream, a); break;
-            case 3: AMP_TIMED_LAUNCH((conv_mfma_kernel<BM, 128, 3>), dim3(a.nblk), dim3(256), 0, ctx->stream, a); break;
-            default: AMP_TIMED_LAUNCH((conv_mfma_kernel<BM, 128, 0>), dim3(a.nblk), dim3(256), 0, ctx->stream, a);
+        if (stem) {
+            p.epi = epi == 2 ? 0 : epi;
+            return take(ConvKernel::F16X3_STEM, 1, ntm);
         }
-    } else {
-        a.ntn = 1;
-        a.nblk = ntm;
-        AMP_TIMED_LAUNCH((conv_mfma_kernel<BM, 64>), dim3(a.nblk), dim3(256), 0, ctx->stream, a);
+        if (grouped) return take(ConvKernel::F16X3_64, Cout / 64, ntm * (Cout / 64));     // the window of a 64-wide N tile is the tile's own 64 input channels
+        if (wide256) return take(ConvKernel::F16X3_256, Cout / 256, ntm * (Cout / 256));
+        if (Cout > 64 && nblk128 >= 512) return take(ConvKernel::F16X3_128, amp::cdiv(Cout, 128), nblk128);
+        return take(ConvKernel::F16X3_64, amp::cdiv(Cout, 64), ntm * amp::cdiv(Cout, 64));
+    }
+    if (stem) return take(ConvKernel::GLDS_STEM, 1, ntm);
+    if (glds) {     // BN = 64 also for wide layers whose 128-wide grid would leave CUs idle (2 workgroups fit per CU)
+        if (!grouped && Cout > 64 && nblk128 >= 512) return take(ConvKernel::GLDS_128, amp::cdiv(Cout, 128), nblk128, true);
+        return take(ConvKernel::GLDS_64, amp::cdiv(Cout, 64), ntm * amp::cdiv(Cout, 64));
+    }
+    if (Cout > 64) return take(ConvKernel::MFMA_128, amp::cdiv(Cout, 128), nblk128);
+    return take(ConvKernel::MFMA_64, 1, ntm);
+}
+}  // namespace
+
+amp::ConvKernel amp::conv_kernel_for(int conv_mode, const amp_conv_desc& d, int groups, int fmt, int in_shift, bool res, bool mask) {
+    ConvPlan p;
+    return conv_plan({conv_mode, d, groups, fmt, in_shift, 0, res, mask, false, 0, 0}, g_sw, &p) == AMP_OK ? p.kernel : amp::ConvKernel::COUNT;
+}
+
+int amp::conv_run(amp_ctx* ctx, const amp_conv_desc* d, int groups, const float* x, const float* w, const float* w_split, int force_f32,
+                  const float* scale, const float* shift, const float* res, const float* mask, float* y, int in_shift, int fmt,
+                  const amp::PredictFuse* fuse, const amp::RpnFuse* rpn) {
+    AMP_REQUIRE(ctx && d && x && w && y, "amp_conv2d_nhwc: null argument");
+    AMP_REQUIRE(!fuse || (fuse->pred_w && fuse->pred_b && fuse->cls && fuse->prob && fuse->K >= 1), "conv: incomplete PredictFuse");
+    AMP_REQUIRE(!rpn || (rpn->w_split && rpn->bias && rpn->pred), "conv: incomplete RpnFuse");
+    AMP_REQUIRE(!(fuse && rpn), "conv: the fused RPN epilogue needs a split input, Cout = 256, ReLU and the ring kernel");
+    ConvPlan p;
+    AMP_TRY_STATUS(conv_plan({ctx->conv_mode, *d, groups, fmt, in_shift, force_f32, res != nullptr, mask != nullptr, scale != nullptr,
+                              fuse ? 1 : (rpn ? 2 : 0), rpn ? rpn->ld : 0}, g_sw, &p));
+    // the profiling record: useful flops; algorithmic bytes of this launch: every operand once (amp_prof_launches; a 1x1 conv reads only the pixels its stride samples)
+    const double MN = (double)p.M * d->Cout;
+    const double in_rows = (d->KH == 1 && d->KW == 1) ? (double)p.M : (double)d->B * d->H * d->W;
+    const double out_vals = p.out_mode == 3 ? (double)p.M * 4.0 : p.out_mode == 4 ? (double)p.M * 16.0 * p.rpn_nbp : MN;
+    const double res_vals = !res ? 0.0 : (d->res_mode == 2 ? MN / 4.0 : MN);
+    amp_prof_rec* rec = prof_open(ctx, 2.0 * MN * (double)d->KH * (double)d->KW * (double)p.cpg,
+                                  4.0 * (in_rows * d->Cin + (double)d->Cout * p.K + out_vals + res_vals + (mask ? MN : 0.0)),
+                                  p.M, d->Cout, d->KH * d->KW * p.cpg, p.dominant ? 0 : 1);
+    amp::ProfLaunchScope timed(rec ? rec->e0 : nullptr, rec ? rec->e1 : nullptr);      // the convolution kernel launched below carries the events
+    if (p.f16x3 && !w_split) {   // per-call split into the context's scratch (stream order makes the reuse safe)
+        if (ctx->split_bytes < p.w_bytes) {
+            AMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+            if (ctx->split_scratch) AMP_HIP_CHECK(hipFree(ctx->split_scratch));
+            ctx->split_scratch = nullptr; ctx->split_bytes = 0;
+            AMP_HIP_CHECK(hipMalloc(&ctx->split_scratch, p.w_bytes));
+            ctx->split_bytes = p.w_bytes;
+        }
+        hipLaunchKernelGGL(split_weights_kernel, dim3(2048), dim3(256), 0, ctx->stream, w, (size_t)d->Cout, p.K,
+                           reinterpret_cast<unsigned int*>(ctx->split_scratch));
+        w_split = ctx->split_scratch;
+    }
+    ConvArgs a;
+    a.x = x; a.w = p.f16x3 ? w_split : w; a.scale = scale; a.shift = shift; a.res = res; a.mask = mask; a.y = y;
+    a.B = d->B; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Cout = d->Cout;
+    a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad;
+    a.Ho = p.Ho; a.Wo = p.Wo; a.M = p.M; a.K = p.K; a.nsteps = p.nsteps;
+    a.grouped = groups > 1; a.cin_win = p.cin_win;
+    a.relu = d->relu; a.res_mode = d->res_mode; a.out_mode = p.out_mode;
+    a.ntn = p.ntn; a.nblk = p.nblk; a.stagger = p.stagger; a.korder = p.korder; a.direct_epi = 1;
+    a.in_scale = (in_shift != 0) ? ldexpf(1.0f, in_shift) : 1.0f;
+    a.out_scale = (in_shift != 0) ? ldexpf(1.0f, -in_shift) : 1.0f;
+    a.y_split = p.y_split; a.res_split = (fmt & 4) ? 1 : 0; a.mask_split = (fmt & 8) ? 1 : 0;
+    a.range_flag = ctx->d_conv_flag;
+    a.pred_w = fuse ? fuse->pred_w : nullptr; a.pred_b = fuse ? fuse->pred_b : nullptr; a.pred_cls = fuse ? fuse->cls : nullptr;
+    a.pred_K = fuse ? fuse->K : 0; a.prob = fuse ? fuse->prob : nullptr;
+    a.rpn_w = rpn ? rpn->w_split : nullptr; a.rpn_b = rpn ? rpn->bias : nullptr; a.rpn_pred = rpn ? rpn->pred : nullptr;
+    set_fastdiv((unsigned int)(a.Ho * a.Wo), &a.div_howo_mul, &a.div_howo_shr);
+    set_fastdiv((unsigned int)a.Wo, &a.div_wo_mul, &a.div_wo_shr);
+    const unsigned int xb = (unsigned int)p.x_bytes, wb = (unsigned int)p.w_bytes;
+    hipStream_t st = ctx->stream;
+    using amp::ConvKernel;
+    // (templates are instantiated in the order of their first use, so the cases stand in the order the listing has had its kernels in)
+    switch (p.kernel) {
+        case ConvKernel::C64_PATCH_DIAG: AMP_TIMED_LAUNCH(conv3x3_c64_kernel<true>, dim3(a.nblk), dim3(256), 0, st, a, xb, wb, p.tiles_x, p.tiles_y, Fuse3Args()); break;
+        case ConvKernel::C64_PATCH: AMP_TIMED_LAUNCH(conv3x3_c64_kernel<false>, dim3(a.nblk), dim3(256), 0, st, a, xb, wb, p.tiles_x, p.tiles_y, Fuse3Args()); break;
+        case ConvKernel::PATCH256:
+            if (p.epi == 5) AMP_TIMED_LAUNCH(conv3x3_patch_kernel<5>, dim3(a.nblk), dim3(512), 0, st, a, xb, wb, p.tiles_x, p.tiles_y);
+            else if (p.epi == 4) AMP_TIMED_LAUNCH(conv3x3_patch_kernel<4>, dim3(a.nblk), dim3(512), 0, st, a, xb, wb, p.tiles_x, p.tiles_y);
+            else if (p.epi == 3) AMP_TIMED_LAUNCH(conv3x3_patch_kernel<3>, dim3(a.nblk), dim3(512), 0, st, a, xb, wb, p.tiles_x, p.tiles_y);
+            else AMP_TIMED_LAUNCH(conv3x3_patch_kernel<1>, dim3(a.nblk), dim3(512), 0, st, a, xb, wb, p.tiles_x, p.tiles_y);
+            break;
+        case ConvKernel::MASK_TAIL: AMP_TIMED_LAUNCH(mask_tail_kernel, dim3(a.nblk), dim3(512), 0, st, a, xb, wb); break;
+        case ConvKernel::SPLIT_128x256: launch_split<128, 256>(a, p.epi, st, xb, wb); break;
+        case ConvKernel::SPLIT_SHORT_128x128: launch_split_short(a, p.epi, st, xb, wb); break;
+        case ConvKernel::NLOOP_SCATTER: AMP_TIMED_LAUNCH(conv1x1_nloop_kernel<true>, dim3(a.nblk), dim3(512), 0, st, a, xb, wb, p.nloop_nt); break;
+        case ConvKernel::NLOOP: AMP_TIMED_LAUNCH(conv1x1_nloop_kernel<false>, dim3(a.nblk), dim3(512), 0, st, a, xb, wb, p.nloop_nt); break;
+        case ConvKernel::SPLIT_256x128: launch_split<256, 128>(a, p.epi, st, xb, wb); break;
+        case ConvKernel::SPLIT_TALL64: launch_split_tall64(a, st, xb, wb); break;
+        case ConvKernel::F16X3S_256: launch_f16x3s<256>(a, p.epi, st, xb, wb); break;
+        case ConvKernel::F16X3S_128: launch_f16x3s<128>(a, p.epi, st, xb, wb); break;
+        case ConvKernel::F16X3S_G32: launch_f16x3s_g32(a, p.epi, st, xb, wb); break;
+        case ConvKernel::F16X3S_64: launch_f16x3s<64>(a, p.epi, st, xb, wb); break;
+        case ConvKernel::F16X3_STEM: launch_f16x3_stem(a, p.epi, st, xb, wb); break;
+        case ConvKernel::F16X3_64: launch_f16x3<64>(a, p.epi, st, xb, wb); break;
+        case ConvKernel::F16X3_256: launch_f16x3<256>(a, p.epi, st, xb, wb); break;
+        case ConvKernel::F16X3_128: launch_f16x3<128>(a, p.epi, st, xb, wb); break;
+        case ConvKernel::GLDS_STEM: launch_glds<64, true>(a, p.epi, st, xb, wb); break;
+        case ConvKernel::GLDS_128: launch_glds<128, false>(a, p.epi, st, xb, wb); break;
+        case ConvKernel::GLDS_64: launch_glds<64, false>(a, p.epi, st, xb, wb); break;
+        case ConvKernel::MFMA_128:
+            if (g_sw.ablate == 1) AMP_TIMED_LAUNCH((conv_mfma_kernel<128, 128, 1>), dim3(a.nblk), dim3(256), 0, st, a);
+            else if (g_sw.ablate == 2) AMP_TIMED_LAUNCH((conv_mfma_kernel<128, 128, 2>), dim3(a.nblk), dim3(256), 0, st, a);
+            else if (g_sw.ablate == 3) AMP_TIMED_LAUNCH((conv_mfma_kernel<128, 128, 3>), dim3(a.nblk), dim3(256), 0, st, a);
+            else AMP_TIMED_LAUNCH((conv_mfma_kernel<128, 128, 0>), dim3(a.nblk), dim3(256), 0, st, a);
+            break;
+        case ConvKernel::MFMA_64: AMP_TIMED_LAUNCH((conv_mfma_kernel<128, 64>), dim3(a.nblk), dim3(256), 0, st, a); break;
+        case ConvKernel::COUNT: break;
     }
     AMP_HIP_CHECK(hipGetLastError());
     return AMP_OK;
 }
 
+// Host-only view of conv_plan for tests/test_conv_plan.py and tools/conv_plan_table.py: no device, no context.  in: the 22 integers of ConvPlanIn in
+// declaration order (mode, the 12 of amp_conv_desc, groups, fmt, in_shift, force_f32, res, mask, scale, fuse, rpn_ld); sw: the 12 switches in the
+// order of ConvSwitches, or null for the process's current state.
+struct amp_debug_conv_plan_out { int kernel, epi, ntn, nblk, stagger, dominant, tiles_x, tiles_y, nloop_nt, rpn_nbp; };
+extern "C" int amp_debug_conv_plan(const int* in, const int* sw, amp_debug_conv_plan_out* out) {
+    AMP_REQUIRE(in && out, "amp_debug_conv_plan: null argument");
+    ConvPlanIn pi;
+    pi.mode = in[0];
+    pi.d.B = in[1]; pi.d.H = in[2]; pi.d.W = in[3]; pi.d.Cin = in[4]; pi.d.Cout = in[5]; pi.d.KH = in[6]; pi.d.KW = in[7]; pi.d.stride = in[8]; pi.d.pad = in[9];
+    pi.d.relu = in[10]; pi.d.res_mode = in[11]; pi.d.out_mode = in[12];
+    pi.groups = in[13]; pi.fmt = in[14]; pi.in_shift = in[15]; pi.force_f32 = in[16];
+    pi.res = in[17] != 0; pi.mask = in[18] != 0; pi.scale = in[19] != 0; pi.fuse = in[20]; pi.rpn_ld = in[21];
+    ConvSwitches s = g_sw;
+    if (sw) {
+        s.f16x3_bn256 = sw[0]; s.short_k = sw[1]; s.tall64 = sw[2]; s.split_ring = sw[3]; s.korder = sw[4]; s.patch256 = sw[5]; s.nloop = sw[6];
+        s.mask_tail_loop = sw[7]; s.patch_conv = sw[8]; s.stagger = sw[9]; s.generic_epi = sw[10]; s.ablate = sw[11];
+    }
+    ConvPlan p;
+    AMP_TRY_STATUS(conv_plan(pi, s, &p));
+    *out = {(int)p.kernel, p.epi, p.ntn, p.nblk, p.stagger, p.dominant ? 1 : 0, p.tiles_x, p.tiles_y, p.nloop_nt, p.rpn_nbp};
+    return AMP_OK;
+}
+extern "C" const char* amp_debug_conv_kernel_name(int kernel) {      // null past the last value
+    static const char* const names[] = {"C64_PATCH", "C64_PATCH_DIAG", "PATCH256", "MASK_TAIL", "SPLIT_128x256", "SPLIT_SHORT_128x128", "SPLIT_256x128", "SPLIT_TALL64",
+                                        "NLOOP", "NLOOP_SCATTER", "F16X3S_256", "F16X3S_128", "F16X3S_64", "F16X3S_G32", "F16X3_STEM", "F16X3_256", "F16X3_128", "F16X3_64",
+                                        "GLDS_STEM", "GLDS_128", "GLDS_64", "MFMA_128", "MFMA_64"};
+    static_assert(sizeof(names) / sizeof(names[0]) == (size_t)amp::ConvKernel::COUNT, "one name per ConvKernel");
+    return (kernel >= 0 && kernel < (int)amp::ConvKernel::COUNT) ? names[kernel] : nullptr;
+}
 
 // conv2 (3x3, 64 -> 64, FrozenBN, ReLU) + conv3 (1x1, 64 -> C3, FrozenBN, + residual, ReLU) of a res2 bottleneck in one launch (conv3x3_c64_kernel<false, true>):
 // every operand in the split row format; returns 1 when the fused kernel does not apply (the caller launches the two convolutions).
@@ -3794,11 +3833,11 @@ static int g_fuse23 = getenv("AMP_NO_FUSE23") ? 0 : 1;      // EXPERIMENT switch
 extern "C" void amp_debug_set_fuse23(int v) { g_fuse23 = v; }
 int amp::conv_c64_fused3_run(amp_ctx* ctx, int B, int H, int W, const float* x_split, const float* w2_split, const float* scale2, const float* shift2,
                              const float* w3_split, const float* scale3, const float* shift3, int C3, const float* res_split, float* y_split) {
-    if (!g_fuse23 || g_patch_conv == 0 || !g_direct_epi || ctx->conv_mode != AMP_CONV_F16X3 || !w2_split || !w3_split) return 1;
+    if (!g_fuse23 || g_sw.patch_conv == 0 || ctx->conv_mode != AMP_CONV_F16X3 || !w2_split || !w3_split) return 1;
     if (C3 % 64 != 0 || C3 > 256 || B < 1 || H < 1 || W < 1) return 1;
     const size_t x_bytes = (size_t)B * H * W * 64 * sizeof(float), w_bytes = (size_t)64 * 576 * sizeof(float), r_bytes = (size_t)B * H * W * C3 * sizeof(float);
     const long long tiles = (long long)B * amp::cdiv(H, 8) * amp::cdiv(W, 16);
-    if (x_bytes >= (size_t)OOB_VOFF || r_bytes >= ((size_t)1 << 32) || (long long)B * H * W >= (1ll << 29) / 4 || (g_patch_conv != 2 && tiles < 512)) return 1;
+    if (x_bytes >= (size_t)OOB_VOFF || r_bytes >= ((size_t)1 << 32) || (long long)B * H * W >= (1ll << 29) / 4 || !c64_patch_fills(g_sw, tiles)) return 1;
     ConvArgs a = ConvArgs();
     a.x = x_split; a.w = w2_split; a.scale = scale2; a.shift = shift2;
     a.B = B; a.H = H; a.W = W; a.Cin = 64; a.Cout = 64; a.KH = 3; a.KW = 3; a.stride = 1; a.pad = 1; a.Ho = H; a.Wo = W;
@@ -3810,18 +3849,9 @@ int amp::conv_c64_fused3_run(amp_ctx* ctx, int B, int H, int W, const float* x_s
     set_fastdiv((unsigned int)a.Wo, &a.div_wo_mul, &a.div_wo_shr);
     Fuse3Args f3;
     f3.w3 = w3_split; f3.scale3 = scale3; f3.shift3 = shift3; f3.res = res_split; f3.y = y_split; f3.C3 = C3; f3.w3_bytes = (unsigned int)((size_t)C3 * 64 * sizeof(float));
-    amp_prof_rec* rec = nullptr;
-    if (ctx->prof_on) {
-        if (ctx->prof_used < ctx->prof_pool.size()) {
-            rec = &ctx->prof_pool[ctx->prof_used++];
-            rec->flops = 2.0 * (double)a.M * (64.0 * 576.0 + (double)C3 * 64.0);
-            rec->variant = 1;
-            rec->bytes = (double)x_bytes + (double)w_bytes + (double)f3.w3_bytes + 2.0 * (double)r_bytes;      // input + weights + residual + output (t2 is never in memory)
-            rec->M = a.M; rec->N = C3; rec->K = 576 + 64;
-        } else {
-            ctx->prof_truncated = true;
-        }
-    }
+    // bytes: input + weights + residual + output (t2 is never in memory)
+    amp_prof_rec* rec = prof_open(ctx, 2.0 * (double)a.M * (64.0 * 576.0 + (double)C3 * 64.0),
+                                  (double)x_bytes + (double)w_bytes + (double)f3.w3_bytes + 2.0 * (double)r_bytes, a.M, C3, 576 + 64);
     amp::ProfLaunchScope timed(rec ? rec->e0 : nullptr, rec ? rec->e1 : nullptr);
     AMP_TIMED_LAUNCH((conv3x3_c64_kernel<false, true>), dim3(a.nblk), dim3(256), 0, ctx->stream, a, (unsigned int)x_bytes, (unsigned int)w_bytes, amp::cdiv(W, 16), amp::cdiv(H, 8), f3);
     AMP_HIP_CHECK(hipGetLastError());

@@ -480,7 +480,7 @@ int run_trunk(amp_model* m, const uint8_t* imgs_d, int B, int H, int W, Trunk& T
             const ConvW& rp = CONV("proposal_generator.rpn_head.pred");
             static const bool no_rpn_fuse = getenv("AMP_NO_RPN_FUSE") != nullptr;      // EXPERIMENT switch
             const long long Ml = (long long)B * fh[l] * fw[l];
-            if (native_all && (!m->saving || m->rpn_train_fused) && !m->split_stale && !no_rpn_fuse && rc.cout == 256 && rc.w_split && rp.w_split && rp.cout == ld_rpn && rp.cin == 256 && Ml >= 24576) {
+            if (native_all && (!m->saving || m->rpn_train_fused) && !m->split_stale && !no_rpn_fuse && rc.cout == 256 && rc.w_split && rp.w_split && rp.cout == ld_rpn && rp.cin == 256 && Ml >= amp::RPN_FUSE_MIN_PIXELS) {
                 // inference on the native trunk -- and a training step whose backward pass takes the sparse route (it recomputes the hidden rows it needs):
                 // the predictors run in the 3x3 conv's epilogue, the hidden tensor is never written
                 fused_rpn = true;
@@ -1207,11 +1207,11 @@ int run_train(amp_model* m, const uint8_t* imgs_d, int B, int H, int W, const am
         // subnormals) -- unless the weight gradient of the same dy has just left that very tensor in dys_scratch: then the ring kernel stages
         // it as it is and undoes the 2^16 in its fold
         static const bool no_reuse = getenv("AMP_NO_DY_REUSE") != nullptr;      // EXPERIMENT switch
-        const long long nblk256 = (((long long)B_ * Hy * Wy + 127) / 128) * (cw.cin / 256);      // conv_run takes the 128 x 256 ring kernel for this
-        const bool ring_fits = cw.cin % 256 == 0 && (nblk256 >= 512 || (nblk256 >= 192 && cw.kh * cw.kw * cw.cout / 32 >= 64));
-        if (dy == dys_of && !no_reuse && dys_rows == (long long)B_ * Hy * Wy && ring_fits && ctx->conv_mode == AMP_CONV_F16X3)
-            return amp::conv_run(ctx, &d, 1, dys_scratch, wt, wsp, 0, nullptr, nullptr, res, mask, dx, 16, 1 | ((mask && mask_split) ? 8 : 0));
-        return amp::conv_run(ctx, &d, 1, dy, wt, wsp, 0, nullptr, nullptr, res, mask, dx, 16, (mask && mask_split) ? 8 : 0);
+        const int fmt = (mask && mask_split) ? 8 : 0;
+        if (dy == dys_of && !no_reuse && dys_rows == (long long)B_ * Hy * Wy &&
+            amp::conv_kernel_for(ctx->conv_mode, d, 1, 1 | fmt, 16, res != nullptr, mask != nullptr) == amp::ConvKernel::SPLIT_128x256)      // only the ring kernel undoes the 2^16
+            return amp::conv_run(ctx, &d, 1, dys_scratch, wt, wsp, 0, nullptr, nullptr, res, mask, dx, 16, 1 | fmt);
+        return amp::conv_run(ctx, &d, 1, dy, wt, wsp, 0, nullptr, nullptr, res, mask, dx, 16, fmt);
     };
     // The backbone's chain on SCALED SPLIT gradients (GS): a gradient tensor is kept as the split rows of d * 2^16, so its data-gradient
     // convolution stages both operands by LDS-DMA on the ring kernel (no split, no scaling: the scale rides through the linear chain),
