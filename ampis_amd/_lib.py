@@ -158,6 +158,7 @@ def _declare(L):
         "amp_resize_scratch_bytes": ([i, i, i, i], C.c_size_t),
         "amp_resize_bilinear_u8": ([vp, vp, i, i, vp, i, i, vp], i),
         "amp_resize_flip_u8": ([vp, vp, i, i, vp, i, i, i, i, vp], i),
+        "amp_crop_resize_flip_u8": ([vp, vp, i, i, i, vp, i, i, i, i, vp], i),
         "amp_compact_dets": ([vp, i, i, vp, vp, vp, vp, vp, vp, vp, vp], i),
         "amp_set_conv_mode": ([vp, i], i),
         "amp_get_conv_mode": ([vp], i),
@@ -203,6 +204,8 @@ def _declare(L):
         "amp_rle_iou_matrix": ([vp, vp, vp, i, vp, vp, vp, i, vp, i, vp], i),
         "amp_rle_merge2": ([vp, i, vp, i, i, vp, i, C.POINTER(i)], i),
         "amp_rle_resize_nearest": ([vp, i, i, i, i, i, i, vp, i, C.POINTER(i)], i),
+        "amp_rle_crop_resize_nearest": ([vp, i, i, i, i, i, i, i, i, i, i, vp, i, C.POINTER(i)], i),
+        "amp_polygon_clip_rect": ([vp, vp, vp, i, C.c_double, C.c_double, C.c_double, C.c_double, vp, C.c_longlong, vp], i),
         "amp_rle_pair_overlap": ([vp, vp, vp, vp, vp, vp, vp, vp, i, vp, vp, vp], i),
         "amp_rle_from_polygon": ([vp, i, i, i, vp, i, C.POINTER(i)], i),
         "amp_model_cfg_default": ([C.POINTER(ModelCfg)], i),

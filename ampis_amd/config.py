@@ -91,7 +91,9 @@ _DEFAULTS = {
         "ROI_MASK_HEAD": {"NAME": "MaskRCNNConvUpsampleHead", "NUM_CONV": 0, "POOLER_RESOLUTION": 14},
     },
     "INPUT": {"MIN_SIZE_TRAIN": (800,), "MAX_SIZE_TRAIN": 1333, "MIN_SIZE_TEST": 800, "MAX_SIZE_TEST": 1333,
-              "FORMAT": "BGR", "MASK_FORMAT": "polygon", "RANDOM_FLIP": "horizontal"},
+              "FORMAT": "BGR", "MASK_FORMAT": "polygon", "RANDOM_FLIP": "horizontal",
+              # detectron2's defaults; engine/defaults.py input_kwargs validates them, data.py DatasetMapper draws and applies them
+              "MIN_SIZE_TRAIN_SAMPLING": "choice", "CROP": {"ENABLED": False, "TYPE": "relative_range", "SIZE": [0.9, 0.9]}},
     "DATASETS": {"TRAIN": (), "TEST": ()},
     "DATALOADER": {"NUM_WORKERS": 4},
     "SOLVER": {"IMS_PER_BATCH": 16, "BASE_LR": 0.001, "MOMENTUM": 0.9, "WEIGHT_DECAY": 0.0001, "WEIGHT_DECAY_NORM": 0.0,

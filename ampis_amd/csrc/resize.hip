@@ -52,51 +52,53 @@ __device__ __forceinline__ unsigned char clip8(int v) {
 }
 
 // out[y][xx][c] = clip8(round_half + sum_x in[y][xmin+x][c] * k[xx][x])
-// opitch: pixels per output row (>= w: the output may be the top-left part of a wider frame); flip: output column xx lands at w - 1 - xx
-__global__ void resample_h_kernel(const unsigned char* __restrict__ in, int H, int W, unsigned char* __restrict__ out, int w,
+// ipitch: pixels per input row (>= W: the input may be a window of a wider image); opitch: pixels per output row (>= w: the output may be
+// the top-left part of a wider frame); flip bit 0: output column xx lands at w - 1 - xx; bit 1: output row y lands at H - 1 - y
+__global__ void resample_h_kernel(const unsigned char* __restrict__ in, int ipitch, int H, unsigned char* __restrict__ out, int w,
                                   const int* __restrict__ bounds, const int* __restrict__ kk, int ksize, int opitch, int flip) {
     const size_t total = (size_t)H * w;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const int xx = (int)(i % w), y = (int)(i / w);
         const int xmin = bounds[2 * xx], n = bounds[2 * xx + 1];
         const int* k = kk + (size_t)xx * ksize;
-        const unsigned char* p = in + ((size_t)y * W + xmin) * 3;
+        const unsigned char* p = in + ((size_t)y * ipitch + xmin) * 3;
         int s0 = 1 << (PRECISION_BITS - 1), s1 = s0, s2 = s0;
         for (int x = 0; x < n; ++x) {
             const int c = k[x];
             s0 += p[3 * x] * c; s1 += p[3 * x + 1] * c; s2 += p[3 * x + 2] * c;
         }
-        unsigned char* o = out + ((size_t)y * opitch + (flip ? w - 1 - xx : xx)) * 3;
+        unsigned char* o = out + ((size_t)((flip & 2) ? H - 1 - y : y) * opitch + ((flip & 1) ? w - 1 - xx : xx)) * 3;
         o[0] = clip8(s0); o[1] = clip8(s1); o[2] = clip8(s2);
     }
 }
 
-__global__ void resample_v_kernel(const unsigned char* __restrict__ in, int H, int W, unsigned char* __restrict__ out, int h,
+// vertical pass over H rows of W pixels, ipitch pixels apart; flip bit 1: output row yy lands at h - 1 - yy
+__global__ void resample_v_kernel(const unsigned char* __restrict__ in, int ipitch, int W, unsigned char* __restrict__ out, int h,
                                   const int* __restrict__ bounds, const int* __restrict__ kk, int ksize, int opitch, int flip) {
     const size_t total = (size_t)h * W;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const int x = (int)(i % W), yy = (int)(i / W);
         const int ymin = bounds[2 * yy], n = bounds[2 * yy + 1];
         const int* k = kk + (size_t)yy * ksize;
-        const unsigned char* p = in + ((size_t)ymin * W + x) * 3;
+        const unsigned char* p = in + ((size_t)ymin * ipitch + x) * 3;
         int s0 = 1 << (PRECISION_BITS - 1), s1 = s0, s2 = s0;
         for (int y = 0; y < n; ++y) {
             const int c = k[y];
-            const unsigned char* q = p + (size_t)y * W * 3;
+            const unsigned char* q = p + (size_t)y * ipitch * 3;
             s0 += q[0] * c; s1 += q[1] * c; s2 += q[2] * c;
         }
-        unsigned char* o = out + ((size_t)yy * opitch + (flip ? W - 1 - x : x)) * 3;
+        unsigned char* o = out + ((size_t)((flip & 2) ? h - 1 - yy : yy) * opitch + ((flip & 1) ? W - 1 - x : x)) * 3;
         o[0] = clip8(s0); o[1] = clip8(s1); o[2] = clip8(s2);
     }
 }
 
-// no resize: rows copied into a pitched frame, optionally mirrored
-__global__ void copy_flip_kernel(const unsigned char* __restrict__ in, int H, int W, unsigned char* __restrict__ out, int opitch, int flip) {
+// no resize: rows of a pitched source copied into a pitched frame, optionally mirrored left-right (bit 0) and up-down (bit 1)
+__global__ void copy_flip_kernel(const unsigned char* __restrict__ in, int ipitch, int H, int W, unsigned char* __restrict__ out, int opitch, int flip) {
     const size_t total = (size_t)H * W;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const int x = (int)(i % W), y = (int)(i / W);
-        const unsigned char* p = in + i * 3;
-        unsigned char* o = out + ((size_t)y * opitch + (flip ? W - 1 - x : x)) * 3;
+        const unsigned char* p = in + ((size_t)y * ipitch + x) * 3;
+        unsigned char* o = out + ((size_t)((flip & 2) ? H - 1 - y : y) * opitch + ((flip & 1) ? W - 1 - x : x)) * 3;
         o[0] = p[0]; o[1] = p[1]; o[2] = p[2];
     }
 }
@@ -113,16 +115,20 @@ size_t amp_resize_scratch_bytes(int H, int W, int h, int w) {
     return (((size_t)H * w * 3 + 255) & ~(size_t)255) + 4 * ((size_t)2 * (h + w) + (size_t)h * ky + (size_t)w * kx) + 1024;
 }
 
-/* The same resize into the top-left h x w pixels of a frame whose rows are dst_pitch pixels apart (dst_pitch >= w), optionally mirrored
- * left-right afterwards -- detectron2's ResizeShortestEdge + RandomFlip of a training image, written where ImageList.from_tensors would
- * stack it (ampis/data_utils.py:171-175 DatasetMapper; round 4: the train loader does this on the device).  Pixels of the frame outside
- * the h x w part are not touched. */
-int amp_resize_flip_u8(amp_ctx* ctx, const unsigned char* src, int H, int W, unsigned char* dst, int dst_pitch, int h, int w, int flip, void* tmp) {
-    AMP_REQUIRE(ctx && src && dst && H > 0 && W > 0 && h > 0 && w > 0 && dst_pitch >= w, "amp_resize_flip_u8: bad argument");
-    AMP_REQUIRE(tmp || (h == H && w == W), "amp_resize_flip_u8: a resize needs scratch (amp_resize_scratch_bytes)");
+/* RandomCrop + ResizeShortestEdge + RandomFlip of a training image in one call (detectron2 DatasetMapper with INPUT.CROP.ENABLED): `src` points
+ * at the first pixel of an H x W window inside an uploaded image whose rows are src_pitch pixels apart (src_pitch >= W); the window is resized
+ * to h x w with Pillow's arithmetic and written into the top-left h x w pixels of a frame whose rows are dst_pitch pixels apart (dst_pitch >= w),
+ * where ImageList.from_tensors would stack it.  flip bit 0 mirrors left-right, bit 1 up-down (numpy out[:, ::-1] / out[::-1] of the resized
+ * window): both are applied where the last pass writes its pixels, so neither costs a pass or a buffer.  Pixels of the frame outside the h x w
+ * part are not touched.  tmp: amp_resize_scratch_bytes(H, W, h, w) bytes, may be null when h == H and w == W. */
+int amp_crop_resize_flip_u8(amp_ctx* ctx, const unsigned char* src, int src_pitch, int H, int W, unsigned char* dst, int dst_pitch, int h, int w,
+                            int flip, void* tmp) {
+    AMP_REQUIRE(ctx && src && dst && H > 0 && W > 0 && h > 0 && w > 0 && dst_pitch >= w && src_pitch >= W && flip >= 0 && flip <= 3,
+                "amp_crop_resize_flip_u8: bad argument");
+    AMP_REQUIRE(tmp || (h == H && w == W), "amp_crop_resize_flip_u8: a resize needs scratch (amp_resize_scratch_bytes)");
     if (h == H && w == W) {
-        if (!flip && dst_pitch == w) AMP_HIP_CHECK(hipMemcpyAsync(dst, src, (size_t)H * W * 3, hipMemcpyDeviceToDevice, ctx->stream));
-        else hipLaunchKernelGGL(copy_flip_kernel, dim3((unsigned)std::min<size_t>(((size_t)H * W + 255) / 256, 16384)), dim3(256), 0, ctx->stream, src, H, W, dst, dst_pitch, flip);
+        if (!flip && dst_pitch == w && src_pitch == W) AMP_HIP_CHECK(hipMemcpyAsync(dst, src, (size_t)H * W * 3, hipMemcpyDeviceToDevice, ctx->stream));
+        else hipLaunchKernelGGL(copy_flip_kernel, dim3((unsigned)std::min<size_t>(((size_t)H * W + 255) / 256, 16384)), dim3(256), 0, ctx->stream, src, src_pitch, H, W, dst, dst_pitch, flip);
         AMP_HIP_CHECK(hipGetLastError());
         return AMP_OK;
     }
@@ -139,19 +145,27 @@ int amp_resize_flip_u8(amp_ctx* ctx, const unsigned char* src, int H, int W, uns
     AMP_HIP_CHECK(hipMemcpyAsync(d_yk, yk.data(), yk.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     AMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));      // the host vectors go out of scope
     const unsigned char* vin = src;
-    int vW = W;
+    int vpitch = src_pitch, vW = W;
     const bool two = (w != W) && (h != H);
-    if (w != W) {       // Pillow: horizontal pass first, into a temporary when a vertical pass follows (then the flip belongs to the vertical pass)
+    if (w != W) {       // Pillow: horizontal pass first, into a temporary when a vertical pass follows (then the flips belong to the vertical pass)
         hipLaunchKernelGGL(resample_h_kernel, dim3((unsigned)std::min<size_t>(((size_t)H * w + 255) / 256, 16384)), dim3(256), 0, ctx->stream,
-                           src, H, W, two ? mid : dst, w, d_xb, d_xk, kx, two ? w : dst_pitch, two ? 0 : flip);
-        vin = mid; vW = w;
+                           src, src_pitch, H, two ? mid : dst, w, d_xb, d_xk, kx, two ? w : dst_pitch, two ? 0 : flip);
+        vin = mid; vpitch = w; vW = w;
     }
     if (h != H) {
         hipLaunchKernelGGL(resample_v_kernel, dim3((unsigned)std::min<size_t>(((size_t)h * vW + 255) / 256, 16384)), dim3(256), 0, ctx->stream,
-                           vin, H, vW, dst, h, d_yb, d_yk, ky, dst_pitch, flip);
+                           vin, vpitch, vW, dst, h, d_yb, d_yk, ky, dst_pitch, flip);
     }
     AMP_HIP_CHECK(hipGetLastError());
     return AMP_OK;
+}
+
+/* The same without a crop window and with the left-right mirror only (flip != 0): ResizeShortestEdge + RandomFlip("horizontal") of a training
+ * image (ampis/data_utils.py:171-175 DatasetMapper; round 4: the train loader does this on the device). */
+int amp_resize_flip_u8(amp_ctx* ctx, const unsigned char* src, int H, int W, unsigned char* dst, int dst_pitch, int h, int w, int flip, void* tmp) {
+    AMP_REQUIRE(ctx && src && dst && H > 0 && W > 0 && h > 0 && w > 0 && dst_pitch >= w, "amp_resize_flip_u8: bad argument");
+    AMP_REQUIRE(tmp || (h == H && w == W), "amp_resize_flip_u8: a resize needs scratch (amp_resize_scratch_bytes)");
+    return amp_crop_resize_flip_u8(ctx, src, W, H, W, dst, dst_pitch, h, w, flip ? 1 : 0, tmp);
 }
 
 int amp_resize_bilinear_u8(amp_ctx* ctx, const unsigned char* src, int H, int W, unsigned char* dst, int h, int w, void* tmp) {

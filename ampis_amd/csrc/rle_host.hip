@@ -333,22 +333,23 @@ int amp_rle_from_polygon(const double* xy, int k, int h, int w, uint32_t* cnts, 
 // the host (476 instances at 1024 x 1536: 2.1 s); the same result from the runs costs microseconds.  The pixel correspondence is Pillow's
 // ImagingScaleAffine, restated with its double-precision ACCUMULATION (xo += a0 per step, COORD() = truncation): output column x reads source
 // column xin[x], output row y reads source row yin[y]; both tables are non-decreasing, so a run boundary of a source column maps to the
-// first output row whose source row reaches it.
-extern "C" int amp_rle_resize_nearest(const uint32_t* cnts, int m, int h, int w, int nh, int nw, int flip, uint32_t* out, int cap, int* m_out) {
-    AMP_REQUIRE(cnts && out && m_out && m > 0 && h > 0 && w > 0 && nh > 0 && nw > 0 && cap > 0, "amp_rle_resize_nearest: bad argument");
-    auto table = [](int n_in, int n_out, std::vector<int>& tab) {
+// first output row whose source row reaches it.  A crop (CropTransform before the resize: mask[y0:y0+ch, x0:x0+cw]) only shifts the two tables;
+// the up-down mirror (VFlipTransform) emits a column's stretches in reverse order.
+static int rle_window_resize(const char* who, const uint32_t* cnts, int m, int h, int w, int y0, int x0, int ch, int cw, int nh, int nw, int flip,
+                             uint32_t* out, int cap, int* m_out) {
+    auto table = [](int n_in, int n_out, int first_in, std::vector<int>& tab) {
         tab.resize((size_t)n_out);
         const double a = (double)n_in / (double)n_out;
         double o = a * 0.5;
         for (int i = 0; i < n_out; ++i) {
             int v = o < 0.0 ? -1 : (int)o;
-            tab[(size_t)i] = v < n_in ? v : n_in - 1;          // (Pillow skips coordinates beyond the image; they cannot occur for a pure scale)
+            tab[(size_t)i] = first_in + (v < n_in ? v : n_in - 1);   // (Pillow skips coordinates beyond the image; they cannot occur for a pure scale)
             o += a;
         }
     };
     std::vector<int> xin, yin;
-    table(w, nw, xin);
-    table(h, nh, yin);
+    table(cw, nw, x0, xin);
+    table(ch, nh, y0, yin);
     // first output row that reads source row >= r, for r in [0, h]
     std::vector<int> first((size_t)h + 1);
     {
@@ -365,7 +366,7 @@ extern "C" int amp_rle_resize_nearest(const uint32_t* cnts, int m, int h, int w,
     {
         unsigned long long total = 0;
         for (int j = 0; j < m; ++j) total += cnts[j];
-        AMP_REQUIRE(total == (unsigned long long)h * w, "amp_rle_resize_nearest: the runs cover %llu pixels, the mask has %d x %d", total, h, w);
+        AMP_REQUIRE(total == (unsigned long long)h * w, "%s: the runs cover %llu pixels, the mask has %d x %d", who, total, h, w);
         int j = 0;
         unsigned long long run_end = cnts[0];
         unsigned char v = 0;
@@ -390,20 +391,95 @@ extern "C" int amp_rle_resize_nearest(const uint32_t* cnts, int m, int h, int w,
         cur = v; run = n;
         return true;
     };
+    std::vector<int> seg;            // up-down mirror: the lengths of one column's stretches, to be emitted last to first
     for (int ox = 0; ox < nw; ++ox) {
-        const int sx = xin[(size_t)(flip ? nw - 1 - ox : ox)];
-        unsigned char v = col_v0[(size_t)sx];
-        int y0 = 0;
+        const int sx = xin[(size_t)((flip & 1) ? nw - 1 - ox : ox)];
+        unsigned char v = col_v0[(size_t)sx];      // the value at source row 0; transitions above the window map to output row 0 and only toggle it
+        int ya = 0;
+        seg.clear();
         for (int t = col_start[(size_t)sx]; t < col_start[(size_t)sx + 1]; ++t) {
-            const int y1 = first[(size_t)trans[(size_t)t]];
-            if (!put(v, (unsigned long long)(y1 - y0))) { amp::set_error("amp_rle_resize_nearest: output capacity %d too small", cap); return AMP_ERR_NOMEM; }
-            y0 = y1;
+            const int yb = first[(size_t)trans[(size_t)t]];
+            if (flip & 2) seg.push_back(yb - ya);
+            else if (!put(v, (unsigned long long)(yb - ya))) { amp::set_error("%s: output capacity %d too small", who, cap); return AMP_ERR_NOMEM; }
+            ya = yb;
             v ^= 1;
         }
-        if (!put(v, (unsigned long long)(nh - y0))) { amp::set_error("amp_rle_resize_nearest: output capacity %d too small", cap); return AMP_ERR_NOMEM; }
+        if (flip & 2) {
+            seg.push_back(nh - ya);
+            for (size_t k = seg.size(); k-- > 0; v ^= 1)
+                if (!put(v, (unsigned long long)seg[k])) { amp::set_error("%s: output capacity %d too small", who, cap); return AMP_ERR_NOMEM; }
+        } else if (!put(v, (unsigned long long)(nh - ya))) { amp::set_error("%s: output capacity %d too small", who, cap); return AMP_ERR_NOMEM; }
     }
-    if (mo >= cap) { amp::set_error("amp_rle_resize_nearest: output capacity %d too small", cap); return AMP_ERR_NOMEM; }
+    if (mo >= cap) { amp::set_error("%s: output capacity %d too small", who, cap); return AMP_ERR_NOMEM; }
     out[mo++] = (uint32_t)run;
     *m_out = mo;
+    return AMP_OK;
+}
+
+extern "C" int amp_rle_resize_nearest(const uint32_t* cnts, int m, int h, int w, int nh, int nw, int flip, uint32_t* out, int cap, int* m_out) {
+    AMP_REQUIRE(cnts && out && m_out && m > 0 && h > 0 && w > 0 && nh > 0 && nw > 0 && cap > 0, "amp_rle_resize_nearest: bad argument");
+    return rle_window_resize("amp_rle_resize_nearest", cnts, m, h, w, 0, 0, h, w, nh, nw, flip ? 1 : 0, out, cap, m_out);
+}
+
+extern "C" int amp_rle_crop_resize_nearest(const uint32_t* cnts, int m, int h, int w, int y0, int x0, int ch, int cw, int nh, int nw, int flip,
+                                           uint32_t* out, int cap, int* m_out) {
+    AMP_REQUIRE(cnts && out && m_out && m > 0 && h > 0 && w > 0 && nh > 0 && nw > 0 && cap > 0 && flip >= 0 && flip <= 3,
+                "amp_rle_crop_resize_nearest: bad argument");
+    AMP_REQUIRE(y0 >= 0 && x0 >= 0 && ch > 0 && cw > 0 && y0 <= h - ch && x0 <= w - cw,
+                "amp_rle_crop_resize_nearest: the window %d x %d at (%d, %d) leaves the %d x %d mask", ch, cw, y0, x0, h, w);
+    return rle_window_resize("amp_rle_crop_resize_nearest", cnts, m, h, w, y0, x0, ch, cw, nh, nw, flip, out, cap, m_out);
+}
+
+// ---- polygons under a crop ---------------------------------------------------------------------------------------------------------------
+// fvcore's CropTransform.apply_polygons intersects every polygon with the crop rectangle (through shapely).  The same REGION from
+// Sutherland-Hodgman against the four half-planes, in float64: a non-convex polygon that leaves and re-enters the window comes back as one
+// vertex list whose pieces are joined along the window's border (edges walked once in each direction: they enclose nothing, and the
+// rasteriser's crossings along them cancel).  An intersection is computed from the edge's start towards its end and held between the two.
+extern "C" int amp_polygon_clip_rect(const double* xy, const long long* off, const int* sel, int nsel, double x0, double y0, double x1, double y1,
+                                     double* out, long long cap, long long* out_off) {
+    AMP_REQUIRE(nsel >= 0 && out_off && (nsel == 0 || (xy && off && sel && out)) && x0 <= x1 && y0 <= y1, "amp_polygon_clip_rect: bad argument");
+    std::vector<double> a, b;
+    long long o = 0;
+    out_off[0] = 0;
+    for (int j = 0; j < nsel; ++j) {
+        const long long lo = off[sel[j]], hi = off[sel[j] + 1];
+        AMP_REQUIRE(lo >= 0 && hi >= lo && (hi - lo) % 2 == 0, "amp_polygon_clip_rect: polygon %d has %lld coordinates", sel[j], hi - lo);
+        a.assign(xy + lo, xy + hi);
+        for (int plane = 0; plane < 4 && a.size() >= 6; ++plane) {
+            const int ax = plane >> 1;                       // 0: a bound on x, 1: a bound on y
+            const bool lower = !(plane & 1);
+            const double c = ax == 0 ? (lower ? x0 : x1) : (lower ? y0 : y1);
+            auto in = [&](const double* p) { return lower ? p[ax] >= c : p[ax] <= c; };
+            b.clear();
+            const size_t n = a.size() / 2;
+            for (size_t i = 0; i < n; ++i) {
+                const double* p = &a[2 * ((i + n - 1) % n)];     // the edge that ENDS at vertex i: a polygon inside the window keeps its order
+                const double* q = &a[2 * i];
+                const bool pi = in(p), qi = in(q);
+                if (pi != qi) {
+                    const double t = (c - p[ax]) / (q[ax] - p[ax]);
+                    double v = p[1 - ax] + t * (q[1 - ax] - p[1 - ax]);
+                    v = std::min(std::max(v, std::min(p[1 - ax], q[1 - ax])), std::max(p[1 - ax], q[1 - ax]));
+                    double r[2];
+                    r[ax] = c; r[1 - ax] = v;
+                    b.push_back(r[0]); b.push_back(r[1]);
+                }
+                if (qi) { b.push_back(q[0]); b.push_back(q[1]); }
+            }
+            a.swap(b);
+        }
+        double area2 = 0.0;
+        const size_t n = a.size() / 2;
+        for (size_t i = 0; i < n; ++i) {
+            const size_t k = (i + 1) % n;
+            area2 += (a[2 * i] - a[0]) * (a[2 * k + 1] - a[1]) - (a[2 * k] - a[0]) * (a[2 * i + 1] - a[1]);   // relative to vertex 0: exact 0 on a border line
+        }
+        if (n >= 3 && area2 != 0.0) {
+            AMP_REQUIRE(o + (long long)a.size() <= cap, "amp_polygon_clip_rect: more than cap=%lld output coordinates", cap);
+            std::copy(a.begin(), a.end(), out + o);
+            o += (long long)a.size();
+        }
+        out_off[j + 1] = o;
+    }
     return AMP_OK;
 }

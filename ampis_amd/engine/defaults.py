@@ -130,6 +130,85 @@ def solver_kwargs(cfg):
     return kw
 
 
+_CROP_DEFAULTS = {"ENABLED": False, "TYPE": "relative_range", "SIZE": [0.9, 0.9]}
+_CROP_TYPES = ("relative_range", "relative", "absolute", "absolute_range")
+
+
+def input_kwargs(cfg):
+    """The train-time augmentations of cfg.INPUT as detectron2's DatasetMapper.from_config reads them for a Mask R-CNN config:
+    dict(sizes, sampling "choice" | "range", flip "horizontal" | "vertical" | "none", crop None | (TYPE, (s0, s1)) with SIZE as (h, w),
+    recompute_boxes = crop enabled: a mask head is always present here).  A cfg without these keys (a hand-built CfgNode) gets detectron2's
+    defaults.  Raises ValueError naming the cfg key for what the mapper cannot honour, before any device work."""
+    c = cfg.INPUT
+    sizes = c.MIN_SIZE_TRAIN
+    sizes = (int(sizes),) if isinstance(sizes, (int, np.integer)) else tuple(int(v) for v in sizes)
+    sampling = c.get("MIN_SIZE_TRAIN_SAMPLING", "choice")
+    if sampling not in ("choice", "range"):
+        raise ValueError(f"INPUT.MIN_SIZE_TRAIN_SAMPLING = {sampling!r}: 'choice' or 'range'")
+    if sampling == "range" and (len(sizes) != 2 or sizes[0] > sizes[1]):
+        raise ValueError(f"INPUT.MIN_SIZE_TRAIN = {sizes!r}: exactly two values (min, max) are required with INPUT.MIN_SIZE_TRAIN_SAMPLING = 'range'")
+    if len(sizes) == 0:
+        raise ValueError("INPUT.MIN_SIZE_TRAIN = (): at least one size is required")
+    flip = c.get("RANDOM_FLIP", "horizontal")
+    if flip not in ("horizontal", "vertical", "none"):
+        raise ValueError(f"INPUT.RANDOM_FLIP = {flip!r}: 'horizontal', 'vertical' or 'none'")
+    cr = c.get("CROP", None) or {}
+    cget = lambda k: cr.get(k, _CROP_DEFAULTS[k])
+    enabled = cget("ENABLED")
+    if not isinstance(enabled, (bool, np.bool_)):
+        raise ValueError(f"INPUT.CROP.ENABLED = {enabled!r}: True or False is required")
+    crop = None
+    if enabled:
+        kind = cget("TYPE")
+        if kind not in _CROP_TYPES:
+            raise ValueError(f"INPUT.CROP.TYPE = {kind!r}: one of {', '.join(_CROP_TYPES)}")
+        size = cget("SIZE")
+        if not isinstance(size, (list, tuple)) or len(size) != 2:
+            raise ValueError(f"INPUT.CROP.SIZE = {size!r}: two numbers (h, w) are required")
+        s0, s1 = (_positive(v, "INPUT.CROP.SIZE") for v in size)
+        if kind.startswith("relative") and (s0 > 1 or s1 > 1):
+            raise ValueError(f"INPUT.CROP.SIZE = {size!r}: a relative size lies in (0, 1]")
+        if kind.startswith("absolute"):
+            if s0 != int(s0) or s1 != int(s1):
+                raise ValueError(f"INPUT.CROP.SIZE = {size!r}: an absolute size is a whole number of pixels")
+            s0, s1 = int(s0), int(s1)
+        if kind == "absolute_range" and s0 > s1:
+            raise ValueError(f"INPUT.CROP.SIZE = {size!r}: INPUT.CROP.TYPE = 'absolute_range' draws both extents from [SIZE[0], SIZE[1]], so SIZE[0] <= SIZE[1]")
+        crop = (kind, (s0, s1))
+    return dict(sizes=sizes, sampling=sampling, flip=flip, crop=crop, recompute_boxes=crop is not None)
+
+
+def crop_extent_bounds(crop, h, w):
+    """((ch_min, ch_max), (cw_min, cw_max)) of the windows `crop_window` can return on an h x w image."""
+    kind, (s0, s1) = crop
+    clamp = lambda v, n: max(1, min(int(v), n))
+    if kind == "relative":
+        a = clamp(h * s0 + 0.5, h), clamp(w * s1 + 0.5, w)
+        return (a[0], a[0]), (a[1], a[1])
+    if kind == "relative_range":
+        return (clamp(h * s0 + 0.5, h), h), (clamp(w * s1 + 0.5, w), w)
+    if kind == "absolute":
+        return (min(s0, h), min(s0, h)), (min(s1, w), min(s1, w))
+    return (min(h, s0), min(h, s1)), (min(w, s0), min(w, s1))
+
+
+def crop_window(crop, h, w, u):
+    """detectron2 RandomCrop.get_crop_size + get_transform on an h x w image, from four uniform numbers u in [0, 1) (drawn by
+    DatasetMapper.draw: extent h, extent w, origin y, origin x): the window (y0, x0, ch, cw).
+      relative: int(h * s0 + 0.5), int(w * s1 + 0.5) | relative_range: the same with s = SIZE + u * (1 - SIZE) | absolute: min(s0, h), min(s1, w)
+      | absolute_range: uniform integers in [min(h, s0), min(h, s1)] and [min(w, s0), min(w, s1)]; the origin is a uniform integer in
+    [0, h - ch] x [0, w - cw]."""
+    kind, (s0, s1) = crop
+    (hlo, hhi), (wlo, whi) = crop_extent_bounds(crop, h, w)
+    pick = lambda u_, n: min(int(u_ * n), n - 1)          # a uniform integer in [0, n)
+    if kind == "relative_range":
+        ch = max(1, min(int(h * (s0 + u[0] * (1.0 - s0)) + 0.5), h))
+        cw = max(1, min(int(w * (s1 + u[1] * (1.0 - s1)) + 0.5), w))
+    else:
+        ch, cw = hlo + pick(u[0], hhi - hlo + 1), wlo + pick(u[1], whi - wlo + 1)
+    return pick(u[2], h - ch + 1), pick(u[3], w - cw + 1), ch, cw
+
+
 def read_image_bgr(path):
     """cv2.imread stand-in (notebook cells 26/28): 8-bit image -> HxWx3 BGR uint8 (grayscale replicated)."""
     from PIL import Image
@@ -405,9 +484,10 @@ class _Uploader:
         return ptr
 
     def frames(self, batch):
-        """The stacked frame of a deferred batch, built in HBM: every decoded image goes up once as it is, amp_resize_flip_u8 (PIL-exact
-        resize + mirror) writes it into its slot of the zeroed frame -- what DatasetMapper + ImageList.from_tensors do on the host, byte for
-        byte (tests/test_train_input_gpu.py).  An image that needs neither resize nor flip and fills the frame is copied straight into it."""
+        """The stacked frame of a deferred batch, built in HBM: every decoded image goes up once as it is (under a crop: the rows of its
+        window), amp_crop_resize_flip_u8 (window + PIL-exact resize + mirrors) writes it into its slot of the zeroed frame -- what DatasetMapper +
+        ImageList.from_tensors do on the host, byte for byte (tests/test_train_input_gpu.py, tests/test_input_aug_gpu.py).  An image that needs
+        neither crop, resize nor flip and fills the frame is copied straight into it."""
         import ctypes as C
         from ..data import mapped_hw
         hw = [mapped_hw(d) for d in batch]
@@ -427,17 +507,21 @@ class _Uploader:
                 _lib.check(L.amp_memset(self.ctx.handle, C.c_void_p(ptr), 0, nbytes), "amp_memset")       # the padding of the smaller images
             for b, d in enumerate(batch):
                 img = np.ascontiguousarray(d["image_bgr"], dtype=np.uint8)
-                h0, w0 = img.shape[:2]
-                (h, w), flip = hw[b], bool(d["device_plan"][2])
+                w0 = img.shape[1]
+                plan = d["device_plan"]
+                (h, w), bits = hw[b], int(plan[2])                            # bit 0 left-right, bit 1 up-down (a plain bool: left-right)
+                y0, x0, ch, cw = plan[3:7] if len(plan) > 3 else (0, 0) + img.shape[:2]
+                assert 0 <= y0 <= img.shape[0] - ch and 0 <= x0 <= w0 - cw and ch > 0 and cw > 0, f"crop window {plan[3:7]} leaves the {img.shape[:2]} image"
+                rows = img[y0:y0 + ch]                                        # whole rows of the window: contiguous, pitch w0
                 slot = ptr + b * H * W * 3
-                if (h, w) == (h0, w0) and not flip and w == W:
-                    self.ctx.h2d(slot, img)                                   # rows contiguous in the slot: no kernel
+                if (h, w) == (ch, cw) and not bits and w == W and cw == w0:
+                    self.ctx.h2d(slot, rows)                                  # rows contiguous in the slot: no kernel
                     continue
-                src = self._scratch("src", img.nbytes)
-                self.ctx.h2d(src, img)
-                tmp = self._scratch("tmp", int(L.amp_resize_scratch_bytes(h0, w0, h, w))) if (h, w) != (h0, w0) else 0
-                _lib.check(L.amp_resize_flip_u8(self.ctx.handle, C.c_void_p(src), h0, w0, C.c_void_p(slot), W, h, w, int(flip), C.c_void_p(tmp) if tmp else None),
-                           "amp_resize_flip_u8")
+                src = self._scratch("src", rows.nbytes)
+                self.ctx.h2d(src, rows)
+                tmp = self._scratch("tmp", int(L.amp_resize_scratch_bytes(ch, cw, h, w))) if (h, w) != (ch, cw) else 0
+                _lib.check(L.amp_crop_resize_flip_u8(self.ctx.handle, C.c_void_p(src + 3 * x0), w0, ch, cw, C.c_void_p(slot), W, h, w, bits,
+                                                     C.c_void_p(tmp) if tmp else None), "amp_crop_resize_flip_u8")
                 self.ctx.sync()                                               # `src` is re-used by the next image
             self.ctx.sync()
             self.k = (self.k + 1) % len(self.bufs)
@@ -486,6 +570,7 @@ class DefaultTrainer:
         from ..data import build_detection_train_loader
         from ..utils import comm
         self.cfg = cfg
+        input_kwargs(cfg)                    # an INPUT augmentation the mapper cannot honour fails here, naming its key, before the device is touched
         self.iter = self.start_iter = 0
         self.max_iter = int(cfg.SOLVER.MAX_ITER)
         self.storage = None
@@ -557,14 +642,14 @@ class DefaultTrainer:
     # ---- model / weights ----
     def _capacity_from_cfg(self):
         """Upper bound (padded h, w) of every frame the train mapper can produce from cfg.DATASETS.TRAIN + TEST (the validation-loss
-        hook maps TEST images with the same augmentation): ResizeShortestEdge of each image's (height, width) for every
-        MIN_SIZE_TRAIN choice, both orientations kept apart.  Falls back to MAX_SIZE_TRAIN x MAX_SIZE_TRAIN when a dataset does not
+        hook maps TEST images with the same augmentation): ResizeShortestEdge of each image's (height, width) -- under INPUT.CROP of its
+        extreme crop windows -- for every MIN_SIZE_TRAIN choice (or both ends of the range), both orientations kept apart.  Falls back to MAX_SIZE_TRAIN x MAX_SIZE_TRAIN when a dataset does not
         say how large its images are.  Sized once, the net is never re-created mid-run (which would reset nothing any more -- the
         momentum arena is carried over -- but costs seconds)."""
         from ..data import DatasetCatalog
         c = self.cfg
-        mins = c.INPUT.MIN_SIZE_TRAIN
-        mins = [int(mins)] if isinstance(mins, (int, float)) else [int(v) for v in mins]
+        kw = input_kwargs(c)
+        mins = [int(v) for v in kw["sizes"]]       # "range" draws between its two values: the frame grows with the scale, the ends bound it
         mx = int(c.INPUT.MAX_SIZE_TRAIN)
         hmax = wmax = 0
         try:
@@ -576,9 +661,14 @@ class DefaultTrainer:
                         h0, w0 = d["image_bgr"].shape[:2]
                     else:
                         raise KeyError("height")
-                    for m_ in mins:
-                        h, w = shortest_edge_size(h0, w0, m_, mx)
-                        hmax, wmax = max(hmax, h), max(wmax, w)
+                    # INPUT.CROP: the frame's height grows with the window's height and shrinks with its width (and the other way round),
+                    # so the extreme windows bound every frame a drawn one can give; a deterministic crop type has one extent
+                    hs, ws = ((h0,), (w0,)) if kw["crop"] is None else (sorted(set(v)) for v in crop_extent_bounds(kw["crop"], h0, w0))
+                    for ch in hs:
+                        for cw in ws:
+                            for m_ in mins:
+                                h, w = shortest_edge_size(ch, cw, m_, mx)
+                                hmax, wmax = max(hmax, h), max(wmax, w)
         except Exception:          # unknown dataset / no sizes: the square bound
             hmax = wmax = mx
         pad = lambda v: (int(v) + 31) // 32 * 32

@@ -114,17 +114,70 @@ def resize_nearest(r, new_h, new_w, flip=False):
     bitmask annotation under ResizeShortestEdge + RandomFlip, without decoding."""
     h, w = int(r["size"][0]), int(r["size"][1])
     c = _counts(r)
-    cap = 2 * int(new_w) + 2 * len(c) * max(1, -(-int(new_w) // max(w, 1))) + 8      # every source transition repeats for each output column that reads its column
+    fn = lambda out, cap, m: lib().amp_rle_resize_nearest(c.ctypes.data_as(C.c_void_p), len(c), h, w, int(new_h), int(new_w), int(bool(flip)),
+                                                          out.ctypes.data_as(C.c_void_p), cap, C.byref(m))
+    return _resized(fn, "amp_rle_resize_nearest", len(c), w, int(new_h), int(new_w))
+
+
+def _resized(fn, name, runs, src_w, new_h, new_w):
+    cap = 2 * new_w + 2 * runs * max(1, -(-new_w // max(src_w, 1))) + 8      # every source transition repeats for each output column that reads its column
     while True:
         out = np.empty(cap, dtype=np.uint32)
         m = C.c_int()
-        st = lib().amp_rle_resize_nearest(c.ctypes.data_as(C.c_void_p), len(c), h, w, int(new_h), int(new_w), int(bool(flip)),
-                                          out.ctypes.data_as(C.c_void_p), cap, C.byref(m))
+        st = fn(out, cap, m)
         if st == 0:
-            return {"size": [int(new_h), int(new_w)], "counts": counts_to_string(out[: m.value])}
-        if cap >= int(new_h) * int(new_w) + 2:
-            check(st, "amp_rle_resize_nearest")
-        cap = min(cap * 4, int(new_h) * int(new_w) + 2)
+            return {"size": [new_h, new_w], "counts": counts_to_string(out[: m.value])}
+        if cap >= new_h * new_w + 2:
+            check(st, name)
+        cap = min(cap * 4, new_h * new_w + 2)
+
+
+def crop_resize_nearest(r, crop, new_h, new_w, hflip=False, vflip=False):
+    """RLE of flips(PIL.Image.resize(decode(r)[y0:y0+ch, x0:x0+cw], (new_w, new_h), NEAREST)) computed on the runs
+    (amp_rle_crop_resize_nearest): a bitmask annotation under RandomCrop + ResizeShortestEdge + RandomFlip.  crop = (y0, x0, ch, cw)."""
+    h, w = int(r["size"][0]), int(r["size"][1])
+    y0, x0, ch, cw = (int(v) for v in crop)
+    c = _counts(r)
+    fn = lambda out, cap, m: lib().amp_rle_crop_resize_nearest(c.ctypes.data_as(C.c_void_p), len(c), h, w, y0, x0, ch, cw, int(new_h), int(new_w),
+                                                               int(bool(hflip)) | 2 * int(bool(vflip)), out.ctypes.data_as(C.c_void_p), cap, C.byref(m))
+    return _resized(fn, "amp_rle_crop_resize_nearest", len(c), cw, int(new_h), int(new_w))
+
+
+def bbox(r):
+    """(x0, y0, x1, y1) of the set pixels of a mask, x1 / y1 one past the last (detectron2 BitMasks.get_bounding_boxes); None when empty."""
+    h = int(r["size"][0])
+    c = _counts(r).astype(np.int64)
+    end = np.cumsum(c)
+    ln, end = c[1::2], end[1::2]
+    keep = ln > 0
+    if h <= 0 or not keep.any():
+        return None
+    a, b = (end - ln)[keep], end[keep] - 1          # first and last pixel of every run of ones, column-major
+    xa, xb = a // h, b // h
+    one = xa == xb                                  # a run that crosses a column border covers rows 0 and h - 1
+    ya = np.where(one, a % h, 0).min()
+    yb = np.where(one, b % h, h - 1).max()
+    return int(xa.min()), int(ya), int(xb.max()) + 1, int(yb) + 1
+
+
+def clip_polygons(flat, off, sel, x0, y0, x1, y1):
+    """Polygons sel[j] of a pool (polygon i = flat[off[i] : off[i + 1]], flat x,y values) clipped against the rectangle [x0, x1] x [y0, y1]
+    in one call (amp_polygon_clip_rect: Sutherland-Hodgman in float64, untranslated).  Returns (out, out_off): result j = out[out_off[j] :
+    out_off[j + 1]], empty when nothing with an area is left."""
+    flat = np.ascontiguousarray(flat, dtype=np.float64)
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    sel = np.ascontiguousarray(sel, dtype=np.int32)
+    n = len(sel)
+    out_off = np.zeros(n + 1, dtype=np.int64)
+    if n == 0:
+        return np.zeros(0, np.float64), out_off
+    assert sel.min() >= 0 and sel.max() < len(off) - 1 and int(off[-1]) <= len(flat)
+    cap = int(6 * (off[sel + 1] - off[sel]).sum() + 16 * n)
+    out = np.empty(cap, dtype=np.float64)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    check(lib().amp_polygon_clip_rect(vp(flat), vp(off), vp(sel), n, float(x0), float(y0), float(x1), float(y1), vp(out), cap, vp(out_off)),
+          "amp_polygon_clip_rect")
+    return out[: int(out_off[-1])], out_off
 
 
 def pair_overlap(a, b, pairs):

@@ -113,6 +113,12 @@ int amp_resize_bilinear_u8(amp_ctx* ctx, const unsigned char* src, int H, int W,
  * ImageList.from_tensors): the same resize written into the top-left h x w pixels of a frame slot whose rows are dst_pitch pixels apart,
  * mirrored left-right when flip != 0 (== numpy out[:, ::-1] of the resized image).  h == H and w == W: a (mirrored) copy, tmp may be null. */
 int amp_resize_flip_u8(amp_ctx* ctx, const unsigned char* src, int H, int W, unsigned char* dst, int dst_pitch, int h, int w, int flip, void* tmp);
+/* RandomCrop + ResizeShortestEdge + RandomFlip (INPUT.CROP, INPUT.RANDOM_FLIP "horizontal" | "vertical"): `src` points at the first pixel of
+ * an H x W window of an uploaded image whose rows are src_pitch pixels apart (src_pitch >= W); the window is resized like above into the frame
+ * slot.  flip bit 0 mirrors left-right, bit 1 up-down; both are applied where the last pass writes (no extra pass, no extra buffer).  With
+ * src_pitch == W and flip in {0, 1} this is amp_resize_flip_u8, byte for byte. */
+int amp_crop_resize_flip_u8(amp_ctx* ctx, const unsigned char* src, int src_pitch, int H, int W, unsigned char* dst, int dst_pitch, int h, int w,
+                            int flip, void* tmp);
 
 /* Stage a9/a10/a11/a14/a16: implicit-GEMM convolution on fp32 MFMA ------------------------- */
 typedef struct amp_conv_desc {
@@ -448,6 +454,16 @@ int amp_rle_pair_overlap(const uint32_t* apool, const unsigned long long* aoff, 
  * flip(PIL.Image.resize(decode(cnts), (nw, nh), NEAREST)) -- what detectron2's ResizeTransform.apply_segmentation + HFlipTransform do to a bitmask
  * annotation -- without decoding (Pillow's ImagingScaleAffine pixel correspondence, restated).  cap >= nh * nw + 1 is always enough. */
 int amp_rle_resize_nearest(const uint32_t* cnts, int m, int h, int w, int nh, int nw, int flip, uint32_t* out, int cap, int* m_out);
+/* The same for a crop: the runs of flips(PIL.Image.resize(decode(cnts)[y0:y0+ch, x0:x0+cw], (nw, nh), NEAREST)) -- CropTransform +
+ * ResizeTransform + HFlip / VFlipTransform on a bitmask annotation.  flip bit 0 mirrors left-right, bit 1 up-down. */
+int amp_rle_crop_resize_nearest(const uint32_t* cnts, int m, int h, int w, int y0, int x0, int ch, int cw, int nh, int nw, int flip,
+                                uint32_t* out, int cap, int* m_out);
+/* Sutherland-Hodgman clip of polygons against the rectangle [x0, x1] x [y0, y1] in float64 (the region CropTransform.apply_polygons keeps; the
+ * vertex order is this routine's own).  Polygon j of the call is polygon sel[j] of the pool: xy[off[sel[j]] .. off[sel[j] + 1]) flat x,y values.
+ * Results go back to back into out (cap doubles; 6 * input + 16 per polygon is always enough) with out_off[nsel + 1]; a result with fewer
+ * than 3 vertices or zero area is empty.  Coordinates are NOT translated. */
+int amp_polygon_clip_rect(const double* xy, const long long* off, const int* sel, int nsel, double x0, double y0, double x1, double y1,
+                          double* out, long long cap, long long* out_off);
 int amp_rle_merge2(const uint32_t* A, int ka, const uint32_t* B, int kb, int intersect, uint32_t* out, int cap, int* m_out);
 /* polygon (k vertices, flat xy) -> runs of an h x w mask (pycocotools rleFrPoly / frPyObjects) */
 int amp_rle_from_polygon(const double* xy, int k, int h, int w, uint32_t* cnts, int cap, int* m_out);

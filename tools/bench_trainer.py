@@ -13,6 +13,9 @@ N, S, B, ITERS = 32, 1024, 16, 12
 # the batch frame changes from iteration to iteration, so the weight-gradient row tables (wgrad.hip) are re-used only through the cache --
 # its hit rate is printed (the fixed 1024 x 1024 bench says nothing about that).  B = 8 there, 40 iterations.
 MULTI = len(sys.argv) > 1 and sys.argv[1] == "multiscale"
+# --augment (after the mode): INPUT.CROP relative_range [0.9, 0.9] + RANDOM_FLIP "vertical" on top of it -- the crop window, the polygon clipper and the
+# up-down mirror in the loader; compare loader_wait_ms_median and images_per_s with the same mode without the switch, same session.
+AUG = "--augment" in sys.argv[1:]
 if MULTI:
     N, B, ITERS = 16, 8, 40
 dd = []
@@ -35,6 +38,8 @@ for workers in ((4,) if MULTI else (0, 4)):
     cfg.MODEL.WEIGHTS, cfg.MODEL.ROI_HEADS.NUM_CLASSES = os.path.join(tmp, "init.pth"), 1
     if not MULTI:
         cfg.INPUT.MIN_SIZE_TRAIN, cfg.INPUT.MAX_SIZE_TRAIN = (S,), S
+    if AUG:
+        cfg.INPUT.CROP.ENABLED, cfg.INPUT.CROP.TYPE, cfg.INPUT.CROP.SIZE, cfg.INPUT.RANDOM_FLIP = True, "relative_range", [0.9, 0.9], "vertical"
     cfg.DATALOADER.NUM_WORKERS = workers
     cfg.OUTPUT_DIR = os.path.join(tmp, f"out{workers}")
     tr = DefaultTrainer(cfg)
@@ -73,4 +78,6 @@ for workers in ((4,) if MULTI else (0, 4)):
     except Exception as e:   # noqa: BLE001
         out[f"NUM_WORKERS={workers}"]["wgrad_rowtab_cache"] = repr(e)
     del tr
+if AUG:
+    out["augment"] = "INPUT.CROP relative_range [0.9, 0.9] + RANDOM_FLIP vertical"
 print(json.dumps(out))
