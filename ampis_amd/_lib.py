@@ -89,6 +89,40 @@ def sgd_opts(lr, momentum=0.9, weight_decay=1e-4, grad_scale=1.0, nesterov=False
     return o
 
 
+class LossOpts(C.Structure):
+    """amp_loss_opts (include/ampis_hip.h): the box regression losses and loss weights of the RPN and the box head."""
+    _fields_ = [("rpn_loss_type", C.c_int), ("rpn_smooth_l1_beta", C.c_float), ("rpn_loss_weight", C.c_float),
+                ("rpn_bbox_reg_loss_weight", C.c_float), ("box_loss_type", C.c_int), ("box_smooth_l1_beta", C.c_float),
+                ("box_bbox_reg_loss_weight", C.c_float)]
+
+
+BOXLOSS_SMOOTH_L1, BOXLOSS_GIOU = 0, 1
+BOXLOSS_TYPES = {"smooth_l1": BOXLOSS_SMOOTH_L1, "giou": BOXLOSS_GIOU}
+LOSS_OPT_KEYS = tuple(n for n, _ in LossOpts._fields_)
+
+
+def loss_opts(loss=None):
+    """LossOpts from the `loss=` dict of MaskRCNN (keys = the fields of amp_loss_opts; a loss type is "smooth_l1" / "giou" or its
+    AMP_BOXLOSS_* number; missing keys keep amp_loss_opts_default's value).  Raises ValueError for an unknown key or loss type, a bool where
+    a number is required, and a negative or non-finite number; the library validates the values again."""
+    import math
+    o = LossOpts()
+    check(lib().amp_loss_opts_default(C.byref(o)), "amp_loss_opts_default")
+    for k, v in dict(loss or {}).items():
+        if k not in LOSS_OPT_KEYS:
+            raise ValueError(f"loss: unknown key {k!r} (one of {', '.join(LOSS_OPT_KEYS)})")
+        if k.endswith("_loss_type"):
+            t = BOXLOSS_TYPES.get(v.lower()) if isinstance(v, str) else (int(v) if not isinstance(v, bool) and v in (0, 1) else None)
+            if t is None:
+                raise ValueError(f"loss[{k!r}] = {v!r}: 'smooth_l1' or 'giou'")
+            setattr(o, k, t)
+        else:
+            if isinstance(v, bool) or not isinstance(v, (int, float)) and not hasattr(v, "__float__") or not math.isfinite(float(v)) or float(v) < 0:
+                raise ValueError(f"loss[{k!r}] = {v!r}: a finite number >= 0 is required")
+            setattr(o, k, float(v))
+    return o
+
+
 class Gt(C.Structure):
     _fields_ = [("B", C.c_int), ("gt_off", C.POINTER(C.c_int)), ("boxes", C.POINTER(C.c_float)),
                 ("classes", C.POINTER(C.c_int)), ("poly_off", C.POINTER(C.c_int)), ("poly_xy", C.POINTER(C.c_double)),
@@ -225,6 +259,11 @@ def _declare(L):
         "amp_rpn_sample_loss": ([vp, C.POINTER(RpnLevels), vp, i, vp, vp, vp, vp, vp, i, i, C.c_uint, vp, vp, vp], i),
         "amp_roi_sample": ([vp, i, vp, vp, i, vp, vp, vp, i, i, i, f, C.c_uint, vp, vp, vp, i, vp, vp, vp, vp, vp, i], i),
         "amp_box_loss": ([vp, i, i, i, vp, i, vp, vp, vp, vp, vp, vp, C.POINTER(f), i, vp], i),
+        "amp_loss_opts_default": ([C.POINTER(LossOpts)], i),
+        "amp_rpn_sample_loss_ex": ([vp, C.POINTER(RpnLevels), vp, i, vp, vp, vp, vp, vp, i, i, C.c_uint, vp, vp, vp, C.POINTER(LossOpts)], i),
+        "amp_box_loss_ex": ([vp, i, i, i, vp, i, vp, vp, vp, vp, vp, vp, C.POINTER(f), i, vp, C.POINTER(LossOpts)], i),
+        "amp_model_set_loss_opts": ([vp, C.POINTER(LossOpts)], i),
+        "amp_model_get_loss_opts": ([vp, C.POINTER(LossOpts)], i),
         "amp_mask_target_loss": ([vp, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp], i),
         "amp_grouped_wgrad_scratch_floats": ([C.POINTER(ConvDesc)], C.c_size_t),
         "amp_conv2d_grouped_wgrad": ([vp, C.POINTER(ConvDesc), i, vp, vp, vp, vp, vp], i),

@@ -82,12 +82,16 @@ _DEFAULTS = {
         "ANCHOR_GENERATOR": {"SIZES": [[32, 64, 128, 256, 512]], "ASPECT_RATIOS": [[0.5, 1.0, 2.0]]},
         "RPN": {"IN_FEATURES": ["res4"], "PRE_NMS_TOPK_TRAIN": 12000, "PRE_NMS_TOPK_TEST": 6000,
                 "POST_NMS_TOPK_TRAIN": 2000, "POST_NMS_TOPK_TEST": 1000, "NMS_THRESH": 0.7,
-                "BATCH_SIZE_PER_IMAGE": 256, "POSITIVE_FRACTION": 0.5, "IOU_THRESHOLDS": [0.3, 0.7]},
+                "BATCH_SIZE_PER_IMAGE": 256, "POSITIVE_FRACTION": 0.5, "IOU_THRESHOLDS": [0.3, 0.7],
+                # detectron2's defaults; engine/defaults.py loss_kwargs maps them to the native losses (amp_loss_opts)
+                "LOSS_WEIGHT": 1.0, "BBOX_REG_LOSS_TYPE": "smooth_l1", "BBOX_REG_LOSS_WEIGHT": 1.0, "SMOOTH_L1_BETA": 0.0,
+                "BBOX_REG_WEIGHTS": [1.0, 1.0, 1.0, 1.0]},
         "ROI_HEADS": {"NAME": "Res5ROIHeads", "NUM_CLASSES": 80, "BATCH_SIZE_PER_IMAGE": 512,
                       "POSITIVE_FRACTION": 0.25, "SCORE_THRESH_TEST": 0.05, "NMS_THRESH_TEST": 0.5,
                       "IOU_THRESHOLDS": [0.5], "IN_FEATURES": ["res4"]},
         "ROI_BOX_HEAD": {"NAME": "", "NUM_FC": 0, "FC_DIM": 1024, "POOLER_RESOLUTION": 14,
-                         "BBOX_REG_WEIGHTS": [10.0, 10.0, 5.0, 5.0]},
+                         "BBOX_REG_WEIGHTS": [10.0, 10.0, 5.0, 5.0], "SMOOTH_L1_BETA": 0.0, "BBOX_REG_LOSS_TYPE": "smooth_l1",
+                         "BBOX_REG_LOSS_WEIGHT": 1.0, "CLS_AGNOSTIC_BBOX_REG": False, "TRAIN_ON_PRED_BOXES": False},
         "ROI_MASK_HEAD": {"NAME": "MaskRCNNConvUpsampleHead", "NUM_CONV": 0, "POOLER_RESOLUTION": 14},
     },
     "INPUT": {"MIN_SIZE_TRAIN": (800,), "MAX_SIZE_TRAIN": 1333, "MIN_SIZE_TEST": 800, "MAX_SIZE_TEST": 1333,

@@ -284,6 +284,9 @@ struct SgdPlan {
 int sgd_plan_build(const unsigned long long* off, const unsigned long long* n, const unsigned long long* nstat, const unsigned char* is_bias,
                    int ntensors, SgdPlan* plan);
 void sgd_plan_free(SgdPlan* plan);
+// train_fwd.hip: amp_loss_opts validation (AMP_ERR_ARG naming the field) and the loss kernels' mode of one head (0 L1, 1 smooth-L1, 2 GIoU)
+int loss_opts_check(const amp_loss_opts* o, const char* fn);
+int reg_mode(int loss_type, float beta);
 int sgd_opts_check(const amp_sgd_opts* o, const char* fn);
 bool sgd_opts_plain(const amp_sgd_opts* o);     // what sgd_chunks_run computes: no clipping, no Nesterov, one learning rate and one decay
 int sgd_general_run(amp_ctx* ctx, const SgdPlan& plan, float* p, const float* g, float* v, const amp_sgd_opts& o);

@@ -102,6 +102,7 @@ struct amp_model {
     // ---- training ----
     float* garena = nullptr;            // gradients, same offsets as parena
     float* varena = nullptr;            // SGD momentum buffers, same offsets
+    amp_loss_opts loss_opts = {AMP_BOXLOSS_SMOOTH_L1, 0.f, 1.f, 1.f, AMP_BOXLOSS_SMOOTH_L1, 0.f, 1.f};   // amp_model_set_loss_opts (= amp_loss_opts_default)
     bool saving = false;                // run_trunk keeps every activation the backward pass needs
     bool acts_split = false;            // ... and kept them in the split row format (training on the native trunk, AMP_CONV_F16X3)
     int last_rpn_sparse = -1;           // 1: the last backward pass ran the RPN head's gradients over the sampled pixels only (rpn_sparse.hip)
@@ -955,8 +956,8 @@ int run_train(amp_model* m, const uint8_t* imgs_d, int B, int H, int W, const am
         }
         if (npoly) AMP_HIP_CHECK(hipMemcpyAsync(d_poly_xy, gt->poly_xy, (size_t)npoly * 8, hipMemcpyHostToDevice, ctx->stream));
         AMP_TRY(amp_anchor_labels(ctx, &T.lv, B, d_gt_boxes, d_gt_off, total_gt, c.rpn_iou_lo, c.rpn_iou_hi, match_val, match_idx, gt_best, label));
-        AMP_TRY(amp_rpn_sample_loss(ctx, &T.lv, backward ? d_rpn_pred : nullptr, B, d_gt_boxes, d_gt_off, label, match_idx, keys, c.rpn_batch, c.rpn_pos_max, seed,
-                                    rpn_sampled, rpn_counts, rpn_partial));
+        AMP_TRY(amp_rpn_sample_loss_ex(ctx, &T.lv, backward ? d_rpn_pred : nullptr, B, d_gt_boxes, d_gt_off, label, match_idx, keys, c.rpn_batch, c.rpn_pos_max, seed,
+                                       rpn_sampled, rpn_counts, rpn_partial, &m->loss_opts));
         tap(m, "rpn_label", label, 3, {B, A});
         tap(m, "rpn_match_idx", match_idx, 1, {B, A});
         tap(m, "rpn_sampled", rpn_sampled, 1, {B, c.rpn_batch});
@@ -1016,8 +1017,8 @@ int run_train(amp_model* m, const uint8_t* imgs_d, int B, int H, int W, const am
     if (!dry) {
         for (int b = 0; b < B; ++b) { total_rois += h_counts[2 * b] + h_counts[2 * b + 1]; fg_off[b + 1] = fg_off[b] + h_counts[2 * b]; }
         N = fg_off[B];
-        AMP_TRY(amp_box_loss(ctx, B, RB, K, box_pred, ld_box, d_box_pred, rois, roi_cls, roi_gti, d_gt_boxes, d_gt_off, c.bbox_reg_weights, total_rois,
-                             box_partial));
+        AMP_TRY(amp_box_loss_ex(ctx, B, RB, K, box_pred, ld_box, d_box_pred, rois, roi_cls, roi_gti, d_gt_boxes, d_gt_off, c.bbox_reg_weights, total_rois,
+                                box_partial, &m->loss_opts));
     }
     // mask branch on the foreground RoIs (the first nfg of every image's sample)
     const int Nc = std::max(N, 1);
@@ -1120,16 +1121,17 @@ int run_train(amp_model* m, const uint8_t* imgs_d, int B, int H, int W, const am
         for (int i = 0; i < N; ++i) s_mask += h_mpart[i];
         const float rpn_norm = (float)(c.rpn_batch * B);
         losses[0] = total_rois ? s_ce / (float)total_rois : 0.f;
-        losses[1] = s_l1 / (float)std::max(total_rois, 1);
+        const amp_loss_opts& lo = m->loss_opts;      // the weights as detectron2 applies them (x 1.0f by default: the same bits)
+        losses[1] = s_l1 / (float)std::max(total_rois, 1) * lo.box_bbox_reg_loss_weight;
         losses[2] = N ? s_mask / ((float)N * 784.f) : 0.f;
-        losses[3] = s_bce / rpn_norm;
-        losses[4] = s_loc / rpn_norm;
+        losses[3] = s_bce / rpn_norm * lo.rpn_loss_weight;
+        losses[4] = s_loc / rpn_norm * (lo.rpn_loss_weight * lo.rpn_bbox_reg_loss_weight);
     }
     if (!backward) return AMP_OK;
 
     // =============================================== backward ===============================================
-    // Gradients of the five losses (each with weight 1) w.r.t. every trainable parameter, into m->garena (same offsets as the
-    // parameters).  Stem and res2 are frozen (FREEZE_AT = 2), FrozenBN has no parameters; its scale is folded into the weight
+    // Gradients of the five losses (weighted as amp_model_set_loss_opts says: the loss kernels' gradients carry the weights) w.r.t. every
+    // trainable parameter, into m->garena (same offsets as the parameters).  Stem and res2 are frozen (FREEZE_AT = 2), FrozenBN has no parameters; its scale is folded into the weight
     // transforms (data gradients) and the wgrad reduce (weight gradients).
     if (!dry) AMP_TRY(amp::comm_wait_done(ctx));    // a previous exchange of this arena (a step without sgd_step, a re-run) must have finished
     if (!dry) { m->issued_mask = 0; m->grads_valid = false; }
@@ -2498,6 +2500,19 @@ static int train_entry(amp_model* m, const uint8_t* imgs_bgr, int imgs_on_host, 
         }
     }
     return st;
+}
+
+int amp_model_set_loss_opts(amp_model* m, const amp_loss_opts* opts) {
+    AMP_REQUIRE(m && m->cfg.train_enable, "amp_model_set_loss_opts: the model was created without cfg.train_enable");
+    AMP_TRY_STATUS(amp::loss_opts_check(opts, "amp_model_set_loss_opts"));
+    m->loss_opts = *opts;
+    return AMP_OK;
+}
+
+int amp_model_get_loss_opts(amp_model* m, amp_loss_opts* opts) {
+    AMP_REQUIRE(m && opts, "amp_model_get_loss_opts: null argument");
+    *opts = m->loss_opts;
+    return AMP_OK;
 }
 
 int amp_model_set_image_sizes(amp_model* m, const int* hw_h, int B) {

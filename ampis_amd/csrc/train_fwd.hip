@@ -185,7 +185,77 @@ __global__ __launch_bounds__(256) void anchor_label_kernel(const AnchorGeom g, c
     }
 }
 
-// ---- RPN: sample 256 anchors / image, BCE + L1 losses and their gradients -----------------------------------------------------
+// ---- box regression losses (amp_loss_opts): smooth-L1 with a quadratic zone, GIoU through apply_deltas ---------------------------
+// The loss kernels are compiled once per REG mode.  REG_L1 is beta < 1e-5 (fvcore's smooth_l1_loss then is |d|): the arithmetic of the
+// kernels before the options existed, with the loss weights folded into the gradient scales on the host (x 1.0f by default: the same bits).
+enum { REG_L1 = 0, REG_SMOOTH_L1 = 1, REG_GIOU = 2 };
+constexpr float SCALE_CLAMP = 4.135166556742356f;      // log(1000 / 16), Box2BoxTransform.apply_deltas
+
+// fvcore smooth_l1_loss, beta >= 1e-5: 0.5 d^2 / beta for |d| < beta, |d| - 0.5 beta elsewhere; grad = d loss / d d
+__device__ __forceinline__ float smooth_l1(float d, float beta, float& grad) {
+    const float ad = fabsf(d);
+    if (ad < beta) {
+        grad = __fdiv_rn(d, beta);
+        return __fdiv_rn(__fmul_rn(0.5f, __fmul_rn(d, d)), beta);
+    }
+    grad = d > 0.f ? 1.f : -1.f;
+    return __fsub_rn(ad, __fmul_rn(0.5f, beta));
+}
+
+// fvcore giou_loss(apply_deltas(p, src, w), gt, eps = 1e-7) of one box and its gradient w.r.t. the four deltas (not yet scaled).
+// dw / dh are clamped at SCALE_CLAMP after the division by their weight; a clamped delta gets gradient 0.  With I the intersection (0
+// unless both extents are positive), U = Ap + Ag - I the union and C the area of the enclosing box:
+//   loss = 1 - I / (U + eps) + (C - U) / (C + eps)
+//   dloss/dI = -1 / (U + eps) - gU,  dloss/dAp = gU = I / (U + eps)^2 - 1 / (C + eps),  dloss/dC = (U + eps) / (C + eps)^2
+// and I, Ap, C reach the corners (x1, y1, x2, y2) of the predicted box through the min / max that selects them.
+__device__ __forceinline__ float giou_loss_grad(const float p[4], float sx1, float sy1, float sx2, float sy2, float wx, float wy, float ww,
+                                                float wh, const float* gb, float g[4]) {
+    const float eps = 1e-7f;
+    const float sw = __fsub_rn(sx2, sx1), sh = __fsub_rn(sy2, sy1);
+    const float sx = __fadd_rn(sx1, __fmul_rn(0.5f, sw)), sy = __fadd_rn(sy1, __fmul_rn(0.5f, sh));
+    const float dx = __fdiv_rn(p[0], wx), dy = __fdiv_rn(p[1], wy);
+    float dw = __fdiv_rn(p[2], ww), dh = __fdiv_rn(p[3], wh);
+    const bool cw = dw > SCALE_CLAMP, ch = dh > SCALE_CLAMP;
+    dw = fminf(dw, SCALE_CLAMP); dh = fminf(dh, SCALE_CLAMP);
+    const float pcx = __fadd_rn(__fmul_rn(dx, sw), sx), pcy = __fadd_rn(__fmul_rn(dy, sh), sy);
+    const float pw = __fmul_rn(expf(dw), sw), ph = __fmul_rn(expf(dh), sh);
+    const float x1 = __fsub_rn(pcx, __fmul_rn(0.5f, pw)), y1 = __fsub_rn(pcy, __fmul_rn(0.5f, ph));
+    const float x2 = __fadd_rn(pcx, __fmul_rn(0.5f, pw)), y2 = __fadd_rn(pcy, __fmul_rn(0.5f, ph));
+    const float x1g = gb[0], y1g = gb[1], x2g = gb[2], y2g = gb[3];
+    const float bw = __fsub_rn(x2, x1), bh = __fsub_rn(y2, y1);
+    const float iw = __fsub_rn(fminf(x2, x2g), fmaxf(x1, x1g)), ih = __fsub_rn(fminf(y2, y2g), fmaxf(y1, y1g));
+    const bool hit = iw > 0.f && ih > 0.f;
+    const float I = hit ? __fmul_rn(iw, ih) : 0.f;
+    const float U = __fsub_rn(__fadd_rn(__fmul_rn(bw, bh), __fmul_rn(__fsub_rn(x2g, x1g), __fsub_rn(y2g, y1g))), I);
+    const float Ue = __fadd_rn(U, eps);
+    const float ew = __fsub_rn(fmaxf(x2, x2g), fminf(x1, x1g)), eh = __fsub_rn(fmaxf(y2, y2g), fminf(y1, y1g));
+    const float Cc = __fmul_rn(ew, eh), Ce = __fadd_rn(Cc, eps);
+    const float iou = __fdiv_rn(I, Ue);
+    const float loss = __fsub_rn(1.f, __fsub_rn(iou, __fdiv_rn(__fsub_rn(Cc, U), Ce)));
+    const float gU = __fsub_rn(__fdiv_rn(iou, Ue), __fdiv_rn(1.f, Ce));
+    const float gI = __fsub_rn(__fdiv_rn(-1.f, Ue), gU);
+    const float gC = __fdiv_rn(Ue, __fmul_rn(Ce, Ce));
+    // d loss / d corner = gU dAp + gI dI + gC dC
+    float gx1 = __fmul_rn(gU, -bh), gx2 = __fmul_rn(gU, bh), gy1 = __fmul_rn(gU, -bw), gy2 = __fmul_rn(gU, bw);
+    if (hit) {
+        if (x1 > x1g) gx1 = __fsub_rn(gx1, __fmul_rn(gI, ih));
+        if (x2 < x2g) gx2 = __fadd_rn(gx2, __fmul_rn(gI, ih));
+        if (y1 > y1g) gy1 = __fsub_rn(gy1, __fmul_rn(gI, iw));
+        if (y2 < y2g) gy2 = __fadd_rn(gy2, __fmul_rn(gI, iw));
+    }
+    if (x1 < x1g) gx1 = __fsub_rn(gx1, __fmul_rn(gC, eh));
+    if (x2 > x2g) gx2 = __fadd_rn(gx2, __fmul_rn(gC, eh));
+    if (y1 < y1g) gy1 = __fsub_rn(gy1, __fmul_rn(gC, ew));
+    if (y2 > y2g) gy2 = __fadd_rn(gy2, __fmul_rn(gC, ew));
+    // corners -> deltas: x1,2 = pcx -+ 0.5 pw, pcx = p0 / wx * sw + sx, pw = exp(p2 / ww) * sw
+    g[0] = __fdiv_rn(__fmul_rn(__fadd_rn(gx1, gx2), sw), wx);
+    g[1] = __fdiv_rn(__fmul_rn(__fadd_rn(gy1, gy2), sh), wy);
+    g[2] = cw ? 0.f : __fdiv_rn(__fmul_rn(__fmul_rn(0.5f, __fsub_rn(gx2, gx1)), pw), ww);
+    g[3] = ch ? 0.f : __fdiv_rn(__fmul_rn(__fmul_rn(0.5f, __fsub_rn(gy2, gy1)), ph), wh);
+    return loss;
+}
+
+// ---- RPN: sample 256 anchors / image, BCE + box regression losses and their gradients --------------------------------------------
 struct RpnLossArgs {
     AnchorGeom g;
     const float* pred[NL];        // [B, hw, ld]: A logits, 4 A deltas (+ padding)
@@ -198,10 +268,12 @@ struct RpnLossArgs {
     uint32_t* keys_scratch;       // [B][total]
     int batch, num_pos_max;       // 256, 128
     uint32_t seed;
-    float inv_norm;               // 1 / (batch * B)
+    float cls_scale;              // RPN.LOSS_WEIGHT / (batch * B): scales d(loss_rpn_cls)
+    float loc_scale;              // RPN.LOSS_WEIGHT * RPN.BBOX_REG_LOSS_WEIGHT / (batch * B): scales d(loss_rpn_loc)
+    float beta;                   // RPN.SMOOTH_L1_BETA (REG_SMOOTH_L1)
     int* sampled;                 // [B][batch] anchor indices: positives then negatives, ascending hash
     int* counts;                  // [B][2] npos, nneg
-    float* partial;               // [B][2] sum BCE, sum L1 (unnormalised)
+    float* partial;               // [B][2] sum BCE, sum of the regression loss (unnormalised, unweighted)
     // chunked selection (rpn_sample_select_kernel): the anchors of an image are cut into nch chunks of <= SAMPLE_CHUNK, every (image,
     // positives | negatives, chunk) keeps its best `batch` words; rpn_sample_loss_kernel then orders the <= nch * batch words of a class
     unsigned long long* cand;     // [B][2][nch][batch] sorted words (key << 32 | ~anchor), null: one workgroup per image selects from all anchors
@@ -227,6 +299,7 @@ __global__ __launch_bounds__(1024) void rpn_sample_select_kernel(const RpnLossAr
     if (threadIdx.x == 0) a.cand_count[blockIdx.x] = k;
 }
 
+template <int REG>
 __global__ __launch_bounds__(1024) void rpn_sample_loss_kernel(const RpnLossArgs a) {
     __shared__ amp::SelectSmem sm;
     __shared__ int s_idx[512];
@@ -281,8 +354,16 @@ __global__ __launch_bounds__(1024) void rpn_sample_loss_kernel(const RpnLossArgs
         const float y = tid < npos ? 1.f : 0.f;
         // binary_cross_entropy_with_logits: max(x,0) - x*y + log1p(exp(-|x|)); d/dx = sigmoid(x) - y
         bce = __fadd_rn(__fsub_rn(fmaxf(x, 0.f), __fmul_rn(x, y)), log1pf(expf(-fabsf(x))));
-        if (dp) dp[k] = __fmul_rn(__fsub_rn(__fdiv_rn(1.f, __fadd_rn(1.f, expf(-x))), y), a.inv_norm);
-        if (tid < npos) {
+        if (dp) dp[k] = __fmul_rn(__fsub_rn(__fdiv_rn(1.f, __fadd_rn(1.f, expf(-x))), y), a.cls_scale);
+        if (REG == REG_GIOU && tid < npos) {     // the anchor moved by its four deltas (box weights 1) against the matched GT box
+            const float* gb = a.gt_boxes + (size_t)(a.gt_off[b] + a.match_idx[(size_t)b * n + an]) * 4;
+            const float pd[4] = {p[A + 4 * k], p[A + 4 * k + 1], p[A + 4 * k + 2], p[A + 4 * k + 3]};
+            float g[4];
+            l1 = giou_loss_grad(pd, x1, y1, x2, y2, 1.f, 1.f, 1.f, 1.f, gb, g);
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (dp) dp[A + 4 * k + q] = __fmul_rn(g[q], a.loc_scale);
+        } else if (tid < npos) {
             const float* gb = a.gt_boxes + (size_t)(a.gt_off[b] + a.match_idx[(size_t)b * n + an]) * 4;
             const float sw = __fsub_rn(x2, x1), sh = __fsub_rn(y2, y1);
             const float sx = __fadd_rn(x1, __fmul_rn(0.5f, sw)), sy = __fadd_rn(y1, __fmul_rn(0.5f, sh));
@@ -293,8 +374,14 @@ __global__ __launch_bounds__(1024) void rpn_sample_loss_kernel(const RpnLossArgs
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const float d = __fsub_rn(p[A + 4 * k + q], t[q]);
-                l1 = __fadd_rn(l1, fabsf(d));
-                if (dp) dp[A + 4 * k + q] = (d > 0.f ? a.inv_norm : (d < 0.f ? -a.inv_norm : 0.f));
+                if (REG == REG_SMOOTH_L1) {
+                    float gd;
+                    l1 = __fadd_rn(l1, smooth_l1(d, a.beta, gd));
+                    if (dp) dp[A + 4 * k + q] = __fmul_rn(gd, a.loc_scale);
+                } else {
+                    l1 = __fadd_rn(l1, fabsf(d));
+                    if (dp) dp[A + 4 * k + q] = (d > 0.f ? a.loc_scale : (d < 0.f ? -a.loc_scale : 0.f));
+                }
             }
         }
     }
@@ -400,10 +487,13 @@ struct BoxLossArgs {
     const int* gt_off;
     int batch, K, ld;
     float wx, wy, ww, wh;
-    float inv_total;              // 1 / (number of sampled RoIs in the batch)
-    float* partial;               // [B][2] sum CE, sum L1
+    float inv_total;              // 1 / (number of sampled RoIs in the batch): scales d(loss_cls)
+    float reg_scale;              // ROI_BOX_HEAD.BBOX_REG_LOSS_WEIGHT / (number of sampled RoIs): scales d(loss_box_reg)
+    float beta;                   // ROI_BOX_HEAD.SMOOTH_L1_BETA (REG_SMOOTH_L1)
+    float* partial;               // [B][2] sum CE, sum of the regression loss (unweighted)
 };
 
+template <int REG>
 __global__ __launch_bounds__(512) void box_loss_kernel(const BoxLossArgs a) {
     __shared__ float s_red[2][512];
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -428,7 +518,15 @@ __global__ __launch_bounds__(512) void box_loss_kernel(const BoxLossArgs a) {
                 dp[k] = __fmul_rn(__fsub_rn(__fdiv_rn(expf(__fsub_rn(p[k], mx)), sum), k == c ? 1.f : 0.f), a.inv_total);
             for (int k = a.K + 1; k < a.ld; ++k) dp[k] = 0.f;
         }
-        if (c < a.K) {
+        if (REG == REG_GIOU && c < a.K) {       // the RoI moved by its GT-class deltas against the matched GT box
+            const float* s = a.rois + row * 4;
+            const float* g = a.gt_boxes + (size_t)(a.gt_off[b] + a.roi_gti[row]) * 4;
+            const int col = a.K + 1 + 4 * c;
+            const float pd[4] = {p[col], p[col + 1], p[col + 2], p[col + 3]};
+            float gd[4];
+            l1 = __fadd_rn(l1, giou_loss_grad(pd, s[0], s[1], s[2], s[3], a.wx, a.wy, a.ww, a.wh, g, gd));
+            if (dp) for (int q = 0; q < 4; ++q) dp[col + q] = __fmul_rn(gd[q], a.reg_scale);
+        } else if (c < a.K) {
             const float* s = a.rois + row * 4;
             const float* g = a.gt_boxes + (size_t)(a.gt_off[b] + a.roi_gti[row]) * 4;
             const float sw = __fsub_rn(s[2], s[0]), sh = __fsub_rn(s[3], s[1]);
@@ -440,8 +538,14 @@ __global__ __launch_bounds__(512) void box_loss_kernel(const BoxLossArgs a) {
             for (int q = 0; q < 4; ++q) {
                 const int col = a.K + 1 + 4 * c + q;
                 const float d = __fsub_rn(p[col], t[q]);
-                l1 = __fadd_rn(l1, fabsf(d));
-                if (dp) dp[col] = (d > 0.f ? a.inv_total : (d < 0.f ? -a.inv_total : 0.f));
+                if (REG == REG_SMOOTH_L1) {
+                    float gd;
+                    l1 = __fadd_rn(l1, smooth_l1(d, a.beta, gd));
+                    if (dp) dp[col] = __fmul_rn(gd, a.reg_scale);
+                } else {
+                    l1 = __fadd_rn(l1, fabsf(d));
+                    if (dp) dp[col] = (d > 0.f ? a.reg_scale : (d < 0.f ? -a.reg_scale : 0.f));
+                }
             }
         }
     }
@@ -756,6 +860,25 @@ bool fill_geom(AnchorGeom& g, const amp_rpn_levels* lv) {
 
 }  // namespace
 
+// amp_loss_opts: every scalar finite and >= 0, the types known (the message names the field)
+int amp::loss_opts_check(const amp_loss_opts* o, const char* fn) {
+    AMP_REQUIRE(o, "%s: null amp_loss_opts", fn);
+    const struct { const char* name; float v; } scalars[] = {{"rpn_smooth_l1_beta", o->rpn_smooth_l1_beta}, {"rpn_loss_weight", o->rpn_loss_weight},
+        {"rpn_bbox_reg_loss_weight", o->rpn_bbox_reg_loss_weight}, {"box_smooth_l1_beta", o->box_smooth_l1_beta},
+        {"box_bbox_reg_loss_weight", o->box_bbox_reg_loss_weight}};
+    for (auto& s : scalars) AMP_REQUIRE(std::isfinite(s.v) && s.v >= 0.f, "%s: amp_loss_opts.%s = %g must be finite and not negative", fn, s.name, (double)s.v);
+    AMP_REQUIRE(o->rpn_loss_type == AMP_BOXLOSS_SMOOTH_L1 || o->rpn_loss_type == AMP_BOXLOSS_GIOU,
+                "%s: amp_loss_opts.rpn_loss_type %d (AMP_BOXLOSS_SMOOTH_L1 or AMP_BOXLOSS_GIOU)", fn, o->rpn_loss_type);
+    AMP_REQUIRE(o->box_loss_type == AMP_BOXLOSS_SMOOTH_L1 || o->box_loss_type == AMP_BOXLOSS_GIOU,
+                "%s: amp_loss_opts.box_loss_type %d (AMP_BOXLOSS_SMOOTH_L1 or AMP_BOXLOSS_GIOU)", fn, o->box_loss_type);
+    return AMP_OK;
+}
+
+// which instantiation of the loss kernels a head runs: fvcore's smooth_l1_loss is |d| below beta = 1e-5
+int amp::reg_mode(int loss_type, float beta) {
+    return loss_type == AMP_BOXLOSS_GIOU ? REG_GIOU : (beta < 1e-5f ? REG_L1 : REG_SMOOTH_L1);
+}
+
 extern "C" {
 
 int amp_anchor_labels(amp_ctx* ctx, const amp_rpn_levels* lv, int B, const float* gt_boxes, const int* gt_off, int total_gt,
@@ -772,9 +895,27 @@ int amp_anchor_labels(amp_ctx* ctx, const amp_rpn_levels* lv, int B, const float
     return AMP_OK;
 }
 
+int amp_loss_opts_default(amp_loss_opts* o) {
+    AMP_REQUIRE(o, "amp_loss_opts_default: null argument");
+    o->rpn_loss_type = o->box_loss_type = AMP_BOXLOSS_SMOOTH_L1;
+    o->rpn_smooth_l1_beta = o->box_smooth_l1_beta = 0.f;
+    o->rpn_loss_weight = o->rpn_bbox_reg_loss_weight = o->box_bbox_reg_loss_weight = 1.f;
+    return AMP_OK;
+}
+
 int amp_rpn_sample_loss(amp_ctx* ctx, const amp_rpn_levels* lv, float* const dpred[5], int B, const float* gt_boxes,
                         const int* gt_off, const signed char* label, const int* match_idx, uint32_t* keys_scratch, int batch,
                         int num_pos_max, unsigned int seed, int* sampled, int* counts, float* partial) {
+    amp_loss_opts o;
+    amp_loss_opts_default(&o);
+    return amp_rpn_sample_loss_ex(ctx, lv, dpred, B, gt_boxes, gt_off, label, match_idx, keys_scratch, batch, num_pos_max, seed, sampled, counts,
+                                  partial, &o);
+}
+
+int amp_rpn_sample_loss_ex(amp_ctx* ctx, const amp_rpn_levels* lv, float* const dpred[5], int B, const float* gt_boxes,
+                           const int* gt_off, const signed char* label, const int* match_idx, uint32_t* keys_scratch, int batch,
+                           int num_pos_max, unsigned int seed, int* sampled, int* counts, float* partial, const amp_loss_opts* opts) {
+    AMP_TRY_STATUS(amp::loss_opts_check(opts, "amp_rpn_sample_loss"));
     AMP_REQUIRE(ctx && lv && gt_boxes && gt_off && label && match_idx && keys_scratch && sampled && counts && partial, "amp_rpn_sample_loss: null argument");
     AMP_REQUIRE(batch >= 1 && batch <= 512, "amp_rpn_sample_loss: batch must be in [1,512]");
     AMP_REQUIRE(num_pos_max >= 0 && num_pos_max <= batch, "amp_rpn_sample_loss: num_pos_max %d outside [0, batch %d]", num_pos_max, batch);
@@ -784,7 +925,11 @@ int amp_rpn_sample_loss(amp_ctx* ctx, const amp_rpn_levels* lv, float* const dpr
     for (int l = 0; l < NL; ++l) { a.pred[l] = lv->pred[l]; a.dpred[l] = dpred ? dpred[l] : nullptr; }
     a.ld = lv->ld;
     a.gt_boxes = gt_boxes; a.gt_off = gt_off; a.label = label; a.match_idx = match_idx; a.keys_scratch = keys_scratch;
-    a.batch = batch; a.num_pos_max = num_pos_max; a.seed = seed; a.inv_norm = 1.0f / (float)(batch * B);
+    a.batch = batch; a.num_pos_max = num_pos_max; a.seed = seed;
+    const float inv_norm = 1.0f / (float)(batch * B);
+    a.cls_scale = inv_norm * opts->rpn_loss_weight;
+    a.loc_scale = inv_norm * opts->rpn_loss_weight * opts->rpn_bbox_reg_loss_weight;
+    a.beta = opts->rpn_smooth_l1_beta;
     a.sampled = sampled; a.counts = counts; a.partial = partial;
     // chunked selection when the chunks' candidate lists fit the caller's scratch ([B][total] uint32) and one LDS sort (nch * batch <= 2048)
     a.cand = nullptr; a.cand_count = nullptr; a.nch = amp::cdiv(a.g.total, SAMPLE_CHUNK);
@@ -797,7 +942,11 @@ int amp_rpn_sample_loss(amp_ctx* ctx, const amp_rpn_levels* lv, float* const dpr
         hipLaunchKernelGGL(rpn_sample_select_kernel, dim3(B * 2 * a.nch), dim3(1024), 0, ctx->stream, a);
     }
     ctx->last_rpn_sample_chunked = a.cand ? 1 : 0;
-    hipLaunchKernelGGL(rpn_sample_loss_kernel, dim3(B), dim3(1024), 0, ctx->stream, a);
+    switch (amp::reg_mode(opts->rpn_loss_type, opts->rpn_smooth_l1_beta)) {
+        case REG_GIOU: hipLaunchKernelGGL(rpn_sample_loss_kernel<REG_GIOU>, dim3(B), dim3(1024), 0, ctx->stream, a); break;
+        case REG_SMOOTH_L1: hipLaunchKernelGGL(rpn_sample_loss_kernel<REG_SMOOTH_L1>, dim3(B), dim3(1024), 0, ctx->stream, a); break;
+        default: hipLaunchKernelGGL(rpn_sample_loss_kernel<REG_L1>, dim3(B), dim3(1024), 0, ctx->stream, a);
+    }
     AMP_HIP_CHECK(hipGetLastError());
     return AMP_OK;
 }
@@ -825,13 +974,28 @@ int amp_roi_sample(amp_ctx* ctx, int B, const float* prop_boxes, const int* prop
 
 int amp_box_loss(amp_ctx* ctx, int B, int batch, int K, const float* pred, int ld, float* dpred, const float* rois, const int* roi_cls,
                  const int* roi_gti, const float* gt_boxes, const int* gt_off, const float reg_weights[4], int total_rois, float* partial) {
+    amp_loss_opts o;
+    amp_loss_opts_default(&o);
+    return amp_box_loss_ex(ctx, B, batch, K, pred, ld, dpred, rois, roi_cls, roi_gti, gt_boxes, gt_off, reg_weights, total_rois, partial, &o);
+}
+
+int amp_box_loss_ex(amp_ctx* ctx, int B, int batch, int K, const float* pred, int ld, float* dpred, const float* rois, const int* roi_cls,
+                    const int* roi_gti, const float* gt_boxes, const int* gt_off, const float reg_weights[4], int total_rois, float* partial,
+                    const amp_loss_opts* opts) {
+    AMP_TRY_STATUS(amp::loss_opts_check(opts, "amp_box_loss"));
     AMP_REQUIRE(ctx && pred && rois && roi_cls && roi_gti && gt_boxes && gt_off && reg_weights && partial, "amp_box_loss: null argument");
     BoxLossArgs a;
     a.pred = pred; a.dpred = dpred; a.rois = rois; a.roi_cls = roi_cls; a.roi_gti = roi_gti; a.gt_boxes = gt_boxes; a.gt_off = gt_off;
     a.batch = batch; a.K = K; a.ld = ld; a.wx = reg_weights[0]; a.wy = reg_weights[1]; a.ww = reg_weights[2]; a.wh = reg_weights[3];
     a.inv_total = 1.0f / (float)(total_rois > 0 ? total_rois : 1);
+    a.reg_scale = a.inv_total * opts->box_bbox_reg_loss_weight;
+    a.beta = opts->box_smooth_l1_beta;
     a.partial = partial;
-    hipLaunchKernelGGL(box_loss_kernel, dim3(B), dim3(512), 0, ctx->stream, a);
+    switch (amp::reg_mode(opts->box_loss_type, opts->box_smooth_l1_beta)) {
+        case REG_GIOU: hipLaunchKernelGGL(box_loss_kernel<REG_GIOU>, dim3(B), dim3(512), 0, ctx->stream, a); break;
+        case REG_SMOOTH_L1: hipLaunchKernelGGL(box_loss_kernel<REG_SMOOTH_L1>, dim3(B), dim3(512), 0, ctx->stream, a); break;
+        default: hipLaunchKernelGGL(box_loss_kernel<REG_L1>, dim3(B), dim3(512), 0, ctx->stream, a);
+    }
     AMP_HIP_CHECK(hipGetLastError());
     return AMP_OK;
 }

@@ -57,7 +57,8 @@ def _num_anchors(anchor_kw):
 
 def train_model_kwargs(cfg, per_rank):
     """The MaskRCNN keyword arguments a training net takes from cfg (the trainer adds classes, capacity and backbone): batch size per
-    rank, training top-k, pixel statistics and every sampling setting of MODEL.RPN / MODEL.ROI_HEADS.  Refuses (ValueError naming the
+    rank, training top-k, pixel statistics, every sampling setting of MODEL.RPN / MODEL.ROI_HEADS, the anchors and the loss definition
+    (loss_kwargs).  Refuses (ValueError naming the
     key) what the native sampler cannot represent, before any device work."""
     from ..model import sampling_caps
     r, h = cfg.MODEL.RPN, cfg.MODEL.ROI_HEADS
@@ -69,6 +70,7 @@ def train_model_kwargs(cfg, per_rank):
               roi_batch=h.BATCH_SIZE_PER_IMAGE, roi_fg_frac=h.POSITIVE_FRACTION, roi_iou=seq(h.IOU_THRESHOLDS))
     sampling_caps(kw["rpn_batch"], kw["rpn_pos_frac"], kw["rpn_iou"], kw["roi_batch"], kw["roi_fg_frac"], kw["roi_iou"])
     kw.update(anchor_kwargs(cfg))
+    kw.update(loss_kwargs(cfg))
     return kw
 
 
@@ -128,6 +130,64 @@ def solver_kwargs(cfg):
                 raise ValueError(f"SOLVER.CLIP_GRADIENTS.NORM_TYPE = {nt!r}: 1, 2 or inf")
             kw["clip"] = ("norm", value, float(nt))
     return kw
+
+
+_RPN_LOSS_DEFAULTS = {"LOSS_WEIGHT": 1.0, "BBOX_REG_LOSS_TYPE": "smooth_l1", "BBOX_REG_LOSS_WEIGHT": 1.0, "SMOOTH_L1_BETA": 0.0,
+                      "BBOX_REG_WEIGHTS": (1.0, 1.0, 1.0, 1.0)}
+_BOX_LOSS_DEFAULTS = {"SMOOTH_L1_BETA": 0.0, "BBOX_REG_LOSS_TYPE": "smooth_l1", "BBOX_REG_LOSS_WEIGHT": 1.0, "CLS_AGNOSTIC_BBOX_REG": False,
+                      "TRAIN_ON_PRED_BOXES": False, "BBOX_REG_WEIGHTS": (10.0, 10.0, 5.0, 5.0)}
+
+
+def box_head_weights(cfg):
+    """MODEL.ROI_BOX_HEAD.BBOX_REG_WEIGHTS as the `bbox_reg_weights=` keyword of MaskRCNN (the predictor and the trainer both read it): four
+    positive finite numbers, ValueError naming the key otherwise."""
+    from ..model import box_weights
+    v = (cfg.MODEL.get("ROI_BOX_HEAD", None) or {}).get("BBOX_REG_WEIGHTS", _BOX_LOSS_DEFAULTS["BBOX_REG_WEIGHTS"])
+    return box_weights(tuple(v) if isinstance(v, (list, tuple)) else v, "MODEL.ROI_BOX_HEAD.BBOX_REG_WEIGHTS")
+
+
+def loss_kwargs(cfg):
+    """The MaskRCNN keyword arguments for the loss definition of MODEL.RPN and MODEL.ROI_BOX_HEAD as detectron2's RPN.from_config and
+    FastRCNNOutputLayers.from_config read it: dict(loss={the fields of amp_loss_opts}, bbox_reg_weights=(wx, wy, ww, wh)).
+    BBOX_REG_LOSS_TYPE "smooth_l1" (with SMOOTH_L1_BETA; 0 = L1) or "giou" on either head; loss_rpn_cls carries RPN.LOSS_WEIGHT,
+    loss_rpn_loc RPN.LOSS_WEIGHT x RPN.BBOX_REG_LOSS_WEIGHT, loss_box_reg ROI_BOX_HEAD.BBOX_REG_LOSS_WEIGHT.  A cfg without these keys (an
+    older yaml, a hand-built CfgNode) gets detectron2's defaults: the losses this project has always computed.  Raises ValueError naming
+    the cfg key for what the native losses cannot represent -- "diou" / "ciou", CLS_AGNOSTIC_BBOX_REG, TRAIN_ON_PRED_BOXES, RPN box
+    weights other than ones (they also enter the proposal decoding) -- before any device work."""
+    r = cfg.MODEL.get("RPN", None) or {}
+    h = cfg.MODEL.get("ROI_BOX_HEAD", None) or {}
+    rget = lambda k: r.get(k, _RPN_LOSS_DEFAULTS[k])
+    hget = lambda k: h.get(k, _BOX_LOSS_DEFAULTS[k])
+
+    def weight(v, key):
+        v = _number(v, key)
+        if v < 0:
+            raise ValueError(f"{key} = {v!r}: must not be negative")
+        return v
+
+    def kind(v, key):
+        if not isinstance(v, str) or v not in _lib.BOXLOSS_TYPES:
+            raise ValueError(f"{key} = {v!r}: 'smooth_l1' or 'giou' have a native path")
+        return v
+
+    for k in ("CLS_AGNOSTIC_BBOX_REG", "TRAIN_ON_PRED_BOXES"):
+        v = hget(k)
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError(f"MODEL.ROI_BOX_HEAD.{k} = {v!r}: True or False is required")
+        if v:
+            raise ValueError(f"MODEL.ROI_BOX_HEAD.{k} = True has no native path (False only)")
+    rw = rget("BBOX_REG_WEIGHTS")
+    if isinstance(rw, (str, bytes)) or not hasattr(rw, "__len__") or len(rw) != 4 or \
+            any(isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or float(x) != 1.0 for x in rw):
+        raise ValueError(f"MODEL.RPN.BBOX_REG_WEIGHTS = {rw!r}: the native RPN decodes and regresses with (1, 1, 1, 1)")
+    loss = dict(rpn_loss_type=kind(rget("BBOX_REG_LOSS_TYPE"), "MODEL.RPN.BBOX_REG_LOSS_TYPE"),
+                rpn_smooth_l1_beta=weight(rget("SMOOTH_L1_BETA"), "MODEL.RPN.SMOOTH_L1_BETA"),
+                rpn_loss_weight=weight(rget("LOSS_WEIGHT"), "MODEL.RPN.LOSS_WEIGHT"),
+                rpn_bbox_reg_loss_weight=weight(rget("BBOX_REG_LOSS_WEIGHT"), "MODEL.RPN.BBOX_REG_LOSS_WEIGHT"),
+                box_loss_type=kind(hget("BBOX_REG_LOSS_TYPE"), "MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_TYPE"),
+                box_smooth_l1_beta=weight(hget("SMOOTH_L1_BETA"), "MODEL.ROI_BOX_HEAD.SMOOTH_L1_BETA"),
+                box_bbox_reg_loss_weight=weight(hget("BBOX_REG_LOSS_WEIGHT"), "MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_WEIGHT"))
+    return dict(loss=loss, bbox_reg_weights=box_head_weights(cfg))
 
 
 _CROP_DEFAULTS = {"ENABLED": False, "TYPE": "relative_range", "SIZE": [0.9, 0.9]}
@@ -289,6 +349,7 @@ class DefaultPredictor:
         self.arch = P.arch_from_cfg(cfg)
         self._anchor_kw = anchor_kwargs(cfg)               # an anchor setting the native path cannot represent fails here, naming its key
         self.num_anchors = _num_anchors(self._anchor_kw)
+        self._box_weights = box_head_weights(cfg)          # MODEL.ROI_BOX_HEAD.BBOX_REG_WEIGHTS decodes the detections
         if w:
             self.params = checkpoint.load_checkpoint(w, self.num_classes, self.arch, num_anchors=self.num_anchors)
         else:
@@ -309,7 +370,7 @@ class DefaultPredictor:
                                    pre_nms_topk=int(c.MODEL.RPN.PRE_NMS_TOPK_TEST), post_nms_topk=int(c.MODEL.RPN.POST_NMS_TOPK_TEST),
                                    rpn_nms_thresh=float(c.MODEL.RPN.NMS_THRESH), score_thresh=float(c.MODEL.ROI_HEADS.SCORE_THRESH_TEST),
                                    nms_thresh=float(c.MODEL.ROI_HEADS.NMS_THRESH_TEST), pixel_mean=tuple(c.MODEL.PIXEL_MEAN),
-                                   pixel_std=tuple(c.MODEL.PIXEL_STD), arch=self.arch, **self._anchor_kw)
+                                   pixel_std=tuple(c.MODEL.PIXEL_STD), arch=self.arch, bbox_reg_weights=self._box_weights, **self._anchor_kw)
             self._model.load_params(self.params)
             self._cap = cap
         return self._model
@@ -352,7 +413,8 @@ class DefaultPredictor:
         return dict(detections_per_image=int(c.TEST.DETECTIONS_PER_IMAGE), pre_nms_topk=int(c.MODEL.RPN.PRE_NMS_TOPK_TEST),
                     post_nms_topk=int(c.MODEL.RPN.POST_NMS_TOPK_TEST), rpn_nms_thresh=float(c.MODEL.RPN.NMS_THRESH),
                     score_thresh=float(c.MODEL.ROI_HEADS.SCORE_THRESH_TEST), nms_thresh=float(c.MODEL.ROI_HEADS.NMS_THRESH_TEST),
-                    pixel_mean=tuple(c.MODEL.PIXEL_MEAN), pixel_std=tuple(c.MODEL.PIXEL_STD), arch=self.arch, **self._anchor_kw)
+                    pixel_mean=tuple(c.MODEL.PIXEL_MEAN), pixel_std=tuple(c.MODEL.PIXEL_STD), arch=self.arch, bbox_reg_weights=self._box_weights,
+                    **self._anchor_kw)
 
     def stream(self, images, depth=2):
         """`predictor(img)` for every image of an iterable, with `depth` images in flight on the GPU (amp_pipeline: the next image's

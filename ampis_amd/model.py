@@ -271,13 +271,30 @@ def anchor_lists(sizes=None, ratios=None):
     return s, r
 
 
+def box_weights(v, key="bbox_reg_weights"):
+    """MODEL.ROI_BOX_HEAD.BBOX_REG_WEIGHTS as the native config holds it: four positive finite floats (wx, wy, ww, wh).  Raises ValueError
+    naming `key` otherwise."""
+    if isinstance(v, (str, bytes)) or not hasattr(v, "__len__") or len(v) != 4:
+        raise ValueError(f"{key} = {v!r}: four numbers (wx, wy, ww, wh) are required")
+    for x in v:
+        if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not np.isfinite(x) or x <= 0:
+            raise ValueError(f"{key} = {v!r}: entry {x!r} is not a positive finite number")
+    return tuple(float(x) for x in v)
+
+
 class MaskRCNN:
     def __init__(self, ctx, num_classes, max_batch=1, max_h=1344, max_w=1344, max_out_hw=4096,
                  detections_per_image=100, pre_nms_topk=1000, post_nms_topk=1000, rpn_nms_thresh=0.7,
                  score_thresh=0.05, nms_thresh=0.5, mask_threshold=0.5, pixel_mean=(103.530, 116.280, 123.675),
                  pixel_std=(1.0, 1.0, 1.0), rle_pool_counts=0, train=False, max_gt=16384, max_poly_doubles=16384 * 80,
                  pre_nms_topk_train=2000, post_nms_topk_train=1000, rpn_batch=256, roi_batch=512, arch="R50",
-                 rpn_pos_frac=0.5, rpn_iou=(0.3, 0.7), roi_fg_frac=0.25, roi_iou=0.5, anchor_sizes=None, aspect_ratios=None):
+                 rpn_pos_frac=0.5, rpn_iou=(0.3, 0.7), roi_fg_frac=0.25, roi_iou=0.5, anchor_sizes=None, aspect_ratios=None,
+                 bbox_reg_weights=None, loss=None):
+        """bbox_reg_weights: MODEL.ROI_BOX_HEAD.BBOX_REG_WEIGHTS (None = (10, 10, 5, 5)), read by the box head in inference and in training.
+        loss: dict of amp_loss_opts fields (set_loss_opts), a training model only."""
+        if loss and not train:
+            raise ValueError("loss= configures the training losses: it needs train=True")
+        loss = _lib.loss_opts(loss) if loss else None
         caps = sampling_caps(rpn_batch, rpn_pos_frac, rpn_iou, roi_batch, roi_fg_frac, roi_iou)
         # MODEL.ANCHOR_GENERATOR.{SIZES, ASPECT_RATIOS}: lists of lists (one inner list = every level); None = the zoo's FPN anchors
         self.anchor_sizes, self.aspect_ratios = anchor_lists(anchor_sizes, aspect_ratios)
@@ -293,6 +310,9 @@ class MaskRCNN:
         cfg.rpn_nms_thresh, cfg.score_thresh, cfg.nms_thresh = float(rpn_nms_thresh), float(score_thresh), float(nms_thresh)
         cfg.detections_per_image = int(detections_per_image)
         cfg.mask_threshold = float(mask_threshold)
+        if bbox_reg_weights is not None:
+            for i_, v in enumerate(box_weights(bbox_reg_weights)):
+                cfg.bbox_reg_weights[i_] = v
         pad = lambda v: (int(v) + 31) // 32 * 32
         cfg.max_batch, cfg.max_h, cfg.max_w, cfg.max_out_hw = int(max_batch), pad(max_h), pad(max_w), int(max_out_hw)
         cfg.rle_pool_counts = int(rle_pool_counts)
@@ -314,6 +334,8 @@ class MaskRCNN:
             anchors = _lib.fill_anchors(_lib.AnchorCfg(), self.anchor_sizes, self.aspect_ratios)
             check(lib().amp_model_create_anchors(ctx.handle, C.byref(cfg), C.byref(anchors), C.byref(self._h)), "amp_model_create_anchors")
         self._finalized = False
+        if loss is not None:
+            check(lib().amp_model_set_loss_opts(self._h, C.byref(loss)), "amp_model_set_loss_opts")
 
     # ---- parameters ----
     def tensor_names(self):
@@ -423,6 +445,21 @@ class MaskRCNN:
         check(fn(self._h, img_p, on_host, B, H, W, C.byref(packed.struct), int(seed) & 0xFFFFFFFF, out),
               "amp_model_forward_backward" if backward else "amp_model_forward_losses")
         return {n: float(out[i]) for i, n in enumerate(self.LOSS_NAMES)}
+
+    def set_loss_opts(self, loss=None, **kw):
+        """The box regression losses and loss weights of the following training steps (amp_model_set_loss_opts; include/ampis_hip.h
+        documents the formulas): a dict and / or keyword arguments named after the fields of amp_loss_opts -- rpn_loss_type / box_loss_type
+        ("smooth_l1" | "giou"), rpn_smooth_l1_beta / box_smooth_l1_beta, rpn_loss_weight, rpn_bbox_reg_loss_weight,
+        box_bbox_reg_loss_weight.  Fields not named return to their defaults (plain L1, weights 1)."""
+        o = _lib.loss_opts(dict(loss or {}, **kw))
+        check(lib().amp_model_set_loss_opts(self._h, C.byref(o)), "amp_model_set_loss_opts")
+
+    def loss_opts(self):
+        """The options in force, as a dict of the amp_loss_opts fields (loss types as "smooth_l1" / "giou")."""
+        o = _lib.LossOpts()
+        check(lib().amp_model_get_loss_opts(self._h, C.byref(o)), "amp_model_get_loss_opts")
+        names = {v: k for k, v in _lib.BOXLOSS_TYPES.items()}
+        return {k: names[getattr(o, k)] if k.endswith("_loss_type") else float(getattr(o, k)) for k in _lib.LOSS_OPT_KEYS}
 
     def set_image_sizes(self, sizes):
         """sizes: list of (h, w) valid extents inside the common frame for the next batches, or None."""

@@ -405,6 +405,44 @@ int amp_roi_sample(amp_ctx* ctx, int B, const float* prop_boxes, const int* prop
                    int* counts, const int* prop_anchor /* [B,Pcap] stable ids for the sampling hash */, int num_anchors);
 int amp_box_loss(amp_ctx* ctx, int B, int batch, int K, const float* pred, int ld, float* dpred, const float* rois, const int* roi_cls,
                  const int* roi_gti, const float* gt_boxes, const int* gt_off, const float reg_weights[4], int total_rois, float* partial);
+/* The box regression losses of the RPN and the box head as detectron2 configures them (MODEL.RPN.{BBOX_REG_LOSS_TYPE, SMOOTH_L1_BETA,
+ * LOSS_WEIGHT, BBOX_REG_LOSS_WEIGHT}, MODEL.ROI_BOX_HEAD.{BBOX_REG_LOSS_TYPE, SMOOTH_L1_BETA, BBOX_REG_LOSS_WEIGHT}).  Per sampled positive
+ * anchor / foreground RoI, every operation rounded on its own, sums in a fixed order:
+ *   AMP_BOXLOSS_SMOOTH_L1 (fvcore smooth_l1_loss, reduction sum), d = predicted delta - get_deltas(source, matched GT, box weights):
+ *     beta < 1e-5:  |d|, gradient sign(d)                                  (the default, beta = 0: plain L1)
+ *     otherwise:    0.5 d^2 / beta with gradient d / beta for |d| < beta,  |d| - 0.5 beta with gradient sign(d) elsewhere
+ *   AMP_BOXLOSS_GIOU (fvcore giou_loss, reduction sum, eps = 1e-7) on box = apply_deltas(predicted deltas, source, box weights), where
+ *     dw and dh are clamped at log(1000 / 16) after the division by their weight and a clamped delta gets gradient 0:
+ *     I = intersection with the GT box (0 unless both extents are strictly positive), U = area(box) + area(GT) - I,
+ *     C = area of the smallest enclosing box;  loss = 1 - I / (U + eps) + (C - U) / (C + eps);  the gradient reaches the four deltas
+ *     through the corners of the box.
+ * The box weights are (1, 1, 1, 1) for the RPN and amp_model_cfg.bbox_reg_weights for the box head.  Normalisers and weights:
+ *   loss_rpn_cls = rpn_loss_weight * sum BCE / (rpn_batch * B)
+ *   loss_rpn_loc = rpn_loss_weight * rpn_bbox_reg_loss_weight * sum / (rpn_batch * B)
+ *   loss_box_reg = box_bbox_reg_loss_weight * sum / max(number of sampled RoIs, 1);   loss_cls and loss_mask carry no weight.
+ * The weights multiply the reported losses and the gradients alike. */
+enum { AMP_BOXLOSS_SMOOTH_L1 = 0, AMP_BOXLOSS_GIOU = 1 };
+typedef struct amp_loss_opts {
+    int rpn_loss_type;               /* AMP_BOXLOSS_* */
+    float rpn_smooth_l1_beta;
+    float rpn_loss_weight;
+    float rpn_bbox_reg_loss_weight;
+    int box_loss_type;               /* AMP_BOXLOSS_* */
+    float box_smooth_l1_beta;
+    float box_bbox_reg_loss_weight;
+} amp_loss_opts;
+/* AMP_BOXLOSS_SMOOTH_L1 with beta 0 on both heads, every weight 1: the losses of amp_rpn_sample_loss / amp_box_loss.  No device call. */
+int amp_loss_opts_default(amp_loss_opts* opts);
+/* amp_rpn_sample_loss / amp_box_loss with the options (the fields of the other head are validated and otherwise unused).  dpred carries
+ * the loss weights; partial stays the unnormalised, UNWEIGHTED sums ([B][2]: classification, regression).  With amp_loss_opts_default
+ * both run the arithmetic of the entry points above: the same bits in dpred and partial, the same launches.  Refuse (AMP_ERR_ARG, naming the
+ * field) a non-finite or negative beta or weight and an unknown loss type. */
+int amp_rpn_sample_loss_ex(amp_ctx* ctx, const amp_rpn_levels* lv, float* const dpred[5], int B, const float* gt_boxes,
+                           const int* gt_off, const signed char* label, const int* match_idx, uint32_t* keys_scratch, int batch,
+                           int num_pos_max, unsigned int seed, int* sampled, int* counts, float* partial, const amp_loss_opts* opts);
+int amp_box_loss_ex(amp_ctx* ctx, int B, int batch, int K, const float* pred, int ld, float* dpred, const float* rois, const int* roi_cls,
+                    const int* roi_gti, const float* gt_boxes, const int* gt_off, const float reg_weights[4], int total_rois, float* partial,
+                    const amp_loss_opts* opts);
 /* Sigmoid focal loss (fvcore sigmoid_focal_loss, reduction 'sum', times `scale`) over logits [N,K] with integer labels (label K =
  * background, negative = the row is ignored), forward and gradient in one pass: *loss_d = scale * sum, dlogits (optional) = scale *
  * d sum / d logits.  alpha < 0 switches the class weighting off.  partial: device scratch of partial_cap floats (<= 2048 used); sums run in a
@@ -567,6 +605,11 @@ int  amp_model_forward_losses(amp_model* m, const uint8_t* imgs_bgr, int imgs_on
  * the gradient arena (same offsets as the parameters; amp_model_grad_arena exposes it for the RCCL all-reduce of row a20). */
 int  amp_model_forward_backward(amp_model* m, const uint8_t* imgs_bgr, int imgs_on_host, int B, int H, int W, const amp_gt* gt,
                                 unsigned int seed, float losses_h[5]);
+/* The regression losses and loss weights (amp_loss_opts above) of the following amp_model_forward_losses / amp_model_forward_backward
+ * calls: the five reported losses and the gradients carry the weights.  Valid on a model created with train_enable, at any time between
+ * steps; a new model holds amp_loss_opts_default.  Refuses (AMP_ERR_ARG, naming the field) what amp_rpn_sample_loss_ex refuses. */
+int  amp_model_set_loss_opts(amp_model* m, const amp_loss_opts* opts);
+int  amp_model_get_loss_opts(amp_model* m, amp_loss_opts* opts);
 int  amp_model_grad_arena(amp_model* m, float** grads_dev, size_t* nfloats);
 /* the SGD momentum buffers: one arena with the parameters' offsets (like amp_model_grad_arena).  The layout depends on the model
  * configuration only (classes, backbone), not on the capacity: a host can carry it over to a re-created model or into a checkpoint. */
