@@ -13,6 +13,10 @@ pycocotools:
       - a prediction no ground-truth instance took is a false positive.
   * Pixel-level scores come from ONE `amp_rle_pair_overlap` call over the matched pairs (|g and p|, |g minus p|, |p minus g|) instead
     of a merge + three area calls per pair.
+  * `mask_edge_distance` (ampis/analyze.py:416-499; helpers `merge_boxes` :342) measures how far the disagreeing pixels of every matched pair
+    lie from the other mask: ONE `amp_mask_edge_distance` call for all pairs, on the device or on the host.  The reference broadcasts
+    [queries x targets x 2] doubles per pair and takes torch.sqrt; here the exact integer squared distance comes back (an exact nearest-pixel
+    search on bit planes, csrc/edge_distance.hip) and the root is numpy's correctly rounded one.
 With no prediction at all the detection precision is 0/0: like the reference this raises ZeroDivisionError.
 The independent checker is oracle/matcher.py (a loop-for-loop restatement of the reference, pinned by its known-answer test)."""
 import numpy as np
@@ -73,3 +77,86 @@ def det_seg_scores(gt, pred, iou_thresh=0.5, size=None):
         seg_precision, seg_recall = both / (both + pred_only), both / (both + gt_only)
     return {"det_precision": n_tp / (n_tp + n_fp), "det_recall": n_tp / (n_tp + n_fn), "seg_precision": seg_precision, "seg_recall": seg_recall,
             "det_tp": m["tp"], "det_fn": m["fn"], "det_fp": m["fp"], "seg_tp": both, "seg_fn": gt_only, "seg_fp": pred_only, "det_tp_iou": m["iou"]}
+
+
+def merge_boxes(box1, box2):
+    """The smallest index box [r1, r2, c1, c2] (the region im[r1:r2, c1:c2]) that holds box1 and box2 (ampis/analyze.py:342)."""
+    r11, r12, c11, c12 = box1
+    r21, r22, c21, c22 = box2
+    return np.array([min(r11, r21), max(r12, r22), min(c11, c21), max(c12, c22)])
+
+
+def _index_boxes(boxes, masks, name):
+    """[len(masks), 4] int64 index boxes of argument `name`: the caller's, checked, or (None) the tight boxes of the runs."""
+    if boxes is None:
+        tight = [rle.bbox(m) for m in masks]                      # (x0, y0, x1, y1), None for an empty mask
+        return np.array([(0, 0, 0, 0) if b is None else (b[1], b[3], b[0], b[2]) for b in tight], dtype=np.int64).reshape(-1, 4)
+    out = np.zeros((len(boxes), 4), dtype=np.int64)
+    for i, b in enumerate(boxes):
+        try:
+            v = [x for x in np.asarray(b).reshape(-1).tolist()]
+            ok = len(v) == 4 and all(not isinstance(x, bool) and float(x) == int(x) for x in v)
+        except (TypeError, ValueError, OverflowError):
+            ok = False
+        if not ok:
+            raise ValueError(f"mask_edge_distance: {name}[{i}] = {b!r} is not four integers [r1, r2, c1, c2]")
+        r1, r2, c1, c2 = (int(x) for x in v)
+        if min(r1, r2, c1, c2) < 0 or r1 > r2 or c1 > c2:
+            raise ValueError(f"mask_edge_distance: {name}[{i}] = {[r1, r2, c1, c2]}: indices must not be negative and r1 <= r2, c1 <= c2")
+        out[i] = (r1, r2, c1, c2)
+    return out
+
+
+_edge_ctx = {}
+
+
+def _edge_context():
+    """The context of the device path: one per HIP device, with a stream of its own (the call uploads, computes and downloads by itself)."""
+    import torch
+    from . import _lib
+    if not torch.cuda.is_available():
+        raise _lib.AmpError("mask_edge_distance(device='cuda'): no HIP device is visible (device='cpu' computes on the host)")
+    dev = torch.cuda.current_device()
+    if dev not in _edge_ctx:
+        _edge_ctx[dev] = _lib.Context(dev)
+    return _edge_ctx[dev]
+
+
+def mask_edge_distance(gt_mask, pred_mask, gt_box, pred_box, matches, device='auto', squared=False, size=None):
+    """For every matched pair matches[i] = (gt index, pred index): the distance in pixels from each false-positive pixel (pred & ~gt) to the nearest
+    ground-truth pixel and from each false-negative pixel (gt & ~pred) to the nearest predicted pixel, inside the pair's merged box
+    (ampis/analyze.py:416-499: same arguments, same two lists of CPU float64 tensors, pixels in torch.where order).
+
+    gt_mask, pred_mask: anything masks_to_rle accepts (size=(h, w) for polygons); gt_box, pred_box: one index box [r1, r2, c1, c2] per mask, or None
+    for the tight box of each mask; device: 'cpu' (host), 'cuda' (HIP device, an error without one) or 'auto' (the device when one is visible);
+    squared=True returns the exact squared distances as int64 tensors.  ValueError for a malformed box, a match index out of range, masks of
+    different sizes, and a pair with disagreeing pixels whose other mask has no pixel in the box (the reference fails there too)."""
+    import torch
+    gt, pred = masks_to_rle(gt_mask, size), masks_to_rle(pred_mask, size)
+    dev = str(device).lower()
+    if dev not in ("auto", "cpu", "cuda"):
+        raise ValueError(f"mask_edge_distance: device = {device!r} ('auto', 'cpu' or 'cuda')")
+    m = np.asarray(matches)
+    if m.size and (m.ndim != 2 or m.shape[1] != 2 or not np.issubdtype(m.dtype, np.integer)):
+        raise ValueError(f"mask_edge_distance: matches must be an [n, 2] integer array of (gt, pred) indices, got shape {m.shape} {m.dtype}")
+    m = m.reshape(-1, 2).astype(np.int64)
+    for i, (g, p) in enumerate(m.tolist()):
+        if not (0 <= g < len(gt) and 0 <= p < len(pred)):
+            raise ValueError(f"mask_edge_distance: matches[{i}] = ({g}, {p}) is outside the {len(gt)} ground-truth and {len(pred)} predicted masks")
+    sizes = {tuple(int(v) for v in r["size"]) for r in gt + pred}
+    if len(sizes) > 1:
+        raise ValueError(f"mask_edge_distance: gt_mask / pred_mask hold masks of different sizes {sorted(sizes)}")
+    gb, pb = _index_boxes(gt_box, gt, "gt_box"), _index_boxes(pred_box, pred, "pred_box")
+    if len(gb) < len(gt) and len(m) and m[:, 0].max() >= len(gb):
+        raise ValueError(f"mask_edge_distance: gt_box has {len(gb)} boxes, matches name ground-truth mask {int(m[:, 0].max())}")
+    if len(pb) < len(pred) and len(m) and m[:, 1].max() >= len(pb):
+        raise ValueError(f"mask_edge_distance: pred_box has {len(pb)} boxes, matches name predicted mask {int(m[:, 1].max())}")
+    boxes = np.array([merge_boxes(gb[g], pb[p]) for g, p in m.tolist()], dtype=np.int64).reshape(-1, 4)
+    boxes = np.minimum(boxes, 1 << 30)                            # beyond any image: the slice ends at the image's border
+    ctx = _edge_context() if dev == "cuda" or (dev == "auto" and len(m) and torch.cuda.is_available()) else None
+    fp, fn = rle.edge_distance(gt, pred, m, boxes, ctx=ctx)
+    if squared:
+        conv = lambda d: torch.from_numpy(d.astype(np.int64))
+    else:
+        conv = lambda d: torch.from_numpy(np.sqrt(d.astype(np.float64)))
+    return [conv(d) for d in fp], [conv(d) for d in fn]

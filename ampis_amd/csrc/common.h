@@ -253,6 +253,15 @@ int comm_wait_done(amp_ctx* ctx);              // compute stream waits (device s
 int comm_agree_flag(amp_ctx* ctx, int* d_flag); // MAX of a device int over the ranks, complete on return
 int rle_strings_run(amp_ctx* ctx, const unsigned int* pool, const unsigned long long* off, const int* len, int n, char* str,
                     unsigned long long cap, unsigned long long* str_off, int* str_len, unsigned long long* total);
+// rle_host.hip: amp_mask_edge_distance's argument checks (every named run list non-empty and summing to h * w, pair indices, boxes; crop = the
+// boxes clamped to the image, [n][4]) and its host evaluation; edge_distance.hip holds the entry point and the device evaluation
+int edge_distance_check(const uint32_t* gpool, const unsigned long long* goff, const int* glen, int ng, const uint32_t* ppool,
+                        const unsigned long long* poff, const int* plen, int np, const int* pair_g, const int* pair_p, const int* box, int n,
+                        int h, int w, const uint32_t* fp_d2, unsigned long long fp_cap, const unsigned long long* fp_off, const uint32_t* fn_d2,
+                        unsigned long long fn_cap, const unsigned long long* fn_off, std::vector<int>& crop);
+int edge_distance_host(const uint32_t* gpool, const unsigned long long* goff, const int* glen, const uint32_t* ppool, const unsigned long long* poff,
+                       const int* plen, const int* pair_g, const int* pair_p, const int* crop, int n, int h, uint32_t* fp_d2,
+                       unsigned long long fp_cap, unsigned long long* fp_off, uint32_t* fn_d2, unsigned long long fn_cap, unsigned long long* fn_off);
 int roi_align_run(amp_ctx* ctx, const amp_fpn_feats* f, const float* rois, const int* batch_idx, const int* roi_count, int R, int P,
                   float* out, int* level_out, int out_split, int in_split = 0);   // out_split / in_split = 1: pooled tensor / feature maps in the split row format
 int box_candidates_run(amp_ctx* ctx, const float* pred, int ld, const float* proposals, const int* prop_count, int B, int Rcap, int K,

@@ -483,3 +483,124 @@ extern "C" int amp_polygon_clip_rect(const double* xy, const long long* off, con
     }
     return AMP_OK;
 }
+
+// ---- mask_edge_distance (ampis/analyze.py:416-499): argument checks shared with the device path, and the host evaluation ------------------
+// For each (ground truth, prediction) pair and its crop [r1:r2, c1:c2]: the squared distance from every false-positive pixel (pred & ~gt) to the
+// nearest gt pixel of the crop, and from every false-negative pixel (gt & ~pred) to the nearest pred pixel, queries in row-major order.
+// The reference forms a dense [queries x targets x 2] double tensor per pair; here a column pass stores each pixel's distance to the nearest
+// target of its own column, and a query walks the columns outward until the column offset alone is no better than what it has: exact
+// (integers throughout), memory linear in the crop.
+namespace amp {
+
+static int edge_runs_check(const char* which, int p, const uint32_t* c, int m, unsigned long long area) {
+    AMP_REQUIRE(m > 0, "amp_mask_edge_distance: pair %d names an empty %s run list", p, which);
+    unsigned long long s = 0;
+    for (int j = 0; j < m; ++j) s += c[j];
+    AMP_REQUIRE(s == area, "amp_mask_edge_distance: the %s runs of pair %d cover %llu pixels, the image has %llu", which, p, s, area);
+    return AMP_OK;
+}
+
+int edge_distance_check(const uint32_t* gpool, const unsigned long long* goff, const int* glen, int ng, const uint32_t* ppool,
+                        const unsigned long long* poff, const int* plen, int np, const int* pair_g, const int* pair_p, const int* box, int n,
+                        int h, int w, const uint32_t* fp_d2, unsigned long long fp_cap, const unsigned long long* fp_off, const uint32_t* fn_d2,
+                        unsigned long long fn_cap, const unsigned long long* fn_off, std::vector<int>& crop) {
+    AMP_REQUIRE(n >= 0 && ng >= 0 && np >= 0 && fp_off && fn_off && (fp_d2 || fp_cap == 0) && (fn_d2 || fn_cap == 0),
+                "amp_mask_edge_distance: bad argument");
+    AMP_REQUIRE(n == 0 || (gpool && goff && glen && ppool && poff && plen && pair_g && pair_p && box), "amp_mask_edge_distance: null argument");
+    AMP_REQUIRE(h >= 1 && w >= 1 && h <= 32768 && w <= 32768,
+                "amp_mask_edge_distance: image size %d x %d (1 .. 32768 a side: squared distances are 32-bit)", h, w);
+    const unsigned long long area = (unsigned long long)h * w;
+    std::vector<unsigned char> gok((size_t)ng, 0), pok((size_t)np, 0);          // a run list named by many pairs is summed once
+    crop.assign((size_t)n * 4, 0);
+    for (int p = 0; p < n; ++p) {
+        const int g = pair_g[p], q = pair_p[p];
+        AMP_REQUIRE(g >= 0 && g < ng && q >= 0 && q < np, "amp_mask_edge_distance: pair %d = (%d, %d) outside %d x %d masks", p, g, q, ng, np);
+        if (!gok[(size_t)g]) { AMP_TRY_STATUS(edge_runs_check("ground-truth", p, gpool + goff[g], glen[g], area)); gok[(size_t)g] = 1; }
+        if (!pok[(size_t)q]) { AMP_TRY_STATUS(edge_runs_check("prediction", p, ppool + poff[q], plen[q], area)); pok[(size_t)q] = 1; }
+        const int* b = box + 4 * (size_t)p;
+        AMP_REQUIRE(b[0] >= 0 && b[2] >= 0 && b[0] <= b[1] && b[2] <= b[3], "amp_mask_edge_distance: box [%d, %d, %d, %d] of pair %d", b[0], b[1], b[2], b[3], p);
+        int* c = &crop[4 * (size_t)p];                                            // numpy's slice: an end beyond the image is the image's end
+        c[0] = std::min(b[0], h); c[1] = std::min(b[1], h); c[2] = std::min(b[2], w); c[3] = std::min(b[3], w);
+    }
+    return AMP_OK;
+}
+
+// bytes of the crop, row-major, of a column-major run list
+static void edge_decode_crop(const uint32_t* c, int m, int h, const int* cr, std::vector<unsigned char>& out) {
+    const int H = cr[1] - cr[0], W = cr[3] - cr[2];
+    out.assign((size_t)H * W, 0);
+    if (H == 0 || W == 0) return;
+    const unsigned long long stop = (unsigned long long)cr[3] * h;               // nothing of the crop lies behind its last column
+    unsigned long long pos = 0;
+    for (int j = 0; j < m && pos < stop; ++j) {
+        const unsigned long long s = pos, e = pos + c[j];
+        pos = e;
+        if (!(j & 1) || e == s) continue;
+        const long long first = (long long)(s / (unsigned)h), last = (long long)((e - 1) / (unsigned)h);
+        for (long long col = std::max<long long>(first, cr[2]); col <= std::min<long long>(last, cr[3] - 1); ++col) {
+            const unsigned long long cb = (unsigned long long)col * h;
+            const int ya = std::max((int)(std::max(s, cb) - cb), cr[0]), yb = std::min((int)(std::min(e, cb + h) - cb), cr[1]);
+            for (int y = ya; y < yb; ++y) out[(size_t)(y - cr[0]) * W + (size_t)(col - cr[2])] = 1;
+        }
+    }
+}
+
+// squared distance of every pixel of q & ~t to the nearest pixel of t, appended in row-major order
+static void edge_nearest(const std::vector<unsigned char>& q, const std::vector<unsigned char>& t, int H, int W, std::vector<int>& colv,
+                         std::vector<uint32_t>& out) {
+    const int NONE = 1 << 20;
+    bool any = false;
+    for (size_t i = 0; i < q.size() && !any; ++i) any = q[i] && !t[i];
+    if (!any) return;
+    colv.assign((size_t)H * W, NONE);                                            // distance to the nearest target of the pixel's own column
+    for (int c = 0; c < W; ++c) {
+        int d = NONE;
+        for (int r = 0; r < H; ++r) { d = t[(size_t)r * W + c] ? 0 : std::min(d + 1, NONE); colv[(size_t)r * W + c] = d; }
+        d = NONE;
+        for (int r = H - 1; r >= 0; --r) { d = t[(size_t)r * W + c] ? 0 : std::min(d + 1, NONE); int& v = colv[(size_t)r * W + c]; v = std::min(v, d); }
+    }
+    for (int r = 0; r < H; ++r)
+        for (int c = 0; c < W; ++c) {
+            if (!q[(size_t)r * W + c] || t[(size_t)r * W + c]) continue;
+            uint32_t best = 0xffffffffu;
+            const int* row = &colv[(size_t)r * W];
+            for (int dc = 0; (uint32_t)dc * (uint32_t)dc < best && (c - dc >= 0 || c + dc < W); ++dc) {
+                const uint32_t d2c = (uint32_t)dc * (uint32_t)dc;
+                if (c - dc >= 0 && row[c - dc] != NONE) best = std::min(best, (uint32_t)row[c - dc] * (uint32_t)row[c - dc] + d2c);
+                if (c + dc < W && row[c + dc] != NONE) best = std::min(best, (uint32_t)row[c + dc] * (uint32_t)row[c + dc] + d2c);
+            }
+            out.push_back(best);
+        }
+}
+
+int edge_distance_host(const uint32_t* gpool, const unsigned long long* goff, const int* glen, const uint32_t* ppool, const unsigned long long* poff,
+                       const int* plen, const int* pair_g, const int* pair_p, const int* crop, int n, int h, uint32_t* fp_d2,
+                       unsigned long long fp_cap, unsigned long long* fp_off, uint32_t* fn_d2, unsigned long long fn_cap, unsigned long long* fn_off) {
+    std::vector<uint32_t> fp, fn;                                                // results are handed over whole or not at all
+    std::vector<unsigned long long> fpo((size_t)n + 1, 0), fno((size_t)n + 1, 0);
+    std::vector<unsigned char> gm, pm;
+    std::vector<int> colv;
+    for (int p = 0; p < n; ++p) {
+        const int* cr = crop + 4 * (size_t)p;
+        const int H = cr[1] - cr[0], W = cr[3] - cr[2];
+        if (H > 0 && W > 0) {
+            edge_decode_crop(gpool + goff[pair_g[p]], glen[pair_g[p]], h, cr, gm);
+            edge_decode_crop(ppool + poff[pair_p[p]], plen[pair_p[p]], h, cr, pm);
+            edge_nearest(pm, gm, H, W, colv, fp);
+            edge_nearest(gm, pm, H, W, colv, fn);
+        }
+        fpo[(size_t)p + 1] = fp.size();
+        fno[(size_t)p + 1] = fn.size();
+    }
+    if (fp.size() > fp_cap || fn.size() > fn_cap) {
+        set_error("amp_mask_edge_distance: %zu false-positive and %zu false-negative pixels, capacities %llu and %llu", fp.size(), fn.size(), fp_cap, fn_cap);
+        return AMP_ERR_NOMEM;
+    }
+    std::copy(fp.begin(), fp.end(), fp_d2);
+    std::copy(fn.begin(), fn.end(), fn_d2);
+    std::copy(fpo.begin(), fpo.end(), fp_off);
+    std::copy(fno.begin(), fno.end(), fn_off);
+    return AMP_OK;
+}
+
+}  // namespace amp

@@ -197,6 +197,40 @@ def pair_overlap(a, b, pairs):
     return tuple(o.astype(np.int64) for o in out)
 
 
+def edge_distance(gt, pred, pairs, boxes, ctx=None):
+    """mask_edge_distance on run lists, one C call (amp_mask_edge_distance): for index pairs (g, p) and one merged index box [r1, r2, c1, c2]
+    per pair (the crop [r1:r2, c1:c2]), two lists of uint32 arrays -- for every crop pixel of pred[p] & ~gt[g] in row-major order the SQUARED
+    distance to the nearest crop pixel of gt[g], and for every pixel of gt[g] & ~pred[p] to the nearest of pred[p].  ctx: a _lib.Context
+    (computed on its device) or None (on the host).  ValueError when a pair has such pixels and the other mask has none in the crop."""
+    pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+    boxes = np.ascontiguousarray(np.asarray(boxes, dtype=np.int32).reshape(-1, 4))
+    n = len(pairs)
+    assert len(boxes) == n, "one box per pair"
+    if n == 0:
+        return [], []
+    assert pairs.min() >= 0 and pairs[:, 0].max() < len(gt) and pairs[:, 1].max() < len(pred)
+    h, w = (int(v) for v in gt[int(pairs[0, 0])]["size"])
+    gc, pc = [_counts(x) for x in gt], [_counts(x) for x in pred]
+    gp, go, gl = _pool(gc)
+    pp, po, pl = _pool(pc)
+    pg, pq = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
+    ga = np.array([int(c[1::2].sum(dtype=np.uint64)) for c in gc], dtype=np.uint64)       # amp_rle_area of every mask
+    pa = np.array([int(c[1::2].sum(dtype=np.uint64)) for c in pc], dtype=np.uint64)
+    fp_cap, fn_cap = int(pa[pq].sum()), int(ga[pg].sum())                                 # a pair has no more queries than its mask has pixels
+    fp, fn = np.empty(max(fp_cap, 1), dtype=np.uint32), np.empty(max(fn_cap, 1), dtype=np.uint32)
+    fpo, fno = np.zeros(n + 1, dtype=np.uint64), np.zeros(n + 1, dtype=np.uint64)
+    vp = lambda x: x.ctypes.data_as(C.c_void_p)
+    check(lib().amp_mask_edge_distance(ctx.handle if ctx is not None else None, vp(gp), vp(go), vp(gl), len(gc), vp(pp), vp(po), vp(pl), len(pc),
+                                       vp(pg), vp(pq), vp(boxes), n, h, w, vp(fp), fp_cap, vp(fpo), vp(fn), fn_cap, vp(fno)), "amp_mask_edge_distance")
+    out = ([fp[int(fpo[i]): int(fpo[i + 1])].copy() for i in range(n)], [fn[int(fno[i]): int(fno[i + 1])].copy() for i in range(n)])
+    for name, lst in (("ground-truth", out[0]), ("predicted", out[1])):
+        for i, d in enumerate(lst):
+            if len(d) and d[0] == 0xFFFFFFFF:
+                raise ValueError(f"mask_edge_distance: pair {i} (gt {int(pg[i])}, pred {int(pq[i])}) has no {name} pixel inside its box "
+                                 f"{boxes[i].tolist()} to measure a distance to")
+    return out
+
+
 def merge(rles, intersect=False):
     assert len(rles) >= 1
     h, w = rles[0]["size"]

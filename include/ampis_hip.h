@@ -488,6 +488,22 @@ int amp_rle_iou_matrix(const uint32_t* dpool, const unsigned long long* doff, co
 int amp_rle_pair_overlap(const uint32_t* apool, const unsigned long long* aoff, const int* alen, const uint32_t* bpool,
                          const unsigned long long* boff, const int* blen, const int* pair_a, const int* pair_b, int npairs,
                          unsigned long long* inter, unsigned long long* only_a, unsigned long long* only_b);
+/* mask_edge_distance (ampis/analyze.py:416-499) for `n` (ground truth, prediction) pairs in one call.  ALL POINTERS ARE HOST POINTERS.
+ * Masks are run lists out of two pools (list i = pool[off[i] .. off[i] + len[i]), ng / np lists) over one h x w image, h, w <= 32768;
+ * pair p = (pair_g[p], pair_p[p]), any pairs, repeats allowed; box[p] = {r1, r2, c1, c2}, the merged index box of the pair, applied as the
+ * slice [r1:r2, c1:c2] (0 <= r1 <= r2, 0 <= c1 <= c2; an end beyond the image is the image's end).  Pixels outside the crop do not exist for
+ * the pair.  fp_d2[fp_off[p] .. fp_off[p + 1]): for every crop pixel of pred & ~gt in row-major order, the minimum over the crop's gt pixels of
+ * dr^2 + dc^2, exact; fn_d2 / fn_off: the same for gt & ~pred against pred.  A query whose target mask has no pixel in the crop gets
+ * 0xffffffff.  fp_cap / fn_cap: capacity of fp_d2 / fn_d2 in values (the summed areas of the pairs' masks always suffice); a smaller one is
+ * AMP_ERR_NOMEM with the need in the message and nothing written.  Every run list a pair names is checked on the host first (length > 0,
+ * runs summing to h * w): a malformed list is AMP_ERR_ARG and never a device access.
+ * ctx == NULL: computed on the host (rle_host.hip).  Otherwise on ctx's device and stream (edge_distance.hip): the function uploads, runs a
+ * fixed number of launches whatever n is, downloads and returns with the results in host memory; the order and the bytes do not depend on
+ * the device's scheduling. */
+int amp_mask_edge_distance(amp_ctx* ctx, const uint32_t* gpool, const unsigned long long* goff, const int* glen, int ng,
+                           const uint32_t* ppool, const unsigned long long* poff, const int* plen, int np, const int* pair_g,
+                           const int* pair_p, const int* box, int n, int h, int w, uint32_t* fp_d2, unsigned long long fp_cap,
+                           unsigned long long* fp_off, uint32_t* fn_d2, unsigned long long fn_cap, unsigned long long* fn_off);
 /* Nearest-neighbour resize (+ horizontal mirror when flip) of a mask in the run-length domain: the runs of
  * flip(PIL.Image.resize(decode(cnts), (nw, nh), NEAREST)) -- what detectron2's ResizeTransform.apply_segmentation + HFlipTransform do to a bitmask
  * annotation -- without decoding (Pillow's ImagingScaleAffine pixel correspondence, restated).  cap >= nh * nw + 1 is always enough. */
