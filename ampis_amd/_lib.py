@@ -205,6 +205,9 @@ def _declare(L):
         "amp_conv2d_wgrad": ([vp, C.POINTER(ConvDesc), vp, vp, vp, vp, vp, i], i),
         "amp_conv2d_wgrad_scaled": ([vp, C.POINTER(ConvDesc), vp, vp, vp, vp, vp, i, i, i], i),
         "amp_colsum": ([vp, vp, i, i, vp, vp, i], i),
+        "amp_colsum_split": ([vp, vp, i, i, vp, vp, i, vp, i], i),
+        "amp_colsum_of_split": ([vp, vp, i, i, vp, vp, i, i], i),
+        "amp_colsum_finish": ([vp, vp, i, i, vp, i], i),
         "amp_dgrad_weights": ([vp, vp, vp, i, i, i, i, vp], i),
         "amp_dgrad_weights_split": ([vp, vp, vp, i, i, i, i, vp], i),
         "amp_preprocess": ([vp, vp, i, i, i, i, i, C.POINTER(f), C.POINTER(f), vp, vp], i),
@@ -282,9 +285,18 @@ def _declare(L):
         "amp_roi_align_bwd": ([vp, vp, vp, vp, vp, i, vp, vp, i, i, vp], i),
         "amp_roi_align_bwd_batched": ([vp, vp, vp, vp, vp, i, vp, vp, i, i, vp, i], i),
         "amp_upsample2_bwd": ([vp, vp, vp, i, i, i, i], i),
+        "amp_upsample2_bwd_init": ([vp, vp, vp, i, i, i, i], i),
         "amp_subsample2_bwd": ([vp, vp, vp, i, i, i, i], i),
         "amp_relu_mask": ([vp, vp, vp, C.c_size_t], i),
+        "amp_relu_mask_split": ([vp, vp, vp, C.c_size_t, i], i),
+        "amp_relu_mask_to_split": ([vp, vp, vp, vp, C.c_size_t, i, i], i),
+        "amp_subsample2_bwd_split": ([vp, vp, vp, i, i, i, i, i], i),
+        "amp_accumulate_split": ([vp, vp, vp, C.c_longlong, i, i], i),
+        "amp_scatter2_rows": ([vp, vp, vp, i, i, i, i], i),
         "amp_small_k_dgrad": ([vp, vp, i, i, vp, i, vp, vp, C.c_size_t], i),
+        "amp_small_k_dgrad_split": ([vp, vp, i, vp, i, vp, vp, i, i, vp, vp, i], i),
+        "amp_small_k_dgrad_split_ld": ([vp, vp, i, i, vp, i, vp, vp, i, i, vp, vp, i], i),
+        "amp_small_k_dgrad_split_f32act": ([vp, vp, i, i, vp, i, vp, vp, i, i, vp, vp, i], i),
         "amp_deconv_grad_transpose": ([vp, vp, vp, i, i, i, i], i),
         "amp_sgd_update": ([vp, vp, vp, vp, C.c_size_t, f, f, f, f], i),
         "amp_sgd_opts_default": ([C.POINTER(SgdOpts)], i),

@@ -930,6 +930,10 @@ int amp_upsample2_bwd(amp_ctx* ctx, const float* dfine, float* dcoarse, int B, i
     return amp::upsample2_bwd_run(ctx, dfine, dcoarse, B, Hc, Wc, C, 0);
 }
 
+int amp_upsample2_bwd_init(amp_ctx* ctx, const float* dfine, float* dcoarse, int B, int Hc, int Wc, int C) {
+    return amp::upsample2_bwd_run(ctx, dfine, dcoarse, B, Hc, Wc, C, 1);
+}
+
 int amp_subsample2_bwd(amp_ctx* ctx, const float* dy, float* dx, int B, int H, int W, int C) {
     AMP_REQUIRE(ctx && dy && dx && C % 4 == 0, "amp_subsample2_bwd: bad argument");
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;

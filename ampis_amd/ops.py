@@ -157,12 +157,209 @@ def dgrad_weights_split(ctx, w, scale=None):
     return wt
 
 
-def colsum(ctx, dy):
+def _colsum_out(dy, out, accumulate):
+    """(M, N, scratch, out) of a column-sum call on dy [M, N]: the wrapper owns the scratch of ceil(M / 512) slices."""
     M, N = dy.shape
-    scratch = torch.empty(((M + 511) // 512 + 1) * N, device=dy.device)
-    out = torch.empty(N, device=dy.device)
-    check(lib().amp_colsum(ctx.handle, ptr(_f32c(dy)), M, N, ptr(scratch), ptr(out), 0), "amp_colsum")
+    scratch = torch.empty((max((M + 511) // 512, 1), N), device=dy.device)
+    if out is None:
+        assert not accumulate, "accumulate needs the tensor to add to"
+        out = torch.empty(N, device=dy.device)
+    assert _f32c(out).shape == (N,)
+    return M, N, scratch, out
+
+
+def _rows_ptr(t, spare):
+    """Pointer of a [M, N] operand; an empty one (M == 0: no row is read or written) stands on `spare`, since the library refuses NULL."""
+    return ptr(t if t.numel() else spare)
+
+
+def colsum(ctx, dy, out=None, accumulate=False):
+    """out[n] (= or +=) sum over the rows of dy [M, N] (N % 4 == 0, M >= 0), fixed summation order (amp_colsum)."""
+    M, N, scratch, out = _colsum_out(_f32c(dy), out, accumulate)
+    check(lib().amp_colsum(ctx.handle, _rows_ptr(dy, scratch), M, N, ptr(scratch), ptr(out), int(bool(accumulate))), "amp_colsum")
     return out
+
+
+def colsum_split(ctx, dy, shift=0, out=None, accumulate=False):
+    """colsum that also returns dy * 2**shift as split rows (amp_colsum_split; N % 32 == 0): (out, dy_split)."""
+    M, N, scratch, out = _colsum_out(_f32c(dy), out, accumulate)
+    dy_split = torch.empty_like(dy)
+    check(lib().amp_colsum_split(ctx.handle, _rows_ptr(dy, scratch), M, N, ptr(scratch), ptr(out), int(bool(accumulate)), _rows_ptr(dy_split, scratch),
+                                 int(shift)), "amp_colsum_split")
+    return out, dy_split
+
+
+def colsum_of_split(ctx, dy_split, shift=0, out=None, accumulate=False):
+    """The column sums of a dy given as split rows of dy * 2**shift (amp_colsum_of_split; N % 32 == 0)."""
+    M, N, scratch, out = _colsum_out(_f32c(dy_split), out, accumulate)
+    check(lib().amp_colsum_of_split(ctx.handle, _rows_ptr(dy_split, scratch), M, N, ptr(scratch), ptr(out), int(bool(accumulate)), int(shift)),
+          "amp_colsum_of_split")
+    return out
+
+
+def colsum_finish(ctx, partial, out=None, accumulate=False):
+    """out[n] (= or +=) the sum of partial [parts, N] over its parts (parts >= 1), the second pass of the column sums (amp_colsum_finish)."""
+    parts, N = _f32c(partial).shape
+    if out is None:
+        assert not accumulate, "accumulate needs the tensor to add to"
+        out = torch.empty(N, device=partial.device)
+    assert _f32c(out).shape == (N,)
+    check(lib().amp_colsum_finish(ctx.handle, ptr(partial), parts, N, ptr(out), int(bool(accumulate))), "amp_colsum_finish")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Backward and pointwise kernels between the convolutions of a training step (train_bwd.hip, pointwise.hip).  Gradient maps are
+# NHWC fp32 or split rows; `shift`: a split gradient holds value * 2**shift.  In-place functions return the tensor they changed.
+# ------------------------------------------------------------------------------------------------------------------
+def _half(n):
+    return (n - 1) // 2 + 1
+
+
+def upsample2_bwd(ctx, dfine, dcoarse, init=False):
+    """dcoarse [B,Hc,Wc,C] += the 2x2 sums of dfine [B,2Hc,2Wc,C] (amp_upsample2_bwd); init: dcoarse = the sums, its content is not read
+    (amp_upsample2_bwd_init)."""
+    B, Hc, Wc, Cc = _f32c(dcoarse).shape
+    assert _f32c(dfine).shape == (B, 2 * Hc, 2 * Wc, Cc)
+    fn = lib().amp_upsample2_bwd_init if init else lib().amp_upsample2_bwd
+    check(fn(ctx.handle, ptr(dfine), ptr(dcoarse), B, Hc, Wc, Cc), "amp_upsample2_bwd_init" if init else "amp_upsample2_bwd")
+    return dcoarse
+
+
+def subsample2_bwd(ctx, dy, dx):
+    """dx [B,H,W,C][:, ::2, ::2] += dy [B,ceil(H/2),ceil(W/2),C] (amp_subsample2_bwd)."""
+    B, H, W, Cc = _f32c(dx).shape
+    assert _f32c(dy).shape == (B, _half(H), _half(W), Cc)
+    check(lib().amp_subsample2_bwd(ctx.handle, ptr(dy), ptr(dx), B, H, W, Cc), "amp_subsample2_bwd")
+    return dx
+
+
+def subsample2_bwd_split(ctx, dy_split, dx, shift=0):
+    """dx[:, ::2, ::2] += decode(dy_split) * 2**-shift (amp_subsample2_bwd_split; C % 32 == 0)."""
+    B, H, W, Cc = _f32c(dx).shape
+    assert _f32c(dy_split).shape == (B, _half(H), _half(W), Cc)
+    check(lib().amp_subsample2_bwd_split(ctx.handle, ptr(dy_split), ptr(dx), B, H, W, Cc, int(shift)), "amp_subsample2_bwd_split")
+    return dx
+
+
+def accumulate_split(ctx, dy_split, dx, shift=0):
+    """dx += decode(dy_split) * 2**-shift, same shape [..., C], C % 32 == 0 (amp_accumulate_split)."""
+    assert _f32c(dy_split).shape == _f32c(dx).shape
+    Cc = dx.shape[-1]
+    check(lib().amp_accumulate_split(ctx.handle, ptr(dy_split), ptr(dx), dx.numel() // Cc, Cc, int(shift)), "amp_accumulate_split")
+    return dx
+
+
+def scatter2_rows(ctx, src, H, W, out=None):
+    """up [B,H,W,C] with up[:, ::2, ::2] = src [B,ceil(H/2),ceil(W/2),C] as raw bytes and +0.0 everywhere else (amp_scatter2_rows)."""
+    B, Ho, Wo, Cc = _f32c(src).shape
+    assert (Ho, Wo) == (_half(H), _half(W))
+    up = torch.empty((B, H, W, Cc), device=src.device) if out is None else _f32c(out)
+    assert up.shape == (B, H, W, Cc)
+    check(lib().amp_scatter2_rows(ctx.handle, ptr(src), ptr(up), B, H, W, Cc), "amp_scatter2_rows")
+    return up
+
+
+def relu_mask(ctx, g, act):
+    """g = act > 0 ? g : 0 in place (amp_relu_mask; numel % 4 == 0)."""
+    assert _f32c(g).shape == _f32c(act).shape
+    check(lib().amp_relu_mask(ctx.handle, ptr(g), ptr(act), g.numel()), "amp_relu_mask")
+    return g
+
+
+def relu_mask_split(ctx, g, act_split):
+    """the same with act [..., C] as split rows, C % 32 == 0 (amp_relu_mask_split)."""
+    assert _f32c(g).shape == _f32c(act_split).shape
+    check(lib().amp_relu_mask_split(ctx.handle, ptr(g), ptr(act_split), g.numel(), g.shape[-1]), "amp_relu_mask_split")
+    return g
+
+
+def relu_mask_to_split(ctx, g, act_split, shift=0):
+    """split rows of 2**shift * (act > 0 ? g : 0) with act [..., C] as split rows (amp_relu_mask_to_split)."""
+    assert _f32c(g).shape == _f32c(act_split).shape
+    out = torch.empty_like(g)
+    check(lib().amp_relu_mask_to_split(ctx.handle, ptr(g), ptr(act_split), ptr(out), g.numel(), g.shape[-1], int(shift)), "amp_relu_mask_to_split")
+    return out
+
+
+def small_k_dgrad(ctx, dl, w, act=None):
+    """dx [npix, C] = act > 0 ? dl[:, :K] @ w : 0 for dl [npix, ld], w [K, C], K <= ld (amp_small_k_dgrad); act None: no mask."""
+    (npix, ld), (K, Cc) = _f32c(dl).shape, _f32c(w).shape
+    assert act is None or _f32c(act).shape == (npix, Cc)
+    dx = torch.empty((npix, Cc), device=dl.device)
+    check(lib().amp_small_k_dgrad(ctx.handle, ptr(dl), ld, K, ptr(w), Cc, ptr(act), ptr(dx), npix), "amp_small_k_dgrad")
+    return dx
+
+
+def small_k_dgrad_split(ctx, dl, w, act, shift=0, act_split=True, rows16=False, colsum_out=None, accumulate=False):
+    """The same product as split rows of dx * 2**shift, plus colsum_out[c] (= or +=) the column sums of dx: (dx_split, colsum_out).
+    act_split: act is split rows (amp_small_k_dgrad_split_ld; rows16: the entry for dl rows of 16 floats, amp_small_k_dgrad_split), else
+    fp32 rows (amp_small_k_dgrad_split_f32act).  dl [npix, ld], ld in (4, 8, 12, 16), w [K, C], C % 32 == 0."""
+    (npix, ld), (K, Cc) = _f32c(dl).shape, _f32c(w).shape
+    assert _f32c(act).shape == (npix, Cc)
+    dx = torch.empty((npix, Cc), device=dl.device)
+    scratch = torch.empty(((npix + 511) // 512, Cc), device=dl.device)
+    if colsum_out is None:
+        assert not accumulate, "accumulate needs the tensor to add to"
+        colsum_out = torch.empty(Cc, device=dl.device)
+    assert _f32c(colsum_out).shape == (Cc,)
+    tail = (ptr(w), Cc, ptr(act), ptr(dx), npix, int(shift), ptr(scratch), ptr(colsum_out), int(bool(accumulate)))
+    if rows16:
+        assert act_split and ld == 16
+        check(lib().amp_small_k_dgrad_split(ctx.handle, ptr(dl), K, *tail), "amp_small_k_dgrad_split")
+    elif act_split:
+        check(lib().amp_small_k_dgrad_split_ld(ctx.handle, ptr(dl), ld, K, *tail), "amp_small_k_dgrad_split_ld")
+    else:
+        check(lib().amp_small_k_dgrad_split_f32act(ctx.handle, ptr(dl), ld, K, *tail), "amp_small_k_dgrad_split_f32act")
+    return dx, colsum_out
+
+
+def deconv_grad_transpose(ctx, grad_in, out=None, accumulate=False):
+    """out [T, C2, Cin] (= or +=) grad_in [Cin, T, C2] transposed: the ConvTranspose weight gradient from its wgrad form
+    (amp_deconv_grad_transpose)."""
+    Cin, T, C2 = _f32c(grad_in).shape
+    if out is None:
+        assert not accumulate, "accumulate needs the tensor to add to"
+        out = torch.empty((T, C2, Cin), device=grad_in.device)
+    assert _f32c(out).shape == (T, C2, Cin)
+    check(lib().amp_deconv_grad_transpose(ctx.handle, ptr(grad_in), ptr(out), Cin, T, C2, int(bool(accumulate))), "amp_deconv_grad_transpose")
+    return out
+
+
+def sgd_update(ctx, p, g, v, lr, momentum=0.9, weight_decay=1e-4, grad_scale=1.0):
+    """torch.optim.SGD in place on flat tensors: g' = grad_scale * g + wd * p; v = mu * v + g'; p -= lr * v (amp_sgd_update)."""
+    assert _f32c(p).shape == _f32c(g).shape == _f32c(v).shape
+    check(lib().amp_sgd_update(ctx.handle, ptr(p), ptr(g), ptr(v), p.numel(), float(lr), float(momentum), float(weight_decay), float(grad_scale)),
+          "amp_sgd_update")
+    return p, v
+
+
+def preprocess(ctx, img_bgr, Hp, Wp, mean, std, img_hw=None):
+    """uint8 BGR [B,H,W,3] -> fp32 [B,Hp,Wp,4] = (x - mean) / std, zero in the padding, in the 4th channel and beyond img_hw[b] = (h, w)
+    (int32 [B,2] on the device, optional) (amp_preprocess)."""
+    assert img_bgr.is_cuda and img_bgr.dtype == torch.uint8 and img_bgr.is_contiguous() and img_bgr.shape[3] == 3
+    assert img_hw is None or (img_hw.is_cuda and img_hw.dtype == torch.int32 and img_hw.is_contiguous() and img_hw.shape == (img_bgr.shape[0], 2))
+    B, H, W, _ = img_bgr.shape
+    out = torch.empty((B, Hp, Wp, 4), device=img_bgr.device)
+    check(lib().amp_preprocess(ctx.handle, ptr(img_bgr), B, H, W, int(Hp), int(Wp), (C.c_float * 3)(*mean), (C.c_float * 3)(*std), ptr(img_hw), ptr(out)),
+          "amp_preprocess")
+    return out
+
+
+def maxpool3x3s2(ctx, x):
+    """max_pool2d(kernel 3, stride 2, padding 1) of x [B,H,W,C], C % 4 == 0 (amp_maxpool3x3s2)."""
+    B, H, W, Cc = _f32c(x).shape
+    y = torch.empty((B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Cc), device=x.device)
+    check(lib().amp_maxpool3x3s2(ctx.handle, ptr(x), B, H, W, Cc, ptr(y)), "amp_maxpool3x3s2")
+    return y
+
+
+def subsample2(ctx, x):
+    """x[:, ::2, ::2] of x [B,H,W,C], C % 4 == 0 (amp_subsample2)."""
+    B, H, W, Cc = _f32c(x).shape
+    y = torch.empty((B, _half(H), _half(W), Cc), device=x.device)
+    check(lib().amp_subsample2(ctx.handle, ptr(x), B, H, W, Cc, ptr(y)), "amp_subsample2")
+    return y
 
 
 # ------------------------------------------------------------------------------------------------------------------

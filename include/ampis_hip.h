@@ -212,9 +212,14 @@ int amp_roi_align_bwd(amp_ctx* ctx, float* const dfeat[4], const int fh[4], cons
 int amp_roi_align_bwd_batched(amp_ctx* ctx, float* const dfeat[4], const int fh[4], const int fw[4], const int stride[4], int C, const float* rois,
                               const int* batch_idx, int R, int P, const float* dout, int B);
 int amp_upsample2_bwd(amp_ctx* ctx, const float* dfine, float* dcoarse, int B, int Hc, int Wc, int C);   /* dcoarse += 2x2 sums */
+/* dcoarse = the 2x2 sums: what amp_upsample2_bwd leaves in a zero-filled dcoarse, bit for bit; dcoarse may be uninitialised (it is written,
+ * never read).  The form a training step of amp_model runs. */
+int amp_upsample2_bwd_init(amp_ctx* ctx, const float* dfine, float* dcoarse, int B, int Hc, int Wc, int C);
 int amp_subsample2_bwd(amp_ctx* ctx, const float* dy, float* dx, int B, int H, int W, int C);           /* dx[::2, ::2] += dy */
-int amp_relu_mask(amp_ctx* ctx, float* g, const float* act, size_t n);
-/* The same with the activation in the split hi|lo' row format ([.., C] rows, C % 32 == 0). */
+int amp_relu_mask(amp_ctx* ctx, float* g, const float* act, size_t n);                                                         /* g = act > 0 ? g : 0 */
+/* The same with the activation in the split hi|lo' row format ([.., C] rows, C % 32 == 0): the mask is decode(act_split) > 0, so it sees
+ * what the split kept of the activation.  The floor: a positive activation down to 2^-35 still decodes positive (hi = 0, lo' = 2^-24, the
+ * smallest f16 subnormal); 2^-36 and below splits to all zeros and is masked out like 0.  -0.0 is not positive. */
 int amp_relu_mask_split(amp_ctx* ctx, float* g, const float* act_split, size_t n, int C);
 /* Scaled split gradients (the backbone's backward pass on the ring kernel): out = split(2^shift * (act > 0 ? g : 0)), and the
  * stride-2 scatter-add back into an fp32 gradient: dx[b,2y,2x,:] += 2^-shift * decode(dy_split[b,y,x,:]). */
@@ -225,7 +230,9 @@ int amp_subsample2_bwd_split(amp_ctx* ctx, const float* dy_split, float* dx, int
 int amp_accumulate_split(amp_ctx* ctx, const float* dy_split, float* dx, long long rows, int C, int shift);
 /* up[b, 2y, 2x, :] = src[b, y, x, :] as raw 16-byte chunks (split rows stay split rows), every other pixel of `up` zero: the input of the stride-1
  * data gradient of a stride-2 convolution whose gradient arrives in the split format.  up: [B, H, W, C], src: [B, ceil(H/2), ceil(W/2), C]. */
-int amp_scatter2_rows(amp_ctx* ctx, const float* src, float* up, int B, int H, int W, int C);                                  /* g *= (act > 0) */
+int amp_scatter2_rows(amp_ctx* ctx, const float* src, float* up, int B, int H, int W, int C);
+/* dx[p][c] = act[p][c] > 0 ? sum_k dl[p][k] * w[k][c] : 0 over dl [npix][ld] (K <= ld), w [K][C]; the sum runs over k in index order from 0,
+ * the product and the sum each rounded in fp32.  act == NULL: no mask. */
 int amp_small_k_dgrad(amp_ctx* ctx, const float* dl, int ld, int K, const float* w, int C, const float* act, float* dx, size_t npix);
 /* The same product for dl rows of 16 floats (K <= 16), C % 32 == 0 and act in the split row format, leaving dx * 2^shift as split rows (the
  * dy operand of the ring kernels) and colsum_out[c] (= or +=) the sum over the pixels of dx[.][c] (the bias gradient of the layer that
@@ -236,7 +243,10 @@ int amp_small_k_dgrad_split(amp_ctx* ctx, const float* dl, int K, const float* w
  * is fp32): dx is amp_small_k_dgrad's value, * 2^shift, as split rows; colsum_out = the deconv's bias gradient. */
 int amp_small_k_dgrad_split_f32act(amp_ctx* ctx, const float* dl, int ld, int K, const float* w, int C, const float* act, float* dx_split, int npix,
                                    int shift, float* scratch, float* colsum_out, int accumulate);
-/* ... and with act in the split row format again (a deconv output kept split: amp_conv2d_nhwc_fmt with out_mode 1 and AMP_FMT y split) */
+/* ... and with act in the split row format again (a deconv output kept split: amp_conv2d_nhwc_fmt with out_mode 1 and AMP_FMT y split).
+ * The dl columns k >= K: _f32act does not read their values (they may hold anything, NaN included).  The two variants with act in the split
+ * format multiply them by a zero weight, so they must be FINITE (a NaN or inf there reaches every dx of the row).  The model zero-fills
+ * them: it calls amp_mask_target_loss_fmt with K = Kp, which writes every column of the padded rows. */
 int amp_small_k_dgrad_split_ld(amp_ctx* ctx, const float* dl, int ld, int K, const float* w, int C, const float* act_split, float* dx_split, int npix,
                                int shift, float* scratch, float* colsum_out, int accumulate);
 int amp_colsum_finish(amp_ctx* ctx, const float* partial, int parts, int N, float* out, int accumulate);
