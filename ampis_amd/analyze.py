@@ -17,6 +17,10 @@ pycocotools:
     lie from the other mask: ONE `amp_mask_edge_distance` call for all pairs, on the device or on the host.  The reference broadcasts
     [queries x targets x 2] doubles per pair and takes torch.sqrt; here the exact integer squared distance comes back (an exact nearest-pixel
     search on bit planes, csrc/edge_distance.hip) and the root is numpy's correctly rounded one.
+  * `region_properties`, `compute_rprops`, `regionprops_table` (ampis/structures.py:474-514, InstanceSet.compute_rprops on
+    skimage.measure.regionprops_table): ONE `amp_mask_region_props` call gives 13 exact integers per mask from the run lists, on the device
+    (csrc/region_props.hip) or on the host, and `region_floats` derives every column from them.  The reference decodes each mask to the full
+    image first.
 With no prediction at all the detection precision is 0/0: like the reference this raises ZeroDivisionError.
 The independent checker is oracle/matcher.py (a loop-for-loop restatement of the reference, pinned by its known-answer test)."""
 import numpy as np
@@ -110,12 +114,12 @@ def _index_boxes(boxes, masks, name):
 _edge_ctx = {}
 
 
-def _edge_context():
+def _edge_context(who="mask_edge_distance"):
     """The context of the device path: one per HIP device, with a stream of its own (the call uploads, computes and downloads by itself)."""
     import torch
     from . import _lib
     if not torch.cuda.is_available():
-        raise _lib.AmpError("mask_edge_distance(device='cuda'): no HIP device is visible (device='cpu' computes on the host)")
+        raise _lib.AmpError(f"{who}(device='cuda'): no HIP device is visible (device='cpu' computes on the host)")
     dev = torch.cuda.current_device()
     if dev not in _edge_ctx:
         _edge_ctx[dev] = _lib.Context(dev)
@@ -160,3 +164,107 @@ def mask_edge_distance(gt_mask, pred_mask, gt_box, pred_box, matches, device='au
     else:
         conv = lambda d: torch.from_numpy(np.sqrt(d.astype(np.float64)))
     return [conv(d) for d in fp], [conv(d) for d in fn]
+
+
+# ---- region properties (ampis/structures.py:474-514, InstanceSet.compute_rprops) ----------------------------------------------------------------
+
+RPROPS_DEFAULT_KEYS = ["area", "equivalent_diameter", "major_axis_length", "perimeter", "solidity", "orientation"]       # ampis/structures.py:505
+RPROPS_KEYS = ("area", "bbox", "bbox_area", "centroid", "convex_area", "eccentricity", "equivalent_diameter", "extent", "major_axis_length",
+               "minor_axis_length", "orientation", "perimeter", "solidity")
+
+
+def region_floats(bbox, vals):
+    """THE derivation of the region-property floats from the exact integers of amp_mask_region_props (bbox: 4 ints, vals: 13 ints of one mask)
+    -> dict of every supported column.  Both the device and the host path go through here, so they return identical bytes.  The differences
+    that cancel (A, B, C, A - C, A C - B^2) are formed in Python integers, which may pass 64 bits, and rounded to float64 once.  B is an exact
+    integer, so a zero is a true zero: atan2 gets +0.0 for it (a mask symmetric about a column wider than tall: +pi/2, never -pi/2 from the
+    sign of a float zero)."""
+    import math
+    N, sr, sc, srr, src, scc, p1, p2, p3, hull = (int(v) for v in vals[:10])
+    r0, c0, r1, c1 = (int(v) for v in bbox)
+    nan = float("nan")
+    out = {"area": N, "bbox-0": r0, "bbox-1": c0, "bbox-2": r1, "bbox-3": c1, "bbox_area": (r1 - r0) * (c1 - c0), "convex_area": hull,
+           "perimeter": p1 + p2 * math.sqrt(2.0) + p3 * ((1.0 + math.sqrt(2.0)) / 2.0), "equivalent_diameter": math.sqrt(4 * N / math.pi)}
+    if N == 0:
+        out.update({k: nan for k in ("centroid-0", "centroid-1", "eccentricity", "extent", "major_axis_length", "minor_axis_length", "orientation",
+                                     "solidity")})
+        return out
+    A, Cc, B = N * scc - sc * sc, N * srr - sr * sr, -(N * src - sr * sc)      # N^2 times the inertia tensor [[a, b], [b, c]]
+    N2 = N * N
+    b = B / N2
+    root = math.sqrt(b * b + ((A - Cc) / (2 * N2)) ** 2)
+    l1 = (A + Cc) / (2 * N2) + root
+    l2 = ((A * Cc - B * B) / (N2 * N2)) / l1 if l1 else 0.0
+    out.update({"centroid-0": sr / N, "centroid-1": sc / N, "extent": N / out["bbox_area"], "solidity": N / hull,
+                "major_axis_length": 4.0 * math.sqrt(l1), "minor_axis_length": 4.0 * math.sqrt(l2),
+                "eccentricity": math.sqrt(2.0 * root / l1) if l1 else 0.0,
+                "orientation": (-math.pi / 4 if B < 0 else math.pi / 4) if A == Cc else 0.5 * math.atan2(-2.0 * b if B else 0.0, (Cc - A) / N2)})
+    return out
+
+
+def _rprops_columns(keys):
+    """regionprops_table's column names of `keys` (None: the reference's default list); ValueError naming a key this module does not have."""
+    keys = list(RPROPS_DEFAULT_KEYS if keys is None else keys)
+    cols = []
+    for k in keys:
+        if k not in RPROPS_KEYS:
+            raise ValueError(f"region_properties: unsupported key {k!r} (supported: {', '.join(RPROPS_KEYS)})")
+        cols += [f"bbox-{i}" for i in range(4)] if k == "bbox" else [f"centroid-{i}" for i in range(2)] if k == "centroid" else [k]
+    return cols
+
+
+def region_properties(masks, keys=None, size=None, device='auto'):
+    """Shape measurements of every mask, the table skimage.measure.regionprops_table gives InstanceSet.compute_rprops (ampis/structures.py:474-514):
+    a dict of column name -> np.ndarray [N], columns named like regionprops_table ('bbox-0' .. 'bbox-3', 'centroid-0', 'centroid-1', the rest by
+    key).  A region is ALL set pixels of one mask (holes and disconnected parts included), coordinates are (row, column) of the full image.
+
+    masks: anything masks_to_rle accepts (size=(h, w) for polygons); keys: any of RPROPS_KEYS, None for the reference's default list; device:
+    'cpu' (host), 'cuda' (HIP device, an error without one) or 'auto' (the device when one is visible).  One amp_mask_region_props call returns
+    13 exact integers per mask (csrc/region_props.hip, or rle_host.hip on the host); region_floats derives the floats from them for both
+    paths, so they agree bit for bit.  An empty mask: area, perimeter, convex_area, equivalent_diameter 0, bbox (0, 0, 0, 0), NaN elsewhere.
+
+    UNPINNED PARITY: skimage is not part of this environment and the reference stores no region-property output, so no vector of the reference's
+    pins this function.  The definitions are skimage's regionprops (rc coordinates, 0.16 and later) restated in DESIGN §7e; the tests hold
+    the integers to an independent scipy / brute-force evaluation of those definitions and the floats to their exact-rational value.
+    ValueError for an unknown key (before any device work), a bad `device`, masks of different sizes."""
+    import torch
+    cols = _rprops_columns(keys)
+    dev = str(device).lower()
+    if dev not in ("auto", "cpu", "cuda"):
+        raise ValueError(f"region_properties: device = {device!r} ('auto', 'cpu' or 'cuda')")
+    rles = masks_to_rle(masks, size)
+    sizes = {tuple(int(v) for v in r["size"]) for r in rles}
+    if len(sizes) > 1:
+        raise ValueError(f"region_properties: masks of different sizes {sorted(sizes)}")
+    ctx = _edge_context("region_properties") if dev == "cuda" or (dev == "auto" and len(rles) and torch.cuda.is_available()) else None
+    bbox, vals = rle.region_props(rles, ctx=ctx)
+    rows = [region_floats(b, v) for b, v in zip(bbox.tolist(), vals.tolist())]
+    ints = ("area", "bbox_area", "convex_area", "bbox-0", "bbox-1", "bbox-2", "bbox-3")
+    return {c: np.array([r[c] for r in rows], dtype=np.int64 if c in ints else np.float64) for c in cols}
+
+
+def compute_rprops(iset, keys=None, return_df=False, device='auto'):
+    """InstanceSet.compute_rprops (ampis/structures.py:474-514) as a function: stores in iset.rprops a pandas DataFrame with one row per instance
+    -- the region_properties columns of `keys` plus 'class_idx' -- and returns it when return_df.  Duck-typed: iset.instances.masks,
+    iset.instances.image_size (for polygon masks), iset.instances.class_idx.  Unlike the reference, whose cells are the one-element arrays of
+    one regionprops_table call per mask, the cells here are scalars."""
+    import pandas as pd
+    inst = iset.instances
+    table = region_properties(inst.masks, keys, size=tuple(int(v) for v in inst.image_size), device=device)
+    df = pd.DataFrame(table)
+    df["class_idx"] = np.asarray(inst.class_idx).reshape(-1)
+    iset.rprops = df
+    return df if return_df else None
+
+
+def regionprops_table(label_image, properties=RPROPS_DEFAULT_KEYS):
+    """The import swap for the one use AMPIS makes of skimage.measure.regionprops_table: a 2-D integer label image (0 = background) -> dict of
+    column -> array with one entry per label in ascending order."""
+    cols = _rprops_columns(properties)
+    lab = np.asarray(label_image)
+    if lab.ndim != 2 or not np.issubdtype(lab.dtype, np.integer):
+        raise ValueError(f"regionprops_table: a 2-D integer label image is required, got shape {lab.shape} {lab.dtype}")
+    labels = [int(v) for v in np.unique(lab) if v != 0]
+    if not labels:
+        return {c: np.zeros(0) for c in cols}
+    return region_properties([rle.encode(np.asfortranarray(lab == v)) for v in labels], properties)

@@ -157,6 +157,24 @@ struct amp_ctx {
 };
 
 namespace amp {
+struct DevBuf {                  // device memory of one call (edge_distance.hip, region_props.hip: upload, compute, download, free)
+    void* p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    template <class T> T* as() const { return static_cast<T*>(p); }
+};
+inline int dev_alloc(DevBuf& b, size_t bytes) {
+    AMP_HIP_CHECK(hipMalloc(&b.p, bytes ? bytes : 16));
+    return AMP_OK;
+}
+template <class T>
+inline int dev_upload(amp_ctx* ctx, DevBuf& b, const std::vector<T>& v) {
+    AMP_TRY_STATUS(dev_alloc(b, v.size() * sizeof(T)));
+    if (!v.empty()) AMP_HIP_CHECK(hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    return AMP_OK;
+}
+}
+
+namespace amp {
 // internal convolution entry (conv.hip): w_split = weights already in the f16x3 split layout (amp_split_weights) or null;
 // force_f32 = 1 runs the fp32-MFMA kernel whatever the context mode is; in_shift = s: (AMP_CONV_F16X3 only) the input is multiplied
 // by 2^s before the operand split and the sum by 2^-s (data gradients: tiny values would otherwise sit in the f16 subnormals).
@@ -262,6 +280,12 @@ int edge_distance_check(const uint32_t* gpool, const unsigned long long* goff, c
 int edge_distance_host(const uint32_t* gpool, const unsigned long long* goff, const int* glen, const uint32_t* ppool, const unsigned long long* poff,
                        const int* plen, const int* pair_g, const int* pair_p, const int* crop, int n, int h, uint32_t* fp_d2,
                        unsigned long long fp_cap, unsigned long long* fp_off, uint32_t* fn_d2, unsigned long long fn_cap, unsigned long long* fn_off);
+// rle_host.hip: amp_mask_region_props' argument checks (every run list non-empty and summing to h * w, the size limits; box = the tight boxes
+// {r0, c0, r1, c1} with exclusive ends, [n][4], zeros for an empty mask) and its host evaluation; region_props.hip holds the entry point and
+// the device evaluation, region_props.h the word arithmetic both use
+int region_props_check(const uint32_t* pool, const unsigned long long* off, const int* len, int n, int h, int w, const long long* bbox,
+                       const unsigned long long* vals, std::vector<int>& box);
+int region_props_host(const uint32_t* pool, const unsigned long long* off, const int* len, const int* box, int n, int h, unsigned long long* vals);
 int roi_align_run(amp_ctx* ctx, const amp_fpn_feats* f, const float* rois, const int* batch_idx, const int* roi_count, int R, int P,
                   float* out, int* level_out, int out_split, int in_split = 0);   // out_split / in_split = 1: pooled tensor / feature maps in the split row format
 int box_candidates_run(amp_ctx* ctx, const float* pred, int ld, const float* proposals, const int* prop_count, int B, int Rcap, int K,

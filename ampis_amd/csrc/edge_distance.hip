@@ -184,24 +184,6 @@ __global__ __launch_bounds__(256) void ed_search_kernel(const EdPair* __restrict
     }
 }
 
-struct DevBuf {                  // device memory of one call
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-
-static int ed_alloc(DevBuf& b, size_t bytes) {
-    AMP_HIP_CHECK(hipMalloc(&b.p, bytes ? bytes : 16));
-    return AMP_OK;
-}
-
-template <class T>
-static int ed_upload(amp_ctx* ctx, DevBuf& b, const std::vector<T>& v) {
-    AMP_TRY_STATUS(ed_alloc(b, v.size() * sizeof(T)));
-    if (!v.empty()) AMP_HIP_CHECK(hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-    return AMP_OK;
-}
-
 static int edge_distance_device(amp_ctx* ctx, const uint32_t* gpool, const unsigned long long* goff, const int* glen, int ng, const uint32_t* ppool,
                                 const unsigned long long* poff, const int* plen, int np, const int* pair_g, const int* pair_p, const int* crop, int n,
                                 int h, int w, uint32_t* fp_d2, unsigned long long fp_cap, unsigned long long* fp_off, uint32_t* fn_d2,
@@ -244,15 +226,15 @@ static int edge_distance_device(amp_ctx* ctx, const uint32_t* gpool, const unsig
 
     AMP_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    DevBuf d_pairs, d_dt, d_rt, d_pre, d_planes, d_rows, d_off, d_out;
+    amp::DevBuf d_pairs, d_dt, d_rt, d_pre, d_planes, d_rows, d_off, d_out;
     std::vector<unsigned long long> off((size_t)2 * (n + 1), 0);
-    AMP_TRY_STATUS(ed_upload(ctx, d_pairs, pairs));
-    AMP_TRY_STATUS(ed_upload(ctx, d_dt, dtiles));
-    AMP_TRY_STATUS(ed_upload(ctx, d_rt, rtiles));
-    AMP_TRY_STATUS(ed_upload(ctx, d_pre, pre));
-    AMP_TRY_STATUS(ed_alloc(d_planes, words * 8));
-    AMP_TRY_STATUS(ed_alloc(d_rows, (size_t)nrows * 16));
-    AMP_TRY_STATUS(ed_alloc(d_off, off.size() * 8));
+    AMP_TRY_STATUS(amp::dev_upload(ctx, d_pairs, pairs));
+    AMP_TRY_STATUS(amp::dev_upload(ctx, d_dt, dtiles));
+    AMP_TRY_STATUS(amp::dev_upload(ctx, d_rt, rtiles));
+    AMP_TRY_STATUS(amp::dev_upload(ctx, d_pre, pre));
+    AMP_TRY_STATUS(amp::dev_alloc(d_planes, words * 8));
+    AMP_TRY_STATUS(amp::dev_alloc(d_rows, (size_t)nrows * 16));
+    AMP_TRY_STATUS(amp::dev_alloc(d_off, off.size() * 8));
     unsigned long long* rows_fp = d_rows.as<unsigned long long>();
     unsigned long long* rows_fn = rows_fp + nrows;
     unsigned long long* off_fp = d_off.as<unsigned long long>();
@@ -279,7 +261,7 @@ static int edge_distance_device(amp_ctx* ctx, const uint32_t* gpool, const unsig
         return AMP_ERR_NOMEM;
     }
     if (tot) {
-        AMP_TRY_STATUS(ed_alloc(d_out, (size_t)tot * 4));
+        AMP_TRY_STATUS(amp::dev_alloc(d_out, (size_t)tot * 4));
         unsigned int* out = d_out.as<unsigned int>();
         hipLaunchKernelGGL(ed_rows_kernel<true>, dim3(rblocks), dim3(256), 0, st, d_pairs.as<EdPair>(), d_rt.as<int2>(), nrt,
                            d_planes.as<unsigned long long>(), rows_fp, rows_fn, out, out + tot_fp);

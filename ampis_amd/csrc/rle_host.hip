@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "common.h"
+#include "region_props.h"
 
 extern "C" {
 
@@ -600,6 +601,93 @@ int edge_distance_host(const uint32_t* gpool, const unsigned long long* goff, co
     std::copy(fn.begin(), fn.end(), fn_d2);
     std::copy(fpo.begin(), fpo.end(), fp_off);
     std::copy(fno.begin(), fno.end(), fn_off);
+    return AMP_OK;
+}
+
+}  // namespace amp
+
+// ---- region properties (ampis/structures.py:474-514, skimage.measure.regionprops restated): argument checks and tight boxes shared with the
+// device path, and the host evaluation.  Per mask 13 exact integers {N, sum r, sum c, sum r^2, sum r c, sum c^2, P1, P2, P3, convex area, 0, 0, 0}:
+// the moments in closed form from the runs, the perimeter classes and the hull on a column-major bit plane of the tight box (region_props.h:
+// the same word arithmetic as the kernels of region_props.hip).
+namespace amp {
+
+int region_props_check(const uint32_t* pool, const unsigned long long* off, const int* len, int n, int h, int w, const long long* bbox,
+                       const unsigned long long* vals, std::vector<int>& box) {
+    AMP_REQUIRE(n >= 0, "amp_mask_region_props: n = %d", n);
+    AMP_REQUIRE(n == 0 || (pool && off && len && bbox && vals), "amp_mask_region_props: null argument");
+    AMP_REQUIRE(h >= 1 && w >= 1 && h <= 32768 && w <= 32768 && (unsigned long long)h * w <= (1ull << 30),
+                "amp_mask_region_props: image size %d x %d (1 .. 32768 a side, at most 2^30 pixels: the moment sums are 64-bit)", h, w);
+    const unsigned long long area = (unsigned long long)h * w;
+    box.assign((size_t)n * 4, 0);
+    for (int p = 0; p < n; ++p) {
+        const uint32_t* c = pool + off[p];
+        AMP_REQUIRE(len[p] > 0, "amp_mask_region_props: mask %d has an empty run list", p);
+        unsigned long long pos = 0;
+        int r0 = h, r1 = -1, c0 = w, c1 = -1;
+        for (int j = 0; j < len[p]; ++j) {
+            const unsigned long long s = pos, e = pos + c[j];
+            pos = e;
+            AMP_REQUIRE(e <= area, "amp_mask_region_props: the runs of mask %d cover more than the image's %llu pixels", p, area);
+            if (!(j & 1) || e == s) continue;
+            const int cf = (int)(s / (unsigned)h), cl = (int)((e - 1) / (unsigned)h);
+            c0 = std::min(c0, cf); c1 = std::max(c1, cl);
+            if (cf == cl) { r0 = std::min(r0, (int)(s % (unsigned)h)); r1 = std::max(r1, (int)((e - 1) % (unsigned)h)); }
+            else { r0 = 0; r1 = h - 1; }                                          // a run that wraps covers the last and the first row
+        }
+        AMP_REQUIRE(pos == area, "amp_mask_region_props: the runs of mask %d cover %llu pixels, the image has %llu", p, pos, area);
+        if (r1 >= 0) { int* b = &box[4 * (size_t)p]; b[0] = r0; b[1] = c0; b[2] = r1 + 1; b[3] = c1 + 1; }
+    }
+    return AMP_OK;
+}
+
+int region_props_host(const uint32_t* pool, const unsigned long long* off, const int* len, const int* box, int n, int h, unsigned long long* vals) {
+    std::vector<rp_u64> mask, border;
+    std::vector<int> pts;
+    for (int p = 0; p < n; ++p) {
+        unsigned long long* v = vals + 13 * (size_t)p;
+        std::fill(v, v + 13, 0ull);
+        const int* b = box + 4 * (size_t)p;
+        const int r0 = b[0], c0 = b[1], H = b[2] - b[0], W = b[3] - b[1], pitch = (H + 63) >> 6;
+        if (H == 0) continue;
+        mask.assign((size_t)W * pitch, 0ull);
+        border.assign((size_t)W * pitch, 0ull);
+        const uint32_t* c = pool + off[p];
+        unsigned long long pos = 0;
+        for (int j = 0; j < len[p]; ++j) {
+            const unsigned long long s = pos, e = pos + c[j];
+            pos = e;
+            if (!(j & 1) || e == s) continue;
+            rp_run_sums(s, e, (rp_u64)h, v);
+            for (unsigned long long col = s / (unsigned)h; col <= (e - 1) / (unsigned)h; ++col) {         // inside the tight box by construction
+                const unsigned long long cb = col * (unsigned)h;
+                const int ya = (int)(std::max(s, cb) - cb) - r0, yb = (int)(std::min(e, cb + (unsigned)h) - cb) - r0;
+                rp_u64* pc = &mask[(size_t)(col - c0) * pitch];
+                for (int wv = ya >> 6; wv <= (yb - 1) >> 6; ++wv) {
+                    const int lo = std::max(ya - (wv << 6), 0), hi = std::min(yb - (wv << 6), 64);
+                    pc[wv] |= (hi == 64 ? ~0ull : ((1ull << hi) - 1ull)) & ~((1ull << lo) - 1ull);
+                }
+            }
+        }
+        for (int q = 0; q < W; ++q)
+            for (int wv = 0; wv < pitch; ++wv) border[(size_t)q * pitch + wv] = rp_border_at(mask.data(), W, pitch, q, wv);
+        for (int q = 0; q < W; ++q)
+            for (int wv = 0; wv < pitch; ++wv) {
+                if (!border[(size_t)q * pitch + wv]) continue;
+                rp_u64 cls[3];
+                rp_classify_at(border.data(), W, pitch, q, wv, cls);
+                for (int k = 0; k < 3; ++k) v[6 + k] += (unsigned)rp_popc(cls[k]);
+            }
+        const int np = 2 * W + 1;
+        pts.assign((size_t)4 * np, 0);
+        int *lo = pts.data(), *hi = lo + np, *sl = hi + np, *su = sl + np;
+        for (int i = 0; i < np; ++i) rp_point(i, W, mask.data(), pitch, &lo[i], &hi[i]);
+        const int kl = rp_chain(lo, np, +1, sl), ku = rp_chain(hi, np, -1, su);
+        long long fill = W;                                                      // sum over the columns of floor(upper / 2) - ceil(lower / 2) + 1
+        for (int k = 0; k + 1 < ku; ++k) fill += rp_edge_sum(su[k], hi[su[k]], su[k + 1], hi[su[k + 1]], true);
+        for (int k = 0; k + 1 < kl; ++k) fill -= rp_edge_sum(sl[k], lo[sl[k]], sl[k + 1], lo[sl[k + 1]], false);
+        v[9] = (unsigned long long)fill;
+    }
     return AMP_OK;
 }
 

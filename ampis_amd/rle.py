@@ -231,6 +231,20 @@ def edge_distance(gt, pred, pairs, boxes, ctx=None):
     return out
 
 
+def region_props(masks, ctx=None):
+    """Region properties of RLE dicts of one image size, one C call (amp_mask_region_props): (bbox, vals) = int64 [n, 4] boxes (rmin, cmin,
+    rmax + 1, cmax + 1) and uint64 [n, 13] exact integers {N, sum r, sum c, sum r^2, sum r c, sum c^2, P1, P2, P3, convex area, 0, 0, 0}; all
+    zero for an empty mask.  ctx: a _lib.Context (computed on its device) or None (on the host): the same bytes."""
+    n = len(masks)
+    bbox, vals = np.zeros((n, 4), dtype=np.int64), np.zeros((n, 13), dtype=np.uint64)
+    h, w = (int(v) for v in masks[0]["size"]) if n else (1, 1)
+    pool, off, ln = _pool([_counts(x) for x in masks])
+    vp = lambda x: x.ctypes.data_as(C.c_void_p)
+    check(lib().amp_mask_region_props(ctx.handle if ctx is not None else None, vp(pool), vp(off), vp(ln), n, h, w, vp(bbox), vp(vals)),
+          "amp_mask_region_props")
+    return bbox, vals
+
+
 def merge(rles, intersect=False):
     assert len(rles) >= 1
     h, w = rles[0]["size"]

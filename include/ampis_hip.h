@@ -514,6 +514,21 @@ int amp_mask_edge_distance(amp_ctx* ctx, const uint32_t* gpool, const unsigned l
                            const uint32_t* ppool, const unsigned long long* poff, const int* plen, int np, const int* pair_g,
                            const int* pair_p, const int* box, int n, int h, int w, uint32_t* fp_d2, unsigned long long fp_cap,
                            unsigned long long* fp_off, uint32_t* fn_d2, unsigned long long fn_cap, unsigned long long* fn_off);
+/* Region properties (ampis/structures.py:474-514, skimage.measure.regionprops restated) of `n` masks in one call.  ALL POINTERS ARE HOST
+ * POINTERS.  Mask i is the run list pool[off[i] .. off[i] + len[i]) over one h x w image, h, w <= 32768 and h * w <= 2^30.  A region is ALL set
+ * pixels of a mask, holes and disconnected parts included; r = row, c = column of the full image.
+ *   bbox[i] = {rmin, cmin, rmax + 1, cmax + 1}, {0, 0, 0, 0} for an empty mask;
+ *   vals[i] = {N, sum r, sum c, sum r^2, sum r c, sum c^2, P1, P2, P3, convex area, 0, 0, 0}, exact (every sum < 2^60), all 0 for an empty mask.
+ * P1, P2, P3 count the border pixels (mask minus its erosion by the 4-connected cross, outside the image = 0) by n4 / nd, the numbers of their
+ * 4-neighbours / diagonal neighbours on the border: P1: n4 in {2, 3} and nd <= 2; P2: (n4, nd) in {(0, 2), (1, 3)}; P3: (1, 1), (1, 2) --
+ * skimage's perimeter = P1 + P2 sqrt(2) + P3 (1 + sqrt(2)) / 2.  convex area = the pixel centres inside or on the convex hull of the four edge
+ * midpoints (r -+ 1/2, c), (r, c -+ 1/2) of every pixel (convex_hull_image, offset_coordinates=True), decided in half-pixel integers.
+ * Every run list is checked on the host first (length > 0, runs summing to h * w, the size limits): a malformed list is AMP_ERR_ARG, nothing
+ * written and never a device access.  ctx == NULL: computed on the host (rle_host.hip).  Otherwise on ctx's device and stream
+ * (region_props.hip): the function uploads, runs a fixed number of launches whatever n is, downloads and returns with the results in host
+ * memory; integer arithmetic only, the bytes do not depend on the device's scheduling and equal the host's. */
+int amp_mask_region_props(amp_ctx* ctx, const uint32_t* pool, const unsigned long long* off, const int* len, int n, int h, int w,
+                          long long* bbox /* [n][4] */, unsigned long long* vals /* [n][13] */);
 /* Nearest-neighbour resize (+ horizontal mirror when flip) of a mask in the run-length domain: the runs of
  * flip(PIL.Image.resize(decode(cnts), (nw, nh), NEAREST)) -- what detectron2's ResizeTransform.apply_segmentation + HFlipTransform do to a bitmask
  * annotation -- without decoding (Pillow's ImagingScaleAffine pixel correspondence, restated).  cap >= nh * nw + 1 is always enough. */
