@@ -21,6 +21,9 @@ pycocotools:
     skimage.measure.regionprops_table): ONE `amp_mask_region_props` call gives 13 exact integers per mask from the run lists, on the device
     (csrc/region_props.hip) or on the host, and `region_floats` derives every column from them.  The reference decodes each mask to the full
     image first.
+  * `overlap_matrix` (the all-pairs RLE.merge(intersect=True) + RLE.area loop of ampis/applications/powder.py:82) and `mask_areas`
+    (ampis/structures.py:536-583): ONE `amp_rle_overlap_groups` call gives the exact pixel count of every pair of masks of an image, or of
+    every image of a sample (ampis_amd/applications/powder.py), on the device (csrc/rle_overlap.hip) or on the host.
 With no prediction at all the detection precision is 0/0: like the reference this raises ZeroDivisionError.
 The independent checker is oracle/matcher.py (a loop-for-loop restatement of the reference, pinned by its known-answer test)."""
 import numpy as np
@@ -268,3 +271,58 @@ def regionprops_table(label_image, properties=RPROPS_DEFAULT_KEYS):
     if not labels:
         return {c: np.zeros(0) for c in cols}
     return region_properties([rle.encode(np.asfortranarray(lab == v)) for v in labels], properties)
+
+
+# ---- all-pairs overlap and mask areas (ampis/applications/powder.py:80-83, ampis/structures.py:536-583) -----------------------------------------
+
+def _device_context(who, device, work):
+    """The context of `device` for function `who`: None for the host -- 'cpu', or 'auto' with no visible device or nothing to do (`work`
+    false) --, the current device's context for 'cuda' (an error without one) and for 'auto' otherwise.  ValueError for any other value."""
+    import torch
+    dev = str(device).lower()
+    if dev not in ("auto", "cpu", "cuda"):
+        raise ValueError(f"{who}: device = {device!r} ('auto', 'cpu' or 'cuda')")
+    return _edge_context(who) if dev == "cuda" or (dev == "auto" and work and torch.cuda.is_available()) else None
+
+
+def overlap_matrix(a, b, device='auto', size=None):
+    """[len(a), len(b)] int64: the exact pixel count of a[i] AND b[j] for every pair of masks of one image -- what the reference gets from one
+    RLE.merge(intersect=True) + RLE.area per pair (ampis/applications/powder.py:82).  One amp_rle_overlap_groups call with one group.  a, b:
+    anything masks_to_rle accepts (size=(h, w) for polygons); device: 'cpu' (host), 'cuda' (HIP device, an error without one) or 'auto' (the
+    device when one is visible); the paths return identical bytes.  ValueError for a bad `device` and for masks of different sizes."""
+    ra, rb = masks_to_rle(a, size), masks_to_rle(b, size)
+    ctx = _device_context("overlap_matrix", device, len(ra) and len(rb))
+    try:
+        return rle.overlap_groups([ra], [rb], ctx=ctx)[0][0]
+    except ValueError as e:
+        raise ValueError(str(e).replace("overlap_groups: group 0 holds", "overlap_matrix: a / b hold")) from None
+
+
+def _shoelace_area(x, y):
+    """Area of a simple polygon from its vertices (ampis/structures.py:586-610)."""
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    return 0.5 * np.abs(np.dot(x, np.roll(y, 1)) - np.dot(y, np.roll(x, 1)))
+
+
+def mask_areas(masks):
+    """Area in pixels of every mask, with the reference's dispatch (ampis/structures.py:536-583): an ndarray [N, H, W] -> its pixel sums
+    (unsigned); PolygonMasks -> the shoelace area of each instance's FIRST polygon (float64, as the reference: further polygons of an instance
+    are not counted); a list of RLE dicts, RLEBitMasks or anything with .rle -> the run sums (uint32, like pycocotools' area); an object with
+    .masks or .instances -> the areas of those; any other list -> the list of its elements' areas."""
+    if isinstance(masks, np.ndarray):
+        return masks.sum(axis=(1, 2), dtype=np.uint)
+    if isinstance(masks, PolygonMasks):
+        return np.asarray([_shoelace_area(np.asarray(inst[0]).reshape(-1)[::2], np.asarray(inst[0]).reshape(-1)[1::2]) for inst in masks.polygons])
+    if isinstance(masks, RLEBitMasks) or hasattr(masks, "rle"):
+        return rle.area(list(masks.rle))
+    if isinstance(masks, (list, tuple)) and len(masks) and isinstance(masks[0], dict):
+        return rle.area(list(masks))
+    if isinstance(masks, BitMasks):
+        return mask_areas(masks.tensor.numpy().astype(bool))
+    if hasattr(masks, "masks"):
+        return mask_areas(masks.masks)
+    if hasattr(masks, "instances"):
+        return mask_areas(masks.instances)
+    if isinstance(masks, (list, tuple)):
+        return [mask_areas(x) for x in masks]
+    raise NotImplementedError(f"Not implemented for type {type(masks)}")

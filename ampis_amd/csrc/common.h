@@ -286,6 +286,25 @@ int edge_distance_host(const uint32_t* gpool, const unsigned long long* goff, co
 int region_props_check(const uint32_t* pool, const unsigned long long* off, const int* len, int n, int h, int w, const long long* bbox,
                        const unsigned long long* vals, std::vector<int>& box);
 int region_props_host(const uint32_t* pool, const unsigned long long* off, const int* len, const int* box, int n, int h, unsigned long long* vals);
+// rle_host.hip: amp_rle_overlap_groups' argument checks, which also build the plan both paths evaluate, and its host evaluation; rle_overlap.hip
+// holds the entry point and the device evaluation.  The plan of one pool: per mask its non-empty runs of ones k = 0 .. n - 1 as pixel positions
+// [S[ro + k], E[ro + k]) of the column-major image, P[ro + k] = the pixels of the runs before k, and one closing entry S = E = 0xffffffff,
+// P = the area, so that "the first run that ends beyond x" needs no special case at the end of the list.
+struct OvMask {
+    unsigned int ro;              // where the mask's entries start in S / E / P
+    int n;                        // runs of ones (0: an empty mask; its box is all zeros and meets nothing)
+    int r0, c0, r1, c1;           // the tight box, ends exclusive
+    unsigned int area;
+};
+struct OvPlan {
+    std::vector<uint32_t> S, E, P;
+    std::vector<OvMask> m;
+};
+int overlap_groups_check(const uint32_t* apool, const unsigned long long* aoff, const int* alen, const uint32_t* bpool,
+                         const unsigned long long* boff, const int* blen, const int* a_first, const int* b_first, const int* gh, const int* gw,
+                         int ngroups, const uint32_t* inter, size_t inter_cap, const unsigned long long* area_a, const unsigned long long* area_b,
+                         OvPlan& a, OvPlan& b);
+int overlap_groups_host(const OvPlan& a, const OvPlan& b, const int* a_first, const int* b_first, int ngroups, uint32_t* inter);
 int roi_align_run(amp_ctx* ctx, const amp_fpn_feats* f, const float* rois, const int* batch_idx, const int* roi_count, int R, int P,
                   float* out, int* level_out, int out_split, int in_split = 0);   // out_split / in_split = 1: pooled tensor / feature maps in the split row format
 int box_candidates_run(amp_ctx* ctx, const float* pred, int ld, const float* proposals, const int* prop_count, int B, int Rcap, int K,

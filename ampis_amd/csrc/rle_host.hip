@@ -692,3 +692,98 @@ int region_props_host(const uint32_t* pool, const unsigned long long* off, const
 }
 
 }  // namespace amp
+
+// ---- all-pairs mask intersection inside groups (ampis/applications/powder.py:80-83, RLE.merge(intersect=True) + RLE.area for every satellite
+// against every particle of an image): argument checks that also build the plan (common.h OvPlan), shared with the device path, and the host
+// evaluation: the box test, then one walk over both lists of runs for the pairs it leaves.
+namespace amp {
+
+static int overlap_plan_pool(const char* which, const uint32_t* pool, const unsigned long long* off, const int* len, const int* first,
+                             const int* gh, const int* gw, int ngroups, OvPlan& pl) {
+    pl.m.assign((size_t)first[ngroups], OvMask{0, 0, 0, 0, 0, 0, 0});
+    for (int g = 0; g < ngroups; ++g) {
+        const int h = gh[g];
+        const unsigned long long area = (unsigned long long)h * gw[g];
+        for (int p = first[g]; p < first[g + 1]; ++p) {
+            AMP_REQUIRE(len[p] > 0, "amp_rle_overlap_groups: mask %d of pool %s (group %d) has an empty run list", p, which, g);
+            const uint32_t* c = pool + off[p];
+            OvMask& e = pl.m[(size_t)p];
+            e.ro = (unsigned int)pl.S.size();
+            unsigned long long pos = 0, ones = 0;
+            int r0 = h, r1 = -1, c0 = gw[g], c1 = -1;
+            for (int j = 0; j < len[p]; ++j) {
+                const unsigned long long s = pos, t = pos + c[j];
+                pos = t;
+                AMP_REQUIRE(t <= area, "amp_rle_overlap_groups: the runs of mask %d of pool %s (group %d) cover more than the image's %llu pixels",
+                            p, which, g, area);
+                if (!(j & 1) || t == s) continue;
+                pl.S.push_back((uint32_t)s); pl.E.push_back((uint32_t)t); pl.P.push_back((uint32_t)ones);
+                ones += t - s;
+                const int cf = (int)(s / (unsigned)h), cl = (int)((t - 1) / (unsigned)h);
+                c0 = std::min(c0, cf); c1 = std::max(c1, cl);
+                if (cf == cl) { r0 = std::min(r0, (int)(s % (unsigned)h)); r1 = std::max(r1, (int)((t - 1) % (unsigned)h)); }
+                else { r0 = 0; r1 = h - 1; }                                      // a run that wraps covers the last and the first row
+            }
+            AMP_REQUIRE(pos == area, "amp_rle_overlap_groups: the runs of mask %d of pool %s (group %d) cover %llu pixels, the image has %llu",
+                        p, which, g, pos, area);
+            e.n = (int)(pl.S.size() - e.ro);
+            e.area = (unsigned int)ones;
+            if (e.n) { e.r0 = r0; e.c0 = c0; e.r1 = r1 + 1; e.c1 = c1 + 1; }
+            pl.S.push_back(0xffffffffu); pl.E.push_back(0xffffffffu); pl.P.push_back((uint32_t)ones);
+            AMP_REQUIRE(pl.S.size() < (1ull << 31), "amp_rle_overlap_groups: the masks of pool %s have more than 2^31 runs", which);
+        }
+    }
+    return AMP_OK;
+}
+
+int overlap_groups_check(const uint32_t* apool, const unsigned long long* aoff, const int* alen, const uint32_t* bpool,
+                         const unsigned long long* boff, const int* blen, const int* a_first, const int* b_first, const int* gh, const int* gw,
+                         int ngroups, const uint32_t* inter, size_t inter_cap, const unsigned long long* area_a, const unsigned long long* area_b,
+                         OvPlan& a, OvPlan& b) {
+    AMP_REQUIRE(ngroups >= 0, "amp_rle_overlap_groups: ngroups = %d", ngroups);
+    if (ngroups == 0) return AMP_OK;
+    AMP_REQUIRE(a_first && b_first && gh && gw, "amp_rle_overlap_groups: null argument");
+    AMP_REQUIRE(a_first[0] == 0 && b_first[0] == 0, "amp_rle_overlap_groups: a_first[0] = %d, b_first[0] = %d (group 0 starts at mask 0)",
+                a_first[0], b_first[0]);
+    unsigned long long total = 0;
+    for (int g = 0; g < ngroups; ++g) {
+        AMP_REQUIRE(a_first[g + 1] >= a_first[g], "amp_rle_overlap_groups: a_first[%d] = %d is below a_first[%d] = %d", g + 1, a_first[g + 1], g,
+                    a_first[g]);
+        AMP_REQUIRE(b_first[g + 1] >= b_first[g], "amp_rle_overlap_groups: b_first[%d] = %d is below b_first[%d] = %d", g + 1, b_first[g + 1], g,
+                    b_first[g]);
+        AMP_REQUIRE(gh[g] >= 1 && gw[g] >= 1 && gh[g] <= 32768 && gw[g] <= 32768 && (unsigned long long)gh[g] * gw[g] <= (1ull << 30),
+                    "amp_rle_overlap_groups: image size %d x %d of group %d (1 .. 32768 a side, at most 2^30 pixels)", gh[g], gw[g], g);
+        total += (unsigned long long)(a_first[g + 1] - a_first[g]) * (unsigned long long)(b_first[g + 1] - b_first[g]);
+    }
+    const int na = a_first[ngroups], nb = b_first[ngroups];
+    AMP_REQUIRE((na == 0 || (apool && aoff && alen && area_a)) && (nb == 0 || (bpool && boff && blen && area_b)) && (total == 0 || inter),
+                "amp_rle_overlap_groups: null argument");
+    AMP_REQUIRE(total <= inter_cap, "amp_rle_overlap_groups: inter_cap = %zu, the groups have %llu pairs", inter_cap, total);
+    AMP_TRY_STATUS(overlap_plan_pool("A", apool, aoff, alen, a_first, gh, gw, ngroups, a));
+    AMP_TRY_STATUS(overlap_plan_pool("B", bpool, boff, blen, b_first, gh, gw, ngroups, b));
+    return AMP_OK;
+}
+
+int overlap_groups_host(const OvPlan& a, const OvPlan& b, const int* a_first, const int* b_first, int ngroups, uint32_t* inter) {
+    size_t out = 0;
+    for (int g = 0; g < ngroups; ++g)
+        for (int i = a_first[g]; i < a_first[g + 1]; ++i) {
+            const OvMask& A = a.m[(size_t)i];
+            for (int j = b_first[g]; j < b_first[g + 1]; ++j, ++out) {
+                const OvMask& B = b.m[(size_t)j];
+                uint32_t sum = 0;
+                if (A.n && B.n && A.r0 < B.r1 && B.r0 < A.r1 && A.c0 < B.c1 && B.c0 < A.c1) {
+                    const uint32_t *as = &a.S[A.ro], *ae = &a.E[A.ro], *bs = &b.S[B.ro], *be = &b.E[B.ro];
+                    for (int p = 0, q = 0; p < A.n && q < B.n;) {
+                        const uint32_t lo = std::max(as[p], bs[q]), hi = std::min(ae[p], be[q]);
+                        if (hi > lo) sum += hi - lo;
+                        if (ae[p] <= be[q]) ++p; else ++q;
+                    }
+                }
+                inter[out] = sum;
+            }
+        }
+    return AMP_OK;
+}
+
+}  // namespace amp

@@ -245,6 +245,39 @@ def region_props(masks, ctx=None):
     return bbox, vals
 
 
+def overlap_groups(a_groups, b_groups, ctx=None):
+    """All-pairs intersection inside groups, one C call (amp_rle_overlap_groups): a_groups, b_groups are equally long lists of lists of RLE
+    dicts, group g = the masks of one image.  Returns (inters, areas_a, areas_b): lists of int64 arrays, inters[g][i, j] = the pixels of
+    a_groups[g][i] AND b_groups[g][j] ([na_g, nb_g]), areas_a[g][i] / areas_b[g][j] the pixels of each mask.  Pairs across groups are never
+    formed; a group without masks on one side has no image size of its own and gives empty arrays.  ctx: a _lib.Context (computed on its
+    device) or None (on the host): the same bytes."""
+    assert len(a_groups) == len(b_groups), "one list of B masks per list of A masks"
+    ng = len(a_groups)
+    na, nb = [len(x) for x in a_groups], [len(x) for x in b_groups]
+    gh, gw = np.ones(max(ng, 1), dtype=np.int32), np.ones(max(ng, 1), dtype=np.int32)
+    for g in range(ng):
+        sizes = {tuple(int(v) for v in r["size"]) for r in list(a_groups[g]) + list(b_groups[g])}
+        if len(sizes) > 1:
+            raise ValueError(f"overlap_groups: group {g} holds masks of different sizes {sorted(sizes)}")
+        if sizes:
+            gh[g], gw[g] = sizes.pop()
+    af, bf = np.zeros(ng + 1, dtype=np.int32), np.zeros(ng + 1, dtype=np.int32)
+    af[1:], bf[1:] = np.cumsum(na), np.cumsum(nb)
+    ap, ao, al = _pool([_counts(x) for grp in a_groups for x in grp])
+    bp, bo, bl = _pool([_counts(x) for grp in b_groups for x in grp])
+    first = np.zeros(ng + 1, dtype=np.int64)
+    first[1:] = np.cumsum(np.asarray(na, dtype=np.int64) * np.asarray(nb, dtype=np.int64))
+    total = int(first[-1])
+    inter = np.zeros(max(total, 1), dtype=np.uint32)
+    area_a, area_b = np.zeros(max(int(af[-1]), 1), dtype=np.uint64), np.zeros(max(int(bf[-1]), 1), dtype=np.uint64)
+    vp = lambda x: x.ctypes.data_as(C.c_void_p)
+    check(lib().amp_rle_overlap_groups(ctx.handle if ctx is not None else None, vp(ap), vp(ao), vp(al), vp(bp), vp(bo), vp(bl), vp(af), vp(bf),
+                                       vp(gh), vp(gw), ng, vp(inter), total, vp(area_a), vp(area_b)), "amp_rle_overlap_groups")
+    inters = [inter[int(first[g]): int(first[g + 1])].astype(np.int64).reshape(na[g], nb[g]) for g in range(ng)]
+    return (inters, [area_a[int(af[g]): int(af[g + 1])].astype(np.int64) for g in range(ng)],
+            [area_b[int(bf[g]): int(bf[g + 1])].astype(np.int64) for g in range(ng)])
+
+
 def merge(rles, intersect=False):
     assert len(rles) >= 1
     h, w = rles[0]["size"]

@@ -529,6 +529,22 @@ int amp_mask_edge_distance(amp_ctx* ctx, const uint32_t* gpool, const unsigned l
  * memory; integer arithmetic only, the bytes do not depend on the device's scheduling and equal the host's. */
 int amp_mask_region_props(amp_ctx* ctx, const uint32_t* pool, const unsigned long long* off, const int* len, int n, int h, int w,
                           long long* bbox /* [n][4] */, unsigned long long* vals /* [n][13] */);
+/* All-pairs mask intersection inside groups (ampis/applications/powder.py:80-83: every satellite of an image against every particle).  ALL
+ * POINTERS ARE HOST POINTERS.  Masks are run lists out of two pools (list i = pool[off[i] .. off[i] + len[i])).  Group g -- one image of
+ * gh[g] x gw[g] pixels, 1 .. 32768 a side and at most 2^30 pixels -- owns the masks a_first[g] .. a_first[g + 1] of pool A and b_first[g] ..
+ * b_first[g + 1] of pool B (a_first[0] = b_first[0] = 0, both non-decreasing); na_g, nb_g are their numbers.  The block of group g in `inter`
+ * starts at the sum of na_k nb_k over the groups before it, is row-major [na_g][nb_g] and holds the exact pixel count of a_i AND b_j; pairs
+ * across groups are never formed.  area_a / area_b receive the pixel count of every mask of pool A / B.  inter_cap: capacity of `inter` in
+ * values.  ngroups == 0, groups without masks on one side and masks without a set pixel (a row or column of zeros) are valid.  Everything is
+ * checked on the host first -- the image sizes, every run list non-empty and summing to its group's h * w, the order of a_first / b_first,
+ * inter_cap -- and refused with AMP_ERR_ARG naming the offending index: nothing written and never a device access.
+ * ctx == NULL: computed on the host (rle_host.hip).  Otherwise on ctx's device and stream (rle_overlap.hip): the function uploads, runs one
+ * launch whatever the number of groups, downloads and returns with the results in host memory; integer arithmetic only, every output word
+ * written once, the bytes do not depend on the device's scheduling and equal the host's. */
+int amp_rle_overlap_groups(amp_ctx* ctx, const uint32_t* apool, const unsigned long long* aoff, const int* alen, const uint32_t* bpool,
+                           const unsigned long long* boff, const int* blen, const int* a_first /* [ngroups + 1] */,
+                           const int* b_first /* [ngroups + 1] */, const int* gh, const int* gw /* [ngroups] */, int ngroups, uint32_t* inter,
+                           size_t inter_cap, unsigned long long* area_a, unsigned long long* area_b);
 /* Nearest-neighbour resize (+ horizontal mirror when flip) of a mask in the run-length domain: the runs of
  * flip(PIL.Image.resize(decode(cnts), (nw, nh), NEAREST)) -- what detectron2's ResizeTransform.apply_segmentation + HFlipTransform do to a bitmask
  * annotation -- without decoding (Pillow's ImagingScaleAffine pixel correspondence, restated).  cap >= nh * nw + 1 is always enough. */
