@@ -29,7 +29,7 @@ The independent checker is oracle/matcher.py (a loop-for-loop restatement of the
 import numpy as np
 
 from . import rle
-from .structures import BitMasks, PolygonMasks, RLEBitMasks
+from .structures import BitMasks, Instances, InstanceSet, PolygonMasks, RLEBitMasks, RLEMasks
 
 
 def masks_to_rle(masks, size=None):
@@ -326,3 +326,146 @@ def mask_areas(masks):
     if isinstance(masks, (list, tuple)):
         return [mask_areas(x) for x in masks]
     raise NotImplementedError(f"Not implemented for type {type(masks)}")
+
+
+# ---- detection / segmentation performance overlays (ampis/analyze.py:19-51, 502-699; ampis/structures.py:717-774) ------------------------------
+
+def align_instance_sets(a, b):
+    """Lists of instance sets a, b -> (a_ordered, b_ordered): the items of `a` whose file NAME (the last part of .filepath) some item of `b`
+    carries, in the order of `a`, and beside each the item of `b` of that name (ampis/analyze.py:19-51).  Items of either list without a partner
+    are left out -- the tutorial uses exactly that to drop images labelled in one dataset only --; of several items of `b` with one name the
+    last is taken."""
+    from pathlib import Path
+    by_name = {Path(item.filepath).name: item for item in b}
+    a_ordered, b_ordered = [], []
+    for item in a:
+        x = by_name.get(Path(item.filepath).name, None)
+        if x is not None:
+            a_ordered.append(item)
+            b_ordered.append(x)
+    return a_ordered, b_ordered
+
+
+def _unwrap_masks(obj, size):
+    """(masks, size) of an InstanceSet-like (.instances), an Instances-like (.masks, .image_size) or the masks themselves"""
+    if hasattr(obj, "instances") and obj.instances is not None:
+        obj = obj.instances
+    if hasattr(obj, "masks") and hasattr(obj, "image_size"):
+        return obj.masks, (tuple(int(v) for v in obj.image_size) if size is None else size)
+    return obj, size
+
+
+def _image_size(who, rles, size):
+    sizes = {tuple(int(v) for v in r["size"]) for r in rles}
+    if size is not None:
+        sizes.add(tuple(int(v) for v in size))
+    if len(sizes) > 1:
+        raise ValueError(f"{who}: masks of different sizes {sorted(sizes)}")
+    if not sizes:
+        raise ValueError(f"{who}: size=(height, width) is required when there is no mask to take it from")
+    return sizes.pop()
+
+
+def masks_to_bitmask_array(masks, size=None):
+    """Any of the mask forms -> bool ndarray [N, H, W] (ampis/structures.py:717-774): the decode for callers that really want the dense array.
+    masks: a bool ndarray (returned as it is), anything masks_to_rle accepts (size=(h, w) for polygons), an Instances or an InstanceSet.  Polygons
+    are rasterised like everywhere in this module (masks_to_rle), not by skimage.  Nothing in this package calls it."""
+    if isinstance(masks, np.ndarray):
+        assert masks.dtype == bool, "a mask array must be boolean"
+        return masks
+    m, size = _unwrap_masks(masks, size)
+    rles = masks_to_rle(m, size)
+    h, w = _image_size("masks_to_bitmask_array", rles, size)
+    if not rles:
+        return np.zeros((0, h, w), dtype=bool)
+    return np.stack([rle.decode(r).astype(bool) for r in rles])
+
+
+SEG_LABELS = {"reduced": ["TP", "FN", "FP", "other"],                                             # ampis/analyze.py:675, 689: the 'all' list names
+              "all": ["Other", "TP", "FN", "TP+FN", "FP", "TP+FP", "FN+FP", "TP+FN+FP"]}          # code 0 as well, one more than the classes
+SEG_COLORS = {"reduced": [[0.5, 0., 1.], [1., 0., 0.], [0., 1., 1.], [1., 1., 0.]],               # ampis/analyze.py:664-672, 685-688
+              "all": [[0.153, 0.153, 0.000], [0.286, 1., 0.], [1., 0.857, 0.], [1., 0., 0.], [0., 0.571, 1.], [0., 1., 0.571], [0.285, 0., 1.]]}
+
+
+def seg_class_map(gt, pred, match_results=None, mode='reduced', size=None, device='auto'):
+    """Every pixel of the image classed by the matched pairs (the computation of ampis/analyze.py:626-692): for the pairs match_results['tp']
+    TP = OR (g & p), FN = OR (g & ~p), FP = OR (~g & p), code = TP + 2 FN + 4 FP.  mode 'reduced': the classes TP only, FN only, FP only and
+    'other' (more than one of them); 'all': the seven codes 1 .. 7.  Returns {'masks': K RLE dicts over the whole image, 'labels', 'colors'
+    ([K, 3], the reference's tables), 'pixel_counts': int64 [8] pixels of every code, 'match_results'}.
+
+    gt, pred: anything masks_to_rle accepts (size=(h, w) for polygons and for two empty sides), an Instances or an InstanceSet; match_results:
+    the dict of rle_instance_matcher, None to call it at the default threshold; device: 'cpu' (host), 'cuda' (HIP device, an error without one)
+    or 'auto' (the device when one is visible).  One amp_seg_class_map call on the run lists (csrc/seg_class_map.hip, or rle_host.hip on the
+    host: identical bytes); no mask is decoded.  ValueError for an unknown mode or device and for masks of different sizes."""
+    mode = str(mode).lower()
+    if mode not in SEG_LABELS:
+        raise ValueError(f"seg_class_map: mode = {mode!r} ('reduced' or 'all')")
+    gm, size = _unwrap_masks(gt, size)
+    pm, size = _unwrap_masks(pred, size)
+    g, p = masks_to_rle(gm, size), masks_to_rle(pm, size)
+    h, w = _image_size("seg_class_map", g + p, size)
+    if match_results is None:
+        match_results = match_instances(iou_matrix(g, p), 0.5)
+    pairs = np.asarray(match_results["tp"], dtype=np.int64).reshape(-1, 2)
+    for i, (a, b) in enumerate(pairs.tolist()):
+        if not (0 <= a < len(g) and 0 <= b < len(p)):
+            raise ValueError(f"seg_class_map: match_results['tp'][{i}] = ({a}, {b}) is outside the {len(g)} ground-truth and {len(p)} predicted masks")
+    ctx = _device_context("seg_class_map", device, len(pairs))
+    counts, pixels = rle.seg_class_map(g, p, pairs, mode, ctx=ctx, size=(h, w))
+    return {"masks": [{"size": [h, w], "counts": rle.counts_to_string(c)} for c in counts], "labels": list(SEG_LABELS[mode]),
+            "colors": np.array(SEG_COLORS[mode]), "pixel_counts": pixels, "match_results": match_results}
+
+
+def seg_perf_iset(gt_masks, pred_masks, match_results=None, mode='reduced', size=None, device='auto'):
+    """ampis/analyze.py:589-699 with its arguments and its return: (iset, [colors, labels]) -- an InstanceSet whose instances hold the class masks
+    of seg_class_map ('masks': RLEMasks, 'colors', 'boxes': zeros [K, 4]) for visualize.display_iset, and the colour table and labels of the
+    mode.  size, device: as seg_class_map.  Departures from the reference are listed in DESIGN 7g."""
+    r = seg_class_map(gt_masks, pred_masks, match_results, mode, size, device)
+    masks = RLEMasks(r["masks"])
+    colors = [r["colors"], r["labels"]]
+    iset = InstanceSet()
+    iset.instances = Instances(image_size=masks.rle[0]["size"], **{"masks": masks, "colors": colors[0], "boxes": np.zeros((len(masks), 4))})
+    return iset, colors
+
+
+def _xyxy_boxes(inst, rles):
+    """[N, 4] boxes of an Instances-like (its `boxes` field, an ndarray or a Boxes) or, without one, the tight XYXY boxes of the run lists"""
+    if inst is not None and hasattr(inst, "boxes"):
+        b = inst.boxes
+        return b if type(b) == np.ndarray else b.tensor.numpy()
+    tight = [rle.bbox(m) for m in rles]
+    return np.array([(0, 0, 0, 0) if b is None else b for b in tight], dtype=np.float64).reshape(-1, 4)
+
+
+def det_perf_iset(gt, pred, match_results=None, colormap=None, tp_gt=False, size=None):
+    """ampis/analyze.py:502-586 with its arguments and its return convention: an InstanceSet of the true-positive, false-positive and false-negative
+    INSTANCES in that order ('masks': RLEMasks, 'boxes', 'colors': the class colour tiled per instance) for visualize.display_iset; returned as
+    (iset, colormap) when `colormap` is None -- the default {'TP', 'FP', 'FN'} table -- and alone when the caller gave one.  True positives are
+    shown by their predicted mask and box, by the ground truth's with tp_gt.  gt, pred: InstanceSets or Instances (masks, boxes, image size) or
+    anything masks_to_rle accepts (the boxes are then the tight boxes of the masks; size=(h, w) for polygons)."""
+    gi = gt.instances if hasattr(gt, "instances") else (gt if hasattr(gt, "masks") and hasattr(gt, "image_size") else None)
+    pi = pred.instances if hasattr(pred, "instances") else (pred if hasattr(pred, "masks") and hasattr(pred, "image_size") else None)
+    gm, size = _unwrap_masks(gt, size)
+    pm, size = _unwrap_masks(pred, size)
+    gt_masks, pred_masks = masks_to_rle(gm, size), masks_to_rle(pm, size)
+    h, w = _image_size("det_perf_iset", gt_masks + pred_masks, size)
+    if match_results is None:
+        match_results = match_instances(iou_matrix(gt_masks, pred_masks), 0.5)
+    return_colormap = colormap is None
+    gt_bbox, pred_bbox = _xyxy_boxes(gi, gt_masks), _xyxy_boxes(pi, pred_masks)
+    if colormap is None:
+        colormap = {"TP": np.asarray([0.5, 0., 1.], float), "FP": np.asarray([0., 1., 1.], float), "FN": np.asarray([1., 0., 0.], float)}
+    tp = np.asarray(match_results["tp"], dtype=np.int64).reshape(-1, 2)
+    tp_idx = tp[:, 0] if tp_gt else tp[:, 1]
+    tp_src, tp_box = (gt_masks, gt_bbox) if tp_gt else (pred_masks, pred_bbox)
+    fp_idx, fn_idx = np.asarray(match_results["fp"], dtype=np.int64).reshape(-1), np.asarray(match_results["fn"], dtype=np.int64).reshape(-1)
+    parts = [([tp_src[i] for i in tp_idx], tp_box[tp_idx], colormap["TP"]), ([pred_masks[i] for i in fp_idx], pred_bbox[fp_idx], colormap["FP"]),
+             ([gt_masks[i] for i in fn_idx], gt_bbox[fn_idx], colormap["FN"])]
+    masks = RLEMasks([m for part in parts for m in part[0]])
+    bbox = np.concatenate([part[1] for part in parts], axis=0)
+    colors = np.concatenate([np.tile(part[2], (len(part[0]), 1)) for part in parts], axis=0)
+    iset = InstanceSet()
+    iset.instances = Instances(image_size=[h, w], **{"masks": masks, "boxes": bbox, "colors": colors})
+    if return_colormap:
+        return iset, colormap
+    return iset

@@ -305,6 +305,15 @@ int overlap_groups_check(const uint32_t* apool, const unsigned long long* aoff, 
                          int ngroups, const uint32_t* inter, size_t inter_cap, const unsigned long long* area_a, const unsigned long long* area_b,
                          OvPlan& a, OvPlan& b);
 int overlap_groups_host(const OvPlan& a, const OvPlan& b, const int* a_first, const int* b_first, int ngroups, uint32_t* inter);
+// rle_host.hip: amp_seg_class_map's argument checks, which also build the plan both paths evaluate (an OvPlan per pool, with entries for the masks
+// the pairs name and n = -1 for the others, which are never read) and the sufficient counts capacity `need`, and its host evaluation;
+// seg_class_map.hip holds the entry point and the device evaluation, seg_class_map.h the word arithmetic both use
+int seg_class_map_check(const uint32_t* gpool, const unsigned long long* goff, const int* glen, int ng, const uint32_t* ppool,
+                        const unsigned long long* poff, const int* plen, int np, const int* pair_g, const int* pair_p, int n, int h, int w,
+                        int mode, const uint32_t* counts, unsigned long long counts_cap, const unsigned long long* counts_off,
+                        const unsigned long long* pixels, OvPlan& g, OvPlan& p, unsigned long long* need);
+int seg_class_map_host(const OvPlan& g, const OvPlan& p, const int* pair_g, const int* pair_p, int n, int h, int w, int mode, uint32_t* counts,
+                       unsigned long long* counts_off, unsigned long long* pixels);
 int roi_align_run(amp_ctx* ctx, const amp_fpn_feats* f, const float* rois, const int* batch_idx, const int* roi_count, int R, int P,
                   float* out, int* level_out, int out_split, int in_split = 0);   // out_split / in_split = 1: pooled tensor / feature maps in the split row format
 int box_candidates_run(amp_ctx* ctx, const float* pred, int ld, const float* proposals, const int* prop_count, int B, int Rcap, int K,

@@ -12,6 +12,7 @@
 
 #include "common.h"
 #include "region_props.h"
+#include "seg_class_map.h"
 
 extern "C" {
 
@@ -783,6 +784,148 @@ int overlap_groups_host(const OvPlan& a, const OvPlan& b, const int* a_first, co
                 inter[out] = sum;
             }
         }
+    return AMP_OK;
+}
+
+}  // namespace amp
+
+// ---- segmentation class map (ampis/analyze.py:589-699, seg_perf_iset): argument checks that also build the plan (common.h OvPlan, entries for
+// the masks the pairs name), shared with the device path, and the host evaluation.  TP = OR over the pairs of g & q, FN of g & ~q, FP of
+// ~g & q as three column-major bit planes of the image (64 rows a word), painted from the runs of every pair by one walk over both lists; the
+// classes of the mode and their run lists then come from the plane words (seg_class_map.h: the same word arithmetic as the kernels of
+// seg_class_map.hip).  Memory: three planes of h * w bits and the result, whatever the number of pairs.
+namespace amp {
+
+static int seg_plan_mask(const char* which, int pair, int idx, const uint32_t* c, int len, int h, int w, OvPlan& pl, unsigned long long& bounds) {
+    AMP_REQUIRE(len > 0, "amp_seg_class_map: pair %d names %s mask %d, which has an empty run list", pair, which, idx);
+    const unsigned long long area = (unsigned long long)h * w;
+    OvMask& e = pl.m[(size_t)idx];
+    e = OvMask{(unsigned int)pl.S.size(), 0, 0, 0, 0, 0, 0};
+    unsigned long long pos = 0, ones = 0;
+    int r0 = h, r1 = -1, c0 = w, c1 = -1;
+    for (int j = 0; j < len; ++j) {
+        const unsigned long long s = pos, t = pos + c[j];
+        pos = t;
+        AMP_REQUIRE(t <= area, "amp_seg_class_map: the runs of %s mask %d (pair %d) cover more than the image's %llu pixels", which, idx, pair, area);
+        if (!(j & 1) || t == s) continue;
+        pl.S.push_back((uint32_t)s); pl.E.push_back((uint32_t)t); pl.P.push_back((uint32_t)ones);
+        ones += t - s;
+        const int cf = (int)(s / (unsigned)h), cl = (int)((t - 1) / (unsigned)h);
+        c0 = std::min(c0, cf); c1 = std::max(c1, cl);
+        if (cf == cl) { r0 = std::min(r0, (int)(s % (unsigned)h)); r1 = std::max(r1, (int)((t - 1) % (unsigned)h)); }
+        else { r0 = 0; r1 = h - 1; }                                              // a run that wraps covers the last and the first row
+    }
+    AMP_REQUIRE(pos == area, "amp_seg_class_map: the runs of %s mask %d (pair %d) cover %llu pixels, the image has %llu", which, idx, pair, pos, area);
+    e.n = (int)(pl.S.size() - e.ro);
+    e.area = (unsigned int)ones;
+    if (e.n) { e.r0 = r0; e.c0 = c0; e.r1 = r1 + 1; e.c1 = c1 + 1; }
+    pl.S.push_back(0xffffffffu); pl.E.push_back(0xffffffffu); pl.P.push_back((uint32_t)ones);
+    AMP_REQUIRE(pl.S.size() < (1ull << 31), "amp_seg_class_map: the %s masks of the pairs have more than 2^31 runs", which);
+    bounds += (unsigned long long)(len - 1);
+    return AMP_OK;
+}
+
+int seg_class_map_check(const uint32_t* gpool, const unsigned long long* goff, const int* glen, int ng, const uint32_t* ppool,
+                        const unsigned long long* poff, const int* plen, int np, const int* pair_g, const int* pair_p, int n, int h, int w,
+                        int mode, const uint32_t* counts, unsigned long long counts_cap, const unsigned long long* counts_off,
+                        const unsigned long long* pixels, OvPlan& g, OvPlan& p, unsigned long long* need) {
+    AMP_REQUIRE(n >= 0 && ng >= 0 && np >= 0, "amp_seg_class_map: n = %d, ng = %d, np = %d", n, ng, np);
+    AMP_REQUIRE(mode == 0 || mode == 1, "amp_seg_class_map: mode = %d (0 reduced, 1 all)", mode);
+    AMP_REQUIRE(counts && counts_off && pixels, "amp_seg_class_map: null argument");
+    AMP_REQUIRE(n == 0 || (gpool && goff && glen && ppool && poff && plen && pair_g && pair_p), "amp_seg_class_map: null argument");
+    AMP_REQUIRE(h >= 1 && w >= 1 && h <= 32768 && w <= 32768 && (unsigned long long)h * w <= (1ull << 30),
+                "amp_seg_class_map: image size %d x %d (1 .. 32768 a side, at most 2^30 pixels)", h, w);
+    g.m.assign((size_t)ng, OvMask{0, -1, 0, 0, 0, 0, 0});                         // n = -1: not named by any pair, never read
+    p.m.assign((size_t)np, OvMask{0, -1, 0, 0, 0, 0, 0});
+    unsigned long long bounds = 0;                                               // every boundary of a class is a boundary of a named run list
+    for (int i = 0; i < n; ++i) {
+        const int a = pair_g[i], b = pair_p[i];
+        AMP_REQUIRE(a >= 0 && a < ng && b >= 0 && b < np, "amp_seg_class_map: pair %d = (%d, %d) outside %d x %d masks", i, a, b, ng, np);
+        if (g.m[(size_t)a].n < 0) AMP_TRY_STATUS(seg_plan_mask("ground-truth", i, a, gpool + goff[a], glen[a], h, w, g, bounds));
+        if (p.m[(size_t)b].n < 0) AMP_TRY_STATUS(seg_plan_mask("predicted", i, b, ppool + poff[b], plen[b], h, w, p, bounds));
+    }
+    *need = (unsigned long long)sc_classes(mode) * (bounds + 1);
+    if (counts_cap < *need) {
+        set_error("amp_seg_class_map: counts_cap = %llu, %llu are needed (classes x (1 + the run boundaries of the masks the pairs name))",
+                  counts_cap, *need);
+        return AMP_ERR_NOMEM;
+    }
+    return AMP_OK;
+}
+
+// pixels [s, e) of the column-major image into a plane
+static void sc_paint(sc_u64* plane, unsigned int s, unsigned int e, int h, int pitch) {
+    for (unsigned int col = s / (unsigned)h; col <= (e - 1) / (unsigned)h; ++col) {
+        const unsigned int cb = col * (unsigned)h;
+        const int ya = (int)(std::max(s, cb) - cb), yb = (int)(std::min(e, cb + (unsigned)h) - cb);
+        sc_u64* pc = plane + (size_t)col * pitch;
+        for (int wv = ya >> 6; wv <= (yb - 1) >> 6; ++wv) {
+            const int lo = std::max(ya - (wv << 6), 0), hi = std::min(yb - (wv << 6), 64);
+            pc[wv] |= (hi == 64 ? ~0ull : ((1ull << hi) - 1ull)) & ~((1ull << lo) - 1ull);
+        }
+    }
+}
+
+// every run of A cut by the runs of B: the parts inside B into `in` (or nowhere), the parts outside into `out`
+static void sc_split(const OvPlan& pa, const OvMask& A, const OvPlan& pb, const OvMask& B, sc_u64* in, sc_u64* out, int h, int pitch) {
+    const uint32_t *as = &pa.S[A.ro], *ae = &pa.E[A.ro], *bs = &pb.S[B.ro], *be = &pb.E[B.ro];
+    int k = 0;
+    for (int i = 0; i < A.n; ++i) {
+        unsigned int pos = as[i];
+        const unsigned int e = ae[i];
+        while (k < B.n && be[k] <= pos) ++k;
+        while (pos < e) {
+            if (k < B.n && bs[k] < e) {
+                const unsigned int lo = std::max(bs[k], pos), hi = std::min(be[k], e);
+                if (lo > pos) sc_paint(out, pos, lo, h, pitch);
+                if (in) sc_paint(in, lo, hi, h, pitch);
+                pos = hi;
+                if (be[k] <= e) ++k;
+            } else {
+                sc_paint(out, pos, e, h, pitch);
+                pos = e;
+            }
+        }
+    }
+}
+
+int seg_class_map_host(const OvPlan& g, const OvPlan& p, const int* pair_g, const int* pair_p, int n, int h, int w, int mode, uint32_t* counts,
+                       unsigned long long* counts_off, unsigned long long* pixels) {
+    const int pitch = (h + 63) >> 6, K = sc_classes(mode);
+    const size_t units = (size_t)w * pitch;
+    std::vector<sc_u64> planes(3 * units, 0ull);
+    sc_u64 *TP = planes.data(), *FN = TP + units, *FP = FN + units;
+    for (int i = 0; i < n; ++i) {
+        const OvMask& G = g.m[(size_t)pair_g[i]];
+        const OvMask& Q = p.m[(size_t)pair_p[i]];
+        sc_split(g, G, p, Q, TP, FN, h, pitch);
+        sc_split(p, Q, g, G, nullptr, FP, h, pitch);
+    }
+    std::vector<uint32_t> bnd[7];
+    unsigned long long px[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int col = 0; col < w; ++col)
+        for (int wv = 0; wv < pitch; ++wv) {
+            const size_t u = (size_t)col * pitch + wv;
+            const sc_u64 valid = sc_valid(h, wv), tp = TP[u], fn = FN[u], fp = FP[u];
+            for (int c = 0; c < 8; ++c) px[c] += (unsigned)sc_popc(sc_code_word(tp, fn, fp, c) & valid);
+            const int pb = sc_prev_bit(h, wv);
+            const sc_u64 qt = u ? TP[u - 1] >> pb : 0ull, qf = u ? FN[u - 1] >> pb : 0ull, qp = u ? FP[u - 1] >> pb : 0ull;
+            const uint32_t base = (uint32_t)col * (uint32_t)h + ((uint32_t)wv << 6);
+            for (int k = 0; k < K; ++k) {
+                sc_u64 t = sc_transitions(sc_class_word(tp, fn, fp, mode, k) & valid, sc_class_word(qt & 1ull, qf & 1ull, qp & 1ull, mode, k), valid);
+                for (; t; t &= t - 1) bnd[k].push_back(base + (uint32_t)sc_ctz(t));
+            }
+        }
+    unsigned long long o = 0;
+    const uint32_t area = (uint32_t)((unsigned long long)h * w);
+    for (int k = 0; k < K; ++k) {
+        counts_off[k] = o;
+        uint32_t prev = 0;
+        for (uint32_t b : bnd[k]) { counts[o++] = b - prev; prev = b; }
+        counts[o++] = area - prev;
+    }
+    counts_off[K] = o;
+    std::copy(px, px + 8, pixels);
     return AMP_OK;
 }
 

@@ -278,6 +278,44 @@ def overlap_groups(a_groups, b_groups, ctx=None):
             [area_b[int(bf[g]): int(bf[g + 1])].astype(np.int64) for g in range(ng)])
 
 
+def seg_class_map(gt, pred, pairs, mode, ctx=None, size=None):
+    """Pixel classes of one image from matched pairs, one C call (amp_seg_class_map): for index pairs (g, p), TP = OR (gt[g] & pred[p]),
+    FN = OR (gt[g] & ~pred[p]), FP = OR (~gt[g] & pred[p]) and code = TP + 2 FN + 4 FP.  mode 'all' (or 1): the 7 classes code == 1 .. 7;
+    'reduced' (or 0): the 4 classes code == 1, 2, 4 and code in {3, 5, 6, 7}.  Returns (class_counts, pixel_counts): a list of K uint32 run lists
+    over the whole image (column-major, COCO order) and an int64 [8] array of the pixels of every code.  size=(h, w): the image size when there
+    is no pair to take it from.  ctx: a _lib.Context (computed on its device) or None (on the host): the same bytes."""
+    m = {"reduced": 0, "all": 1, 0: 0, 1: 1}.get(mode if not isinstance(mode, str) else mode.lower())
+    if m is None:
+        raise ValueError(f"seg_class_map: mode = {mode!r} ('reduced' or 'all')")
+    K = 7 if m else 4
+    pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+    n = len(pairs)
+    if n:
+        assert pairs.min() >= 0 and pairs[:, 0].max() < len(gt) and pairs[:, 1].max() < len(pred)
+        h, w = (int(v) for v in gt[int(pairs[0, 0])]["size"])
+    else:
+        assert size is not None, "size=(height, width) is required when there is no pair"
+        h, w = (int(v) for v in size)
+    named_g, named_p = sorted(set(pairs[:, 0].tolist())), sorted(set(pairs[:, 1].tolist()))
+    empty = np.zeros(0, np.uint32)                                  # masks no pair names are never read: they need not even be decoded
+    gc = [empty] * len(gt)
+    pc = [empty] * len(pred)
+    for i in named_g:
+        gc[i] = _counts(gt[i])
+    for i in named_p:
+        pc[i] = _counts(pred[i])
+    gp, go, gl = _pool(gc)
+    pp, po, pl = _pool(pc)
+    pg, pq = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
+    cap = K * (1 + sum(len(gc[i]) - 1 for i in named_g) + sum(len(pc[i]) - 1 for i in named_p))      # what amp_seg_class_map asks for
+    counts = np.empty(max(cap, K), dtype=np.uint32)
+    coff, pixels = np.zeros(K + 1, dtype=np.uint64), np.zeros(8, dtype=np.uint64)
+    vp = lambda x: x.ctypes.data_as(C.c_void_p)
+    check(lib().amp_seg_class_map(ctx.handle if ctx is not None else None, vp(gp), vp(go), vp(gl), len(gc), vp(pp), vp(po), vp(pl), len(pc),
+                                  vp(pg), vp(pq), n, h, w, m, vp(counts), len(counts), vp(coff), vp(pixels)), "amp_seg_class_map")
+    return [counts[int(coff[k]): int(coff[k + 1])].copy() for k in range(K)], pixels.astype(np.int64)
+
+
 def merge(rles, intersect=False):
     assert len(rles) >= 1
     h, w = rles[0]["size"]

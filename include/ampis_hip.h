@@ -545,6 +545,25 @@ int amp_rle_overlap_groups(amp_ctx* ctx, const uint32_t* apool, const unsigned l
                            const unsigned long long* boff, const int* blen, const int* a_first /* [ngroups + 1] */,
                            const int* b_first /* [ngroups + 1] */, const int* gh, const int* gw /* [ngroups] */, int ngroups, uint32_t* inter,
                            size_t inter_cap, unsigned long long* area_a, unsigned long long* area_b);
+/* Segmentation class map (ampis/analyze.py:589-699, seg_perf_iset): the pixels of one h x w image classed by what the matched pairs say of
+ * them.  ALL POINTERS ARE HOST POINTERS.  Masks are run lists out of two pools (list i = pool[off[i] .. off[i] + len[i])); for pair p, g is the
+ * ground-truth mask pair_g[p] and q the predicted mask pair_p[p].  TP = OR_p (g & q), FN = OR_p (g & ~q), FP = OR_p (~g & q), and
+ * code = TP + 2 FN + 4 FP.  mode 1 ('all'): K = 7 classes, class k - 1 is code == k.  mode 0 ('reduced'): K = 4, the classes are code == 1,
+ * code == 2, code == 4 and code in {3, 5, 6, 7}.  Each class comes back as a COCO run list over the whole image (column-major, the first count is
+ * the run of zeros and may be 0): class k is counts[counts_off[k] .. counts_off[k + 1]).  pixels[c] = the pixels of code c, all 8 codes in both
+ * modes.  A mask or a pair may be named any number of times; n == 0 is valid (every class is the one run h * w); masks no pair names are never
+ * read.  1 <= h, w <= 32768 and h * w <= 2^30.
+ * Everything is checked on the host first -- mode, the image size, the pair indices, every NAMED run list non-empty and summing to h * w,
+ * counts_cap -- and refused with AMP_ERR_ARG naming the offending index, or AMP_ERR_NOMEM naming the capacity needed: nothing written and never
+ * a device access.  The capacity that is always enough, and the one that is asked for, is K x (1 + the sum of len - 1 over the distinct named
+ * run lists): a class changes only where a named mask does.
+ * ctx == NULL: computed on the host (rle_host.hip).  Otherwise on ctx's device and stream (seg_class_map.hip): the function uploads, runs five
+ * launches whatever n is, downloads and returns with the results in host memory; integer arithmetic only, the bytes do not depend on the
+ * device's scheduling and equal the host's.  Memory: three bit planes of the image and the result, nothing proportional to n x h x w. */
+int amp_seg_class_map(amp_ctx* ctx, const uint32_t* gpool, const unsigned long long* goff, const int* glen, int ng, const uint32_t* ppool,
+                      const unsigned long long* poff, const int* plen, int np, const int* pair_g, const int* pair_p, int n, int h, int w,
+                      int mode /* 0 reduced, 1 all */, uint32_t* counts, unsigned long long counts_cap,
+                      unsigned long long* counts_off /* [K + 1] */, unsigned long long* pixels /* [8] */);
 /* Nearest-neighbour resize (+ horizontal mirror when flip) of a mask in the run-length domain: the runs of
  * flip(PIL.Image.resize(decode(cnts), (nw, nh), NEAREST)) -- what detectron2's ResizeTransform.apply_segmentation + HFlipTransform do to a bitmask
  * annotation -- without decoding (Pillow's ImagingScaleAffine pixel correspondence, restated).  cap >= nh * nw + 1 is always enough. */
