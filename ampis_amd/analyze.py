@@ -114,19 +114,29 @@ def _index_boxes(boxes, masks, name):
     return out
 
 
-_edge_ctx = {}
+_device_ctx = {}
 
 
-def _edge_context(who="mask_edge_distance"):
+def _current_device_context(who):
     """The context of the device path: one per HIP device, with a stream of its own (the call uploads, computes and downloads by itself)."""
     import torch
     from . import _lib
     if not torch.cuda.is_available():
         raise _lib.AmpError(f"{who}(device='cuda'): no HIP device is visible (device='cpu' computes on the host)")
     dev = torch.cuda.current_device()
-    if dev not in _edge_ctx:
-        _edge_ctx[dev] = _lib.Context(dev)
-    return _edge_ctx[dev]
+    if dev not in _device_ctx:
+        _device_ctx[dev] = _lib.Context(dev)
+    return _device_ctx[dev]
+
+
+def _device_context(who, device, work):
+    """The context of `device` for function `who`: None for the host -- 'cpu', or 'auto' with no visible device or nothing to do (`work`
+    false) --, the current device's context for 'cuda' (an error without one) and for 'auto' otherwise.  ValueError for any other value."""
+    import torch
+    dev = str(device).lower()
+    if dev not in ("auto", "cpu", "cuda"):
+        raise ValueError(f"{who}: device = {device!r} ('auto', 'cpu' or 'cuda')")
+    return _current_device_context(who) if dev == "cuda" or (dev == "auto" and work and torch.cuda.is_available()) else None
 
 
 def mask_edge_distance(gt_mask, pred_mask, gt_box, pred_box, matches, device='auto', squared=False, size=None):
@@ -140,9 +150,6 @@ def mask_edge_distance(gt_mask, pred_mask, gt_box, pred_box, matches, device='au
     different sizes, and a pair with disagreeing pixels whose other mask has no pixel in the box (the reference fails there too)."""
     import torch
     gt, pred = masks_to_rle(gt_mask, size), masks_to_rle(pred_mask, size)
-    dev = str(device).lower()
-    if dev not in ("auto", "cpu", "cuda"):
-        raise ValueError(f"mask_edge_distance: device = {device!r} ('auto', 'cpu' or 'cuda')")
     m = np.asarray(matches)
     if m.size and (m.ndim != 2 or m.shape[1] != 2 or not np.issubdtype(m.dtype, np.integer)):
         raise ValueError(f"mask_edge_distance: matches must be an [n, 2] integer array of (gt, pred) indices, got shape {m.shape} {m.dtype}")
@@ -160,7 +167,7 @@ def mask_edge_distance(gt_mask, pred_mask, gt_box, pred_box, matches, device='au
         raise ValueError(f"mask_edge_distance: pred_box has {len(pb)} boxes, matches name predicted mask {int(m[:, 1].max())}")
     boxes = np.array([merge_boxes(gb[g], pb[p]) for g, p in m.tolist()], dtype=np.int64).reshape(-1, 4)
     boxes = np.minimum(boxes, 1 << 30)                            # beyond any image: the slice ends at the image's border
-    ctx = _edge_context() if dev == "cuda" or (dev == "auto" and len(m) and torch.cuda.is_available()) else None
+    ctx = _device_context("mask_edge_distance", device, len(m))
     fp, fn = rle.edge_distance(gt, pred, m, boxes, ctx=ctx)
     if squared:
         conv = lambda d: torch.from_numpy(d.astype(np.int64))
@@ -223,23 +230,19 @@ def region_properties(masks, keys=None, size=None, device='auto'):
 
     masks: anything masks_to_rle accepts (size=(h, w) for polygons); keys: any of RPROPS_KEYS, None for the reference's default list; device:
     'cpu' (host), 'cuda' (HIP device, an error without one) or 'auto' (the device when one is visible).  One amp_mask_region_props call returns
-    13 exact integers per mask (csrc/region_props.hip, or rle_host.hip on the host); region_floats derives the floats from them for both
+    13 exact integers per mask (csrc/region_props.hip, or mask_analysis_host.hip on the host); region_floats derives the floats from them for both
     paths, so they agree bit for bit.  An empty mask: area, perimeter, convex_area, equivalent_diameter 0, bbox (0, 0, 0, 0), NaN elsewhere.
 
     UNPINNED PARITY: skimage is not part of this environment and the reference stores no region-property output, so no vector of the reference's
     pins this function.  The definitions are skimage's regionprops (rc coordinates, 0.16 and later) restated in DESIGN §7e; the tests hold
     the integers to an independent scipy / brute-force evaluation of those definitions and the floats to their exact-rational value.
     ValueError for an unknown key (before any device work), a bad `device`, masks of different sizes."""
-    import torch
     cols = _rprops_columns(keys)
-    dev = str(device).lower()
-    if dev not in ("auto", "cpu", "cuda"):
-        raise ValueError(f"region_properties: device = {device!r} ('auto', 'cpu' or 'cuda')")
     rles = masks_to_rle(masks, size)
     sizes = {tuple(int(v) for v in r["size"]) for r in rles}
     if len(sizes) > 1:
         raise ValueError(f"region_properties: masks of different sizes {sorted(sizes)}")
-    ctx = _edge_context("region_properties") if dev == "cuda" or (dev == "auto" and len(rles) and torch.cuda.is_available()) else None
+    ctx = _device_context("region_properties", device, len(rles))
     bbox, vals = rle.region_props(rles, ctx=ctx)
     rows = [region_floats(b, v) for b, v in zip(bbox.tolist(), vals.tolist())]
     ints = ("area", "bbox_area", "convex_area", "bbox-0", "bbox-1", "bbox-2", "bbox-3")
@@ -274,16 +277,6 @@ def regionprops_table(label_image, properties=RPROPS_DEFAULT_KEYS):
 
 
 # ---- all-pairs overlap and mask areas (ampis/applications/powder.py:80-83, ampis/structures.py:536-583) -----------------------------------------
-
-def _device_context(who, device, work):
-    """The context of `device` for function `who`: None for the host -- 'cpu', or 'auto' with no visible device or nothing to do (`work`
-    false) --, the current device's context for 'cuda' (an error without one) and for 'auto' otherwise.  ValueError for any other value."""
-    import torch
-    dev = str(device).lower()
-    if dev not in ("auto", "cpu", "cuda"):
-        raise ValueError(f"{who}: device = {device!r} ('auto', 'cpu' or 'cuda')")
-    return _edge_context(who) if dev == "cuda" or (dev == "auto" and work and torch.cuda.is_available()) else None
-
 
 def overlap_matrix(a, b, device='auto', size=None):
     """[len(a), len(b)] int64: the exact pixel count of a[i] AND b[j] for every pair of masks of one image -- what the reference gets from one
@@ -395,7 +388,7 @@ def seg_class_map(gt, pred, match_results=None, mode='reduced', size=None, devic
 
     gt, pred: anything masks_to_rle accepts (size=(h, w) for polygons and for two empty sides), an Instances or an InstanceSet; match_results:
     the dict of rle_instance_matcher, None to call it at the default threshold; device: 'cpu' (host), 'cuda' (HIP device, an error without one)
-    or 'auto' (the device when one is visible).  One amp_seg_class_map call on the run lists (csrc/seg_class_map.hip, or rle_host.hip on the
+    or 'auto' (the device when one is visible).  One amp_seg_class_map call on the run lists (csrc/seg_class_map.hip, or mask_analysis_host.hip on the
     host: identical bytes); no mask is decoded.  ValueError for an unknown mode or device and for masks of different sizes."""
     mode = str(mode).lower()
     if mode not in SEG_LABELS:

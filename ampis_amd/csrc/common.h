@@ -157,7 +157,7 @@ struct amp_ctx {
 };
 
 namespace amp {
-struct DevBuf {                  // device memory of one call (edge_distance.hip, region_props.hip: upload, compute, download, free)
+struct DevBuf {                  // device memory of one call (the mask analyses: upload, compute, download, free)
     void* p = nullptr;
     ~DevBuf() { if (p) (void)hipFree(p); }
     template <class T> T* as() const { return static_cast<T*>(p); }
@@ -271,49 +271,6 @@ int comm_wait_done(amp_ctx* ctx);              // compute stream waits (device s
 int comm_agree_flag(amp_ctx* ctx, int* d_flag); // MAX of a device int over the ranks, complete on return
 int rle_strings_run(amp_ctx* ctx, const unsigned int* pool, const unsigned long long* off, const int* len, int n, char* str,
                     unsigned long long cap, unsigned long long* str_off, int* str_len, unsigned long long* total);
-// rle_host.hip: amp_mask_edge_distance's argument checks (every named run list non-empty and summing to h * w, pair indices, boxes; crop = the
-// boxes clamped to the image, [n][4]) and its host evaluation; edge_distance.hip holds the entry point and the device evaluation
-int edge_distance_check(const uint32_t* gpool, const unsigned long long* goff, const int* glen, int ng, const uint32_t* ppool,
-                        const unsigned long long* poff, const int* plen, int np, const int* pair_g, const int* pair_p, const int* box, int n,
-                        int h, int w, const uint32_t* fp_d2, unsigned long long fp_cap, const unsigned long long* fp_off, const uint32_t* fn_d2,
-                        unsigned long long fn_cap, const unsigned long long* fn_off, std::vector<int>& crop);
-int edge_distance_host(const uint32_t* gpool, const unsigned long long* goff, const int* glen, const uint32_t* ppool, const unsigned long long* poff,
-                       const int* plen, const int* pair_g, const int* pair_p, const int* crop, int n, int h, uint32_t* fp_d2,
-                       unsigned long long fp_cap, unsigned long long* fp_off, uint32_t* fn_d2, unsigned long long fn_cap, unsigned long long* fn_off);
-// rle_host.hip: amp_mask_region_props' argument checks (every run list non-empty and summing to h * w, the size limits; box = the tight boxes
-// {r0, c0, r1, c1} with exclusive ends, [n][4], zeros for an empty mask) and its host evaluation; region_props.hip holds the entry point and
-// the device evaluation, region_props.h the word arithmetic both use
-int region_props_check(const uint32_t* pool, const unsigned long long* off, const int* len, int n, int h, int w, const long long* bbox,
-                       const unsigned long long* vals, std::vector<int>& box);
-int region_props_host(const uint32_t* pool, const unsigned long long* off, const int* len, const int* box, int n, int h, unsigned long long* vals);
-// rle_host.hip: amp_rle_overlap_groups' argument checks, which also build the plan both paths evaluate, and its host evaluation; rle_overlap.hip
-// holds the entry point and the device evaluation.  The plan of one pool: per mask its non-empty runs of ones k = 0 .. n - 1 as pixel positions
-// [S[ro + k], E[ro + k]) of the column-major image, P[ro + k] = the pixels of the runs before k, and one closing entry S = E = 0xffffffff,
-// P = the area, so that "the first run that ends beyond x" needs no special case at the end of the list.
-struct OvMask {
-    unsigned int ro;              // where the mask's entries start in S / E / P
-    int n;                        // runs of ones (0: an empty mask; its box is all zeros and meets nothing)
-    int r0, c0, r1, c1;           // the tight box, ends exclusive
-    unsigned int area;
-};
-struct OvPlan {
-    std::vector<uint32_t> S, E, P;
-    std::vector<OvMask> m;
-};
-int overlap_groups_check(const uint32_t* apool, const unsigned long long* aoff, const int* alen, const uint32_t* bpool,
-                         const unsigned long long* boff, const int* blen, const int* a_first, const int* b_first, const int* gh, const int* gw,
-                         int ngroups, const uint32_t* inter, size_t inter_cap, const unsigned long long* area_a, const unsigned long long* area_b,
-                         OvPlan& a, OvPlan& b);
-int overlap_groups_host(const OvPlan& a, const OvPlan& b, const int* a_first, const int* b_first, int ngroups, uint32_t* inter);
-// rle_host.hip: amp_seg_class_map's argument checks, which also build the plan both paths evaluate (an OvPlan per pool, with entries for the masks
-// the pairs name and n = -1 for the others, which are never read) and the sufficient counts capacity `need`, and its host evaluation;
-// seg_class_map.hip holds the entry point and the device evaluation, seg_class_map.h the word arithmetic both use
-int seg_class_map_check(const uint32_t* gpool, const unsigned long long* goff, const int* glen, int ng, const uint32_t* ppool,
-                        const unsigned long long* poff, const int* plen, int np, const int* pair_g, const int* pair_p, int n, int h, int w,
-                        int mode, const uint32_t* counts, unsigned long long counts_cap, const unsigned long long* counts_off,
-                        const unsigned long long* pixels, OvPlan& g, OvPlan& p, unsigned long long* need);
-int seg_class_map_host(const OvPlan& g, const OvPlan& p, const int* pair_g, const int* pair_p, int n, int h, int w, int mode, uint32_t* counts,
-                       unsigned long long* counts_off, unsigned long long* pixels);
 int roi_align_run(amp_ctx* ctx, const amp_fpn_feats* f, const float* rois, const int* batch_idx, const int* roi_count, int R, int P,
                   float* out, int* level_out, int out_split, int in_split = 0);   // out_split / in_split = 1: pooled tensor / feature maps in the split row format
 int box_candidates_run(amp_ctx* ctx, const float* pred, int ld, const float* proposals, const int* prop_count, int B, int Rcap, int K,

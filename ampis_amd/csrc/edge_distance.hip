@@ -12,11 +12,13 @@
 //                         query's own, finds the nearest set bit of each with word scans and stops when the column offset squared reaches the
 //                         best so far -- exact, a few columns for the boundary band of matched masks, O(crop width) for a far pixel.
 // Five launches and one memset per call whatever the number of pairs; scratch is two bit planes and two 8-byte words per crop row.  Integer
-// arithmetic only: h, w <= 32768 keeps every squared distance below 2^31.  Work is cut into host-built tile lists -- (pair, mask, 512 runs) for
-// the decoder, (pair, 64 rows) for the row kernels -- so a full-image crop spreads over the chip like three hundred small ones.
+// arithmetic only: h, w <= 32768 keeps every squared distance below 2^31.  Work is cut into host-built tile lists -- (pair, mask, 256 runs of
+// ones) for the decoder, (pair, 64 rows) for the row kernels -- so a full-image crop spreads over the chip like three hundred small ones.  The
+// runs come from the plan the argument checks build (run_list.h, mask_analysis_host.hip); the painter and the scan are run_list.h's.
 #include <vector>
 
 #include "common.h"
+#include "mask_analysis.h"
 
 namespace {
 
@@ -25,38 +27,24 @@ struct EdPair {
     int r1, c1;                   // its origin in the image
     int pitch;                    // 64-bit words per plane column = ceil(H / 64)
     int tile0;                    // first row tile of the pair (== the next pair's when the crop is empty)
-    int glen, plen;               // runs of the two masks
+    int gn, pn;                   // runs of ones of the two masks
+    unsigned int gro, pro;        // where they start in the plan's S / E
     unsigned long long plane;     // word offset of the ground-truth plane; the prediction's follows it (W * pitch words each)
-    unsigned long long gpre, ppre;      // offsets of the masks' run START positions (len + 1 entries each: the last is h * w)
 };
 
-// tile = {2 * pair + mask, first run (even)}: thread t takes run first + 2 t + 1 (the odd runs are the ones)
+// tile = {2 * pair + mask, first run of ones}: thread t takes run first + t
 __global__ __launch_bounds__(256) void ed_decode_kernel(const EdPair* __restrict__ pairs, const int2* __restrict__ tiles, int ntiles,
-                                                        const unsigned int* __restrict__ pre, unsigned long long* __restrict__ planes, int h) {
+                                                        const unsigned int* __restrict__ S, const unsigned int* __restrict__ E,
+                                                        unsigned long long* __restrict__ planes, int h) {
     for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
         const int2 tl = tiles[t];
         const EdPair pr = pairs[tl.x >> 1];
         const int side = tl.x & 1;
-        const int j = tl.y + 2 * (int)threadIdx.x + 1;
-        if (j >= (side ? pr.plen : pr.glen)) continue;
-        const unsigned int* st = pre + (side ? pr.ppre : pr.gpre);
-        const unsigned int s0 = st[j], e0 = st[j + 1];              // pixels [s0, e0) of the column-major image, e0 <= h * w <= 2^30
-        if (e0 == s0) continue;
+        const int k = tl.y + (int)threadIdx.x;
+        if (k >= (side ? pr.pn : pr.gn)) continue;
+        const unsigned int at = (side ? pr.pro : pr.gro) + (unsigned)k;
         unsigned long long* plane = planes + pr.plane + (side ? (unsigned long long)pr.W * pr.pitch : 0ull);
-        const int c_first = (int)(s0 / (unsigned)h), c_last = (int)((e0 - 1) / (unsigned)h);
-        for (int c = max(c_first, pr.c1); c <= min(c_last, pr.c1 + pr.W - 1); ++c) {
-            const unsigned int cb = (unsigned)c * (unsigned)h;
-            int ya = (int)(max(s0, cb) - cb), yb = (int)(min(e0, cb + (unsigned)h) - cb);       // rows [ya, yb) of column c
-            ya = max(ya, pr.r1) - pr.r1;
-            yb = min(yb, pr.r1 + pr.H) - pr.r1;
-            if (yb <= ya) continue;
-            unsigned long long* col = plane + (size_t)(c - pr.c1) * pr.pitch;
-            for (int wv = ya >> 6; wv <= (yb - 1) >> 6; ++wv) {
-                const int lo = max(ya - (wv << 6), 0), hi = min(yb - (wv << 6), 64);            // bits [lo, hi) of word wv
-                const unsigned long long m = (hi == 64 ? ~0ull : ((1ull << hi) - 1ull)) & ~((1ull << lo) - 1ull);
-                atomicOr(&col[wv], m);                                                          // runs of one column share words
-            }
-        }
+        amp::paint_run<true>(S[at], E[at], h, plane, pr.r1, pr.c1, pr.H, pr.W, pr.pitch, amp::OrAtomic());
     }
 }
 
@@ -95,30 +83,23 @@ __global__ __launch_bounds__(256) void ed_rows_kernel(const EdPair* __restrict__
 __global__ __launch_bounds__(1024) void ed_scan_kernel(unsigned long long* rows_fp, unsigned long long* rows_fn, long long nrows,
                                                        const EdPair* __restrict__ pairs, int n, int ntiles, unsigned long long* __restrict__ off_fp,
                                                        unsigned long long* __restrict__ off_fn) {
-    __shared__ unsigned long long s[2][1024];
+    __shared__ unsigned long long s[1024];
     const int tid = threadIdx.x;
     const long long per = (nrows + 1023) / 1024;
     const long long i0 = min((long long)tid * per, nrows), i1 = min(i0 + per, nrows);
     unsigned long long a = 0, b = 0;
     for (long long i = i0; i < i1; ++i) { a += rows_fp[i]; b += rows_fn[i]; }
-    s[0][tid] = a;
-    s[1][tid] = b;
+    unsigned long long ra = amp::block_scan_1024(s, a) - a;          // exclusive
+    const unsigned long long ta = s[1023];
     __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const unsigned long long va = tid >= o ? s[0][tid - o] : 0ull, vb = tid >= o ? s[1][tid - o] : 0ull;
-        __syncthreads();
-        s[0][tid] += va;
-        s[1][tid] += vb;
-        __syncthreads();
-    }
-    unsigned long long ra = s[0][tid] - a, rb = s[1][tid] - b;      // exclusive
+    unsigned long long rb = amp::block_scan_1024(s, b) - b;
+    const unsigned long long tb = s[1023];
     for (long long i = i0; i < i1; ++i) {
         const unsigned long long ca = rows_fp[i], cb = rows_fn[i];
         rows_fp[i] = ra; rows_fn[i] = rb;
         ra += ca; rb += cb;
     }
     __syncthreads();
-    const unsigned long long ta = s[0][1023], tb = s[1][1023];
     for (int p = tid; p <= n; p += 1024) {
         const int t0 = p < n ? pairs[p].tile0 : ntiles;
         off_fp[p] = t0 < ntiles ? rows_fp[(size_t)t0 * 64] : ta;
@@ -165,12 +146,7 @@ __global__ __launch_bounds__(256) void ed_search_kernel(const EdPair* __restrict
         const bool side = q >= tot_fp;
         const unsigned long long i = side ? q - tot_fp : q;
         const unsigned long long* off = side ? off_fn : off_fp;
-        int lo = 0, hi = n;                                          // off[lo] <= i < off[hi]
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (off[mid] <= i) lo = mid; else hi = mid;
-        }
-        const EdPair pr = pairs[lo];
+        const EdPair pr = pairs[amp::owner_of(off, n, i)];
         const unsigned long long* T = planes + pr.plane + (side ? (unsigned long long)pr.W * pr.pitch : 0ull);    // false negatives look for the prediction
         const unsigned int rc = out[q];
         const int r = (int)(rc >> 16), c = (int)(rc & 0xffffu);
@@ -184,40 +160,26 @@ __global__ __launch_bounds__(256) void ed_search_kernel(const EdPair* __restrict
     }
 }
 
-static int edge_distance_device(amp_ctx* ctx, const uint32_t* gpool, const unsigned long long* goff, const int* glen, int ng, const uint32_t* ppool,
-                                const unsigned long long* poff, const int* plen, int np, const int* pair_g, const int* pair_p, const int* crop, int n,
-                                int h, int w, uint32_t* fp_d2, unsigned long long fp_cap, unsigned long long* fp_off, uint32_t* fn_d2,
-                                unsigned long long fn_cap, unsigned long long* fn_off) {
-    // the plan: run start positions of the named masks (each once), pair records, decode and row tiles
-    std::vector<unsigned int> pre;
-    std::vector<long long> gslot((size_t)ng, -1), pslot((size_t)np, -1);
-    auto starts = [&](const uint32_t* c, int m) {
-        const long long at = (long long)pre.size();
-        unsigned int pos = 0;
-        for (int j = 0; j < m; ++j) { pre.push_back(pos); pos += c[j]; }
-        pre.push_back(pos);
-        return at;
-    };
+static int edge_distance_device(amp_ctx* ctx, const amp::RunPlan& runs, int ng, const int* pair_g, const int* pair_p, const int* crop, int n, int h,
+                                uint32_t* fp_d2, unsigned long long fp_cap, unsigned long long* fp_off, uint32_t* fn_d2, unsigned long long fn_cap,
+                                unsigned long long* fn_off) {
+    // pair records, decode and row tiles
     std::vector<EdPair> pairs((size_t)n);
     std::vector<int2> dtiles, rtiles;
     unsigned long long words = 0;
     for (int p = 0; p < n; ++p) {
-        const int g = pair_g[p], q = pair_p[p];
+        const amp::RunMask &G = runs.m[(size_t)pair_g[p]], &Q = runs.m[(size_t)ng + pair_p[p]];
         const int* cr = crop + 4 * (size_t)p;
         EdPair& e = pairs[(size_t)p];
         e.H = cr[1] - cr[0]; e.W = cr[3] - cr[2]; e.r1 = cr[0]; e.c1 = cr[2];
         e.pitch = (e.H + 63) >> 6;
         e.tile0 = (int)rtiles.size();
-        e.glen = glen[g]; e.plen = plen[q];
+        e.gn = G.n; e.pn = Q.n; e.gro = G.ro; e.pro = Q.ro;
         e.plane = words;
-        e.gpre = e.ppre = 0;
         if (e.H == 0 || e.W == 0) { e.H = e.W = e.pitch = 0; continue; }         // an empty crop has no pixel, no tile and no plane
-        if (gslot[(size_t)g] < 0) gslot[(size_t)g] = starts(gpool + goff[g], glen[g]);
-        if (pslot[(size_t)q] < 0) pslot[(size_t)q] = starts(ppool + poff[q], plen[q]);
-        e.gpre = (unsigned long long)gslot[(size_t)g]; e.ppre = (unsigned long long)pslot[(size_t)q];
         words += 2ull * (unsigned long long)e.W * e.pitch;
-        for (int j = 0; j < e.glen; j += 512) dtiles.push_back(make_int2(2 * p, j));
-        for (int j = 0; j < e.plen; j += 512) dtiles.push_back(make_int2(2 * p + 1, j));
+        for (int k = 0; k < e.gn; k += 256) dtiles.push_back(make_int2(2 * p, k));
+        for (int k = 0; k < e.pn; k += 256) dtiles.push_back(make_int2(2 * p + 1, k));
         for (int r = 0; r < e.H; r += 64) rtiles.push_back(make_int2(p, r));
         AMP_REQUIRE(rtiles.size() < (1u << 25) && dtiles.size() < (1u << 30), "amp_mask_edge_distance: the crops of one call have more than 2^31 rows");
     }
@@ -226,12 +188,13 @@ static int edge_distance_device(amp_ctx* ctx, const uint32_t* gpool, const unsig
 
     AMP_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    amp::DevBuf d_pairs, d_dt, d_rt, d_pre, d_planes, d_rows, d_off, d_out;
+    amp::DevBuf d_pairs, d_dt, d_rt, d_S, d_E, d_planes, d_rows, d_off, d_out;
     std::vector<unsigned long long> off((size_t)2 * (n + 1), 0);
     AMP_TRY_STATUS(amp::dev_upload(ctx, d_pairs, pairs));
     AMP_TRY_STATUS(amp::dev_upload(ctx, d_dt, dtiles));
     AMP_TRY_STATUS(amp::dev_upload(ctx, d_rt, rtiles));
-    AMP_TRY_STATUS(amp::dev_upload(ctx, d_pre, pre));
+    AMP_TRY_STATUS(amp::dev_upload(ctx, d_S, runs.S));
+    AMP_TRY_STATUS(amp::dev_upload(ctx, d_E, runs.E));
     AMP_TRY_STATUS(amp::dev_alloc(d_planes, words * 8));
     AMP_TRY_STATUS(amp::dev_alloc(d_rows, (size_t)nrows * 16));
     AMP_TRY_STATUS(amp::dev_alloc(d_off, off.size() * 8));
@@ -242,7 +205,7 @@ static int edge_distance_device(amp_ctx* ctx, const uint32_t* gpool, const unsig
     if (words) AMP_HIP_CHECK(hipMemsetAsync(d_planes.p, 0, words * 8, st));
     if (ndt) {
         hipLaunchKernelGGL(ed_decode_kernel, dim3((unsigned)std::min(ndt, 1 << 20)), dim3(256), 0, st, d_pairs.as<EdPair>(), d_dt.as<int2>(), ndt,
-                           d_pre.as<unsigned int>(), d_planes.as<unsigned long long>(), h);
+                           d_S.as<unsigned int>(), d_E.as<unsigned int>(), d_planes.as<unsigned long long>(), h);
         AMP_HIP_CHECK(hipGetLastError());
     }
     const unsigned rblocks = (unsigned)std::min(amp::cdiv(std::max(nrt, 1), 4), 1 << 20);
@@ -276,7 +239,6 @@ static int edge_distance_device(amp_ctx* ctx, const uint32_t* gpool, const unsig
     }
     std::copy(off.begin(), off.begin() + (n + 1), fp_off);
     std::copy(off.begin() + (n + 1), off.end(), fn_off);
-    (void)w;
     return AMP_OK;
 }
 
@@ -287,12 +249,10 @@ extern "C" int amp_mask_edge_distance(amp_ctx* ctx, const uint32_t* gpool, const
                                       const int* pair_p, const int* box, int n, int h, int w, uint32_t* fp_d2, unsigned long long fp_cap,
                                       unsigned long long* fp_off, uint32_t* fn_d2, unsigned long long fn_cap, unsigned long long* fn_off) {
     std::vector<int> crop;
+    amp::RunPlan runs;
     AMP_TRY_STATUS(amp::edge_distance_check(gpool, goff, glen, ng, ppool, poff, plen, np, pair_g, pair_p, box, n, h, w, fp_d2, fp_cap, fp_off, fn_d2,
-                                            fn_cap, fn_off, crop));
+                                            fn_cap, fn_off, crop, runs));
     if (n == 0) { fp_off[0] = fn_off[0] = 0; return AMP_OK; }
-    if (!ctx)
-        return amp::edge_distance_host(gpool, goff, glen, ppool, poff, plen, pair_g, pair_p, crop.data(), n, h, fp_d2, fp_cap, fp_off, fn_d2, fn_cap,
-                                       fn_off);
-    return edge_distance_device(ctx, gpool, goff, glen, ng, ppool, poff, plen, np, pair_g, pair_p, crop.data(), n, h, w, fp_d2, fp_cap, fp_off, fn_d2,
-                                fn_cap, fn_off);
+    return ctx ? edge_distance_device(ctx, runs, ng, pair_g, pair_p, crop.data(), n, h, fp_d2, fp_cap, fp_off, fn_d2, fn_cap, fn_off)
+               : amp::edge_distance_host(runs, ng, pair_g, pair_p, crop.data(), n, h, fp_d2, fp_cap, fp_off, fn_d2, fn_cap, fn_off);
 }

@@ -20,44 +20,41 @@
 //                          in one wave; the whole call on the 32768 x 32768 full image took 0.09 s in the GPU test.
 // Five launches and two memsets per call whatever the number of masks.  Integer arithmetic only; the only atomics are 64-bit integer adds and
 // ORs, whose results do not depend on the order, so the bytes repeat.  The word arithmetic is region_props.h, shared with the host evaluation
-// (rle_host.hip).  Scratch: two planes per tight box and 4 (2 W + 1) ints per mask.
+// (mask_analysis_host.hip); the runs and the tight boxes come from the plan the argument checks build, the painter is run_list.h's.  Scratch:
+// two planes per tight box and 4 (2 W + 1) ints per mask.
 #include <vector>
 
 #include "common.h"
+#include "mask_analysis.h"
 #include "region_props.h"
 
 namespace {
 
 using amp::RpMask;
-using amp::rp_u64;
+using amp::u64;
+using amp::wave_sum;
 
-// sum over the wave, valid in lane 0
-__device__ __forceinline__ rp_u64 rp_wave_sum(rp_u64 v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
-// tile = {mask, first run (even)}: thread t takes run first + 2 t + 1 (the odd runs are the ones)
+// tile = {mask, first run of ones}: thread t takes run first + t.  runs[k] = pixels [x, y) of the column-major image
 __global__ __launch_bounds__(256) void rp_moments_kernel(const RpMask* __restrict__ masks, const int2* __restrict__ tiles, int ntiles,
-                                                         const unsigned int* __restrict__ pre, unsigned long long* __restrict__ vals, int h) {
-    __shared__ rp_u64 part[4][6];
+                                                         const uint2* __restrict__ runs, unsigned long long* __restrict__ vals, int h) {
+    __shared__ u64 part[4][6];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {           // uniform over the workgroup: every thread meets every barrier
         const int2 tl = tiles[t];
         const RpMask mk = masks[tl.x];
-        const int j = tl.y + 2 * (int)threadIdx.x + 1;
-        rp_u64 acc[6] = {0, 0, 0, 0, 0, 0};
-        if (j < mk.len) {
-            const unsigned int s0 = pre[mk.pre + j], e0 = pre[mk.pre + j + 1];
-            if (e0 > s0) amp::rp_run_sums(s0, e0, (rp_u64)h, acc);
+        const int k = tl.y + (int)threadIdx.x;
+        u64 acc[6] = {0, 0, 0, 0, 0, 0};
+        if (k < mk.n) {
+            const uint2 r = runs[mk.run0 + k];
+            amp::rp_run_sums(r.x, r.y, (u64)h, acc);
         }
         for (int k = 0; k < 6; ++k) {
-            const rp_u64 s = rp_wave_sum(acc[k]);
+            const u64 s = wave_sum(acc[k]);
             if (lane == 0) part[wave][k] = s;
         }
         __syncthreads();
         if (threadIdx.x < 6) {
-            const rp_u64 s = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+            const u64 s = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
             if (s) atomicAdd(&vals[13 * (size_t)tl.x + threadIdx.x], s);
         }
         __syncthreads();
@@ -66,37 +63,15 @@ __global__ __launch_bounds__(256) void rp_moments_kernel(const RpMask* __restric
 
 // same tiles.  Every run of a mask lies inside the mask's tight box, so no clipping is needed
 __global__ __launch_bounds__(256) void rp_decode_kernel(const RpMask* __restrict__ masks, const int2* __restrict__ tiles, int ntiles,
-                                                        const unsigned int* __restrict__ pre, unsigned long long* __restrict__ planes, int h) {
+                                                        const uint2* __restrict__ runs, unsigned long long* __restrict__ planes, int h) {
     for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
         const int2 tl = tiles[t];
         const RpMask mk = masks[tl.x];
-        const int j = tl.y + 2 * (int)threadIdx.x + 1;
-        if (j >= mk.len) continue;
-        const unsigned int s0 = pre[mk.pre + j], e0 = pre[mk.pre + j + 1];   // pixels [s0, e0) of the column-major image, e0 <= h * w <= 2^30
-        if (e0 == s0) continue;
-        unsigned long long* plane = planes + mk.plane;
-        const int c_first = (int)(s0 / (unsigned)h), c_last = (int)((e0 - 1) / (unsigned)h);
-        for (int c = c_first; c <= c_last; ++c) {
-            const unsigned int cb = (unsigned)c * (unsigned)h;
-            const int ya = (int)(max(s0, cb) - cb) - mk.r0, yb = (int)(min(e0, cb + (unsigned)h) - cb) - mk.r0;     // rows [ya, yb) of the box
-            unsigned long long* col = plane + (size_t)(c - mk.c0) * mk.pitch;
-            for (int wv = ya >> 6; wv <= (yb - 1) >> 6; ++wv) {
-                const int lo = max(ya - (wv << 6), 0), hi = min(yb - (wv << 6), 64);            // bits [lo, hi) of word wv
-                const unsigned long long m = (hi == 64 ? ~0ull : ((1ull << hi) - 1ull)) & ~((1ull << lo) - 1ull);
-                atomicOr(&col[wv], m);                                                          // runs of one column share words
-            }
-        }
+        const int k = tl.y + (int)threadIdx.x;
+        if (k >= mk.n) continue;
+        const uint2 r = runs[mk.run0 + k];
+        amp::paint_run<false>(r.x, r.y, h, planes + mk.plane, mk.r0, mk.c0, mk.H, mk.W, mk.pitch, amp::OrAtomic());
     }
-}
-
-// the mask that owns plane word u (uoff[m] <= u < uoff[m + 1]; masks without a plane have an empty range and are never found)
-__device__ __forceinline__ int rp_owner(const unsigned long long* __restrict__ uoff, int n, unsigned long long u) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (uoff[mid] <= u) lo = mid; else hi = mid;
-    }
-    return lo;
 }
 
 // CLASSIFY = false: writes the border plane behind the mask plane.  true: reads it and adds the three class counts to vals[mask][6 .. 8]
@@ -108,9 +83,9 @@ __global__ __launch_bounds__(256) void rp_words_kernel(const RpMask* __restrict_
     for (unsigned long long it = 0; it < rounds; ++it) {             // every lane of a wave makes every round: the wave votes below
         const unsigned long long u = (it * gridDim.x + blockIdx.x) * 256 + threadIdx.x;
         int m = -1;
-        rp_u64 cls[3] = {0, 0, 0};
+        u64 cls[3] = {0, 0, 0};
         if (u < total) {
-            m = rp_owner(uoff, n, u);
+            m = amp::owner_of(uoff, n, u);           // masks without a plane have an empty range and are never found
             const RpMask mk = masks[m];
             const unsigned long long local = u - uoff[m], units = (unsigned long long)mk.W * mk.pitch;
             const int q = (int)(local / (unsigned)mk.pitch), wv = (int)(local % (unsigned)mk.pitch);
@@ -121,16 +96,16 @@ __global__ __launch_bounds__(256) void rp_words_kernel(const RpMask* __restrict_
             }
         }
         if (CLASSIFY) {
-            const int cnt[3] = {amp::rp_popc(cls[0]), amp::rp_popc(cls[1]), amp::rp_popc(cls[2])};
+            const int cnt[3] = {amp::popc(cls[0]), amp::popc(cls[1]), amp::popc(cls[2])};
             const int m0 = __shfl(m, 0, 64);
             if (__all(m == m0)) {                                    // one mask in the wave (or none): one add per class
                 for (int k = 0; k < 3; ++k) {
-                    const rp_u64 s = rp_wave_sum((rp_u64)cnt[k]);
+                    const u64 s = wave_sum((u64)cnt[k]);
                     if ((threadIdx.x & 63) == 0 && s && m0 >= 0) atomicAdd(&vals[13 * (size_t)m0 + 6 + k], s);
                 }
             } else if (m >= 0) {
                 for (int k = 0; k < 3; ++k)
-                    if (cnt[k]) atomicAdd(&vals[13 * (size_t)m + 6 + k], (rp_u64)cnt[k]);
+                    if (cnt[k]) atomicAdd(&vals[13 * (size_t)m + 6 + k], (u64)cnt[k]);
             }
         }
     }
@@ -156,16 +131,16 @@ __global__ __launch_bounds__(64) void rp_hull_kernel(const RpMask* __restrict__ 
         long long s = 0;
         for (int k = lane; k + 1 < ku; k += 64) s += amp::rp_edge_sum(su[k], hi[su[k]], su[k + 1], hi[su[k + 1]], true);
         for (int k = lane; k + 1 < kl; k += 64) s -= amp::rp_edge_sum(sl[k], lo[sl[k]], sl[k + 1], lo[sl[k + 1]], false);
-        const rp_u64 tot = rp_wave_sum((rp_u64)s);                   // two's complement: the wrapped partial sums add up to the true total
-        if (lane == 0) vals[13 * (size_t)m + 9] = tot + (rp_u64)mk.W;
+        const u64 tot = wave_sum((u64)s);                   // two's complement: the wrapped partial sums add up to the true total
+        if (lane == 0) vals[13 * (size_t)m + 9] = tot + (u64)mk.W;
         __syncthreads();                                             // klen is rewritten for the next mask
     }
 }
 
-static int region_props_device(amp_ctx* ctx, const uint32_t* pool, const unsigned long long* off, const int* len, const int* box, int n, int h,
-                               unsigned long long* vals) {
-    // the plan: run start positions, mask records, (mask, 512 runs) tiles, plane and hull scratch offsets
-    std::vector<unsigned int> pre;
+static int region_props_device(amp_ctx* ctx, const amp::RunPlan& plan, int h, unsigned long long* vals) {
+    // mask records, the runs of ones, (mask, 256 runs) tiles, plane and hull scratch offsets
+    const int n = (int)plan.m.size();
+    std::vector<uint2> runs;
     std::vector<RpMask> masks((size_t)n);
     std::vector<int2> tiles;
     std::vector<unsigned long long> uoff((size_t)n + 1, 0);
@@ -174,38 +149,33 @@ static int region_props_device(amp_ctx* ctx, const uint32_t* pool, const unsigne
     // that size, so the full image is a few hundred lanes' work and not one lane's
     const unsigned int piece = (unsigned)h * (unsigned)std::max(1, 4096 / ((h + 63) >> 6));
     for (int p = 0; p < n; ++p) {
-        const int* b = box + 4 * (size_t)p;
+        const amp::RunMask& mk = plan.m[(size_t)p];
         RpMask& e = masks[(size_t)p];
-        e.H = b[2] - b[0]; e.W = b[3] - b[1]; e.r0 = b[0]; e.c0 = b[1];
+        e.H = mk.r1 - mk.r0; e.W = mk.c1 - mk.c0; e.r0 = mk.r0; e.c0 = mk.c0;
         e.pitch = (e.H + 63) >> 6;
-        e.len = len[p];
-        e.plane = 2 * units; e.pre = pre.size(); e.hull = hints;
+        e.plane = 2 * units; e.run0 = runs.size(); e.hull = hints;
         uoff[(size_t)p] = units;
-        if (e.H == 0) continue;                                      // an empty mask has no pixel, no tile and no plane: its 13 integers stay 0
-        const uint32_t* c = pool + off[p];
-        unsigned int pos = 0;
-        for (int j = 0; j < len[p]; ++j) {
-            pre.push_back(pos);
-            if ((j & 1) && c[j] > piece)                             // ones [pos, m), zeros [m, m), ones [m, ...): the same mask, shorter runs
-                for (unsigned int m = pos + piece; m < pos + c[j]; m += piece) { pre.push_back(m); pre.push_back(m); }
-            pos += c[j];
+        for (int k = 0; k < mk.n; ++k) {
+            unsigned int s = plan.S[mk.ro + k];
+            const unsigned int t = plan.E[mk.ro + k];
+            for (; t - s > piece; s += piece) runs.push_back(make_uint2(s, s + piece));
+            runs.push_back(make_uint2(s, t));
         }
-        e.len = (int)(pre.size() - e.pre);
-        pre.push_back(pos);
+        e.n = (int)(runs.size() - e.run0);                           // 0 for an empty mask: no pixel, no tile and no plane, its 13 integers stay 0
         units += (unsigned long long)e.W * e.pitch;
-        hints += 4ull * (2ull * e.W + 1);
-        for (int j = 0; j < e.len; j += 512) tiles.push_back(make_int2(p, j));
-        AMP_REQUIRE(tiles.size() < (1u << 30) && pre.size() < (1ull << 31), "amp_mask_region_props: the masks of one call have more than 2^31 runs");
+        hints += e.n ? 4ull * (2ull * e.W + 1) : 0ull;
+        for (int k = 0; k < e.n; k += 256) tiles.push_back(make_int2(p, k));
+        AMP_REQUIRE(tiles.size() < (1u << 30) && runs.size() < (1ull << 31), "amp_mask_region_props: the masks of one call have more than 2^31 runs");
     }
     uoff[(size_t)n] = units;
     const int nt = (int)tiles.size();
 
     AMP_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    amp::DevBuf d_masks, d_tiles, d_pre, d_uoff, d_planes, d_hull, d_vals;
+    amp::DevBuf d_masks, d_tiles, d_runs, d_uoff, d_planes, d_hull, d_vals;
     AMP_TRY_STATUS(amp::dev_upload(ctx, d_masks, masks));
     AMP_TRY_STATUS(amp::dev_upload(ctx, d_tiles, tiles));
-    AMP_TRY_STATUS(amp::dev_upload(ctx, d_pre, pre));
+    AMP_TRY_STATUS(amp::dev_upload(ctx, d_runs, runs));
     AMP_TRY_STATUS(amp::dev_upload(ctx, d_uoff, uoff));
     AMP_TRY_STATUS(amp::dev_alloc(d_planes, (size_t)units * 16));
     AMP_TRY_STATUS(amp::dev_alloc(d_hull, (size_t)hints * 4));
@@ -216,9 +186,9 @@ static int region_props_device(amp_ctx* ctx, const uint32_t* pool, const unsigne
     if (units) AMP_HIP_CHECK(hipMemsetAsync(planes, 0, (size_t)units * 16, st));
     if (nt) {
         const dim3 grid((unsigned)std::min(nt, 1 << 20));
-        hipLaunchKernelGGL(rp_moments_kernel, grid, dim3(256), 0, st, d_masks.as<RpMask>(), d_tiles.as<int2>(), nt, d_pre.as<unsigned int>(), dv, h);
+        hipLaunchKernelGGL(rp_moments_kernel, grid, dim3(256), 0, st, d_masks.as<RpMask>(), d_tiles.as<int2>(), nt, d_runs.as<uint2>(), dv, h);
         AMP_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(rp_decode_kernel, grid, dim3(256), 0, st, d_masks.as<RpMask>(), d_tiles.as<int2>(), nt, d_pre.as<unsigned int>(), planes, h);
+        hipLaunchKernelGGL(rp_decode_kernel, grid, dim3(256), 0, st, d_masks.as<RpMask>(), d_tiles.as<int2>(), nt, d_runs.as<uint2>(), planes, h);
         AMP_HIP_CHECK(hipGetLastError());
         const dim3 wgrid((unsigned)std::min<unsigned long long>((units + 255) / 256, 1ull << 20));
         hipLaunchKernelGGL(rp_words_kernel<false>, wgrid, dim3(256), 0, st, d_masks.as<RpMask>(), n, d_uoff.as<unsigned long long>(), units, planes, dv);
@@ -237,11 +207,14 @@ static int region_props_device(amp_ctx* ctx, const uint32_t* pool, const unsigne
 
 extern "C" int amp_mask_region_props(amp_ctx* ctx, const uint32_t* pool, const unsigned long long* off, const int* len, int n, int h, int w,
                                      long long* bbox, unsigned long long* vals) {
-    std::vector<int> box;
-    AMP_TRY_STATUS(amp::region_props_check(pool, off, len, n, h, w, bbox, vals, box));
+    amp::RunPlan plan;
+    AMP_TRY_STATUS(amp::region_props_check(pool, off, len, n, h, w, bbox, vals, plan));
     if (n == 0) return AMP_OK;
-    AMP_TRY_STATUS(ctx ? region_props_device(ctx, pool, off, len, box.data(), n, h, vals)
-                       : amp::region_props_host(pool, off, len, box.data(), n, h, vals));
-    std::copy(box.begin(), box.end(), bbox);
+    AMP_TRY_STATUS(ctx ? region_props_device(ctx, plan, h, vals) : amp::region_props_host(plan, h, vals));
+    for (int p = 0; p < n; ++p) {
+        const amp::RunMask& mk = plan.m[(size_t)p];
+        long long* b = bbox + 4 * (size_t)p;
+        b[0] = mk.r0; b[1] = mk.c0; b[2] = mk.r1; b[3] = mk.c1;
+    }
     return AMP_OK;
 }

@@ -1,7 +1,7 @@
 // Segmentation class map on the device (ampis/analyze.py:589-699, seg_perf_iset: decode every mask to the image, three [pairs x h x w] bool
 // arrays, OR over the pairs, code every pixel, encode 4 or 7 class masks).  Here the masks stay run lists until they are three COLUMN-major bit
 // planes of the image -- TP = OR (g & q), FN = OR (g & ~q), FP = OR (~g & q), 64 rows a word, ceil(h / 64) words a column -- and the class
-// masks leave as run lists again.  The host plan (common.h OvPlan, built by the argument checks in rle_host.hip) keeps per named mask the
+// masks leave as run lists again.  The host plan (run_list.h, built by the argument checks in mask_analysis_host.hip) keeps per named mask the
 // positions [S, E) of its runs of ones and the tight box; an item is one (pair, column, word) of the union of a pair's two boxes:
 //   1. sc_paint_kernel   one lane per item, grid-stride.  The lane finds its pair by binary search over the item offsets, builds the 64 rows of
 //                        g and of q from the runs that meet them (binary search over the run ends for the first, then the runs in order: at
@@ -16,17 +16,19 @@
 //   5. sc_diff_kernel    one lane per count: boundary minus the boundary before it (0 in front of a class's first).
 // Five launches and one memset per call whatever the number of pairs.  Integer arithmetic only; the atomics are 64-bit ORs and adds, whose
 // results do not depend on the order, and every other word is written once by the lane that owns it: the bytes repeat and equal the host's
-// (rle_host.hip paints the planes by one walk over the two run lists of a pair and reads the same words).  Scratch: the plan, three planes of
+// (mask_analysis_host.hip paints the planes by one walk over the two run lists of a pair and reads the same words).  Scratch: the plan, three planes of
 // h * w bits, two buffers of the counts capacity.
 #include <vector>
 
 #include "common.h"
+#include "mask_analysis.h"
 #include "seg_class_map.h"
 
 namespace {
 
-using amp::OvMask;
-using amp::sc_u64;
+using amp::RunMask;
+using amp::u64;
+using amp::wave_sum;
 
 struct ScPair {
     int g, q;                     // masks of the two plans
@@ -34,38 +36,27 @@ struct ScPair {
 };
 
 // the 64 rows [a, a + 64) of the column-major image of one mask.  E: the run ends, ascending; S[n] = 0xffffffff closes the list
-__device__ __forceinline__ sc_u64 sc_mask_word(const unsigned int* __restrict__ S, const unsigned int* __restrict__ E, int n, unsigned int a,
+__device__ __forceinline__ u64 sc_mask_word(const unsigned int* __restrict__ S, const unsigned int* __restrict__ E, int n, unsigned int a,
                                                unsigned int b) {
-    int lo = 0, hi = n;                                              // the first run that ends beyond a
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (E[mid] <= a) lo = mid + 1; else hi = mid;
-    }
-    sc_u64 word = 0;
-    for (; S[lo] < b; ++lo) {                                        // lo <= n: the closing entry stops the walk
-        const int from = (int)(max(S[lo], a) - a), to = (int)(min(E[lo], b) - a);              // bits [from, to), 0 <= from < to <= 64
-        word |= (to == 64 ? ~0ull : ((1ull << to) - 1ull)) & ~((1ull << from) - 1ull);
-    }
+    u64 word = 0;
+    for (int k = amp::first_run_ending_after(E, n, a); S[k] < b; ++k)                          // k <= n: the closing entry stops the walk
+        word |= amp::word_span((int)(max(S[k], a) - a), (int)(min(E[k], b) - a));              // bits [from, to), 0 <= from < to <= 64
     return word;
 }
 
 __global__ __launch_bounds__(256) void sc_paint_kernel(const ScPair* __restrict__ pairs, int n, const unsigned long long* __restrict__ ioff,
-                                                       unsigned long long total, const OvMask* __restrict__ gm, const OvMask* __restrict__ pm,
+                                                       unsigned long long total, const RunMask* __restrict__ gm, const RunMask* __restrict__ pm,
                                                        const unsigned int* __restrict__ gS, const unsigned int* __restrict__ gE,
                                                        const unsigned int* __restrict__ pS, const unsigned int* __restrict__ pE,
                                                        unsigned long long* __restrict__ planes, unsigned long long units, int h, int pitch) {
     for (unsigned long long it = (unsigned long long)blockIdx.x * 256 + threadIdx.x; it < total; it += (unsigned long long)gridDim.x * 256) {
-        int lo = 0, hi = n;                                          // the pair that owns item it: ioff[lo] <= it < ioff[lo + 1]
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (ioff[mid] <= it) lo = mid; else hi = mid;
-        }
+        const int lo = amp::owner_of(ioff, n, it);                   // the pair that owns item it
         const ScPair pr = pairs[lo];
         const unsigned int local = (unsigned int)(it - ioff[lo]);
         const int col = pr.c0 + (int)(local / (unsigned)pr.nwords), wv = pr.wv0 + (int)(local % (unsigned)pr.nwords);
         const unsigned int a = (unsigned)col * (unsigned)h + ((unsigned)wv << 6), b = min(a + 64u, ((unsigned)col + 1u) * (unsigned)h);
-        const OvMask G = gm[pr.g], Q = pm[pr.q];
-        const sc_u64 g = sc_mask_word(gS + G.ro, gE + G.ro, G.n, a, b), q = sc_mask_word(pS + Q.ro, pE + Q.ro, Q.n, a, b);
+        const RunMask G = gm[pr.g], Q = pm[pr.q];
+        const u64 g = sc_mask_word(gS + G.ro, gE + G.ro, G.n, a, b), q = sc_mask_word(pS + Q.ro, pE + Q.ro, Q.n, a, b);
         unsigned long long* at = planes + (size_t)col * pitch + wv;
         if (g & q) atomicOr(at, g & q);
         if (g & ~q) atomicOr(at + units, g & ~q);
@@ -75,24 +66,18 @@ __global__ __launch_bounds__(256) void sc_paint_kernel(const ScPair* __restrict_
 
 // the transition words of plane word u for the K classes; false beyond the planes
 __device__ __forceinline__ bool sc_word_transitions(const unsigned long long* __restrict__ planes, unsigned long long units, unsigned long long u,
-                                                    int h, int pitch, int mode, int K, sc_u64* t, sc_u64* tp, sc_u64* fn, sc_u64* fp, sc_u64* valid) {
+                                                    int h, int pitch, int mode, int K, u64* t, u64* tp, u64* fn, u64* fp, u64* valid) {
     for (int k = 0; k < 7; ++k) t[k] = 0;
     if (u >= units) return false;
     const int wv = (int)(u % (unsigned)pitch);
     *valid = amp::sc_valid(h, wv);
     *tp = planes[u]; *fn = planes[units + u]; *fp = planes[2 * units + u];
     const int pb = amp::sc_prev_bit(h, wv);
-    const sc_u64 qt = u ? (planes[u - 1] >> pb) & 1ull : 0ull, qf = u ? (planes[units + u - 1] >> pb) & 1ull : 0ull,
+    const u64 qt = u ? (planes[u - 1] >> pb) & 1ull : 0ull, qf = u ? (planes[units + u - 1] >> pb) & 1ull : 0ull,
                  qp = u ? (planes[2 * units + u - 1] >> pb) & 1ull : 0ull;
     for (int k = 0; k < K; ++k)
         t[k] = amp::sc_transitions(amp::sc_class_word(*tp, *fn, *fp, mode, k) & *valid, amp::sc_class_word(qt, qf, qp, mode, k), *valid);
     return true;
-}
-
-// sum over the wave, valid in lane 0
-__device__ __forceinline__ unsigned long long sc_wave_sum(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
 }
 
 // workgroup b owns plane words [256 b, 256 b + 256); sums[k * nblk + b] = the transitions of class k in them; px[8] += the code counts
@@ -103,14 +88,14 @@ __global__ __launch_bounds__(256) void sc_count_kernel(const unsigned long long*
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (unsigned int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {          // uniform over the workgroup: every thread meets every barrier
         const unsigned long long u = (unsigned long long)blk * 256 + threadIdx.x;
-        sc_u64 t[7], tp = 0, fn = 0, fp = 0, valid = 0;
+        u64 t[7], tp = 0, fn = 0, fp = 0, valid = 0;
         sc_word_transitions(planes, units, u, h, pitch, mode, K, t, &tp, &fn, &fp, &valid);      // beyond the planes: valid = 0, nothing counts
         for (int c = 0; c < 8; ++c) {
-            const unsigned long long s = sc_wave_sum((unsigned long long)amp::sc_popc(amp::sc_code_word(tp, fn, fp, c) & valid));
+            const unsigned long long s = wave_sum((unsigned long long)amp::popc(amp::sc_code_word(tp, fn, fp, c) & valid));
             if (lane == 0 && s) atomicAdd(&px[c], s);
         }
         for (int k = 0; k < K; ++k) {
-            const unsigned long long s = sc_wave_sum((unsigned long long)amp::sc_popc(t[k]));
+            const unsigned long long s = wave_sum((unsigned long long)amp::popc(t[k]));
             if (lane == 0) part[wave][k] = s;
         }
         __syncthreads();
@@ -128,15 +113,7 @@ __global__ __launch_bounds__(1024) void sc_scan_kernel(unsigned long long* __res
     const unsigned long long chunk = (m + 1023) / 1024, first = chunk * threadIdx.x, last = min(first + chunk, m);
     unsigned long long s = 0;
     for (unsigned long long i = first; i < last; ++i) s += sums[i];
-    tot[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {                             // inclusive scan of the 1024 chunk totals
-        const unsigned long long v = (int)threadIdx.x >= o ? tot[threadIdx.x - o] : 0ull;
-        __syncthreads();
-        tot[threadIdx.x] += v;
-        __syncthreads();
-    }
-    unsigned long long run = tot[threadIdx.x] - s;                   // what lies in front of this thread's chunk
+    unsigned long long run = amp::block_scan_1024(tot, s) - s;       // what lies in front of this thread's chunk
     for (unsigned long long i = first; i < last; ++i) {
         const unsigned long long v = sums[i];
         sums[i] = run;
@@ -160,11 +137,11 @@ __global__ __launch_bounds__(256) void sc_write_kernel(const unsigned long long*
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (unsigned int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
         const unsigned long long u = (unsigned long long)blk * 256 + threadIdx.x;
-        sc_u64 t[7], tp = 0, fn = 0, fp = 0, valid = 0;
+        u64 t[7], tp = 0, fn = 0, fp = 0, valid = 0;
         sc_word_transitions(planes, units, u, h, pitch, mode, K, t, &tp, &fn, &fp, &valid);
         const unsigned int base = (unsigned int)(u / (unsigned)pitch) * (unsigned)h + ((unsigned int)(u % (unsigned)pitch) << 6);
         for (int k = 0; k < K; ++k) {
-            const unsigned int c = (unsigned)amp::sc_popc(t[k]);
+            const unsigned int c = (unsigned)amp::popc(t[k]);
             unsigned int inc = c;                                    // inclusive scan over the wave
             for (int o = 1; o < 64; o <<= 1) {
                 const unsigned int v = __shfl_up(inc, o, 64);
@@ -175,7 +152,7 @@ __global__ __launch_bounds__(256) void sc_write_kernel(const unsigned long long*
             unsigned int before = inc - c;
             for (int v = 0; v < wave; ++v) before += wtot[v];
             unsigned long long at = sums[(size_t)k * nblk + blk] + (unsigned long long)k + before;
-            for (sc_u64 x = t[k]; x; x &= x - 1) bnd[at++] = base + (unsigned)amp::sc_ctz(x);
+            for (u64 x = t[k]; x; x &= x - 1) bnd[at++] = base + (unsigned)amp::ctz(x);
             __syncthreads();                                         // wtot is rewritten for the next class
         }
     }
@@ -191,18 +168,18 @@ __global__ __launch_bounds__(256) void sc_diff_kernel(const unsigned int* __rest
     }
 }
 
-static int seg_class_map_device(amp_ctx* ctx, const amp::OvPlan& g, const amp::OvPlan& p, const int* pair_g, const int* pair_p, int n, int h, int w,
+static int seg_class_map_device(amp_ctx* ctx, const amp::RunPlan& g, const amp::RunPlan& p, const int* pair_g, const int* pair_p, int n, int h, int w,
                                 int mode, unsigned long long need, uint32_t* counts, unsigned long long* counts_off, unsigned long long* pixels) {
     const int pitch = (h + 63) >> 6, K = amp::sc_classes(mode);
     const unsigned long long units = (unsigned long long)w * pitch;
     std::vector<ScPair> pairs;
     std::vector<unsigned long long> ioff(1, 0ull);
     for (int i = 0; i < n; ++i) {
-        const OvMask& G = g.m[(size_t)pair_g[i]];
-        const OvMask& Q = p.m[(size_t)pair_p[i]];
+        const RunMask& G = g.m[(size_t)pair_g[i]];
+        const RunMask& Q = p.m[(size_t)pair_p[i]];
         if (G.n == 0 && Q.n == 0) continue;                          // two masks without a pixel paint nothing
-        const OvMask& A = G.n ? G : Q;
-        const OvMask& B = Q.n ? Q : G;
+        const RunMask& A = G.n ? G : Q;
+        const RunMask& B = Q.n ? Q : G;
         const int r0 = std::min(A.r0, B.r0), r1 = std::max(A.r1, B.r1), c0 = std::min(A.c0, B.c0), c1 = std::max(A.c1, B.c1);
         const int wv0 = r0 >> 6, nwords = ((r1 - 1) >> 6) - wv0 + 1;
         pairs.push_back(ScPair{pair_g[i], pair_p[i], c0, wv0, nwords, 0});
@@ -235,7 +212,7 @@ static int seg_class_map_device(amp_ctx* ctx, const amp::OvPlan& g, const amp::O
     if (items) {
         const dim3 grid((unsigned)std::min<unsigned long long>((items + 255) / 256, 1ull << 16));
         hipLaunchKernelGGL(sc_paint_kernel, grid, dim3(256), 0, st, d_pairs.as<ScPair>(), npairs, d_ioff.as<unsigned long long>(), items,
-                           d_gm.as<OvMask>(), d_pm.as<OvMask>(), d_gS.as<unsigned int>(), d_gE.as<unsigned int>(), d_pS.as<unsigned int>(),
+                           d_gm.as<RunMask>(), d_pm.as<RunMask>(), d_gS.as<unsigned int>(), d_gE.as<unsigned int>(), d_pS.as<unsigned int>(),
                            d_pE.as<unsigned int>(), planes, units, h, pitch);
         AMP_HIP_CHECK(hipGetLastError());
     }
@@ -272,7 +249,7 @@ extern "C" int amp_seg_class_map(amp_ctx* ctx, const uint32_t* gpool, const unsi
                                  const unsigned long long* poff, const int* plen, int np, const int* pair_g, const int* pair_p, int n, int h, int w,
                                  int mode, uint32_t* counts, unsigned long long counts_cap, unsigned long long* counts_off,
                                  unsigned long long* pixels) {
-    amp::OvPlan g, p;
+    amp::RunPlan g, p;
     unsigned long long need = 0;
     AMP_TRY_STATUS(amp::seg_class_map_check(gpool, goff, glen, ng, ppool, poff, plen, np, pair_g, pair_p, n, h, w, mode, counts, counts_cap,
                                             counts_off, pixels, g, p, &need));

@@ -8,6 +8,16 @@ import numpy as np
 from ._lib import check, lib
 
 
+def _vp(a):
+    """A numpy array as the void pointer of a C call."""
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _handle(ctx):
+    """The amp_ctx of a _lib.Context, NULL for None (the host path)."""
+    return ctx.handle if ctx is not None else None
+
+
 def counts_to_string(cnts):
     cnts = np.ascontiguousarray(cnts, dtype=np.uint32)
     cap = 7 * len(cnts) + 8
@@ -103,9 +113,8 @@ def iou(dt, gt, iscrowd):
     crowd = np.ascontiguousarray([int(bool(c)) for c in iscrowd], dtype=np.uint8) if len(iscrowd) else None
     assert crowd is None or len(crowd) == len(gt)
     h = int(dt[0]["size"][0]) if isinstance(dt[0], dict) and "size" in dt[0] else 0
-    vp = lambda a: a.ctypes.data_as(C.c_void_p)
-    check(lib().amp_rle_iou_matrix(vp(dp), vp(do), vp(dl), len(dt), vp(gp), vp(go), vp(gl), len(gt),
-                                   vp(crowd) if crowd is not None else None, h, vp(out)), "amp_rle_iou_matrix")
+    check(lib().amp_rle_iou_matrix(_vp(dp), _vp(do), _vp(dl), len(dt), _vp(gp), _vp(go), _vp(gl), len(gt),
+                                   _vp(crowd) if crowd is not None else None, h, _vp(out)), "amp_rle_iou_matrix")
     return out
 
 
@@ -174,8 +183,7 @@ def clip_polygons(flat, off, sel, x0, y0, x1, y1):
     assert sel.min() >= 0 and sel.max() < len(off) - 1 and int(off[-1]) <= len(flat)
     cap = int(6 * (off[sel + 1] - off[sel]).sum() + 16 * n)
     out = np.empty(cap, dtype=np.float64)
-    vp = lambda a: a.ctypes.data_as(C.c_void_p)
-    check(lib().amp_polygon_clip_rect(vp(flat), vp(off), vp(sel), n, float(x0), float(y0), float(x1), float(y1), vp(out), cap, vp(out_off)),
+    check(lib().amp_polygon_clip_rect(_vp(flat), _vp(off), _vp(sel), n, float(x0), float(y0), float(x1), float(y1), _vp(out), cap, _vp(out_off)),
           "amp_polygon_clip_rect")
     return out[: int(out_off[-1])], out_off
 
@@ -191,8 +199,7 @@ def pair_overlap(a, b, pairs):
         bp, bo, bl = _pool([_counts(x) for x in b])
         assert pairs[:, 0].max() < len(a) and pairs[:, 1].max() < len(b) and pairs.min() >= 0
         pa, pb = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
-        vp = lambda x: x.ctypes.data_as(C.c_void_p)
-        check(lib().amp_rle_pair_overlap(vp(ap), vp(ao), vp(al), vp(bp), vp(bo), vp(bl), vp(pa), vp(pb), n, vp(out[0]), vp(out[1]), vp(out[2])),
+        check(lib().amp_rle_pair_overlap(_vp(ap), _vp(ao), _vp(al), _vp(bp), _vp(bo), _vp(bl), _vp(pa), _vp(pb), n, _vp(out[0]), _vp(out[1]), _vp(out[2])),
               "amp_rle_pair_overlap")
     return tuple(o.astype(np.int64) for o in out)
 
@@ -219,9 +226,8 @@ def edge_distance(gt, pred, pairs, boxes, ctx=None):
     fp_cap, fn_cap = int(pa[pq].sum()), int(ga[pg].sum())                                 # a pair has no more queries than its mask has pixels
     fp, fn = np.empty(max(fp_cap, 1), dtype=np.uint32), np.empty(max(fn_cap, 1), dtype=np.uint32)
     fpo, fno = np.zeros(n + 1, dtype=np.uint64), np.zeros(n + 1, dtype=np.uint64)
-    vp = lambda x: x.ctypes.data_as(C.c_void_p)
-    check(lib().amp_mask_edge_distance(ctx.handle if ctx is not None else None, vp(gp), vp(go), vp(gl), len(gc), vp(pp), vp(po), vp(pl), len(pc),
-                                       vp(pg), vp(pq), vp(boxes), n, h, w, vp(fp), fp_cap, vp(fpo), vp(fn), fn_cap, vp(fno)), "amp_mask_edge_distance")
+    check(lib().amp_mask_edge_distance(_handle(ctx), _vp(gp), _vp(go), _vp(gl), len(gc), _vp(pp), _vp(po), _vp(pl), len(pc),
+                                       _vp(pg), _vp(pq), _vp(boxes), n, h, w, _vp(fp), fp_cap, _vp(fpo), _vp(fn), fn_cap, _vp(fno)), "amp_mask_edge_distance")
     out = ([fp[int(fpo[i]): int(fpo[i + 1])].copy() for i in range(n)], [fn[int(fno[i]): int(fno[i + 1])].copy() for i in range(n)])
     for name, lst in (("ground-truth", out[0]), ("predicted", out[1])):
         for i, d in enumerate(lst):
@@ -239,8 +245,7 @@ def region_props(masks, ctx=None):
     bbox, vals = np.zeros((n, 4), dtype=np.int64), np.zeros((n, 13), dtype=np.uint64)
     h, w = (int(v) for v in masks[0]["size"]) if n else (1, 1)
     pool, off, ln = _pool([_counts(x) for x in masks])
-    vp = lambda x: x.ctypes.data_as(C.c_void_p)
-    check(lib().amp_mask_region_props(ctx.handle if ctx is not None else None, vp(pool), vp(off), vp(ln), n, h, w, vp(bbox), vp(vals)),
+    check(lib().amp_mask_region_props(_handle(ctx), _vp(pool), _vp(off), _vp(ln), n, h, w, _vp(bbox), _vp(vals)),
           "amp_mask_region_props")
     return bbox, vals
 
@@ -270,9 +275,8 @@ def overlap_groups(a_groups, b_groups, ctx=None):
     total = int(first[-1])
     inter = np.zeros(max(total, 1), dtype=np.uint32)
     area_a, area_b = np.zeros(max(int(af[-1]), 1), dtype=np.uint64), np.zeros(max(int(bf[-1]), 1), dtype=np.uint64)
-    vp = lambda x: x.ctypes.data_as(C.c_void_p)
-    check(lib().amp_rle_overlap_groups(ctx.handle if ctx is not None else None, vp(ap), vp(ao), vp(al), vp(bp), vp(bo), vp(bl), vp(af), vp(bf),
-                                       vp(gh), vp(gw), ng, vp(inter), total, vp(area_a), vp(area_b)), "amp_rle_overlap_groups")
+    check(lib().amp_rle_overlap_groups(_handle(ctx), _vp(ap), _vp(ao), _vp(al), _vp(bp), _vp(bo), _vp(bl), _vp(af), _vp(bf),
+                                       _vp(gh), _vp(gw), ng, _vp(inter), total, _vp(area_a), _vp(area_b)), "amp_rle_overlap_groups")
     inters = [inter[int(first[g]): int(first[g + 1])].astype(np.int64).reshape(na[g], nb[g]) for g in range(ng)]
     return (inters, [area_a[int(af[g]): int(af[g + 1])].astype(np.int64) for g in range(ng)],
             [area_b[int(bf[g]): int(bf[g + 1])].astype(np.int64) for g in range(ng)])
@@ -310,9 +314,8 @@ def seg_class_map(gt, pred, pairs, mode, ctx=None, size=None):
     cap = K * (1 + sum(len(gc[i]) - 1 for i in named_g) + sum(len(pc[i]) - 1 for i in named_p))      # what amp_seg_class_map asks for
     counts = np.empty(max(cap, K), dtype=np.uint32)
     coff, pixels = np.zeros(K + 1, dtype=np.uint64), np.zeros(8, dtype=np.uint64)
-    vp = lambda x: x.ctypes.data_as(C.c_void_p)
-    check(lib().amp_seg_class_map(ctx.handle if ctx is not None else None, vp(gp), vp(go), vp(gl), len(gc), vp(pp), vp(po), vp(pl), len(pc),
-                                  vp(pg), vp(pq), n, h, w, m, vp(counts), len(counts), vp(coff), vp(pixels)), "amp_seg_class_map")
+    check(lib().amp_seg_class_map(_handle(ctx), _vp(gp), _vp(go), _vp(gl), len(gc), _vp(pp), _vp(po), _vp(pl), len(pc),
+                                  _vp(pg), _vp(pq), n, h, w, m, _vp(counts), len(counts), _vp(coff), _vp(pixels)), "amp_seg_class_map")
     return [counts[int(coff[k]): int(coff[k + 1])].copy() for k in range(K)], pixels.astype(np.int64)
 
 

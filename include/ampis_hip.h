@@ -507,7 +507,7 @@ int amp_rle_pair_overlap(const uint32_t* apool, const unsigned long long* aoff, 
  * 0xffffffff.  fp_cap / fn_cap: capacity of fp_d2 / fn_d2 in values (the summed areas of the pairs' masks always suffice); a smaller one is
  * AMP_ERR_NOMEM with the need in the message and nothing written.  Every run list a pair names is checked on the host first (length > 0,
  * runs summing to h * w): a malformed list is AMP_ERR_ARG and never a device access.
- * ctx == NULL: computed on the host (rle_host.hip).  Otherwise on ctx's device and stream (edge_distance.hip): the function uploads, runs a
+ * ctx == NULL: computed on the host (mask_analysis_host.hip).  Otherwise on ctx's device and stream (edge_distance.hip): the function uploads, runs a
  * fixed number of launches whatever n is, downloads and returns with the results in host memory; the order and the bytes do not depend on
  * the device's scheduling. */
 int amp_mask_edge_distance(amp_ctx* ctx, const uint32_t* gpool, const unsigned long long* goff, const int* glen, int ng,
@@ -524,7 +524,7 @@ int amp_mask_edge_distance(amp_ctx* ctx, const uint32_t* gpool, const unsigned l
  * skimage's perimeter = P1 + P2 sqrt(2) + P3 (1 + sqrt(2)) / 2.  convex area = the pixel centres inside or on the convex hull of the four edge
  * midpoints (r -+ 1/2, c), (r, c -+ 1/2) of every pixel (convex_hull_image, offset_coordinates=True), decided in half-pixel integers.
  * Every run list is checked on the host first (length > 0, runs summing to h * w, the size limits): a malformed list is AMP_ERR_ARG, nothing
- * written and never a device access.  ctx == NULL: computed on the host (rle_host.hip).  Otherwise on ctx's device and stream
+ * written and never a device access.  ctx == NULL: computed on the host (mask_analysis_host.hip).  Otherwise on ctx's device and stream
  * (region_props.hip): the function uploads, runs a fixed number of launches whatever n is, downloads and returns with the results in host
  * memory; integer arithmetic only, the bytes do not depend on the device's scheduling and equal the host's. */
 int amp_mask_region_props(amp_ctx* ctx, const uint32_t* pool, const unsigned long long* off, const int* len, int n, int h, int w,
@@ -538,7 +538,7 @@ int amp_mask_region_props(amp_ctx* ctx, const uint32_t* pool, const unsigned lon
  * values.  ngroups == 0, groups without masks on one side and masks without a set pixel (a row or column of zeros) are valid.  Everything is
  * checked on the host first -- the image sizes, every run list non-empty and summing to its group's h * w, the order of a_first / b_first,
  * inter_cap -- and refused with AMP_ERR_ARG naming the offending index: nothing written and never a device access.
- * ctx == NULL: computed on the host (rle_host.hip).  Otherwise on ctx's device and stream (rle_overlap.hip): the function uploads, runs one
+ * ctx == NULL: computed on the host (mask_analysis_host.hip).  Otherwise on ctx's device and stream (rle_overlap.hip): the function uploads, runs one
  * launch whatever the number of groups, downloads and returns with the results in host memory; integer arithmetic only, every output word
  * written once, the bytes do not depend on the device's scheduling and equal the host's. */
 int amp_rle_overlap_groups(amp_ctx* ctx, const uint32_t* apool, const unsigned long long* aoff, const int* alen, const uint32_t* bpool,
@@ -557,7 +557,7 @@ int amp_rle_overlap_groups(amp_ctx* ctx, const uint32_t* apool, const unsigned l
  * counts_cap -- and refused with AMP_ERR_ARG naming the offending index, or AMP_ERR_NOMEM naming the capacity needed: nothing written and never
  * a device access.  The capacity that is always enough, and the one that is asked for, is K x (1 + the sum of len - 1 over the distinct named
  * run lists): a class changes only where a named mask does.
- * ctx == NULL: computed on the host (rle_host.hip).  Otherwise on ctx's device and stream (seg_class_map.hip): the function uploads, runs five
+ * ctx == NULL: computed on the host (mask_analysis_host.hip).  Otherwise on ctx's device and stream (seg_class_map.hip): the function uploads, runs five
  * launches whatever n is, downloads and returns with the results in host memory; integer arithmetic only, the bytes do not depend on the
  * device's scheduling and equal the host's.  Memory: three bit planes of the image and the result, nothing proportional to n x h x w. */
 int amp_seg_class_map(amp_ctx* ctx, const uint32_t* gpool, const unsigned long long* goff, const int* glen, int ng, const uint32_t* ppool,

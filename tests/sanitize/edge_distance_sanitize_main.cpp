@@ -1,4 +1,4 @@
-// Host-only AddressSanitizer / UBSan run of mask_edge_distance's argument checks and host evaluation (ampis_amd/csrc/rle_host.hip:
+// Host-only AddressSanitizer / UBSan run of mask_edge_distance's argument checks and host evaluation (ampis_amd/csrc/mask_analysis_host.hip:
 // amp::edge_distance_check / amp::edge_distance_host, what amp_mask_edge_distance runs with a NULL context), on random masks with boxes from
 // empty to beyond the image -- every value compared with an exhaustive search -- and on hostile input.  Built and run by
 // tests/test_edge_distance_sanitize.py like the codec's own sanitizer run (rle_sanitize_main.cpp).
@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "../../ampis_amd/csrc/mask_analysis.h"
 #include "../../include/ampis_hip.h"
 
 namespace amp {
@@ -20,13 +21,6 @@ void set_error(const char* fmt, ...) {
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
 }
-int edge_distance_check(const uint32_t* gpool, const unsigned long long* goff, const int* glen, int ng, const uint32_t* ppool,
-                        const unsigned long long* poff, const int* plen, int np, const int* pair_g, const int* pair_p, const int* box, int n,
-                        int h, int w, const uint32_t* fp_d2, unsigned long long fp_cap, const unsigned long long* fp_off, const uint32_t* fn_d2,
-                        unsigned long long fn_cap, const unsigned long long* fn_off, std::vector<int>& crop);
-int edge_distance_host(const uint32_t* gpool, const unsigned long long* goff, const int* glen, const uint32_t* ppool, const unsigned long long* poff,
-                       const int* plen, const int* pair_g, const int* pair_p, const int* crop, int n, int h, uint32_t* fp_d2,
-                       unsigned long long fp_cap, unsigned long long* fp_off, uint32_t* fn_d2, unsigned long long fn_cap, unsigned long long* fn_off);
 }  // namespace amp
 
 static unsigned long long rng_state = 0x9E3779B97F4A7C15ull;
@@ -96,23 +90,25 @@ int main() {
         std::vector<uint32_t> fp(wfp.size()), fn(wfn.size());                    // exactly the need: one value more would be a heap overflow
         std::vector<unsigned long long> fpo((size_t)n + 1, 77), fno((size_t)n + 1, 77);
         std::vector<int> crop;
+        amp::RunPlan runs;
         CHECK(amp::edge_distance_check(gp.pool.data(), gp.off.data(), gp.len.data(), nm, pp.pool.data(), pp.off.data(), pp.len.data(), nm, pg.data(), pq.data(),
-                                       box.data(), n, h, w, fp.data(), fp.size(), fpo.data(), fn.data(), fn.size(), fno.data(), crop) == AMP_OK);
-        CHECK(amp::edge_distance_host(gp.pool.data(), gp.off.data(), gp.len.data(), pp.pool.data(), pp.off.data(), pp.len.data(), pg.data(), pq.data(), crop.data(),
+                                       box.data(), n, h, w, fp.data(), fp.size(), fpo.data(), fn.data(), fn.size(), fno.data(), crop, runs) == AMP_OK);
+        CHECK(amp::edge_distance_host(runs, nm, pg.data(), pq.data(), crop.data(),
                                       n, h, fp.data(), fp.size(), fpo.data(), fn.data(), fn.size(), fno.data()) == AMP_OK);
         CHECK(fp == wfp && fn == wfn && fpo == wfpo && fno == wfno);
         if (!wfp.empty()) {                                                      // one value short: refused, nothing written
             std::vector<uint32_t> small(wfp.size() - 1, 5u);
             std::vector<unsigned long long> o2((size_t)n + 1, 77);
-            CHECK(amp::edge_distance_host(gp.pool.data(), gp.off.data(), gp.len.data(), pp.pool.data(), pp.off.data(), pp.len.data(), pg.data(), pq.data(),
+            CHECK(amp::edge_distance_host(runs, nm, pg.data(), pq.data(),
                                           crop.data(), n, h, small.data(), small.size(), o2.data(), fn.data(), fn.size(), fno.data()) == AMP_ERR_NOMEM);
             CHECK(std::all_of(small.begin(), small.end(), [](uint32_t v) { return v == 5u; }) && std::all_of(o2.begin(), o2.end(), [](unsigned long long v) { return v == 77; }));
         }
         if (n > 0) {                                                             // hostile input: every one refused by the check, by name
             std::vector<int> crop2;
+            amp::RunPlan runs2;
             auto check = [&](const Pools& g2, const std::vector<int>& pg2, const std::vector<int>& box2, int hh) {
                 return amp::edge_distance_check(g2.pool.data(), g2.off.data(), g2.len.data(), nm, pp.pool.data(), pp.off.data(), pp.len.data(), nm, pg2.data(), pq.data(),
-                                                box2.data(), n, hh, w, fp.data(), fp.size(), fpo.data(), fn.data(), fn.size(), fno.data(), crop2);
+                                                box2.data(), n, hh, w, fp.data(), fp.size(), fpo.data(), fn.data(), fn.size(), fno.data(), crop2, runs2);
             };
             Pools bad = gp;
             bad.pool[bad.off[pg[0]]] += 1;                                       // runs that do not sum to h * w

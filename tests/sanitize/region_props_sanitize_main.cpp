@@ -1,4 +1,4 @@
-// Host-only AddressSanitizer / UBSan run of the region-property argument checks and host evaluation (ampis_amd/csrc/rle_host.hip:
+// Host-only AddressSanitizer / UBSan run of the region-property argument checks and host evaluation (ampis_amd/csrc/mask_analysis_host.hip:
 // amp::region_props_check / amp::region_props_host, what amp_mask_region_props runs with a NULL context, and through them the word arithmetic
 // of region_props.h that the kernels share), on random masks up to three 64-row words tall -- every integer compared with a per-pixel
 // evaluation -- and on hostile input.  Built and run by tests/test_region_props_sanitize.py like the edge-distance run beside it.
@@ -11,6 +11,7 @@
 #include <utility>
 #include <vector>
 
+#include "../../ampis_amd/csrc/mask_analysis.h"
 #include "../../include/ampis_hip.h"
 
 namespace amp {
@@ -21,9 +22,6 @@ void set_error(const char* fmt, ...) {
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
 }
-int region_props_check(const uint32_t* pool, const unsigned long long* off, const int* len, int n, int h, int w, const long long* bbox,
-                       const unsigned long long* vals, std::vector<int>& box);
-int region_props_host(const uint32_t* pool, const unsigned long long* off, const int* len, const int* box, int n, int h, unsigned long long* vals);
 }  // namespace amp
 
 static unsigned long long rng_state = 0x9E3779B97F4A7C15ull;
@@ -107,24 +105,26 @@ int main() {
         }
         std::vector<long long> bbox((size_t)n * 4);                               // exactly the need
         std::vector<unsigned long long> vals((size_t)n * 13, 99);
-        std::vector<int> box;
-        CHECK(amp::region_props_check(pool.data(), off.data(), len.data(), n, h, w, bbox.data(), vals.data(), box) == AMP_OK);
-        CHECK(amp::region_props_host(pool.data(), off.data(), len.data(), box.data(), n, h, vals.data()) == AMP_OK);
+        amp::RunPlan plan;
+        CHECK(amp::region_props_check(pool.data(), off.data(), len.data(), n, h, w, bbox.data(), vals.data(), plan) == AMP_OK);
+        CHECK(amp::region_props_host(plan, h, vals.data()) == AMP_OK);
+        std::vector<int> box;                                                     // the tight boxes are the plan's
+        for (const amp::RunMask& mk : plan.m) box.insert(box.end(), {mk.r0, mk.c0, mk.r1, mk.c1});
         CHECK(box == wbox && vals == want);
         // hostile input: every one refused by the check
         std::vector<uint32_t> bad = pool;
         bad[off[n - 1]] += 1;                                                     // runs that do not sum to h * w
-        CHECK(amp::region_props_check(bad.data(), off.data(), len.data(), n, h, w, bbox.data(), vals.data(), box) == AMP_ERR_ARG);
+        CHECK(amp::region_props_check(bad.data(), off.data(), len.data(), n, h, w, bbox.data(), vals.data(), plan) == AMP_ERR_ARG);
         bad = pool;
         bad[off[0]] = 0xffffffffu;                                                // a run far beyond the image
-        CHECK(amp::region_props_check(bad.data(), off.data(), len.data(), n, h, w, bbox.data(), vals.data(), box) == AMP_ERR_ARG);
+        CHECK(amp::region_props_check(bad.data(), off.data(), len.data(), n, h, w, bbox.data(), vals.data(), plan) == AMP_ERR_ARG);
         std::vector<int> len2 = len;
         len2[0] = 0;                                                              // an empty run list
-        CHECK(amp::region_props_check(pool.data(), off.data(), len2.data(), n, h, w, bbox.data(), vals.data(), box) == AMP_ERR_ARG);
-        CHECK(amp::region_props_check(pool.data(), off.data(), len.data(), n, 32769, w, bbox.data(), vals.data(), box) == AMP_ERR_ARG);
-        CHECK(amp::region_props_check(pool.data(), off.data(), len.data(), n, h, 0, bbox.data(), vals.data(), box) == AMP_ERR_ARG);
-        CHECK(amp::region_props_check(pool.data(), off.data(), len.data(), -1, h, w, bbox.data(), vals.data(), box) == AMP_ERR_ARG);
-        CHECK(amp::region_props_check(nullptr, off.data(), len.data(), n, h, w, bbox.data(), vals.data(), box) == AMP_ERR_ARG);
+        CHECK(amp::region_props_check(pool.data(), off.data(), len2.data(), n, h, w, bbox.data(), vals.data(), plan) == AMP_ERR_ARG);
+        CHECK(amp::region_props_check(pool.data(), off.data(), len.data(), n, 32769, w, bbox.data(), vals.data(), plan) == AMP_ERR_ARG);
+        CHECK(amp::region_props_check(pool.data(), off.data(), len.data(), n, h, 0, bbox.data(), vals.data(), plan) == AMP_ERR_ARG);
+        CHECK(amp::region_props_check(pool.data(), off.data(), len.data(), -1, h, w, bbox.data(), vals.data(), plan) == AMP_ERR_ARG);
+        CHECK(amp::region_props_check(nullptr, off.data(), len.data(), n, h, w, bbox.data(), vals.data(), plan) == AMP_ERR_ARG);
     }
     printf("REGION PROPS SANITIZE OK\n");
     return 0;

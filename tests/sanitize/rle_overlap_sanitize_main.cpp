@@ -1,4 +1,4 @@
-// Host-only AddressSanitizer / UBSan run of amp_rle_overlap_groups' argument checks, plan and host evaluation (ampis_amd/csrc/rle_host.hip:
+// Host-only AddressSanitizer / UBSan run of amp_rle_overlap_groups' argument checks, plan and host evaluation (ampis_amd/csrc/mask_analysis_host.hip:
 // amp::overlap_groups_check / amp::overlap_groups_host, what the call runs with a NULL context): random groups of random masks, every count
 // compared with a per-pixel evaluation, output buffers of exactly the needed size, and hostile input.  Built and run by
 // tests/test_rle_overlap_sanitize.py like the region-property run beside it.  The device kernel indexes only what these checks let through.
@@ -9,6 +9,7 @@
 
 #include <vector>
 
+#include "../../ampis_amd/csrc/mask_analysis.h"
 #include "../../include/ampis_hip.h"
 
 namespace amp {
@@ -19,13 +20,6 @@ void set_error(const char* fmt, ...) {
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
 }
-struct OvMask { unsigned int ro; int n; int r0, c0, r1, c1; unsigned int area; };
-struct OvPlan { std::vector<uint32_t> S, E, P; std::vector<OvMask> m; };
-int overlap_groups_check(const uint32_t* apool, const unsigned long long* aoff, const int* alen, const uint32_t* bpool,
-                         const unsigned long long* boff, const int* blen, const int* a_first, const int* b_first, const int* gh, const int* gw,
-                         int ngroups, const uint32_t* inter, size_t inter_cap, const unsigned long long* area_a, const unsigned long long* area_b,
-                         OvPlan& a, OvPlan& b);
-int overlap_groups_host(const OvPlan& a, const OvPlan& b, const int* a_first, const int* b_first, int ngroups, uint32_t* inter);
 }  // namespace amp
 
 static unsigned long long rng_state = 0x9E3779B97F4A7C15ull;
@@ -84,7 +78,7 @@ int main() {
         std::vector<unsigned long long> area_a(want_a.size(), 99ull), area_b(want_b.size(), 99ull);
         // the public entry point is device code; the NULL-context path is these two calls
         {
-            amp::OvPlan a, b;
+            amp::RunPlan a, b;
             CHECK(amp::overlap_groups_check(A.pool.data(), A.off.data(), A.len.data(), B.pool.data(), B.off.data(), B.len.data(), af.data(), bf.data(),
                                             gh.data(), gw.data(), ng, inter.data(), inter.size(), area_a.data(), area_b.data(), a, b) == AMP_OK);
             CHECK(amp::overlap_groups_host(a, b, af.data(), bf.data(), ng, inter.data()) == AMP_OK);
@@ -94,7 +88,7 @@ int main() {
             for (size_t p = 0; p < b.m.size(); ++p) CHECK(b.m[p].area == want_b[p]);
         }
         // hostile input: every one refused by the check
-        amp::OvPlan a, b;
+        amp::RunPlan a, b;
 #define REFUSED(AP, AL, AF, BF, GH, GW, NG, CAP)                                                                                                  \
         CHECK(amp::overlap_groups_check(AP, A.off.data(), AL, B.pool.data(), B.off.data(), B.len.data(), AF, BF, GH, GW, NG, inter.data(), CAP, \
                                         area_a.data(), area_b.data(), a, b) == AMP_ERR_ARG)

@@ -1,4 +1,4 @@
-// Host-only AddressSanitizer / UBSan run of amp_seg_class_map's argument checks, plan and host evaluation (ampis_amd/csrc/rle_host.hip:
+// Host-only AddressSanitizer / UBSan run of amp_seg_class_map's argument checks, plan and host evaluation (ampis_amd/csrc/mask_analysis_host.hip:
 // amp::seg_class_map_check / amp::seg_class_map_host, what the call runs with a NULL context): the shapes of tests/seg_class_cases.py restated
 // (one row, one column, 63 / 64 / 65 / 129 rows, masks owning the first and the last pixel, full columns, no pair, repeated pairs, empty masks)
 // and random groups of random masks, every class decoded and compared with a per-pixel evaluation, the counts buffer of exactly the capacity
@@ -11,6 +11,7 @@
 
 #include <vector>
 
+#include "../../ampis_amd/csrc/mask_analysis.h"
 #include "../../include/ampis_hip.h"
 
 namespace amp {
@@ -21,14 +22,6 @@ void set_error(const char* fmt, ...) {
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
 }
-struct OvMask { unsigned int ro; int n; int r0, c0, r1, c1; unsigned int area; };
-struct OvPlan { std::vector<uint32_t> S, E, P; std::vector<OvMask> m; };
-int seg_class_map_check(const uint32_t* gpool, const unsigned long long* goff, const int* glen, int ng, const uint32_t* ppool,
-                        const unsigned long long* poff, const int* plen, int np, const int* pair_g, const int* pair_p, int n, int h, int w,
-                        int mode, const uint32_t* counts, unsigned long long counts_cap, const unsigned long long* counts_off,
-                        const unsigned long long* pixels, OvPlan& g, OvPlan& p, unsigned long long* need);
-int seg_class_map_host(const OvPlan& g, const OvPlan& p, const int* pair_g, const int* pair_p, int n, int h, int w, int mode, uint32_t* counts,
-                       unsigned long long* counts_off, unsigned long long* pixels);
 }  // namespace amp
 
 static unsigned long long rng_state = 0x9E3779B97F4A7C15ull;
@@ -79,14 +72,14 @@ static int one_case(int h, int w, int ng, int np, int n, int it) {
         }
     for (int mode = 0; mode < 2; ++mode) {
         const int K = mode ? 7 : 4;
-        amp::OvPlan g, p;
+        amp::RunPlan g, p;
         unsigned long long need = 0, coff[8], px[8];
         uint32_t probe = 0;
         int st = amp::seg_class_map_check(G.pool.data(), G.off.data(), G.len.data(), ng, P.pool.data(), P.off.data(), P.len.data(), np, pg.data(),
                                           pq.data(), n, h, w, mode, &probe, 0, coff, px, g, p, &need);
         CHECK(st == AMP_ERR_NOMEM && need >= (unsigned long long)K);              // capacity 0: refused, the need reported
         std::vector<uint32_t> counts((size_t)need, 99u);                          // exactly the need
-        g = amp::OvPlan(); p = amp::OvPlan();
+        g = amp::RunPlan(); p = amp::RunPlan();
         CHECK(amp::seg_class_map_check(G.pool.data(), G.off.data(), G.len.data(), ng, P.pool.data(), P.off.data(), P.len.data(), np, pg.data(),
                                        pq.data(), n, h, w, mode, counts.data(), need, coff, px, g, p, &need) == AMP_OK);
         CHECK(amp::seg_class_map_host(g, p, pg.data(), pq.data(), n, h, w, mode, counts.data(), coff, px) == AMP_OK);

@@ -1,6 +1,6 @@
 """The independent reference of amp_seg_class_map: a dense NumPy restatement of the definition (ampis/analyze.py:631-682) -- decode every mask
 of a pair with rle.decode, OR g & q, g & ~q, ~g & q over the pairs, code = TP + 2 FN + 4 FP, one bool image per class, rle.encode of the
-Fortran-ordered array.  It shares no code with the run-domain / bit-plane implementation (rle_host.hip, seg_class_map.hip); every comparison
+Fortran-ordered array.  It shares no code with the run-domain / bit-plane implementation (mask_analysis_host.hip, seg_class_map.hip); every comparison
 against it is exact.  The planes are built pair by pair, so the reference needs three images whatever the number of pairs."""
 import numpy as np
 

@@ -1,4 +1,4 @@
-"""Host-only AddressSanitizer + UndefinedBehaviorSanitizer run of the region-property argument checks and host evaluation (rle_host.hip and
+"""Host-only AddressSanitizer + UndefinedBehaviorSanitizer run of the region-property argument checks and host evaluation (mask_analysis_host.hip and
 region_props.h are plain C++): random masks against a per-pixel evaluation of all 13 integers, output buffers of exactly the needed size, and
 hostile input (tests/sanitize/region_props_sanitize_main.cpp).  The device kernels run the same word arithmetic and index only what these
 checks let through."""
@@ -13,7 +13,7 @@ def test_region_props_host_code_is_clean_under_asan_and_ubsan(tmp_path):
     rocm_inc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")
     cmd = ["g++", "-x", "c++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
            "-D__HIP_PLATFORM_AMD__", "-I" + rocm_inc, "-o", exe,
-           os.path.join(ROOT, "tests", "sanitize", "region_props_sanitize_main.cpp"), os.path.join(ROOT, "ampis_amd", "csrc", "rle_host.hip")]
+           os.path.join(ROOT, "tests", "sanitize", "region_props_sanitize_main.cpp"), os.path.join(ROOT, "ampis_amd", "csrc", "rle_host.hip"), os.path.join(ROOT, "ampis_amd", "csrc", "mask_analysis_host.hip")]
     b = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert b.returncode == 0, b.stderr[-3000:]
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")

@@ -3,7 +3,7 @@ polygons as ground truth, the same masks shifted (even instances) or dilated (od
 own twin, tight boxes, ALL pairs in one call.  Three evaluations alternate inside one process, after a warm-up of each:
 
   device   amp_mask_edge_distance with a context (csrc/edge_distance.hip): upload, five launches, download, stream synchronise -- all inside the window
-  host     the same call with a NULL context (csrc/rle_host.hip)
+  host     the same call with a NULL context (csrc/mask_analysis_host.hip)
   dense    the reference's formulation (ampis/analyze.py:379-413: a [queries x targets x 2] float64 broadcast per pair, torch.sqrt, min) with torch
            on the same card, pair after pair, from crops decoded beforehand; pairs whose broadcast would pass --dense-gib are left out and counted
 

@@ -7,7 +7,7 @@ Evaluations alternate inside one process, after a warm-up of each:
   measure-pairs                the same summary with the matches made by a restatement of the reference's method (ampis/applications/powder.py:
                                80-83): a Python loop of rle.merge(intersect=True) + rle.area for every satellite against every particle
   call-device / call-host      the bare amp_rle_overlap_groups call on arrays pooled once, with a context (csrc/rle_overlap.hip: upload, one
-                               launch, download, stream synchronise -- all in the window) and with a NULL context (csrc/rle_host.hip)
+                               launch, download, stream synchronise -- all in the window) and with a NULL context (csrc/mask_analysis_host.hip)
 
 The three ways are checked to give the same matches, and device and host the same bytes, before anything is timed.  A call-* sample is the mean
 over --inner back-to-back calls; the per-pair method takes seconds to minutes and is sampled --pair-reps times (once at 50 images).  Prints one

@@ -2,7 +2,7 @@
 rasterised through masks_to_rle, ALL instances in one call.  Evaluations alternate inside one process, after a warm-up of each:
 
   device     amp_mask_region_props with a context (csrc/region_props.hip): upload, five launches, download, stream synchronise -- all in the window
-  host       the same call with a NULL context (csrc/rle_host.hip)
+  host       the same call with a NULL context (csrc/mask_analysis_host.hip)
   table-*    ampis_amd.analyze.region_properties(device='cuda' / 'cpu') from the RLE dicts, every key: the call plus run-length string decoding
              and the float derivation in Python -- what a user of the function waits for
   reference  the reference's method (ampis/structures.py:507): every mask decoded to the full image, then the dense scipy / numpy evaluation

@@ -6,7 +6,7 @@ Evaluations alternate inside one process, after a warm-up of each:
                         amp_seg_class_map call, string encoding of the class masks -- what a user waits for
   call-device           the bare amp_seg_class_map call on arrays pooled once, with a context (csrc/seg_class_map.hip: upload, one memset, five
                         launches, download, stream synchronise -- all in the window)
-  call-host             the same call with a NULL context (csrc/rle_host.hip)
+  call-host             the same call with a NULL context (csrc/mask_analysis_host.hip)
   dense                 the dense method as tests/seg_class_ref.py restates it (decode the two masks of every pair, OR into three planes, code,
                         encode the classes) -- already kinder than the reference, which holds every mask of both sides decoded at once
 
