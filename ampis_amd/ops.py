@@ -530,37 +530,108 @@ def sgd_step_tensors(ctx, p, g, v, offsets, sizes, is_bias, lr, momentum=0.9, we
     return norms, coefs
 
 
-def box_candidates(ctx, pred, proposals, prop_count, K, score_thresh, img_h, img_w, weights=(10., 10., 5., 5.), ccap=8192):
+def _i32c(t):
+    assert t.dtype == torch.int32 and t.is_contiguous() and t.is_cuda, "expected a contiguous int32 CUDA tensor"
+    return t
+
+
+def box_candidates(ctx, pred, proposals, prop_count, K, score_thresh, img_h, img_w, weights=(10., 10., 5., 5.), ccap=8192, img_hw=None):
+    """pred [B*Rcap, ld] or [B, Rcap, ld], proposals [B,Rcap,4], prop_count [B] i32; img_hw: optional device int32 [B,2], the (h, w) every
+    image's boxes are clipped to instead of img_h / img_w (amp_box_candidates_sized).
+    Returns (dense_boxes [B,Rcap*K,4], keys [B,ccap] sort words, cand_count [B] (may exceed ccap), overflow [1])."""
     B, Rcap, _ = proposals.shape
     dev = pred.device
+    assert pred.numel() == B * Rcap * pred.shape[-1] and pred.shape[-1] >= 5 * K + 1 and prop_count.numel() == B
     dense = torch.empty((B, Rcap * K, 4), device=dev)
     keys, cnt, ovf = _u64(B, ccap, device=dev), _i32(B, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
     w = (C.c_float * 4)(*weights)
-    check(lib().amp_box_candidates(ctx.handle, ptr(_f32c(pred)), pred.shape[-1], ptr(_f32c(proposals)), ptr(prop_count), B, Rcap,
-                                   K, w, float(score_thresh), img_h, img_w, ptr(dense), ptr(keys), ccap, ptr(cnt), ptr(ovf)),
-          "amp_box_candidates")
+    if img_hw is not None:
+        assert tuple(img_hw.shape) == (B, 2)
+    check(lib().amp_box_candidates_sized(ctx.handle, ptr(_f32c(pred)), pred.shape[-1], ptr(_f32c(proposals)), ptr(_i32c(prop_count)), B, Rcap,
+                                         K, w, float(score_thresh), img_h, img_w, ptr(_i32c(img_hw)) if img_hw is not None else None,
+                                         ptr(dense), ptr(keys), ccap, ptr(cnt), ptr(ovf)), "amp_box_candidates")
     return dense, keys, cnt, ovf
 
 
-def paste_rle(ctx, prob, det_boxes, det_batch, out_h, out_w, in_h, in_w, threshold=0.5, pool_counts=1 << 22):
-    """prob [N,28,28], det_boxes [N,4], det_batch [N] i32, out_h/out_w [B] i32 (device).
-    Returns (out_boxes [N,4], valid [N], list of uint32 run-length arrays)."""
+def gather_dets(ctx, sboxes, sscores, scats, keep_idx, keep_count, payload=None):
+    """amp_gather_dets: sorted candidates sboxes [B,cap,4] / sscores [B,cap] / scats [B,cap] i32 (/ payload [B,cap] i32), keep_idx [B,D] i32
+    positions in [0, cap), keep_count [B] i32 -> (det_boxes [B,D,4], det_scores [B,D], det_classes [B,D], payload [B,D] or None); the rows
+    from keep_count[b] on are zeros, class and payload -1."""
+    B, cap, _ = sboxes.shape
+    D = keep_idx.shape[1]
+    dev = sboxes.device
+    assert tuple(sscores.shape) == (B, cap) and tuple(scats.shape) == (B, cap) and keep_idx.shape[0] == B and keep_count.numel() == B
+    assert payload is None or tuple(payload.shape) == (B, cap)
+    db, ds, dc = torch.empty((B, D, 4), device=dev), torch.empty((B, D), device=dev), _i32(B, D, device=dev)
+    po = _i32(B, D, device=dev) if payload is not None else None
+    check(lib().amp_gather_dets(ctx.handle, B, cap, D, ptr(_f32c(sboxes)), ptr(_f32c(sscores)), ptr(_i32c(scats)), ptr(_i32c(keep_idx)),
+                                ptr(_i32c(keep_count)), ptr(db), ptr(ds), ptr(dc), ptr(_i32c(payload)) if payload is not None else None,
+                                ptr(po) if po is not None else None), "amp_gather_dets")
+    return db, ds, dc, po
+
+
+def compact_dets(ctx, det_count, det_boxes, det_scores, det_classes, out=None):
+    """amp_compact_dets: det_boxes [B,D,4], det_scores [B,D], det_classes [B,D] i32, det_count [B] i32 (device; clamped to D) -> the first
+    min(det_count[b], D) rows of every image in image order: (boxes [B*D,4], scores [B*D], classes [B*D], batch [B*D]), of which the first
+    sum(min(det_count, D)) rows are written.  out: the four tensors to write into (rows beyond the total keep their contents)."""
+    B, D = det_scores.shape
+    dev = det_boxes.device
+    assert tuple(det_boxes.shape) == (B, D, 4) and tuple(det_classes.shape) == (B, D) and det_count.numel() == B
+    if out is None:
+        out = (torch.zeros((B * D, 4), device=dev), torch.zeros((B * D,), device=dev), _i32(B * D, device=dev).zero_(),
+               _i32(B * D, device=dev).zero_())
+    boxes, scores, classes, batch = out
+    assert tuple(boxes.shape) == (B * D, 4) and scores.numel() == B * D and classes.numel() == B * D and batch.numel() == B * D
+    check(lib().amp_compact_dets(ctx.handle, B, D, ptr(_i32c(det_count)), ptr(_f32c(det_boxes)), ptr(_f32c(det_scores)), ptr(_i32c(det_classes)),
+                                 ptr(_f32c(boxes)), ptr(_f32c(scores)), ptr(_i32c(classes)), ptr(_i32c(batch))), "amp_compact_dets")
+    return boxes, scores, classes, batch
+
+
+def mask_prob(ctx, logits, classes):
+    """amp_mask_prob: logits [N,28,28,K], classes [N] i32 -> sigmoid of channel classes[n], [N,28,28] (a class outside [0, K): channel 0)."""
+    N, K = logits.shape[0], logits.shape[-1]
+    assert tuple(logits.shape) == (N, 28, 28, K) and classes.numel() == N
+    prob = torch.empty((N, 28, 28), device=logits.device)
+    check(lib().amp_mask_prob(ctx.handle, ptr(_f32c(logits)), ptr(_i32c(classes)), N, K, ptr(prob)), "amp_mask_prob")
+    return prob
+
+
+def paste_rle(ctx, prob, det_boxes, det_batch, out_h, out_w, in_h, in_w, threshold=0.5, pool_counts=1 << 22, in_hw=None, pos_scratch=False,
+              return_overflow=False, return_pool=False):
+    """prob [N,28,28], det_boxes [N,4], det_batch [N] i32, out_h/out_w [B] i32 (device) (amp_paste_rle_sized).
+    in_hw: optional device int32 [B,2], the network-input (h, w) of each image instead of in_h / in_w.
+    pos_scratch: the transition positions go to a second pool of pool_counts words and the first holds the run lengths only.
+    Returns (out_boxes [N,4], valid [N], list of uint32 run-length arrays); a full pool is an assertion unless return_overflow, which
+    appends the overflow flag (the masks that did not fit have no runs).  return_pool appends dict(used, pos_used, off [N], len [N])."""
     N = prob.shape[0]
     dev = prob.device
+    B = out_h.numel()
+    assert tuple(prob.shape) == (N, 28, 28) and tuple(det_boxes.shape) == (N, 4) and det_batch.numel() == N and out_w.numel() == B
+    assert in_hw is None or tuple(in_hw.shape) == (B, 2)
     ob, valid = torch.empty((N, 4), device=dev), _i32(N, device=dev)
     pool = torch.empty((pool_counts,), dtype=torch.int32, device=dev)
     used, off, ln = torch.zeros(1, dtype=torch.int64, device=dev), _u64(N, device=dev), _i32(N, device=dev)
     ovf = torch.zeros(1, dtype=torch.int32, device=dev)
+    pos = torch.empty((pool_counts,), dtype=torch.int32, device=dev) if pos_scratch else None
+    pos_used = torch.zeros(1, dtype=torch.int64, device=dev) if pos_scratch else None
     max_hw = int(max(out_h.max().item(), out_w.max().item()))
-    check(lib().amp_paste_rle(ctx.handle, ptr(_f32c(prob)), ptr(_f32c(det_boxes)), ptr(det_batch), N, ptr(out_h), ptr(out_w), max_hw,
-                              in_h, in_w, float(threshold), ptr(ob), ptr(valid), ptr(pool), pool_counts, ptr(used), ptr(off),
-                              ptr(ln), ptr(ovf)), "amp_paste_rle")
+    check(lib().amp_paste_rle_sized(ctx.handle, ptr(_f32c(prob)), ptr(_f32c(det_boxes)), ptr(_i32c(det_batch)), N, ptr(_i32c(out_h)),
+                                    ptr(_i32c(out_w)), max_hw, in_h, in_w, ptr(_i32c(in_hw)) if in_hw is not None else None, float(threshold),
+                                    ptr(ob), ptr(valid), ptr(pool), pool_counts, ptr(used), ptr(off), ptr(ln), ptr(ovf),
+                                    ptr(pos) if pos_scratch else None, pool_counts if pos_scratch else 0,
+                                    ptr(pos_used) if pos_scratch else None), "amp_paste_rle")
     torch.cuda.synchronize()
-    assert int(ovf.item()) == 0, "RLE pool overflow"
+    overflow = int(ovf.item())
+    assert return_overflow or overflow == 0, "RLE pool overflow"
     pool_h = pool.cpu().numpy().view("uint32")
     off_h, ln_h = off.cpu().numpy(), ln.cpu().numpy()
     runs = [pool_h[int(o): int(o) + int(l)].copy() for o, l in zip(off_h, ln_h)]
-    return ob, valid, runs
+    ret = (ob, valid, runs)
+    if return_overflow:
+        ret += (overflow,)
+    if return_pool:
+        ret += (dict(used=int(used.item()), pos_used=int(pos_used.item()) if pos_scratch else None, off=off_h, len=ln_h),)
+    return ret
 
 
 def rle_strings_device(ctx, pool, off, ln):

@@ -373,6 +373,8 @@ int amp_compact_dets(amp_ctx* ctx, int B, int D, const int* det_count, const flo
                      float* boxes, float* scores, int* classes, int* batch);
 
 /* Stages a16 / a17 / a3: mask probability, paste + threshold + RLE counts ----------------------- */
+/* logits [N,28,28,K] (channels last), classes [N] -> prob [N,28,28] = sigmoid of channel classes[n].  A class outside [0, K) (the -1 that
+ * amp_gather_dets leaves in unused rows) reads channel 0: the row is computed, never skipped, and nothing is read out of range. */
 int amp_mask_prob(amp_ctx* ctx, const float* logits, const int* classes, int N, int K, float* prob);
 /* the RPN head of one pyramid level in one kernel (AMP_CONV_F16X3; stage a11): x_split [B,H,W,256] (split rows) -> 3x3 conv + bias + ReLU ->
  * the 16 predictor rows (3 objectness logits, 12 anchor deltas, 1 zero row: w_pred [16][256], b_pred [16]) as a second product in the
