@@ -1,6 +1,7 @@
 // The four mask analyses on run lists: what their entry points (edge_distance.hip, region_props.hip, rle_overlap.hip, seg_class_map.hip) share
 // with mask_analysis_host.hip.  Each *_check validates the arguments and builds the plan (run_list.h) that both paths evaluate; each *_host is
-// the evaluation with a NULL context, byte for byte what the kernels give.  Plain C++: the host-only sanitizer builds include this header.
+// the evaluation with a NULL context, byte for byte what the kernels give.  amp_label_runs, the producer of run lists from an annotation image
+// (label_runs.hip, label_runs_host.hip), is declared at the end.  Plain C++: the host-only sanitizer builds include this header.
 #pragma once
 #include "run_list.h"
 
@@ -34,5 +35,23 @@ int seg_class_map_check(const uint32_t* gpool, const unsigned long long* goff, c
                         const unsigned long long* pixels, RunPlan& g, RunPlan& p, unsigned long long* need);
 int seg_class_map_host(const RunPlan& g, const RunPlan& p, const int* pair_g, const int* pair_p, int n, int h, int w, int mode, uint32_t* counts,
                        unsigned long long* counts_off, unsigned long long* pixels);
+
+// amp_label_runs (label_runs_host.hip, label_runs.hip).  The check looks at the arguments only; both paths report their needs through
+// label_runs_capacity before they write anything else.
+int label_runs_check(const void* image, int h, int w, int kind, int connectivity, const int* ids, const int* boxes, const unsigned int* areas,
+                     const uint32_t* counts, const unsigned long long* counts_off, const int* counts_len, int inst_cap,
+                     const unsigned long long* need);
+int label_runs_capacity(unsigned long long instances, unsigned long long counts, int inst_cap, unsigned long long counts_cap,
+                        unsigned long long* need);
+int label_runs_host(const void* image, int h, int w, int kind, int connectivity, int zero_is_background, int* ids, int* boxes,
+                    unsigned int* areas, uint32_t* counts, unsigned long long* counts_off, int* counts_len, int inst_cap,
+                    unsigned long long counts_cap, int* labels, unsigned long long* need);
+
+// the pixel of an annotation image as both paths read it: foreground is 1 in a BINARY image, the id in a LABEL image; a pixel belongs to an
+// instance unless it is 0 and 0 is background
+AMP_HD int label_pixel(const void* image, int kind, size_t i) {
+    return kind == 0 ? (static_cast<const uint8_t*>(image)[i] != 0 ? 1 : 0) : static_cast<const int*>(image)[i];
+}
+AMP_HD bool label_is_instance(int v, int kind, int zero_is_background) { return v != 0 || (kind != 0 && !zero_is_background); }
 
 }  // namespace amp

@@ -70,20 +70,31 @@ def _ddict(image_id, file_name, annotation_file, hw, mask_format, instances, dat
     return d
 
 
-def _label_image_records(fmt, im_root, ann_root, pattern):
+def _label_image_records(fmt, im_root, ann_root, pattern, device="auto"):
     """'binary' / 'label': one annotation image (or .npy) per micrograph; 'binary' is split into its 8-connected components (the
-    default of skimage.measure.label), 'label' already carries one id per instance.  Yields (image path, annotation path, hw, masks)."""
-    from scipy import ndimage
+    default of skimage.measure.label), 'label' already carries one id per instance.  Yields (image path, annotation path, hw, instances):
+    one (box, RLE) per instance from ONE analyze.label_image_to_rle call per image.  An annotation that is not a 2-D integer image ('label':
+    several channels, floats, ids beyond int32) takes the reference's own way: a dense mask, a box and an encode per instance."""
+    from .analyze import label_image_to_rle
     for img_path in im_root.glob(pattern):            # directory order, like the reference (ampis/data_utils.py:394-395): same image_id per file
         found = list(ann_root.glob("*{}*".format(img_path.stem)))
         assert len(found) == 1, f"There must be exactly 1 annotation file for, {img_path.name}, but {len(found)} were found"
         ann = np.load(str(found[0])) if found[0].suffix == ".npy" else _imread(found[0])
         hw = ann.shape[:2]
+        if fmt == "binary" and ann.ndim in (2, 3):
+            ann = (ann if ann.ndim == 2 else ann[..., 0]).astype(bool)
+        fits = ann.ndim == 2 and ann.size and (fmt == "binary" or (np.issubdtype(ann.dtype, np.integer) and
+                                                                  int(ann.min()) >= -2 ** 31 and int(ann.max()) <= 2 ** 31 - 1))
+        if fits:
+            rles, boxes, _, _ = label_image_to_rle(ann, fmt, connectivity=2, device=device)
+            yield img_path, found[0], hw, list(zip(boxes, rles))
+            continue
         if fmt == "binary":
-            fg = (ann if ann.ndim == 2 else ann[..., 0]).astype(bool)
-            ann = ndimage.label(fg, structure=np.ones((3, 3), int))[0]
+            from scipy import ndimage
+            ann = ndimage.label(ann.astype(bool), structure=np.ones((3, 3), int))[0]
         ids = np.unique(ann)
-        yield img_path, found[0], hw, [ann == u for u in ids[ids != 0]] if ids.size and ids[0] == 0 else [ann == u for u in ids]
+        masks = [ann == u for u in ids[ids != 0]] if ids.size and ids[0] == 0 else [ann == u for u in ids]
+        yield img_path, found[0], hw, [(extract_boxes(m)[0], RLE.encode(np.asfortranarray(m))) for m in masks]
 
 
 def _via2_records(json_path):
@@ -122,9 +133,11 @@ def _rle_records(json_path):
         yield Path(json_path.parent, Path(item["file_name"])), tuple(rles[0]["size"]), rles
 
 
-def get_ddicts(label_fmt, im_root, ann_root=None, pattern="*", dataset_class=None):
+def get_ddicts(label_fmt, im_root, ann_root=None, pattern="*", dataset_class=None, device="auto"):
     """Images + single-class instance annotations -> detectron2 dataset dicts. label_fmt: 'binary' | 'label' (annotation images /
-    .npy next to the images), 'via2' (VIA 2 JSON; im_root is the JSON path), 'rle' (JSON list of {'file_name','segmentations'})."""
+    .npy next to the images), 'via2' (VIA 2 JSON; im_root is the JSON path), 'rle' (JSON list of {'file_name','segmentations'}).
+    device ('binary' / 'label' only): where the annotation images are turned into instances -- 'cpu', 'cuda' or 'auto', as
+    analyze.label_image_to_rle; the dicts are the same."""
     from pathlib import Path
     im_root = Path(im_root)
     ann_root = Path(ann_root) if ann_root else None
@@ -138,8 +151,8 @@ def get_ddicts(label_fmt, im_root, ann_root=None, pattern="*", dataset_class=Non
 
     out = []
     if fmt in ("binary", "label"):
-        for img, ann_path, hw, masks in _label_image_records(fmt, im_root, ann_root, pattern):
-            inst = [_instance(extract_boxes(m)[0], RLE.encode(np.asfortranarray(m))) for m in masks]
+        for img, ann_path, hw, found in _label_image_records(fmt, im_root, ann_root, pattern, device):
+            inst = [_instance(box, seg) for box, seg in found]
             out.append(_ddict(len(out), rel(img), rel(ann_path), hw, "bitmask", inst, dataset_class))
     elif fmt == "via2":
         for img, hw, hfw, regions in _via2_records(im_root):

@@ -319,6 +319,40 @@ def seg_class_map(gt, pred, pairs, mode, ctx=None, size=None):
     return [counts[int(coff[k]): int(coff[k + 1])].copy() for k in range(K)], pixels.astype(np.int64)
 
 
+LABEL_KINDS = {"binary": 0, "label": 1}
+
+
+def label_runs(image, kind, connectivity=2, zero_is_background=True, ctx=None, return_labels=False):
+    """The instances of an annotation image as run lists, at most two C calls (amp_label_runs: the first reports the capacities when the guess
+    was too small).  image: 2-D; kind 'binary' (uint8, nonzero is foreground: the connected components, connectivity 1 = 4 neighbours, 2 = 8,
+    numbered by the row-major position of their first pixel) or 'label' (int32 ids: one instance per distinct id in ascending order, id 0 skipped
+    when zero_is_background).  Returns (ids int32 [N], boxes int32 [N, 4] {r0, c0, r1, c1} ends exclusive, areas uint32 [N], pool, off, len) --
+    instance i's COCO counts are pool[off[i] : off[i] + len[i]] -- and the int32 label image (instance number, 0 elsewhere) when return_labels.
+    ctx: a _lib.Context (computed on its device) or None (on the host): the same bytes."""
+    k = LABEL_KINDS.get(kind if not isinstance(kind, str) else kind.lower())
+    if k is None:
+        raise ValueError(f"label_runs: kind = {kind!r} ('binary' or 'label')")
+    img = np.ascontiguousarray(image, dtype=np.int32 if k else np.uint8)
+    if img.ndim != 2:
+        raise ValueError(f"label_runs: a 2-D image is required, got shape {img.shape}")
+    h, w = img.shape
+    labels = np.empty((h, w), dtype=np.int32) if return_labels else None
+    need = np.zeros(2, dtype=np.uint64)
+    icap, ccap = 1024, 4 * (h + w) + 4096
+    for attempt in range(2):
+        ids, boxes, areas = np.empty(icap, np.int32), np.empty((icap, 4), np.int32), np.empty(icap, np.uint32)
+        pool, off, ln = np.empty(ccap, np.uint32), np.empty(icap, np.uint64), np.empty(icap, np.int32)
+        st = lib().amp_label_runs(_handle(ctx), _vp(img), h, w, k, int(connectivity), int(bool(zero_is_background)), _vp(ids), _vp(boxes),
+                                  _vp(areas), _vp(pool), _vp(off), _vp(ln), icap, ccap, _vp(labels) if return_labels else None, _vp(need))
+        if st != -3 or attempt:                                     # AMP_ERR_NOMEM the first time: the needs are known now
+            check(st, "amp_label_runs")
+            break
+        icap, ccap = max(int(need[0]), 1), max(int(need[1]), 1)
+    n, total = int(need[0]), int(need[1])
+    out = (ids[:n], boxes[:n], areas[:n], pool[:total], off[:n], ln[:n])
+    return out + (labels,) if return_labels else out
+
+
 def merge(rles, intersect=False):
     assert len(rles) >= 1
     h, w = rles[0]["size"]

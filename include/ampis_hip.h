@@ -566,6 +566,25 @@ int amp_seg_class_map(amp_ctx* ctx, const uint32_t* gpool, const unsigned long l
                       const unsigned long long* poff, const int* plen, int np, const int* pair_g, const int* pair_p, int n, int h, int w,
                       int mode /* 0 reduced, 1 all */, uint32_t* counts, unsigned long long counts_cap,
                       unsigned long long* counts_off /* [K + 1] */, unsigned long long* pixels /* [8] */);
+/* Instances of an annotation image as COCO run lists (ampis/data_utils.py:412-428, get_ddicts 'binary' / 'label': label the foreground, one dense
+ * mask per instance, encode each).  ALL POINTERS ARE HOST POINTERS.  image: h x w, row-major as numpy holds it, 1 <= h, w and h * w <= 2^30.
+ * kind AMP_LABEL_BINARY: uint8, nonzero is foreground; the instances are the connected components -- connectivity 1: 4 neighbours, 2: 8
+ * neighbours -- numbered 1 .. K by the row-major position of their first pixel (scipy.ndimage.label, skimage.measure.label).
+ * kind AMP_LABEL_IDS: int32 ids; one instance per distinct id in ascending order, disconnected parts included; zero_is_background != 0 skips id 0
+ * (connectivity is checked and not used).  Per instance i, in instance order: ids[i] (the component number or the id), boxes[4 i ..] = {r0, c0,
+ * r1, c1} the tight box with exclusive ends, areas[i], and the run list counts[counts_off[i] .. + counts_len[i]) over the whole image --
+ * column-major, the first count is the run of zeros and may be 0 -- exactly what amp_rle_encode gives for the instance's dense mask.
+ * labels (may be NULL): the int32 h x w image, row-major, of instance number i + 1 at the pixels of instance i and 0 elsewhere.
+ * inst_cap: capacity of ids / boxes / areas / counts_off / counts_len in instances; counts_cap: of counts in values.  With valid arguments
+ * need[0] = the instances and need[1] = the counts are always written; with a capacity below its need the call returns AMP_ERR_NOMEM naming
+ * both and writes nothing else.  Arguments are checked on the host before any device work (AMP_ERR_ARG naming the argument, nothing written).
+ * ctx == NULL: computed on the host (label_runs_host.hip: run-based union-find).  Otherwise on ctx's device and stream (label_runs.hip): upload, a
+ * fixed list of launches whatever the image holds, download; integer arithmetic only, the bytes do not depend on the device's scheduling and
+ * equal the host's. */
+enum { AMP_LABEL_BINARY = 0, AMP_LABEL_IDS = 1 };
+int amp_label_runs(amp_ctx* ctx, const void* image, int h, int w, int kind, int connectivity, int zero_is_background, int* ids, int* boxes,
+                   unsigned int* areas, uint32_t* counts, unsigned long long* counts_off, int* counts_len, int inst_cap,
+                   unsigned long long counts_cap, int* labels, unsigned long long* need /* [2] */);
 /* Nearest-neighbour resize (+ horizontal mirror when flip) of a mask in the run-length domain: the runs of
  * flip(PIL.Image.resize(decode(cnts), (nw, nh), NEAREST)) -- what detectron2's ResizeTransform.apply_segmentation + HFlipTransform do to a bitmask
  * annotation -- without decoding (Pillow's ImagingScaleAffine pixel correspondence, restated).  cap >= nh * nw + 1 is always enough. */
