@@ -248,6 +248,7 @@ def _declare(L):
         "amp_mask_region_props": ([vp, vp, vp, vp, i, i, i, vp, vp], i),
         "amp_rle_overlap_groups": ([vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp, C.c_size_t, vp, vp], i),
         "amp_seg_class_map": ([vp, vp, vp, vp, i, vp, vp, vp, i, vp, vp, i, i, i, i, vp, C.c_ulonglong, vp, vp], i),
+        "amp_render_instances": ([vp, vp, i, i, vp, vp, vp, i, vp, vp, vp, vp, i, vp], i),
         "amp_label_runs": ([vp, vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp, i, C.c_ulonglong, vp, vp], i),
         "amp_rle_from_polygon": ([vp, i, i, i, vp, i, C.POINTER(i)], i),
         "amp_model_cfg_default": ([C.POINTER(ModelCfg)], i),

@@ -24,6 +24,10 @@ pycocotools:
   * `overlap_matrix` (the all-pairs RLE.merge(intersect=True) + RLE.area loop of ampis/applications/powder.py:82) and `mask_areas`
     (ampis/structures.py:536-583): ONE `amp_rle_overlap_groups` call gives the exact pixel count of every pair of masks of an image, or of
     every image of a sample (ampis_amd/applications/powder.py), on the device (csrc/rle_overlap.hip) or on the host.
+  * `render_instances` (detectron2 Visualizer.overlay_instances, what visualize.display_iset / display_ddicts end in): ONE `amp_render_instances`
+    call draws the fill, the edge and the box frame of every instance of an image in draw order from the run lists, on the device
+    (csrc/render.hip) or on the host; the blend arrives as a lookup table built with the dense path's own NumPy expression, so the bytes equal
+    the per-instance full-image passes of utils/visualizer.py.
 With no prediction at all the detection precision is 0/0: like the reference this raises ZeroDivisionError.
 The independent checker is oracle/matcher.py (a loop-for-loop restatement of the reference, pinned by its known-answer test)."""
 import numpy as np
@@ -528,3 +532,66 @@ def det_perf_iset(gt, pred, match_results=None, colormap=None, tp_gt=False, size
     if return_colormap:
         return iset, colormap
     return iset
+
+
+# ---- instance overlays (detectron2 Visualizer.overlay_instances: utils/visualizer.py draw_binary_mask + draw_box per instance) -----------------
+
+def render_order(boxes, n):
+    """The Visualizer's draw order of n instances: large boxes first so that small instances stay visible, the given order without boxes."""
+    return np.argsort(-np.prod(boxes[:, 2:] - boxes[:, :2], axis=1)) if boxes is not None else np.arange(n)
+
+
+def render_inputs(colors, alpha, boxes, h, w):
+    """What amp_render_instances looks up, built with the expressions of Visualizer.draw_binary_mask / draw_box so that the bytes agree by
+    construction: (tables uint8 [n, 256, 3] -- the blend of every pixel value --, edge colours uint8 [n, 3], int32 [n, 4] boxes rounded and
+    clipped to the h x w image or None, box colours uint8 [n, 3]).  colors: [n, 3] in [0, 1]; 0 <= alpha <= 1."""
+    col = np.asarray(colors, dtype=np.float64).reshape(-1, 3) * 255.0
+    tables = (np.arange(256.)[None, :, None] * (1.0 - alpha) + (col * alpha)[:, None, :] + 0.5).astype(np.uint8)
+    edge_rgb = np.clip(col * 0.7, 0, 255).astype(np.uint8)
+    box_rgb = np.clip(col, 0, 255).astype(np.uint8)
+    ibox = None
+    if boxes is not None:
+        b = np.rint(np.asarray(boxes, dtype=np.float64).reshape(-1, 4))           # round half to even, like round() in draw_box
+        if not np.isfinite(b).all():
+            raise ValueError("render_instances: boxes must be finite")
+        ibox = np.stack([np.clip(b[:, 0], 0, w - 1), np.clip(b[:, 1], 0, h - 1), np.clip(b[:, 2], 0, w - 1), np.clip(b[:, 3], 0, h - 1)],
+                        axis=1).astype(np.int32)
+    return tables, edge_rgb, ibox, box_rgb
+
+
+def render_instances(image, masks=None, boxes=None, colors=None, alpha=0.5, edge=True, order=None, line_width=None, size=None, device='auto'):
+    """The overlay of Visualizer.overlay_instances at image scale without its labels, as a new uint8 [H, W, 3] array: for every instance in draw
+    order the mask's pixels blended with its colour (uint8(v (1 - alpha) + 255 colour alpha + 0.5), rounded once per covering instance), its edge
+    pixels -- a 4-neighbour outside the mask, or the image's border -- set to 0.7 of the colour when `edge`, then its XYXY box framed
+    `line_width` wide (None: max(1, round(max(H, W) / 600))).  Byte for byte what Visualizer.draw_binary_mask + draw_box give per instance.
+
+    image: [H, W, 3] (or grey [H, W]); masks: anything masks_to_rle accepts (size=(h, w) defaults to the image's), None for boxes only; boxes:
+    [n, 4] XYXY, a Boxes, or None; colors: [n, 3] in [0, 1], None for the Visualizer's palette; order: the draw order, None for the
+    Visualizer's rule (large boxes first); device: 'cpu' (host), 'cuda' (HIP device, an error without one) or 'auto' (the device when one is
+    visible).  One amp_render_instances call on the run lists (csrc/render.hip, or mask_analysis_host.hip on the host: identical bytes); no
+    mask is decoded.  ValueError for alpha or a colour outside [0, 1], masks of another size than the image, a bad `device`."""
+    from .utils.visualizer import Visualizer, _palette
+    img = np.asarray(image)
+    if img.ndim == 2:
+        img = img[:, :, None]
+    if img.shape[2] == 1:
+        img = np.repeat(img, 3, axis=2)
+    img = np.ascontiguousarray(np.clip(img[:, :, :3], 0, 255).astype(np.uint8))
+    h, w = img.shape[:2]
+    rles = masks_to_rle(masks, (h, w) if size is None else size) if masks is not None else None
+    bx = Visualizer._box_array(boxes)
+    n = len(bx) if bx is not None else (len(rles) if rles is not None else 0)
+    if rles is not None and len(rles) != n:
+        raise ValueError(f"render_instances: {len(rles)} masks for {n} boxes")
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"render_instances: alpha = {alpha!r} (0 .. 1)")
+    col = _palette(n) if colors is None else np.asarray(colors, dtype=np.float64).reshape(n, -1)[:, :3]
+    if n and not (np.isfinite(col).all() and col.min() >= 0.0 and col.max() <= 1.0):
+        raise ValueError("render_instances: colours must lie in [0, 1]")
+    ctx = _device_context("render_instances", device, n)
+    if n == 0:
+        return img.copy()
+    order = render_order(bx, n) if order is None else np.asarray(order, dtype=np.int64).reshape(-1)
+    lw = int(line_width if line_width is not None else max(1, round(max(h, w) / 600)))
+    tables, edge_rgb, ibox, box_rgb = render_inputs(col[order], alpha, bx[order] if bx is not None else None, h, w)
+    return rle.render_instances(img, [rles[i] for i in order] if rles is not None else None, tables, edge_rgb if edge else None, ibox, box_rgb, lw, ctx=ctx)

@@ -1,4 +1,4 @@
-// The four mask analyses on run lists: what their entry points (edge_distance.hip, region_props.hip, rle_overlap.hip, seg_class_map.hip) share
+// The mask analyses on run lists: what their entry points (edge_distance.hip, region_props.hip, rle_overlap.hip, seg_class_map.hip, render.hip) share
 // with mask_analysis_host.hip.  Each *_check validates the arguments and builds the plan (run_list.h) that both paths evaluate; each *_host is
 // the evaluation with a NULL context, byte for byte what the kernels give.  amp_label_runs, the producer of run lists from an annotation image
 // (label_runs.hip, label_runs_host.hip), is declared at the end.  Plain C++: the host-only sanitizer builds include this header.
@@ -35,6 +35,26 @@ int seg_class_map_check(const uint32_t* gpool, const unsigned long long* goff, c
                         const unsigned long long* pixels, RunPlan& g, RunPlan& p, unsigned long long* need);
 int seg_class_map_host(const RunPlan& g, const RunPlan& p, const int* pair_g, const int* pair_p, int n, int h, int w, int mode, uint32_t* counts,
                        unsigned long long* counts_off, unsigned long long* pixels);
+
+// amp_render_instances.  Every mask is planned (none when pool is NULL: the plan stays empty); rects = per instance the four rectangles
+// {row0, row1, col0, col1} of its box outline, ends exclusive and inside the image, [n][4][4], empty without boxes.  render_host draws on img
+// in place.
+int render_check(const uint8_t* image, int h, int w, const uint32_t* pool, const unsigned long long* off, const int* len, int n,
+                 const uint8_t* fill_tab, const uint8_t* edge_rgb, const int* boxes, const uint8_t* box_rgb, int lw, const uint8_t* out,
+                 RunPlan& runs, std::vector<int>& rects);
+int render_host(const RunPlan& runs, const uint8_t* fill_tab, const uint8_t* edge_rgb, const std::vector<int>& rects, const uint8_t* box_rgb,
+                int n, int h, int w, uint8_t* img);
+
+// The pixels of the word m of column col, bit 0 = image row row0, whose four neighbours are all in the mask and that lie in no border row or
+// column of the h x w image (draw_binary_mask's `inner`); up / down / left / right: the mask one row above / below, one column left / right
+AMP_HD u64 render_inner(u64 m, u64 up, u64 down, u64 left, u64 right, int row0, int col, int h, int w) {
+    u64 inner = m & up & down & left & right;
+    if (col == 0 || col == w - 1) inner = 0;
+    if (row0 == 0) inner &= ~1ull;
+    const long long last = (long long)h - 1 - row0;
+    if (last >= 0 && last < 64) inner &= ~(1ull << last);
+    return inner;
+}
 
 // amp_label_runs (label_runs_host.hip, label_runs.hip).  The check looks at the arguments only; both paths report their needs through
 // label_runs_capacity before they write anything else.

@@ -1,7 +1,9 @@
-// Host side of the four mask analyses on COCO run lists -- mask_edge_distance, region properties, group overlap, segmentation class map
+// Host side of the mask analyses on COCO run lists -- mask_edge_distance, region properties, group overlap, segmentation class map, overlays
 // (mask_analysis.h): the argument checks, which build the plan (run_list.h: plan_add_mask, the one walk over a run list) that the device path
 // and the host path both evaluate, and the host evaluations, what each call runs with a NULL context.  Plain C++ throughout: the host-only
 // sanitizer builds of tests/sanitize compile this file with g++.
+#include <string.h>
+
 #include <algorithm>
 #include <vector>
 
@@ -383,3 +385,81 @@ int seg_class_map_host(const RunPlan& g, const RunPlan& p, const int* pair_g, co
 
 }  // namespace amp
 
+
+// ---- instance overlays (ampis_amd/utils/visualizer.py: draw_binary_mask + draw_box per instance, in draw order): the argument checks, which
+// build the plan and the outline rectangles, and the host drawing: per instance one walk over its runs into a bit plane of its tight box, the
+// edge rule on the plane's words (render_inner, shared with render.hip), then the table lookups and the four rectangles on the pixels.
+namespace amp {
+
+int render_check(const uint8_t* image, int h, int w, const uint32_t* pool, const unsigned long long* off, const int* len, int n,
+                 const uint8_t* fill_tab, const uint8_t* edge_rgb, const int* boxes, const uint8_t* box_rgb, int lw, const uint8_t* out,
+                 RunPlan& runs, std::vector<int>& rects) {
+    (void)edge_rgb;
+    AMP_REQUIRE(image && out, "amp_render_instances: null image");
+    AMP_REQUIRE(n >= 0, "amp_render_instances: n = %d", n);
+    AMP_REQUIRE(lw >= 1, "amp_render_instances: lw = %d (at least 1)", lw);
+    AMP_REQUIRE(h >= 1 && w >= 1 && (unsigned long long)h * w <= (1ull << 30), "amp_render_instances: image size %d x %d (at most 2^30 pixels)", h, w);
+    AMP_REQUIRE(n == 0 || !pool || (off && len && fill_tab), "amp_render_instances: null argument (off, len and fill_tab go with pool)");
+    AMP_REQUIRE(n == 0 || !boxes || box_rgb, "amp_render_instances: null argument (box_rgb goes with boxes)");
+    const unsigned long long area = (unsigned long long)h * w;
+    runs.reset(pool ? (size_t)n : 0);
+    for (int p = 0; pool && p < n; ++p) {
+        u64 covered = 0;
+        const RunListFault f = plan_add_mask(runs, (size_t)p, pool + off[p], len[p], h, w, false, &covered);
+        AMP_REQUIRE(f != RUNS_EMPTY, "amp_render_instances: mask %d has an empty run list", p);
+        AMP_REQUIRE(f != RUNS_OVER, "amp_render_instances: the runs of mask %d cover more than the image's %llu pixels", p, area);
+        AMP_REQUIRE(f != RUNS_SHORT, "amp_render_instances: the runs of mask %d cover %llu pixels, the image has %llu", p, covered, area);
+        AMP_REQUIRE(f == RUNS_OK, "amp_render_instances: the masks of one call have more than 2^31 runs");
+    }
+    rects.assign(boxes ? (size_t)n * 16 : 0, 0);
+    for (int p = 0; boxes && p < n; ++p) {
+        const int x0 = boxes[4 * (size_t)p], y0 = boxes[4 * (size_t)p + 1], x1 = boxes[4 * (size_t)p + 2], y1 = boxes[4 * (size_t)p + 3];
+        AMP_REQUIRE(x0 >= 0 && x0 < w && x1 >= 0 && x1 < w && y0 >= 0 && y0 < h && y1 >= 0 && y1 < h,
+                    "amp_render_instances: box %d = (%d, %d, %d, %d) outside the %d x %d image", p, x0, y0, x1, y1, h, w);
+        const int ya = (int)std::min<long long>((long long)y0 + lw, h), yb = (int)std::max<long long>((long long)y1 - lw + 1, 0);
+        const int xa = (int)std::min<long long>((long long)x0 + lw, w), xb = (int)std::max<long long>((long long)x1 - lw + 1, 0);
+        const int r[16] = {y0, ya, x0, x1 + 1, yb, y1 + 1, x0, x1 + 1, y0, y1 + 1, x0, xa, y0, y1 + 1, xb, x1 + 1};
+        std::copy(r, r + 16, &rects[16 * (size_t)p]);
+    }
+    return AMP_OK;
+}
+
+int render_host(const RunPlan& runs, const uint8_t* fill_tab, const uint8_t* edge_rgb, const std::vector<int>& rects, const uint8_t* box_rgb,
+                int n, int h, int w, uint8_t* img) {
+    std::vector<u64> mask;
+    for (int i = 0; i < n; ++i) {
+        if (!runs.m.empty() && runs.m[(size_t)i].n > 0) {
+            const RunMask& mk = runs.m[(size_t)i];
+            const int H = mk.r1 - mk.r0, W = mk.c1 - mk.c0, pitch = (H + 63) >> 6;
+            mask.assign((size_t)W * pitch, 0ull);
+            for (int k = 0; k < mk.n; ++k)                                        // inside the tight box by construction
+                paint_run<false>(runs.S[mk.ro + k], runs.E[mk.ro + k], h, mask.data(), mk.r0, mk.c0, H, W, pitch, OrPlain());
+            const uint8_t* tab = fill_tab + 768 * (size_t)i;
+            for (int q = 0; q < W; ++q)
+                for (int wv = 0; wv < pitch; ++wv) {
+                    const u64* at = &mask[(size_t)q * pitch + wv];
+                    const u64 m = *at;
+                    if (!m) continue;
+                    const int row0 = mk.r0 + (wv << 6), col = mk.c0 + q;
+                    u64 edge = 0;
+                    if (edge_rgb) {                                               // beyond the tight box the mask is empty
+                        const u64 up = (m << 1) | (wv > 0 ? at[-1] >> 63 : 0ull), down = (m >> 1) | (wv + 1 < pitch ? at[1] << 63 : 0ull);
+                        edge = m & ~render_inner(m, up, down, q > 0 ? at[-pitch] : 0ull, q + 1 < W ? at[pitch] : 0ull, row0, col, h, w);
+                    }
+                    for (u64 x = m; x; x &= x - 1) {
+                        const int b = ctz(x);
+                        uint8_t* px = img + ((size_t)(row0 + b) * w + col) * 3;
+                        for (int c = 0; c < 3; ++c) px[c] = (edge >> b) & 1 ? edge_rgb[3 * (size_t)i + c] : tab[3 * px[c] + c];
+                    }
+                }
+        }
+        for (int q = 0; q < 4 && !rects.empty(); ++q) {
+            const int* r = &rects[16 * (size_t)i + 4 * q];
+            for (int y = r[0]; y < r[1]; ++y)
+                for (int x = r[2]; x < r[3]; ++x) memcpy(img + ((size_t)y * w + x) * 3, box_rgb + 3 * (size_t)i, 3);
+        }
+    }
+    return AMP_OK;
+}
+
+}  // namespace amp

@@ -166,6 +166,32 @@ __device__ __forceinline__ int first_run_ending_after(const unsigned int* __rest
     return lo;
 }
 
+// the 64 rows [a, a + 64) of the column-major image of one mask as a word, a and b pixel positions with b <= a + 64 the end of the word or of
+// its column.  S, E: the run starts and ends, ascending; S[n] = 0xffffffff closes the list
+__device__ __forceinline__ u64 mask_word(const unsigned int* __restrict__ S, const unsigned int* __restrict__ E, int n, unsigned int a,
+                                         unsigned int b) {
+    u64 word = 0;
+    for (int k = first_run_ending_after(E, n, a); S[k] < b; ++k)                               // k <= n: the closing entry stops the walk
+        word |= word_span((int)(max(S[k], a) - a), (int)(min(E[k], b) - a));                   // bits [from, to), 0 <= from < to <= 64
+    return word;
+}
+
+// mask_word with the pixels above and below it: positions [a, b) of one column [cb, ce) as the word, *up = the mask at a - 1 (0 when a is
+// the column's first row), *down = the mask at b (0 when b is the column's end).  One search, then the runs in order.
+__device__ __forceinline__ u64 mask_word_halo(const unsigned int* __restrict__ S, const unsigned int* __restrict__ E, int n, unsigned int cb,
+                                              unsigned int ce, unsigned int a, unsigned int b, u64* up, u64* down) {
+    const unsigned int a1 = a > cb ? a - 1 : a, b1 = b < ce ? b + 1 : b;
+    u64 word = 0;
+    *up = 0; *down = 0;
+    for (int k = first_run_ending_after(E, n, a1); S[k] < b1; ++k) {
+        unsigned int s = max(S[k], a1), e = min(E[k], b1);
+        if (s < a) { *up = 1; s = a; }
+        if (e > b) { *down = 1; e = b; }
+        if (s < e) word |= word_span((int)(s - a), (int)(e - a));
+    }
+    return word;
+}
+
 // Inclusive scan of one value per thread over a workgroup of 1024, in the LDS array s[1024]; every thread calls it.  A fixed tree and no
 // atomics: the order is fixed and the bytes repeat.  s[1023] is the total once it returns.
 __device__ __forceinline__ u64 block_scan_1024(u64* s, u64 v) {

@@ -35,15 +35,6 @@ struct ScPair {
     int c0, wv0, nwords, pad;     // first column and first word row of the union box, words per column of the box
 };
 
-// the 64 rows [a, a + 64) of the column-major image of one mask.  E: the run ends, ascending; S[n] = 0xffffffff closes the list
-__device__ __forceinline__ u64 sc_mask_word(const unsigned int* __restrict__ S, const unsigned int* __restrict__ E, int n, unsigned int a,
-                                               unsigned int b) {
-    u64 word = 0;
-    for (int k = amp::first_run_ending_after(E, n, a); S[k] < b; ++k)                          // k <= n: the closing entry stops the walk
-        word |= amp::word_span((int)(max(S[k], a) - a), (int)(min(E[k], b) - a));              // bits [from, to), 0 <= from < to <= 64
-    return word;
-}
-
 __global__ __launch_bounds__(256) void sc_paint_kernel(const ScPair* __restrict__ pairs, int n, const unsigned long long* __restrict__ ioff,
                                                        unsigned long long total, const RunMask* __restrict__ gm, const RunMask* __restrict__ pm,
                                                        const unsigned int* __restrict__ gS, const unsigned int* __restrict__ gE,
@@ -56,7 +47,7 @@ __global__ __launch_bounds__(256) void sc_paint_kernel(const ScPair* __restrict_
         const int col = pr.c0 + (int)(local / (unsigned)pr.nwords), wv = pr.wv0 + (int)(local % (unsigned)pr.nwords);
         const unsigned int a = (unsigned)col * (unsigned)h + ((unsigned)wv << 6), b = min(a + 64u, ((unsigned)col + 1u) * (unsigned)h);
         const RunMask G = gm[pr.g], Q = pm[pr.q];
-        const u64 g = sc_mask_word(gS + G.ro, gE + G.ro, G.n, a, b), q = sc_mask_word(pS + Q.ro, pE + Q.ro, Q.n, a, b);
+        const u64 g = amp::mask_word(gS + G.ro, gE + G.ro, G.n, a, b), q = amp::mask_word(pS + Q.ro, pE + Q.ro, Q.n, a, b);
         unsigned long long* at = planes + (size_t)col * pitch + wv;
         if (g & q) atomicOr(at, g & q);
         if (g & ~q) atomicOr(at + units, g & ~q);

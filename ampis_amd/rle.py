@@ -319,6 +319,38 @@ def seg_class_map(gt, pred, pairs, mode, ctx=None, size=None):
     return [counts[int(coff[k]): int(coff[k + 1])].copy() for k in range(K)], pixels.astype(np.int64)
 
 
+def render_instances(image, masks, tables, edge_rgb, boxes, box_rgb, lw, ctx=None):
+    """Instance overlays of one image, one C call (amp_render_instances): image uint8 [h, w, 3]; per instance in draw order masks[i] (RLE dicts
+    of the image's size; None: no masks), tables[i] uint8 [256, 3] (a mask pixel holding v in channel c becomes tables[i][v][c]), edge_rgb[i]
+    uint8 [3] for the mask's edge pixels (None: no edges), boxes[i] int (x0, y0, x1, y1) inside the image (None: no boxes) framed lw pixels wide
+    in box_rgb[i].  Returns the drawn uint8 [h, w, 3] array; the image is not written.  ctx: a _lib.Context (drawn on its device) or None (on
+    the host): the same bytes."""
+    img = np.ascontiguousarray(image, dtype=np.uint8)
+    assert img.ndim == 3 and img.shape[2] == 3, f"an [h, w, 3] image is required, got shape {img.shape}"
+    h, w = img.shape[:2]
+    n = len(masks) if masks is not None else (len(boxes) if boxes is not None else 0)
+    pool = off = ln = tab = edge = bx = brgb = None
+    if masks is not None:
+        for i, r in enumerate(masks):
+            if tuple(int(v) for v in r["size"]) != (h, w):
+                raise ValueError(f"render_instances: mask {i} has size {list(r['size'])}, the image {[h, w]}")
+        pool, off, ln = _pool([_counts(x) for x in masks])
+        tab = np.ascontiguousarray(tables, dtype=np.uint8).reshape(-1, 256, 3)
+        assert len(tab) == n, "one fill table per mask"
+        if edge_rgb is not None:
+            edge = np.ascontiguousarray(edge_rgb, dtype=np.uint8).reshape(-1, 3)
+            assert len(edge) == n, "one edge colour per mask"
+    if boxes is not None:
+        bx = np.ascontiguousarray(np.asarray(boxes, dtype=np.int32).reshape(-1, 4))
+        brgb = np.ascontiguousarray(box_rgb, dtype=np.uint8).reshape(-1, 3)
+        assert len(bx) == n and len(brgb) == n, "one box and one box colour per instance"
+    out = np.empty_like(img)
+    opt = lambda a: _vp(a) if a is not None else None
+    check(lib().amp_render_instances(_handle(ctx), _vp(img), h, w, opt(pool), opt(off), opt(ln), n, opt(tab), opt(edge), opt(bx), opt(brgb),
+                                     int(lw), _vp(out)), "amp_render_instances")
+    return out
+
+
 LABEL_KINDS = {"binary": 0, "label": 1}
 
 

@@ -6,11 +6,14 @@
         .overlay_instances(boxes=, masks=, labels=, assigned_colors=, alpha=)             -> VisImage
     VisImage.get_image() -> uint8 [H*scale, W*scale, 3]
 
-Host-side drawing, outside the hot path (SURVEY §2.1 lists visualisation as out of scope); it exists so that `import ampis` and
-the notebook cells that call `visualize.display_ddicts` / `display_iset` run on the façade.  Rendering is plain numpy (alpha-blended
-mask fill, 1-px outline, box frame) plus PIL for label text; it does not try to be pixel-identical to detectron2's matplotlib canvas.
-Masks arrive in whatever form the caller holds: COCO RLE dicts (what the MI355X path produces and `RLEMasks.rle` carries), bool
-arrays [N, H, W], BitMasks, PolygonMasks / lists of polygons; they are decoded one at a time, never as one N x H x W block.
+It exists so that `import ampis` and the notebook cells that call `visualize.display_ddicts` / `display_iset` run on the façade.  The
+drawing is defined by the primitives below in plain numpy (alpha-blended mask fill, 1-px outline, box frame) plus PIL for label text; it
+does not try to be pixel-identical to detectron2's matplotlib canvas.  Masks arrive in whatever form the caller holds: COCO RLE dicts
+(what the MI355X path produces and `RLEMasks.rle` carries), bool arrays [N, H, W], BitMasks, PolygonMasks / lists of polygons.
+overlay_instances draws all instances of an image in ONE amp_render_instances call on their run lists (analyze.render_instances: on the
+device when one is visible, else on the host; byte for byte what draw_binary_mask + draw_box give) whenever the output is at image scale,
+alpha and the colours lie in [0, 1] and every mask is an RLE dict of the image's size, a polygon list or a bool array; anything else is
+drawn by the primitives, one decoded mask at a time, never as one N x H x W block.  Labels are drawn in one PIL session per call.
 """
 import colorsys
 from enum import Enum
@@ -52,6 +55,8 @@ def _meta_get(metadata, key, default=None):
 
 
 class Visualizer:
+    render_device = "auto"                  # where overlay_instances draws its one call: 'auto', 'cpu' or 'cuda' (analyze.render_instances)
+
     def __init__(self, img_rgb, metadata=None, scale=1.0, instance_mode=ColorMode.IMAGE):
         img = np.asarray(img_rgb)
         if img.ndim == 2:
@@ -96,6 +101,37 @@ class Visualizer:
             else:
                 arr = np.asarray(m.to_dense() if hasattr(m, "to_dense") else m)
                 out.append(lambda arr=arr: arr.astype(bool))
+        return out
+
+    def _rle_list(self, masks):
+        """The masks as run lists of the image, one RLE dict per instance, for the one-call drawing -- or None when an item is neither an
+        RLE dict of the image's size, a polygon list nor a bool array of the image's size: the primitives then draw what they always drew."""
+        from .. import rle
+        from ..structures import BitMasks, PolygonMasks
+        h, w = self.img.shape[:2]
+        if hasattr(masks, "rle") and not isinstance(masks, (list, tuple)):
+            masks = list(masks.rle)
+        if isinstance(masks, BitMasks):
+            masks = masks.tensor.numpy()
+        if isinstance(masks, PolygonMasks):
+            masks = masks.polygons
+        if hasattr(masks, "detach"):
+            masks = masks.detach().cpu().numpy()
+        out = []
+        for m in masks:
+            if isinstance(m, dict):
+                if "size" not in m or [int(v) for v in m["size"]] != [h, w]:
+                    return None
+                out.append(m)
+            elif isinstance(m, (list, tuple)) or (isinstance(m, np.ndarray) and m.dtype != bool and m.ndim == 1):
+                polys = m if isinstance(m, (list, tuple)) and len(m) and not np.isscalar(m[0]) else [m]
+                polys = [np.asarray(p, dtype=np.float64).reshape(-1).tolist() for p in polys]
+                out.append(rle.merge(rle.frPyObjects(polys, h, w)))
+            else:
+                arr = np.asarray(m.to_dense() if hasattr(m, "to_dense") else m)
+                if arr.dtype != bool or arr.shape != (h, w):
+                    return None
+                out.append(rle.encode(arr))
         return out
 
     @staticmethod
@@ -145,22 +181,28 @@ class Visualizer:
         return self.output
 
     def draw_text(self, text, position, color=(1.0, 1.0, 1.0)):
-        if not text:
+        return self._draw_texts([(text, position)], color)
+
+    def _draw_texts(self, items, color=(1.0, 1.0, 1.0)):
+        """(text, position) pairs in order, in one PIL session: the uint8 RGB round trip is lossless, so the bytes are those of one session each"""
+        items = [(t, p) for t, p in items if t]
+        if not items:
             return self.output
         from PIL import Image, ImageDraw
         pil = Image.fromarray(self.output.img)
         d = ImageDraw.Draw(pil)
-        x, y = position[0] * self.scale, position[1] * self.scale
-        l, t, r, b = d.textbbox((x, y), text)
-        d.rectangle((l - 1, t - 1, r + 1, b + 1), fill=(0, 0, 0))
-        d.text((x, y), text, fill=tuple(int(255 * c) for c in color[:3]))
+        for text, position in items:
+            x, y = position[0] * self.scale, position[1] * self.scale
+            l, t, r, b = d.textbbox((x, y), text)
+            d.rectangle((l - 1, t - 1, r + 1, b + 1), fill=(0, 0, 0))
+            d.text((x, y), text, fill=tuple(int(255 * c) for c in color[:3]))
         self.output.img[:] = np.asarray(pil)
         return self.output
 
     # ---- the three entry points ----
     def overlay_instances(self, *, boxes=None, labels=None, masks=None, keypoints=None, assigned_colors=None, alpha=0.5):
         boxes = self._box_array(boxes)
-        masks = self._mask_list(masks)
+        raw_masks, masks = masks, self._mask_list(masks)
         n = len(boxes) if boxes is not None else (len(masks) if masks is not None else (len(labels) if labels is not None else 0))
         if labels is not None:
             assert len(labels) == n, (len(labels), n)
@@ -171,12 +213,18 @@ class Visualizer:
         colors = _palette(n) if assigned_colors is None else np.asarray(assigned_colors, dtype=np.float64).reshape(n, -1)[:, :3]
         # large instances first so that small ones stay visible (area of the box when there is one, else draw order)
         order = np.argsort(-np.prod(boxes[:, 2:] - boxes[:, :2], axis=1)) if boxes is not None else np.arange(n)
-        for i in order:
-            if masks is not None:
-                self.draw_binary_mask(masks[i](), colors[i], alpha=alpha)
-            if boxes is not None:
-                self.draw_box(boxes[i], colors[i])
+        rles = self._one_call_masks(raw_masks, boxes, colors, alpha)
+        if rles is not False:
+            from .. import analyze
+            self.output.img[:] = analyze.render_instances(self.output.img, rles, boxes, colors, alpha=alpha, order=order, device=self.render_device)
+        else:
+            for i in order:
+                if masks is not None:
+                    self.draw_binary_mask(masks[i](), colors[i], alpha=alpha)
+                if boxes is not None:
+                    self.draw_box(boxes[i], colors[i])
         if labels is not None:
+            texts = []
             for i in order:
                 if labels[i]:
                     if boxes is not None:
@@ -184,8 +232,26 @@ class Visualizer:
                     else:
                         ys, xs = np.nonzero(masks[i]())
                         pos = (float(np.median(xs)), float(np.median(ys))) if len(xs) else (0.0, 0.0)
-                    self.draw_text(str(labels[i]), pos)
+                    texts.append((str(labels[i]), pos))
+            self._draw_texts(texts)
         return self.output
+
+    def _one_call_masks(self, masks, boxes, colors, alpha):
+        """The run lists (None without masks) when overlay_instances may draw its instances in one amp_render_instances call, False when the
+        primitives must: output not at image scale, alpha or a colour outside [0, 1] (the blend is tabulated per uint8 value), a box that is
+        not finite, a mask _rle_list does not take."""
+        if self._out_hw != self.img.shape[:2] or (masks is None and boxes is None):
+            return False
+        try:
+            ok = 0.0 <= alpha <= 1.0 and colors.shape[1] == 3 and bool(np.isfinite(colors).all()) and colors.min() >= 0.0 and colors.max() <= 1.0
+        except TypeError:
+            ok = False
+        if not ok or (boxes is not None and not np.isfinite(boxes).all()):
+            return False
+        if masks is None:
+            return None
+        rles = self._rle_list(masks)
+        return False if rles is None else rles
 
     def _class_names(self, classes, scores=None):
         names = _meta_get(self.metadata, "thing_classes", None)
