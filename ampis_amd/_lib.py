@@ -251,6 +251,7 @@ def _declare(L):
         "amp_render_instances": ([vp, vp, i, i, vp, vp, vp, i, vp, vp, vp, vp, i, vp], i),
         "amp_label_runs": ([vp, vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp, i, C.c_ulonglong, vp, vp], i),
         "amp_rle_from_polygon": ([vp, i, i, i, vp, i, C.POINTER(i)], i),
+        "amp_polygons_to_rle": ([vp, vp, vp, vp, i, i, i, vp, C.c_ulonglong, vp, vp, vp, vp, vp], i),
         "amp_model_cfg_default": ([C.POINTER(ModelCfg)], i),
         "amp_model_create": ([vp, C.POINTER(ModelCfg), C.POINTER(vp)], i),
         "amp_model_create_anchors": ([vp, C.POINTER(ModelCfg), C.POINTER(AnchorCfg), C.POINTER(vp)], i),

@@ -36,15 +36,17 @@ from . import rle
 from .structures import BitMasks, Instances, InstanceSet, PolygonMasks, RLEBitMasks, RLEMasks
 
 
-def masks_to_rle(masks, size=None):
-    """list of RLE dicts | RLEBitMasks | object with .rle | PolygonMasks (needs size=(h,w)) | BitMasks / bool ndarray [N,H,W]."""
+def masks_to_rle(masks, size=None, device='auto'):
+    """list of RLE dicts | RLEBitMasks | object with .rle | PolygonMasks (needs size=(h,w)) | BitMasks / bool ndarray [N,H,W].  Polygon masks
+    become run lists in ONE amp_polygons_to_rle call for all instances (csrc/polygon_runs.hip, or polygon_runs_host.hip on the host: identical
+    bytes, those of rle.merge(rle.frPyObjects(...)) per instance); device: 'cpu', 'cuda' or 'auto' (the device when one is visible)."""
     if isinstance(masks, RLEBitMasks) or hasattr(masks, "rle"):
         return list(masks.rle)
     if isinstance(masks, (list, tuple)) and (len(masks) == 0 or isinstance(masks[0], dict)):
         return list(masks)
     if isinstance(masks, PolygonMasks):
         assert size is not None, "size=(height, width) is required for polygon masks"
-        return [rle.merge(rle.frPyObjects([np.asarray(p).reshape(-1).tolist() for p in inst], size[0], size[1])) for inst in masks.polygons]
+        return rle.polygons_to_rle(masks.polygons, size[0], size[1], ctx=_device_context("masks_to_rle", device, len(masks.polygons)))
     arr = masks.tensor.numpy() if isinstance(masks, BitMasks) else np.asarray(masks)
     if arr.ndim == 3:
         return [rle.encode(np.asfortranarray(m)) for m in arr.astype(bool)]
@@ -74,13 +76,13 @@ def match_instances(iou, iou_thresh=0.5):
             "fp": np.flatnonzero(unclaimed), "iou": best[hit]}
 
 
-def rle_instance_matcher(gt, pred, iou_thresh=0.5, size=None):
-    gt, pred = masks_to_rle(gt, size), masks_to_rle(pred, size)
+def rle_instance_matcher(gt, pred, iou_thresh=0.5, size=None, device='auto'):
+    gt, pred = masks_to_rle(gt, size, device), masks_to_rle(pred, size, device)
     return match_instances(iou_matrix(gt, pred), iou_thresh)
 
 
-def det_seg_scores(gt, pred, iou_thresh=0.5, size=None):
-    gt, pred = masks_to_rle(gt, size), masks_to_rle(pred, size)
+def det_seg_scores(gt, pred, iou_thresh=0.5, size=None, device='auto'):
+    gt, pred = masks_to_rle(gt, size, device), masks_to_rle(pred, size, device)
     m = match_instances(iou_matrix(gt, pred), iou_thresh)
     n_tp, n_fn, n_fp = len(m["tp"]), len(m["fn"]), len(m["fp"])
     both, gt_only, pred_only = rle.pair_overlap(gt, pred, m["tp"])       # per matched pair: pixels in both / missed / spurious
@@ -153,7 +155,7 @@ def mask_edge_distance(gt_mask, pred_mask, gt_box, pred_box, matches, device='au
     squared=True returns the exact squared distances as int64 tensors.  ValueError for a malformed box, a match index out of range, masks of
     different sizes, and a pair with disagreeing pixels whose other mask has no pixel in the box (the reference fails there too)."""
     import torch
-    gt, pred = masks_to_rle(gt_mask, size), masks_to_rle(pred_mask, size)
+    gt, pred = masks_to_rle(gt_mask, size, device), masks_to_rle(pred_mask, size, device)
     m = np.asarray(matches)
     if m.size and (m.ndim != 2 or m.shape[1] != 2 or not np.issubdtype(m.dtype, np.integer)):
         raise ValueError(f"mask_edge_distance: matches must be an [n, 2] integer array of (gt, pred) indices, got shape {m.shape} {m.dtype}")
@@ -242,7 +244,7 @@ def region_properties(masks, keys=None, size=None, device='auto'):
     the integers to an independent scipy / brute-force evaluation of those definitions and the floats to their exact-rational value.
     ValueError for an unknown key (before any device work), a bad `device`, masks of different sizes."""
     cols = _rprops_columns(keys)
-    rles = masks_to_rle(masks, size)
+    rles = masks_to_rle(masks, size, device)
     sizes = {tuple(int(v) for v in r["size"]) for r in rles}
     if len(sizes) > 1:
         raise ValueError(f"region_properties: masks of different sizes {sorted(sizes)}")
@@ -353,7 +355,7 @@ def overlap_matrix(a, b, device='auto', size=None):
     RLE.merge(intersect=True) + RLE.area per pair (ampis/applications/powder.py:82).  One amp_rle_overlap_groups call with one group.  a, b:
     anything masks_to_rle accepts (size=(h, w) for polygons); device: 'cpu' (host), 'cuda' (HIP device, an error without one) or 'auto' (the
     device when one is visible); the paths return identical bytes.  ValueError for a bad `device` and for masks of different sizes."""
-    ra, rb = masks_to_rle(a, size), masks_to_rle(b, size)
+    ra, rb = masks_to_rle(a, size, device), masks_to_rle(b, size, device)
     ctx = _device_context("overlap_matrix", device, len(ra) and len(rb))
     try:
         return rle.overlap_groups([ra], [rb], ctx=ctx)[0][0]
@@ -465,7 +467,7 @@ def seg_class_map(gt, pred, match_results=None, mode='reduced', size=None, devic
         raise ValueError(f"seg_class_map: mode = {mode!r} ('reduced' or 'all')")
     gm, size = _unwrap_masks(gt, size)
     pm, size = _unwrap_masks(pred, size)
-    g, p = masks_to_rle(gm, size), masks_to_rle(pm, size)
+    g, p = masks_to_rle(gm, size, device), masks_to_rle(pm, size, device)
     h, w = _image_size("seg_class_map", g + p, size)
     if match_results is None:
         match_results = match_instances(iou_matrix(g, p), 0.5)
@@ -578,7 +580,7 @@ def render_instances(image, masks=None, boxes=None, colors=None, alpha=0.5, edge
         img = np.repeat(img, 3, axis=2)
     img = np.ascontiguousarray(np.clip(img[:, :, :3], 0, 255).astype(np.uint8))
     h, w = img.shape[:2]
-    rles = masks_to_rle(masks, (h, w) if size is None else size) if masks is not None else None
+    rles = masks_to_rle(masks, (h, w) if size is None else size, device) if masks is not None else None
     bx = Visualizer._box_array(boxes)
     n = len(bx) if bx is not None else (len(rles) if rles is not None else 0)
     if rles is not None and len(rles) != n:

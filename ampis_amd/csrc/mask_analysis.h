@@ -1,7 +1,8 @@
 // The mask analyses on run lists: what their entry points (edge_distance.hip, region_props.hip, rle_overlap.hip, seg_class_map.hip, render.hip) share
 // with mask_analysis_host.hip.  Each *_check validates the arguments and builds the plan (run_list.h) that both paths evaluate; each *_host is
 // the evaluation with a NULL context, byte for byte what the kernels give.  amp_label_runs, the producer of run lists from an annotation image
-// (label_runs.hip, label_runs_host.hip), is declared at the end.  Plain C++: the host-only sanitizer builds include this header.
+// (label_runs.hip, label_runs_host.hip), and amp_polygons_to_rle, the producer from polygons (polygon_runs.hip, polygon_runs_host.hip), are declared
+// at the end.  Plain C++: the host-only sanitizer builds include this header.
 #pragma once
 #include "run_list.h"
 
@@ -66,6 +67,66 @@ int label_runs_capacity(unsigned long long instances, unsigned long long counts,
 int label_runs_host(const void* image, int h, int w, int kind, int connectivity, int zero_is_background, int* ids, int* boxes,
                     unsigned int* areas, uint32_t* counts, unsigned long long* counts_off, int* counts_len, int inst_cap,
                     unsigned long long counts_cap, int* labels, unsigned long long* need);
+
+// amp_polygons_to_rle (polygon_runs_host.hip, polygon_runs.hip).  The check looks at every argument and every coordinate before either path
+// does anything; both paths report the counts they need through polygons_capacity before they write anything else.  The host path is the
+// definition: rle_from_polygon_runs per polygon, united in order with rle_merge2_runs (rle_host.hip: the routines behind amp_rle_from_polygon and
+// amp_rle_merge2, on buffers that are kept from polygon to polygon).
+struct PolygonScratch {
+    std::vector<int> x, y;                        // the vertices on the 5x grid, the first repeated at the end
+    std::vector<unsigned long long> a, b;         // the crossings, then the run lengths
+};
+void rle_from_polygon_runs(const double* xy, int k, int h, int w, PolygonScratch& sc);
+unsigned long long rle_merge2_runs(const uint32_t* A, int ka, const uint32_t* B, int kb, int intersect, uint32_t* out, unsigned long long cap);
+int polygons_check(const double* xy, const unsigned long long* poly_off, const int* inst_first, int n, int h, int w, const uint32_t* counts,
+                   const unsigned long long* counts_off, const int* counts_len, const int* boxes, const unsigned int* areas,
+                   const unsigned long long* need);
+int polygons_capacity(unsigned long long counts, unsigned long long counts_cap, unsigned long long* need);
+int polygons_host(const double* xy, const unsigned long long* poly_off, const int* inst_first, int n, int h, int w, uint32_t* counts,
+                  unsigned long long counts_cap, unsigned long long* counts_off, int* counts_len, int* boxes, unsigned int* areas,
+                  unsigned long long* need);
+#define AMP_POLYGON_COORD_MAX 1.0e6               // beyond it the (int) casts of the edge walk are not defined
+
+// One edge of a polygon as the walk of rle_from_polygon_runs sees it, and step d of the walk (1 <= d <= len) in closed form: u, v of the step
+// and pu, pv of the step before are functions of (edge, d) alone.  The device path evaluates exactly these expressions, in the order the host
+// routine does (the build has -ffp-contract=off, divisions are IEEE).
+struct PolygonEdge {
+    int xs, ys, dx, dy, len;                      // the start after the swap, the extents, the number of steps
+    bool flip;
+    double s;                                     // the slope along the longer extent
+};
+AMP_HD int polygon_grid(double v) { return (int)(5.0 * v + 0.5); }
+AMP_HD PolygonEdge polygon_edge(int xs, int ys, int xe, int ye) {
+    PolygonEdge e;
+    e.dx = xe > xs ? xe - xs : xs - xe;
+    e.dy = ys > ye ? ys - ye : ye - ys;
+    e.flip = (e.dx >= e.dy && xs > xe) || (e.dx < e.dy && ys > ye);
+    if (e.flip) { int t = xs; xs = xe; xe = t; t = ys; ys = ye; ye = t; }
+    e.xs = xs; e.ys = ys;
+    e.len = e.dx >= e.dy ? e.dx : e.dy;
+    e.s = e.dx >= e.dy ? (e.dx ? (double)(ye - ys) / e.dx : 0.0) : (double)(xe - xs) / e.dy;
+    return e;
+}
+AMP_HD void polygon_step(const PolygonEdge& e, int d, int* u, int* v) {
+    const int t = e.flip ? e.len - d : d;
+    if (e.dx >= e.dy) { *u = t + e.xs; *v = (int)(e.ys + e.s * t + 0.5); } else { *v = t + e.ys; *u = (int)(e.xs + e.s * t + 0.5); }
+}
+// does step d toggle the mask, and at which position x * h + y of the column-major image (at most h * w)
+AMP_HD bool polygon_crossing(const PolygonEdge& e, int d, int h, int w, unsigned int* pos) {
+    int u, v, pu, pv;
+    polygon_step(e, d, &u, &v);
+    polygon_step(e, d - 1, &pu, &pv);
+    if (u == pu) return false;
+    double xd = (double)(u < pu ? u : u - 1);
+    xd = (xd + 0.5) / 5.0 - 0.5;
+    if (!(__builtin_floor(xd) == xd && xd >= 0 && xd <= w - 1)) return false;
+    double yd = (double)(v < pv ? v : pv);
+    yd = (yd + 0.5) / 5.0 - 0.5;
+    if (yd < 0) yd = 0; else if (yd > h) yd = h;
+    yd = __builtin_ceil(yd);
+    *pos = (unsigned int)((unsigned long long)xd * (unsigned long long)h + (unsigned long long)yd);
+    return true;
+}
 
 // the pixel of an annotation image as both paths read it: foreground is 1 in a BINARY image, the id in a LABEL image; a pixel belongs to an
 // instance unless it is 0 and 0 is background

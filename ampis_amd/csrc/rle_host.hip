@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "common.h"
+#include "mask_analysis.h"
 
 extern "C" {
 
@@ -131,6 +132,40 @@ int amp_rle_area(const uint32_t* cnts, int m, unsigned long long* area) {
 
 }  // extern "C"
 
+namespace amp {
+
+// The walk of amp_rle_merge2 (pycocotools rleMerge of two lists): writes at most cap runs to out and returns how many the result has.
+unsigned long long rle_merge2_runs(const uint32_t* A, int ka, const uint32_t* B, int kb, int intersect, uint32_t* out, unsigned long long cap) {
+    unsigned long long m = 0;
+    bool v = false;
+    unsigned long long cc = 0;
+    unsigned long long ca = A[0], cb = B[0];
+    int a = 1, b = 1;
+    bool va = false, vb = false;
+    unsigned long long ct = 1;
+    while (ct > 0) {
+        const unsigned long long c = std::min(ca, cb);
+        cc += c;
+        ct = 0;
+        ca -= c;
+        if (!ca && a < ka) { ca = A[a++]; va = !va; }
+        ct += ca;
+        cb -= c;
+        if (!cb && b < kb) { cb = B[b++]; vb = !vb; }
+        ct += cb;
+        const bool vp = v;
+        v = intersect ? (va && vb) : (va || vb);
+        if (v != vp || ct == 0) {
+            if (m < cap) out[m] = (uint32_t)cc;
+            ++m;
+            cc = 0;
+        }
+    }
+    return m;
+}
+
+}  // namespace amp
+
 // Walk two run lists in lock step; fn(len, va, vb) for each maximal stretch where both values are constant.
 template <class F>
 static void rle_zip(const uint32_t* A, int ka, const uint32_t* B, int kb, F fn) {
@@ -238,50 +273,26 @@ int amp_rle_pair_overlap(const uint32_t* apool, const unsigned long long* aoff, 
 
 int amp_rle_merge2(const uint32_t* A, int ka, const uint32_t* B, int kb, int intersect, uint32_t* out, int cap, int* m_out) {
     AMP_REQUIRE(A && B && out && m_out && ka > 0 && kb > 0, "amp_rle_merge2: bad argument");
-    int m = 0;
-    bool v = false;
-    unsigned long long cc = 0;
-    bool overflow = false;
-    unsigned long long ca = A[0], cb = B[0];
-    int a = 1, b = 1;
-    bool va = false, vb = false;
-    unsigned long long ct = 1;
-    while (ct > 0) {
-        const unsigned long long c = std::min(ca, cb);
-        cc += c;
-        ct = 0;
-        ca -= c;
-        if (!ca && a < ka) { ca = A[a++]; va = !va; }
-        ct += ca;
-        cb -= c;
-        if (!cb && b < kb) { cb = B[b++]; vb = !vb; }
-        ct += cb;
-        const bool vp = v;
-        v = intersect ? (va && vb) : (va || vb);
-        if (v != vp || ct == 0) {
-            if (m < cap) out[m++] = (uint32_t)cc; else overflow = true;
-            cc = 0;
-        }
-    }
-    AMP_REQUIRE(!overflow, "amp_rle_merge2: more than cap=%d runs", cap);
-    *m_out = m;
+    const unsigned long long m = amp::rle_merge2_runs(A, ka, B, kb, intersect, out, cap < 0 ? 0ull : (unsigned long long)cap);
+    AMP_REQUIRE(m <= (unsigned long long)(cap < 0 ? 0 : cap), "amp_rle_merge2: more than cap=%d runs", cap);
+    *m_out = (int)m;
     return AMP_OK;
 }
 
 }  // extern "C"
 
-extern "C" {
+namespace amp {
 
-// Polygon (flat x0,y0,x1,y1,... ; k vertices) -> run lengths of an h x w mask: pycocotools maskApi.c rleFrPoly, the routine behind
-// RLE.frPyObjects (ampis/structures.py:677) and detectron2's polygons_to_bitmask.  Boundary is traced on a 5x upsampled grid,
-// x-crossings become run boundaries, sorted, differenced, zero-length runs merged.
-int amp_rle_from_polygon(const double* xy, int k, int h, int w, uint32_t* cnts, int cap, int* m_out) {
-    AMP_REQUIRE(xy && cnts && m_out && k >= 1 && h > 0 && w > 0, "amp_rle_from_polygon: bad argument");
+// The routine of amp_rle_from_polygon on buffers the caller keeps (amp_polygons_to_rle's host path calls it once per polygon): the run
+// lengths are left in sc.b.
+void rle_from_polygon_runs(const double* xy, int k, int h, int w, PolygonScratch& sc) {
     const double scale = 5.0;
-    std::vector<int> x(k + 1), y(k + 1);
+    std::vector<int>&x = sc.x, &y = sc.y;
+    std::vector<unsigned long long>&a = sc.a, &b = sc.b;
+    x.resize((size_t)k + 1); y.resize((size_t)k + 1);
+    a.clear(); b.clear();
     for (int j = 0; j < k; ++j) { x[j] = (int)(scale * xy[2 * j] + 0.5); y[j] = (int)(scale * xy[2 * j + 1] + 0.5); }
     x[k] = x[0]; y[k] = y[0];
-    std::vector<unsigned long long> a;
     for (int j = 0; j < k; ++j) {
         int xs = x[j], xe = x[j + 1], ys = y[j], ye = y[j + 1];
         const int dx = std::abs(xe - xs), dy = std::abs(ys - ye);
@@ -312,16 +323,28 @@ int amp_rle_from_polygon(const double* xy, int k, int h, int w, uint32_t* cnts, 
     std::sort(a.begin(), a.end());
     unsigned long long p = 0;
     for (auto& v : a) { const unsigned long long t = v; v -= p; p = t; }
-    std::vector<unsigned long long> b;
     size_t j = 0;
     b.push_back(a[j++]);
     while (j < a.size()) {
         if (a[j] > 0) b.push_back(a[j++]);
         else { ++j; if (j < a.size()) b.back() += a[j++]; }
     }
-    AMP_REQUIRE((int)b.size() <= cap, "amp_rle_from_polygon: more than cap=%d runs", cap);
-    for (size_t i = 0; i < b.size(); ++i) cnts[i] = (uint32_t)b[i];
-    *m_out = (int)b.size();
+}
+
+}  // namespace amp
+
+extern "C" {
+
+// Polygon (flat x0,y0,x1,y1,... ; k vertices) -> run lengths of an h x w mask: pycocotools maskApi.c rleFrPoly, the routine behind
+// RLE.frPyObjects (ampis/structures.py:677) and detectron2's polygons_to_bitmask.  Boundary is traced on a 5x upsampled grid,
+// x-crossings become run boundaries, sorted, differenced, zero-length runs merged.
+int amp_rle_from_polygon(const double* xy, int k, int h, int w, uint32_t* cnts, int cap, int* m_out) {
+    AMP_REQUIRE(xy && cnts && m_out && k >= 1 && h > 0 && w > 0, "amp_rle_from_polygon: bad argument");
+    amp::PolygonScratch sc;
+    amp::rle_from_polygon_runs(xy, k, h, w, sc);
+    AMP_REQUIRE((int)sc.b.size() <= cap, "amp_rle_from_polygon: more than cap=%d runs", cap);
+    for (size_t i = 0; i < sc.b.size(); ++i) cnts[i] = (uint32_t)sc.b[i];
+    *m_out = (int)sc.b.size();
     return AMP_OK;
 }
 

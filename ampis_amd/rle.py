@@ -385,6 +385,38 @@ def label_runs(image, kind, connectivity=2, zero_is_background=True, ctx=None, r
     return out + (labels,) if return_labels else out
 
 
+def polygons_to_rle(instances, h, w, ctx=None, return_boxes=False):
+    """The polygon instances of one image as RLE dicts, one C call (amp_polygons_to_rle; a second one when the first reports that the capacity
+    guess was too small) and one counts_to_strings: instances[i] is the list of instance i's polygons, a polygon flat [x0, y0, x1, y1, ...].
+    Instance i's mask is what merge(frPyObjects(instances[i], h, w)) gives, byte for byte.  return_boxes: also the int32 [n, 4] tight boxes
+    {r0, c0, r1, c1} (ends exclusive, zeros for an empty mask) and the uint32 [n] areas of those masks.  A coordinate that is not finite or
+    exceeds 10^6 in magnitude is refused (AmpError), like every other malformed argument.  ctx: a _lib.Context (computed on its device) or
+    None (on the host): the same bytes."""
+    h, w = int(h), int(w)
+    n = len(instances)
+    flat = [np.asarray(p, dtype=np.float64).reshape(-1) for inst in instances for p in inst]
+    first = np.zeros(n + 1, dtype=np.int32)
+    first[1:] = np.cumsum([len(inst) for inst in instances], dtype=np.int64)
+    poff = np.zeros(len(flat) + 1, dtype=np.uint64)
+    poff[1:] = np.cumsum([len(p) for p in flat], dtype=np.uint64)
+    xy = np.ascontiguousarray(np.concatenate(flat) if flat else np.zeros(1, np.float64), dtype=np.float64)
+    boxes, areas = np.zeros((n, 4), dtype=np.int32), np.zeros(n, dtype=np.uint32)
+    off, ln = np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.int32)
+    need = np.zeros(1, dtype=np.uint64)
+    cap = 2 * n + len(xy) + 4096                                    # a guess: two boundaries for every vertex
+    for attempt in range(2):
+        pool = np.empty(cap, dtype=np.uint32)
+        st = lib().amp_polygons_to_rle(_handle(ctx), _vp(xy), _vp(poff), _vp(first), n, h, w, _vp(pool), cap, _vp(off), _vp(ln), _vp(boxes),
+                                       _vp(areas), _vp(need))
+        if st != -3 or attempt:                                     # AMP_ERR_NOMEM the first time: the need is known now
+            check(st, "amp_polygons_to_rle")
+            break
+        cap = max(int(need[0]), 1)
+    strings = counts_to_strings(pool[: int(need[0])], off[:n], ln[:n])
+    out = [{"size": [h, w], "counts": c} for c in strings]
+    return (out, boxes, areas) if return_boxes else out
+
+
 def merge(rles, intersect=False):
     assert len(rles) >= 1
     h, w = rles[0]["size"]

@@ -117,7 +117,7 @@ class Visualizer:
             masks = masks.polygons
         if hasattr(masks, "detach"):
             masks = masks.detach().cpu().numpy()
-        out = []
+        out, where, insts = [], [], []                                           # the polygon items: their places in out, their polygon lists
         for m in masks:
             if isinstance(m, dict):
                 if "size" not in m or [int(v) for v in m["size"]] != [h, w]:
@@ -125,13 +125,22 @@ class Visualizer:
                 out.append(m)
             elif isinstance(m, (list, tuple)) or (isinstance(m, np.ndarray) and m.dtype != bool and m.ndim == 1):
                 polys = m if isinstance(m, (list, tuple)) and len(m) and not np.isscalar(m[0]) else [m]
-                polys = [np.asarray(p, dtype=np.float64).reshape(-1).tolist() for p in polys]
-                out.append(rle.merge(rle.frPyObjects(polys, h, w)))
+                where.append(len(out))
+                insts.append([np.asarray(p, dtype=np.float64).reshape(-1) for p in polys])
+                out.append(None)
             else:
                 arr = np.asarray(m.to_dense() if hasattr(m, "to_dense") else m)
                 if arr.dtype != bool or arr.shape != (h, w):
                     return None
                 out.append(rle.encode(arr))
+        if insts:                                                                # every polygon item of the call in one amp_polygons_to_rle
+            from .. import analyze
+            flat = [p for inst in insts for p in inst]
+            if any(len(p) < 2 or len(p) % 2 for p in flat) or not all(np.isfinite(p).all() and np.abs(p).max() <= 1.0e6 for p in flat):
+                return None                                                      # what the call refuses: the primitives draw what they always drew
+            ctx = analyze._device_context("Visualizer", self.render_device, True)
+            for at, r in zip(where, rle.polygons_to_rle(insts, h, w, ctx=ctx)):
+                out[at] = r
         return out
 
     @staticmethod

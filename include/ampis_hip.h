@@ -618,6 +618,26 @@ int amp_polygon_clip_rect(const double* xy, const long long* off, const int* sel
 int amp_rle_merge2(const uint32_t* A, int ka, const uint32_t* B, int kb, int intersect, uint32_t* out, int cap, int* m_out);
 /* polygon (k vertices, flat xy) -> runs of an h x w mask (pycocotools rleFrPoly / frPyObjects) */
 int amp_rle_from_polygon(const double* xy, int k, int h, int w, uint32_t* cnts, int cap, int* m_out);
+/* The polygon instances of one image as run lists in one call (VIA ground truth, detectron2 PolygonMasks): instance i holds polygons
+ * inst_first[i] .. inst_first[i + 1] - 1, polygon p the flat x, y values xy[poly_off[p] .. poly_off[p + 1]).  All pointers are host pointers.
+ * Per instance the call returns, byte for byte, the run list of today's composition -- amp_rle_from_polygon on each of its polygons, united in
+ * order with amp_rle_merge2(intersect = 0), what rle.merge(rle.frPyObjects(polygons, h, w)) encodes; that composition is the definition,
+ * pycocotools' painting across column ends for a polygon that leaves the image sideways included --: counts[counts_off[i] .. + counts_len[i]),
+ * column-major, the first count the run of zeros (it may be 0); boxes[4 i ..] = {r0, c0, r1, c1} the tight box of that list with exclusive
+ * ends (a run across a column end covers the first and the last row; zeros for an empty mask) and areas[i] its pixels.
+ * Checked on the host before any device work (AMP_ERR_ARG naming the offender, nothing written): NULL pointers, n < 0, h, w < 1, h * w > 2^30,
+ * offsets that do not ascend, a polygon with an odd number of values or without a vertex, an instance without a polygon, and THE ONE DEPARTURE
+ * from amp_rle_from_polygon: a coordinate that is not finite or exceeds 10^6 in magnitude is refused, because the routine's (int) casts are
+ * undefined there and differ between host and device.  With valid arguments need[0] = the counts of all instances is always written; with
+ * counts_cap below it the call returns AMP_ERR_NOMEM and writes nothing else.
+ * ctx == NULL: computed on the host (polygon_runs_host.hip: the two routines in a loop, buffers kept across polygons).  Otherwise on ctx's
+ * device and stream (polygon_runs.hip): upload, a fixed list of launches whatever the instances, polygons or crossings, download; work is
+ * spread over (edge, step) items, memory is linear in vertices + crossings + counts, the double arithmetic is the host's operation for
+ * operation, and the bytes do not depend on the device's scheduling and equal the host's. */
+int amp_polygons_to_rle(amp_ctx* ctx, const double* xy, const unsigned long long* poly_off /* [inst_first[n] + 1], in doubles */,
+                        const int* inst_first /* [n + 1] */, int n, int h, int w, uint32_t* counts, unsigned long long counts_cap,
+                        unsigned long long* counts_off /* [n] */, int* counts_len /* [n] */, int* boxes /* [n][4] */, unsigned int* areas /* [n] */,
+                        unsigned long long* need /* [1] */);
 
 /* The model: DefaultPredictor(cfg) / predictor(img) ---------------------------------------------- */
 typedef struct amp_model amp_model;
