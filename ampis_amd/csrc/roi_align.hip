@@ -149,7 +149,7 @@ __global__ __launch_bounds__(256) void roi_align_kernel(const RoiArgs a) {
 // values, next to 32 that do the interpolation.  Here lane j computes the parameters of sample COLUMN j and of sample ROW j of the
 // wave's bin once (same operations, same order: bit-identical), and the sample loops fetch them with v_readlane into scalar
 // registers: per sample the vector unit is left with 4 weight products, 4 loads and the 32 interpolation operations.
-// fp32 feature maps, C <= 256 * k (float4 per lane), sampling grids up to 64 x 64 (larger ones: roi_align_kernel).
+// fp32 feature maps, any C % 4 == 0 (float4 per lane, 64 lanes per trip of the channel loop), sampling grids beyond 64 samples per side in chunks of 64.
 template <int DUMMY>
 __global__ __launch_bounds__(256) void roi_align_lanes_kernel(const RoiArgs a) {
     const int lane = threadIdx.x & 63;
@@ -203,7 +203,13 @@ __global__ __launch_bounds__(256) void roi_align_lanes_kernel(const RoiArgs a) {
 
         const f32x4* f4 = reinterpret_cast<const f32x4*>(a.feat[lv]) + (size_t)b * H * W * C4;
         f32x4* o4 = reinterpret_cast<f32x4*>(a.out) + (size_t)bin * C4;
-        for (int c = lane; c < C4; c += 64) {
+        // The channel loop is wave-uniform: v_readlane below reads the parameter registers of ALL 64 lanes, so every lane must be active
+        // wherever the compiler places their computation.  (With `for (c = lane; c < C4; c += 64)` and C < 256 it placed the row
+        // parameters inside the loop, computed by the lanes below C4 only: the other lanes' registers held garbage row offsets.)  Lanes
+        // beyond C4 redo the last channel group and do not store.
+        for (int c0 = 0; c0 < C4; c0 += 64) {
+            const bool live = c0 + lane < C4;
+            const int c = min(c0 + lane, C4 - 1);
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
             for (int iy = 0; iy < gh; ++iy) {
                 if (gh > 64 && (iy & 63) == 0) row_params(iy, ylo_w, yhi_w, ly, hy);
@@ -235,6 +241,7 @@ __global__ __launch_bounds__(256) void roi_align_lanes_kernel(const RoiArgs a) {
             if (gh > 64) row_params(0, ylo_w, yhi_w, ly, hy);       // ... and for the next channel group
 #pragma unroll
             for (int e = 0; e < 4; ++e) acc[e] = __fdiv_rn(acc[e], count);
+            if (!live) continue;
             if (a.out_split) {
                 f16x4 hi, lo;
 #pragma unroll
@@ -787,7 +794,8 @@ __global__ __launch_bounds__(256) void roi_align_split_tab_kernel(const RoiArgs 
 
 }  // namespace
 
-static int g_roi_share = getenv("AMP_ROI_SHARE") ? atoi(getenv("AMP_ROI_SHARE")) : 1;
+static int g_roi_share = getenv("AMP_ROI_SHARE") ? atoi(getenv("AMP_ROI_SHARE")) : 1;      // roi_align_split_kernel: 1 = a sample row keeps its taps in registers, 0 = every sample loads its four taps
+extern "C" void amp_debug_set_roi_share(int v) { g_roi_share = v; }
 static int g_roi_xcd = getenv("AMP_ROI_XCD") ? atoi(getenv("AMP_ROI_XCD")) : 1;      // XCD-major RoI order (roi_order_kernel): 1 = for >= 1024 RoIs (the box pooler: -10 %; the mask pooler's 1600: +5 % for a third of the fabric traffic), 2 = always, 0 = never
 extern "C" void amp_debug_set_roi_xcd(int v) { g_roi_xcd = v; }
 static int g_roi_tab = getenv("AMP_ROI_TAB") ? atoi(getenv("AMP_ROI_TAB")) : 1;      // 1: sample tables in LDS (roi_align_split_tab_kernel); 0: roi_align_split_kernel

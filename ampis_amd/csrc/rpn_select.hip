@@ -170,7 +170,8 @@ __global__ void rpn_decode_kernel(const DecodeArgs a, int B) {
                 const float w = __fsub_rn(ax2, ax1), h = __fsub_rn(ay2, ay1);
                 const float cx = __fadd_rn(ax1, __fmul_rn(0.5f, w)), cy = __fadd_rn(ay1, __fmul_rn(0.5f, h));
                 const float dx = d[0], dy = d[1];
-                const float dw = fminf(d[2], a.scale_clamp), dh = fminf(d[3], a.scale_clamp);
+                // torch.clamp(max=) keeps a NaN (the box then fails the finite test below); fminf would return the clamp for it
+                const float dw = d[2] > a.scale_clamp ? a.scale_clamp : d[2], dh = d[3] > a.scale_clamp ? a.scale_clamp : d[3];
                 const float pcx = __fadd_rn(__fmul_rn(dx, w), cx), pcy = __fadd_rn(__fmul_rn(dy, h), cy);
                 const float pw = __fmul_rn(expf(dw), w), ph = __fmul_rn(expf(dh), h);
                 x1 = __fsub_rn(pcx, __fmul_rn(0.5f, pw));

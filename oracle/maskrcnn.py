@@ -288,11 +288,13 @@ def rpn_proposals_from_candidates(cands, image_size, cfg):
 
 # ------------------------------------------------------------------------------------------------ RoIAlign
 def assign_levels(boxes, min_level=2, max_level=5, canonical_box_size=224, canonical_level=4):
-    """detectron2 poolers.py assign_boxes_to_levels (fp32)."""
+    """detectron2 poolers.py assign_boxes_to_levels (fp32).  A box with exactly one negative side has a NaN size: detectron2 converts
+    that NaN to int64, which torch leaves undefined; this oracle pins it to the lowest level, as the kernel's fmaxf(NaN, 2) does."""
     area = (boxes[:, 2] - boxes[:, 0]) * (boxes[:, 3] - boxes[:, 1])
     sizes = torch.sqrt(area)
     lv = torch.floor(canonical_level + torch.log2(sizes / canonical_box_size + 1e-8))
     lv = torch.clamp(lv, min=min_level, max=max_level)
+    lv = torch.where(torch.isnan(lv), torch.full_like(lv, float(min_level)), lv)
     return lv.to(torch.int64) - min_level
 
 

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+from proposal_ref import sortkey_ref
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
@@ -93,11 +95,6 @@ def test_single_level_and_empty_levels(gpu_ctx):
     boxes = torch.zeros((B, cap, 4))
     keys = torch.zeros((B, cap), dtype=torch.int64)
     sel = torch.tensor([[128, 40, 128], [128, 128, 0]], dtype=torch.int32)
-
-    def make_sortkeys(score, pos, cat):          # csrc/common.h make_sortkey
-        u = score.astype(np.float32).view(np.uint32).astype(np.uint64)
-        o = np.where(u & 0x80000000, ~u & 0xffffffff, u | 0x80000000).astype(np.uint64)
-        return ((o << np.uint64(32)) | ((np.uint64(0xffffff) - pos.astype(np.uint64)) << np.uint64(8)) | cat.astype(np.uint64)).view(np.int64)
     for b in range(B):
         off = 0
         for l in range(L):
@@ -105,7 +102,7 @@ def test_single_level_and_empty_levels(gpu_ctx):
             c = rng.uniform(0, 200, (n, 2)); s = rng.uniform(10, 60, (n, 2))
             boxes[b, off:off + n] = torch.from_numpy(np.concatenate([c - s / 2, c + s / 2], 1).astype(np.float32))
             sc_ = np.sort(rng.normal(0, 1, n).astype(np.float32))[::-1].copy()
-            kk = make_sortkeys(sc_, np.arange(off, off + n), np.full(n, l))
+            kk = sortkey_ref(sc_, np.arange(off, off + n), np.full(n, l))          # csrc/common.h make_sortkey
             if (b, l) == (0, 1) or b == 1:
                 kk[:] = 0                      # all invalid
             keys[b, off:off + n] = torch.from_numpy(kk)
