@@ -28,6 +28,11 @@ pycocotools:
     call draws the fill, the edge and the box frame of every instance of an image in draw order from the run lists, on the device
     (csrc/render.hip) or on the host; the blend arrives as a lookup table built with the dense path's own NumPy expression, so the bytes equal
     the per-instance full-image passes of utils/visualizer.py.
+  * `mask_topology`, `clean_masks` and the `euler_number` / `filled_area` columns of `region_properties` (what users do today with
+    skimage.morphology.remove_small_objects / remove_small_holes and scipy.ndimage.binary_fill_holes on one decoded array per mask): `amp_mask_parts`
+    calls give the connected components of the ones or of the zeros of every mask of an image from the run lists -- a lock-free union-find
+    over vertical pieces on the device (csrc/mask_parts.hip) or a sequential one on the host --, flip the components a rule picks and return
+    canonical run lists; no mask is decoded.
 With no prediction at all the detection precision is 0/0: like the reference this raises ZeroDivisionError.
 The independent checker is oracle/matcher.py (a loop-for-loop restatement of the reference, pinned by its known-answer test)."""
 import numpy as np
@@ -187,6 +192,7 @@ def mask_edge_distance(gt_mask, pred_mask, gt_box, pred_box, matches, device='au
 RPROPS_DEFAULT_KEYS = ["area", "equivalent_diameter", "major_axis_length", "perimeter", "solidity", "orientation"]       # ampis/structures.py:505
 RPROPS_KEYS = ("area", "bbox", "bbox_area", "centroid", "convex_area", "eccentricity", "equivalent_diameter", "extent", "major_axis_length",
                "minor_axis_length", "orientation", "perimeter", "solidity")
+RPROPS_TOPOLOGY_KEYS = ("euler_number", "filled_area")            # from mask_topology at connectivity 2: the mask as a shape with pieces
 
 
 def region_floats(bbox, vals):
@@ -223,8 +229,8 @@ def _rprops_columns(keys):
     keys = list(RPROPS_DEFAULT_KEYS if keys is None else keys)
     cols = []
     for k in keys:
-        if k not in RPROPS_KEYS:
-            raise ValueError(f"region_properties: unsupported key {k!r} (supported: {', '.join(RPROPS_KEYS)})")
+        if k not in RPROPS_KEYS and k not in RPROPS_TOPOLOGY_KEYS:
+            raise ValueError(f"region_properties: unsupported key {k!r} (supported: {', '.join(RPROPS_KEYS + RPROPS_TOPOLOGY_KEYS)})")
         cols += [f"bbox-{i}" for i in range(4)] if k == "bbox" else [f"centroid-{i}" for i in range(2)] if k == "centroid" else [k]
     return cols
 
@@ -234,7 +240,9 @@ def region_properties(masks, keys=None, size=None, device='auto'):
     a dict of column name -> np.ndarray [N], columns named like regionprops_table ('bbox-0' .. 'bbox-3', 'centroid-0', 'centroid-1', the rest by
     key).  A region is ALL set pixels of one mask (holes and disconnected parts included), coordinates are (row, column) of the full image.
 
-    masks: anything masks_to_rle accepts (size=(h, w) for polygons); keys: any of RPROPS_KEYS, None for the reference's default list; device:
+    masks: anything masks_to_rle accepts (size=(h, w) for polygons); keys: any of RPROPS_KEYS and RPROPS_TOPOLOGY_KEYS ('euler_number' and
+    'filled_area', int64, 0 for an empty mask: skimage's -- foreground 8-connected, holes 4-connected -- from mask_topology at connectivity 2 on
+    the same path), None for the reference's default list; device:
     'cpu' (host), 'cuda' (HIP device, an error without one) or 'auto' (the device when one is visible).  One amp_mask_region_props call returns
     13 exact integers per mask (csrc/region_props.hip, or mask_analysis_host.hip on the host); region_floats derives the floats from them for both
     paths, so they agree bit for bit.  An empty mask: area, perimeter, convex_area, equivalent_diameter 0, bbox (0, 0, 0, 0), NaN elsewhere.
@@ -252,7 +260,8 @@ def region_properties(masks, keys=None, size=None, device='auto'):
     bbox, vals = rle.region_props(rles, ctx=ctx)
     rows = [region_floats(b, v) for b, v in zip(bbox.tolist(), vals.tolist())]
     ints = ("area", "bbox_area", "convex_area", "bbox-0", "bbox-1", "bbox-2", "bbox-3")
-    return {c: np.array([r[c] for r in rows], dtype=np.int64 if c in ints else np.float64) for c in cols}
+    topo = mask_topology(rles, 2, device=device) if any(c in RPROPS_TOPOLOGY_KEYS for c in cols) else {}
+    return {c: topo[c] if c in topo else np.array([r[c] for r in rows], dtype=np.int64 if c in ints else np.float64) for c in cols}
 
 
 def compute_rprops(iset, keys=None, return_df=False, device='auto'):
@@ -267,6 +276,83 @@ def compute_rprops(iset, keys=None, return_df=False, device='auto'):
     df["class_idx"] = np.asarray(inst.class_idx).reshape(-1)
     iset.rprops = df
     return df if return_df else None
+
+
+# ---- parts and holes: mask topology and repair (skimage.morphology.remove_small_objects / remove_small_holes, scipy.ndimage.binary_fill_holes) -
+
+def _parts_input(who, masks, connectivity, size, device):
+    """(rles, ctx) of a mask_topology / clean_masks call; ValueError for a bad connectivity or device and for masks of different sizes"""
+    if connectivity not in (1, 2):
+        raise ValueError(f"{who}: connectivity = {connectivity!r} (1: 4 neighbours, 2: 8 neighbours)")
+    rles = masks_to_rle(masks, size, device)
+    sizes = {tuple(int(v) for v in r["size"]) for r in rles}
+    if len(sizes) > 1:
+        raise ValueError(f"{who}: masks of different sizes {sorted(sizes)}")
+    return rles, _device_context(who, device, len(rles))
+
+
+def mask_topology(masks, connectivity=2, size=None, device='auto'):
+    """Every mask as a shape with pieces: a dict of int64 [N] arrays 'n_parts', 'n_holes', 'euler_number' (parts - holes), 'area',
+    'filled_area' (area + the pixels of all holes) and 'largest_part_area'.  Parts are the connected components of the ones -- connectivity 2:
+    8 neighbours, 1: 4 neighbours; holes the components of the zeros under the dual neighbourhood (4 neighbours for connectivity 2, 8 for 1)
+    with no pixel in the first or last row or column of the image: background that reaches the border is the outside, as in
+    scipy.ndimage.binary_fill_holes.  Connectivity 2 gives skimage.measure.regionprops' euler_number and filled_area.  An empty mask has no
+    part and no hole.
+
+    masks: anything masks_to_rle accepts (size=(h, w) for polygons); device: 'cpu' (host), 'cuda' (HIP device, an error without one) or 'auto'
+    (the device when one is visible).  Two statistics-only amp_mask_parts calls on the run lists (csrc/mask_parts.hip, or mask_parts_host.hip on the
+    host: identical bytes), no mask is decoded.  ValueError for a bad connectivity or device and for masks of different sizes."""
+    rles, ctx = _parts_input("mask_topology", masks, connectivity, size, device)
+    parts, _ = rle.mask_parts(rles, 1, connectivity, ctx=ctx, emit=False)
+    holes, _ = rle.mask_parts(rles, 0, connectivity, ctx=ctx, emit=False)
+    return {"n_parts": parts[:, 0].copy(), "n_holes": holes[:, 0].copy(), "euler_number": parts[:, 0] - holes[:, 0], "area": parts[:, 1].copy(),
+            "filled_area": parts[:, 1] + holes[:, 1], "largest_part_area": parts[:, 2].copy()}
+
+
+def clean_masks(masks, min_size=0, area_threshold=0, keep_largest=False, connectivity=2, size=None, device='auto', return_stats=False):
+    """Repairs every mask on its run list, in two steps one after the other:
+      1. parts: with keep_largest only the part of largest area stays (among equals the one whose first pixel in column-major order comes
+         first); then parts of area < min_size are removed (skimage.morphology.remove_small_objects: strict);
+      2. holes, of the result of step 1: holes of area < area_threshold are filled (remove_small_holes: strict); None fills every hole
+         (scipy.ndimage.binary_fill_holes), 0 none.
+    So a speck inside a ring's hole is removed first and the hole that grows by it is judged as a whole.  Parts, holes and connectivity as in
+    mask_topology.  Returns the list of RLE dicts in canonical form (what rle.encode gives for the dense result), length and order unchanged;
+    a mask may come back empty.  return_stats: also a dict of int64 [N] arrays 'parts_removed', 'pixels_removed', 'holes_filled',
+    'pixels_filled'.
+
+    At most two emitting amp_mask_parts calls (csrc/mask_parts.hip, or mask_parts_host.hip on the host: identical bytes); a step whose
+    arguments change nothing is skipped.  return_stats adds one statistics-only call behind each step that ran: the call reports the pixels it
+    flipped, the number of flipped components is the difference of the counts before and after.  ValueError for a negative threshold, a bad
+    connectivity or device and for masks of different sizes."""
+    if min_size is None or int(min_size) < 0:
+        raise ValueError(f"clean_masks: min_size = {min_size!r} (a pixel count, not negative)")
+    if area_threshold is not None and int(area_threshold) < 0:
+        raise ValueError(f"clean_masks: area_threshold = {area_threshold!r} (a pixel count, not negative; None fills every hole)")
+    rles, ctx = _parts_input("clean_masks", masks, connectivity, size, device)
+    n = len(rles)
+    stats = {k: np.zeros(n, np.int64) for k in ("parts_removed", "pixels_removed", "holes_filled", "pixels_filled")}
+    steps = []
+    if keep_largest or int(min_size) > 1:                            # no part has fewer pixels than one
+        steps.append((1, int(min_size), bool(keep_largest), "parts_removed", "pixels_removed"))
+    if area_threshold is None or int(area_threshold) > 1:
+        steps.append((0, area_threshold, False, "holes_filled", "pixels_filled"))
+    canonical = False
+    for colour, thr, keep, k_count, k_pixels in steps:
+        if n == 0:
+            break
+        st, counts = rle.mask_parts(rles, colour, connectivity, thr, keep, ctx=ctx)
+        pool, off, ln = rle._pool(counts)
+        rles = [{"size": list(r["size"]), "counts": c} for r, c in zip(rles, rle.counts_to_strings(pool, off, ln))]
+        canonical = True
+        stats[k_pixels] = st[:, 3].copy()
+        if return_stats:
+            after, _ = rle.mask_parts(rles, colour, connectivity, ctx=ctx, emit=False)
+            stats[k_count] = st[:, 0] - after[:, 0]
+    if not canonical and n:                                          # nothing to do: the canonical form of the input, by a call that flips nothing
+        _, counts = rle.mask_parts(rles, 1, connectivity, ctx=ctx)
+        pool, off, ln = rle._pool(counts)
+        rles = [{"size": list(r["size"]), "counts": c} for r, c in zip(rles, rle.counts_to_strings(pool, off, ln))]
+    return (rles, stats) if return_stats else rles
 
 
 def _label_runs_input(who, image, kind):

@@ -9,7 +9,7 @@
 //   4. lr_write_kernel    as 2 with a workgroup scan: run k's start S[k], end E[k], id V[k] (LABEL), parent[k] = k, and the first run of
 //                         every column;
 //   5. lr_union_kernel    BINARY: one lane per run, against the runs of the column before whose rows meet its own (one row wider on each side
-//                         for 8 neighbours): lock-free union-find, the larger root hooked under the smaller by compare-and-swap;
+//                         for 8 neighbours): lock-free union-find, the larger root hooked under the smaller by compare-and-swap (union_find.h);
 //   6. lr_flatten_kernel  BINARY: every run's root, and per root the smallest row-major position of its runs (atomic min);
 //   7. lr_keys_kernel     the sort key of every run -- that position, or the id with the sign bit flipped -- and the run's index as the value;
 //   8. rocprim::radix_sort_pairs: stable, so the runs of an instance stay in column-major order and the instances come in key order (the
@@ -31,6 +31,7 @@
 
 #include "common.h"
 #include "mask_analysis.h"
+#include "union_find.h"
 
 namespace {
 
@@ -135,31 +136,6 @@ __global__ __launch_bounds__(256) void lr_write_kernel(const unsigned long long*
     }
 }
 
-// the root of x as far as this lane can see.  Ends: parent[y] <= y always, and the walk goes on only while parent[y] < y.
-template <bool COHERENT>
-__device__ __forceinline__ unsigned int lr_find(unsigned int* parent, unsigned int x) {
-    for (;;) {
-        const unsigned int p = COHERENT ? __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : parent[x];
-        if (p == x) return x;
-        x = p;
-    }
-}
-
-// Unites the sets of runs a and b.  A parent only ever changes from itself to a smaller index (the compare-and-swap below is the only write),
-// so a stale read is an ancestor the set once had and the swap on a node that is no longer a root fails.  Ends: a failed swap returns the
-// node's parent, smaller than the node, so a + b falls with every round; no round waits for another lane.
-__device__ __forceinline__ void lr_unite(unsigned int* parent, unsigned int a, unsigned int b) {
-    for (;;) {
-        a = lr_find<true>(parent, a);
-        b = lr_find<true>(parent, b);
-        if (a == b) return;
-        if (a < b) { const unsigned int t = a; a = b; b = t; }
-        const unsigned int old = atomicCAS(&parent[a], a, b);
-        if (old == a) return;
-        a = old;
-    }
-}
-
 __global__ __launch_bounds__(256) void lr_union_kernel(const unsigned int* __restrict__ S, const unsigned int* __restrict__ E,
                                                        const unsigned int* __restrict__ colstart, unsigned int R, int h, int d,
                                                        unsigned int* parent) {
@@ -174,14 +150,14 @@ __global__ __launch_bounds__(256) void lr_union_kernel(const unsigned int* __res
             const int mid = (lo + hi) >> 1;
             if ((int)E[mid] + shift + d <= s) lo = mid + 1; else hi = mid;
         }
-        for (int j = lo; j < jend && (int)S[j] + shift < e + d; ++j) lr_unite(parent, i, (unsigned)j);      // ends: j grows to jend
+        for (int j = lo; j < jend && (int)S[j] + shift < e + d; ++j) amp::uf_unite(parent, i, (unsigned)j); // ends: j grows to jend
     }
 }
 
 __global__ __launch_bounds__(256) void lr_flatten_kernel(const unsigned int* __restrict__ S, unsigned int* parent, unsigned int R, int h, int w,
                                                          unsigned int* __restrict__ root_of, unsigned int* __restrict__ first) {
     for (unsigned int i = blockIdx.x * 256 + threadIdx.x; i < R; i += gridDim.x * 256) { // ends: i grows by the grid
-        const unsigned int root = lr_find<false>(parent, i);                             // no parent is written in this launch
+        const unsigned int root = amp::uf_find<false>(parent, i);                        // no parent is written in this launch
         const unsigned int c = S[i] / (unsigned)h, r = S[i] - c * (unsigned)h;
         root_of[i] = root;
         atomicMin(&first[root], r * (unsigned)w + c);

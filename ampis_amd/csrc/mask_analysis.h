@@ -2,7 +2,8 @@
 // with mask_analysis_host.hip.  Each *_check validates the arguments and builds the plan (run_list.h) that both paths evaluate; each *_host is
 // the evaluation with a NULL context, byte for byte what the kernels give.  amp_label_runs, the producer of run lists from an annotation image
 // (label_runs.hip, label_runs_host.hip), and amp_polygons_to_rle, the producer from polygons (polygon_runs.hip, polygon_runs_host.hip), are declared
-// at the end.  Plain C++: the host-only sanitizer builds include this header.
+// at the end; amp_mask_parts, the components of every mask and their repair (mask_parts.hip, mask_parts_host.hip), has its shared arithmetic and
+// its declarations in mask_parts.h, included below.  Plain C++: the host-only sanitizer builds include this header.
 #pragma once
 #include "run_list.h"
 
@@ -136,3 +137,6 @@ AMP_HD int label_pixel(const void* image, int kind, size_t i) {
 AMP_HD bool label_is_instance(int v, int kind, int zero_is_background) { return v != 0 || (kind != 0 && !zero_is_background); }
 
 }  // namespace amp
+
+// amp_mask_parts: mask_parts_check / mask_parts_capacity / mask_parts_host and the items both paths evaluate
+#include "mask_parts.h"

@@ -417,6 +417,43 @@ def polygons_to_rle(instances, h, w, ctx=None, return_boxes=False):
     return (out, boxes, areas) if return_boxes else out
 
 
+MASK_PARTS_ALL = 0xFFFFFFFF
+
+
+def mask_parts(masks, colour, connectivity=2, threshold=0, keep_largest=False, ctx=None, emit=True):
+    """Connected components per mask for RLE dicts of one image size, one C call (amp_mask_parts; a second one when the first reports that the
+    capacity was too small).  colour 1: the parts -- components of the ones, connectivity 1 = 4 neighbours, 2 = 8; with keep_largest every part
+    but the largest (ties: the first in column-major order) and then every part of area < threshold is removed.  colour 0: the holes --
+    components of the zeros under the dual neighbourhood that do not touch the border of the mask's tight box; every hole of area < threshold
+    is filled, threshold None fills all.  Returns (stats, counts): stats int64 [n, 4] = {components, their pixels, the largest component's
+    pixels, the pixels flipped} and the list of the results' canonical uint32 counts arrays (None when emit is false: statistics only).
+    ValueError for masks of different sizes.  ctx: a _lib.Context (computed on its device) or None (on the host): the same bytes."""
+    n = len(masks)
+    sizes = {tuple(int(v) for v in r["size"]) for r in masks}
+    if len(sizes) > 1:
+        raise ValueError(f"mask_parts: masks of different sizes {sorted(sizes)}")
+    stats = np.zeros((n, 4), dtype=np.uint64)
+    if n == 0:
+        return stats.astype(np.int64), ([] if emit else None)
+    h, w = sizes.pop()
+    thr = MASK_PARTS_ALL if threshold is None else min(int(threshold), MASK_PARTS_ALL)
+    pool, off, ln = _pool([_counts(x) for x in masks])
+    args = (_handle(ctx), _vp(pool), _vp(off), _vp(ln), n, h, w, int(colour), int(connectivity), thr, int(bool(keep_largest)), _vp(stats))
+    if not emit:
+        check(lib().amp_mask_parts(*args, None, 0, None, None, None), "amp_mask_parts")
+        return stats.astype(np.int64), None
+    out_off, out_len, need = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.int32), np.zeros(1, dtype=np.uint64)
+    cap = int(ln.sum()) + n * (w + 1)                               # always enough: a tight box is no wider than the image
+    for attempt in range(2):
+        out = np.empty(cap, dtype=np.uint32)
+        st = lib().amp_mask_parts(*args, _vp(out), cap, _vp(out_off), _vp(out_len), _vp(need))
+        if st != -3 or attempt:                                     # AMP_ERR_NOMEM the first time: the need is known now
+            check(st, "amp_mask_parts")
+            break
+        cap = max(int(need[0]), 1)
+    return stats.astype(np.int64), [out[int(o): int(o) + int(k)].copy() for o, k in zip(out_off, out_len)]
+
+
 def merge(rles, intersect=False):
     assert len(rles) >= 1
     h, w = rles[0]["size"]

@@ -638,6 +638,28 @@ int amp_polygons_to_rle(amp_ctx* ctx, const double* xy, const unsigned long long
                         const int* inst_first /* [n + 1] */, int n, int h, int w, uint32_t* counts, unsigned long long counts_cap,
                         unsigned long long* counts_off /* [n] */, int* counts_len /* [n] */, int* boxes /* [n][4] */, unsigned int* areas /* [n] */,
                         unsigned long long* need /* [1] */);
+/* The pieces of masks: connected components per mask for the n run lists pool[off[i] : off[i] + len[i]] of one h x w image size (1 <= h, w
+ * <= 32768, h * w <= 2^30) in one call, the components a rule picks flipped, the results as canonical run lists -- what
+ * skimage.morphology.remove_small_objects / remove_small_holes, scipy.ndimage.binary_fill_holes and regionprops' euler_number / filled_area
+ * compute on one decoded array per mask.  ALL POINTERS ARE HOST POINTERS.  connectivity k: 1 or 2.
+ *   colour 1  PARTS: the components of the ones, 4 neighbours for k = 1, 8 for k = 2.  Flipped (removed): with keep_largest every part but the
+ *             one of largest area (among equals the one whose first pixel col * h + row is smallest), and then every part of area < threshold.
+ *   colour 0  HOLES: the components of the zeros under the dual neighbourhood (4 neighbours for k = 2, 8 for k = 1) that lie inside the mask's
+ *             tight box and have no pixel in its border rows or columns; zeros that reach further are the outside, as in binary_fill_holes.
+ *             Flipped (filled): every hole of area < threshold; threshold = 0xffffffff fills all.  keep_largest must be 0.
+ * stats [n][4] = {components, their pixels, the largest component's pixels, the pixels flipped}; an empty mask has no component.
+ * out_pool == NULL: statistics only.  Otherwise mask i's result is out_pool[out_off[i] .. + out_len[i]), the lists back to back in mask order,
+ * each what amp_rle_encode gives for the dense result (the first count is the run of zeros and may be 0; with nothing flipped, the canonical
+ * form of the input).  With valid arguments need[0] = the counts of all results is always written; with out_cap below it the call returns
+ * AMP_ERR_NOMEM and writes nothing else.  sum(len[i] + box width of mask i + 1) always suffices: a flip removes boundaries of the input
+ * and adds them only at column ends inside the tight box.  Arguments are checked on the host before any device work (AMP_ERR_ARG naming the
+ * offender, nothing written): the sizes, colour, connectivity, keep_largest, NULL pointers, every run list non-empty and summing to h * w.
+ * ctx == NULL: computed on the host (mask_parts_host.hip).  Otherwise on ctx's device and stream (mask_parts.hip): upload, a fixed list of
+ * launches whatever n is, download; integer arithmetic only, the bytes do not depend on the device's scheduling and equal the host's. */
+int amp_mask_parts(amp_ctx* ctx, const uint32_t* pool, const unsigned long long* off, const int* len, int n, int h, int w, int colour,
+                   int connectivity, unsigned int threshold, int keep_largest, unsigned long long* stats /* [n][4] */, uint32_t* out_pool,
+                   unsigned long long out_cap, unsigned long long* out_off /* [n] */, int* out_len /* [n] */,
+                   unsigned long long* need /* [1] */);
 
 /* The model: DefaultPredictor(cfg) / predictor(img) ---------------------------------------------- */
 typedef struct amp_model amp_model;
