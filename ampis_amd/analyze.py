@@ -33,6 +33,12 @@ pycocotools:
     calls give the connected components of the ones or of the zeros of every mask of an image from the run lists -- a lock-free union-find
     over vertical pieces on the device (csrc/mask_parts.hip) or a sequential one on the host --, flip the components a rule picks and return
     canonical run lists; no mask is decoded.
+  * `resolve_overlaps` and `instances_to_label_image` (what users do today with a loop of decoded masks, labels[mask_i] = i + 1 in score
+    order, and an encode of labels == i + 1 per instance): ONE `amp_flatten_instances` call gives every pixel that several masks cover to
+    one of them -- the highest score, the smallest area, the first in the list or the smallest given rank -- and returns the disjoint masks
+    as canonical run lists, the int32 label image, the visible areas and boxes; one wave per 64 x 64 tile claims the pixels in priority
+    order on the device (csrc/flatten.hip), a sweep over the sorted run ends on the host; no mask is decoded.  It is the inverse of
+    `label_image_to_rle`.
 With no prediction at all the detection precision is 0/0: like the reference this raises ZeroDivisionError.
 The independent checker is oracle/matcher.py (a loop-for-loop restatement of the reference, pinned by its known-answer test)."""
 import numpy as np
@@ -353,6 +359,95 @@ def clean_masks(masks, min_size=0, area_threshold=0, keep_largest=False, connect
         pool, off, ln = rle._pool(counts)
         rles = [{"size": list(r["size"]), "counts": c} for r, c in zip(rles, rle.counts_to_strings(pool, off, ln))]
     return (rles, stats) if return_stats else rles
+
+
+# ---- overlap-free instances: the owner of every pixel (the labels[mask_i] = i + 1 loop over decoded masks) ---------------------------------------
+
+def flatten_ranks(who, priority, n, scores=None, areas=None):
+    """The uint32 ranks amp_flatten_instances orders the n instances by (the smallest rank owns a pixel, ties go to the lower index), None for
+    index order.  priority 'score': higher score on top (scores required, NaN refused); 'area': smaller area on top (areas: a callable that
+    returns them); 'index'; or an integer array of ranks, any integers.  Stable NumPy sorts on the host."""
+    if isinstance(priority, str):
+        p = priority.lower()
+        if p == "index":
+            return None
+        if p == "score":
+            if scores is None:
+                raise ValueError(f"{who}: priority='score' needs scores (scores=..., or an Instances with a scores field)")
+            s = np.asarray(scores.numpy() if hasattr(scores, "numpy") else scores, dtype=np.float64).reshape(-1)
+            if len(s) != n:
+                raise ValueError(f"{who}: {len(s)} scores for {n} masks")
+            if np.isnan(s).any():
+                raise ValueError(f"{who}: scores[{int(np.flatnonzero(np.isnan(s))[0])}] is NaN")
+            key = -s
+        elif p == "area":
+            key = np.asarray(areas(), dtype=np.int64).reshape(-1)
+        else:
+            raise ValueError(f"{who}: priority = {priority!r} ('score', 'area', 'index' or an integer array of ranks)")
+    else:
+        key = np.asarray(priority)
+        if key.ndim != 1 or len(key) != n or not (n == 0 or (np.issubdtype(key.dtype, np.integer) and key.dtype != bool)):
+            raise ValueError(f"{who}: priority = {priority!r} ('score', 'area', 'index' or an array of {n} integer ranks)")
+    rank = np.empty(n, dtype=np.uint32)
+    rank[np.argsort(key, kind="stable")] = np.arange(n, dtype=np.uint32)          # the place in the order: equal keys keep their index order
+    return rank
+
+
+def _flatten_input(who, masks, priority, scores, size, device):
+    """(rles, rank, (h, w), ctx) of a resolve_overlaps / instances_to_label_image call"""
+    inst = masks.instances if hasattr(masks, "instances") and masks.instances is not None else masks
+    if scores is None and hasattr(inst, "masks") and hasattr(inst, "image_size"):
+        scores = getattr(inst, "scores", None)
+    m, size = _unwrap_masks(masks, size)
+    _device_context(who, device, 0)                                   # a bad device is refused before anything is computed
+    rles = masks_to_rle(m, size, device)
+    h, w = _image_size(who, rles, size)
+    rles = [{"size": r["size"], "counts": rle._counts(r)} for r in rles]               # the strings are read once: the call takes the arrays
+
+    def areas():                                                      # the odd counts of every list, summed without a loop over the masks
+        if not rles:
+            return np.zeros(0, np.int64)
+        pool, off, ln = rle._pool([r["counts"] for r in rles])
+        owner = np.repeat(np.arange(len(rles)), ln)
+        odd = (np.arange(len(owner)) - np.repeat(off.astype(np.int64), ln)) & 1
+        return np.bincount(owner, weights=pool[:len(owner)].astype(np.int64) * odd, minlength=len(rles)).astype(np.int64)
+
+    rank = flatten_ranks(who, priority, len(rles), scores, areas)
+    return rles, rank, (h, w), _device_context(who, device, len(rles))
+
+
+def resolve_overlaps(masks, priority='score', scores=None, size=None, device='auto', return_stats=False):
+    """The instances of an image made disjoint: every pixel several masks cover goes to ONE of them, the rest lose it.  Returns the list of RLE
+    dicts in canonical form (what rle.encode gives for the dense result), length and order unchanged -- a mask may come back empty --; no two
+    share a pixel, and their union is the union of the input.
+
+    priority: which covering instance owns a pixel.  'score': the one of highest score (scores=..., or the `scores` field of an Instances /
+    InstanceSet; NaN is refused); 'area': the one of smallest input area, so a satellite keeps its pixels on its particle; 'index': the first
+    in the list; or an integer array of ranks, smallest on top.  Ties always go to the lower index.
+    masks: anything masks_to_rle accepts (size=(h, w) for polygons and for no mask at all), an Instances or an InstanceSet; device: 'cpu'
+    (host), 'cuda' (HIP device, an error without one) or 'auto' (the device when one is visible).  return_stats: also a dict of int64 arrays
+    'area' [N] (of the input masks), 'visible_area' [N], 'bbox' [N, 4] ({r0, c0, r1, c1} of the visible pixels, ends exclusive, zeros for
+    none) and 'pixels' [3]: the pixels of the image covered by no mask, by one, by two or more.
+
+    One amp_flatten_instances call on the run lists (csrc/flatten.hip, or flatten_host.hip on the host: identical bytes); no mask is decoded.
+    Pass the result to psd, mask_areas or region_properties to count every pixel once.  ValueError for a bad priority or device and for masks
+    of different sizes."""
+    rles, rank, (h, w), ctx = _flatten_input("resolve_overlaps", masks, priority, scores, size, device)
+    stats, boxes, pixels, counts = rle.flatten_instances(rles, rank, ctx=ctx, size=(h, w))
+    pool, off, ln = rle._pool(counts)
+    out = [{"size": [h, w], "counts": c} for c in rle.counts_to_strings(pool, off, ln)]
+    if not return_stats:
+        return out
+    return out, {"area": stats[:, 0].copy(), "visible_area": stats[:, 1].copy(), "bbox": boxes, "pixels": pixels}
+
+
+def instances_to_label_image(masks, priority='score', scores=None, size=None, device='auto'):
+    """The instances of an image as ONE int32 [H, W] label image: instance i's visible pixels hold i + 1, pixels no mask covers 0 -- the form
+    ImageJ, skimage and get_ddicts('label') read; label_image_to_rle(result, 'label') returns the non-empty visible masks in index order.
+    masks, priority, scores, device: as resolve_overlaps; size=(h, w) is required when there is no mask.  One amp_flatten_instances
+    call that emits no list (csrc/flatten.hip: one launch; or flatten_host.hip on the host: identical bytes)."""
+    rles, rank, (h, w), ctx = _flatten_input("instances_to_label_image", masks, priority, scores, size, device)
+    return rle.flatten_instances(rles, rank, ctx=ctx, emit=False, return_labels=True, size=(h, w))[4]
 
 
 def _label_runs_input(who, image, kind):

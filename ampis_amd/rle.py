@@ -454,6 +454,47 @@ def mask_parts(masks, colour, connectivity=2, threshold=0, keep_largest=False, c
     return stats.astype(np.int64), [out[int(o): int(o) + int(k)].copy() for o, k in zip(out_off, out_len)]
 
 
+def flatten_instances(masks, rank=None, ctx=None, emit=True, return_labels=False, size=None):
+    """Which instance a pixel belongs to, for RLE dicts of one image size that may overlap, in ONE C call (amp_flatten_instances; the capacity
+    2 x the input counts always suffices).  The owner of a pixel is the covering instance of smallest rank[i], among equals of smallest index;
+    rank None is index order, any uint32 values are valid.  Returns (stats, boxes, pixels, counts) and, with return_labels, the int32 [h, w]
+    label image of owner + 1 (0: no owner): stats int64 [n, 2] = {area of the input mask, pixels owned}, boxes int64 [n, 4] = {r0, c0, r1, c1}
+    of the owned pixels with exclusive ends (zeros when nothing is owned), pixels int64 [3] = the pixels covered by no instance, by one, by two
+    or more, counts the list of the visible masks' canonical uint32 counts arrays -- what encode(labels == i + 1) gives; [h * w] for an
+    instance that owns nothing -- or None when emit is false.  size=(h, w) is needed only when there is no mask.  ValueError for masks of
+    different sizes, a rank of another length or outside uint32.  ctx: a _lib.Context (computed on its device) or None (on the host): the same
+    bytes."""
+    n = len(masks)
+    sizes = {tuple(int(v) for v in r["size"]) for r in masks}
+    if size is not None:
+        sizes.add((int(size[0]), int(size[1])))
+    if len(sizes) > 1:
+        raise ValueError(f"flatten_instances: masks of different sizes {sorted(sizes)}")
+    if not sizes:
+        raise ValueError("flatten_instances: size=(height, width) is required when there is no mask to take it from")
+    h, w = sizes.pop()
+    rk = None
+    if rank is not None:
+        r = np.asarray(rank)
+        if r.shape != (n,) or not (n == 0 or np.issubdtype(r.dtype, np.integer)):
+            raise ValueError(f"flatten_instances: rank must be {n} integers, got shape {r.shape} {r.dtype}")
+        if n and (int(r.min()) < 0 or int(r.max()) > 0xFFFFFFFF):
+            raise ValueError(f"flatten_instances: ranks {int(r.min())} .. {int(r.max())} do not fit uint32")
+        rk = np.ascontiguousarray(r, dtype=np.uint32)
+    pool, off, ln = _pool([_counts(x) for x in masks])
+    stats, boxes, pixels = np.zeros((n, 2), dtype=np.uint64), np.zeros((n, 4), dtype=np.int32), np.zeros(3, dtype=np.uint64)
+    labels = np.empty((h, w), dtype=np.int32) if return_labels else None
+    cap = 2 * int(ln.sum()) if emit else 0
+    out = np.empty(max(cap, 1), dtype=np.uint32) if emit else None
+    out_off, out_len, need = np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.int32), np.zeros(1, dtype=np.uint64)
+    opt = lambda a: _vp(a) if a is not None else None
+    check(lib().amp_flatten_instances(_handle(ctx), _vp(pool), _vp(off), _vp(ln), n, h, w, opt(rk), opt(labels), opt(out), cap, _vp(out_off),
+                                      _vp(out_len), _vp(stats), _vp(boxes), _vp(pixels), _vp(need)), "amp_flatten_instances")
+    counts = [out[int(o): int(o) + int(k)].copy() for o, k in zip(out_off[:n], out_len[:n])] if emit else None
+    res = (stats.astype(np.int64), boxes.astype(np.int64), pixels.astype(np.int64), counts)
+    return res + (labels,) if return_labels else res
+
+
 def merge(rles, intersect=False):
     assert len(rles) >= 1
     h, w = rles[0]["size"]

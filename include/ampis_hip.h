@@ -660,6 +660,32 @@ int amp_mask_parts(amp_ctx* ctx, const uint32_t* pool, const unsigned long long*
                    int connectivity, unsigned int threshold, int keep_largest, unsigned long long* stats /* [n][4] */, uint32_t* out_pool,
                    unsigned long long out_cap, unsigned long long* out_off /* [n] */, int* out_len /* [n] */,
                    unsigned long long* need /* [1] */);
+/* Overlap-free instances: which instance a pixel belongs to, for the n run lists pool[off[i] : off[i] + len[i]] of one h x w image (1 <= h, w
+ * <= 32768, h * w <= 2^30) in one call -- what users compute with a loop of decoded masks, labels[mask_i] = i + 1 in reverse priority and
+ * encode(labels == i + 1) per instance.  ALL POINTERS ARE HOST POINTERS.  The OWNER of a pixel is, among the instances that cover it, the one
+ * with the smallest rank[i], among equal ranks the one with the smallest index; any rank values are valid, rank == NULL means index order; a
+ * pixel nothing covers has no owner.
+ *   labels (may be NULL): int32 h x w, row-major as numpy holds it: owner + 1, or 0 where there is no owner.
+ *   counts (may be NULL: no list is emitted, counts_cap must be 0, counts_off / counts_len / need are not used): instance i's VISIBLE list
+ *     -- the pixels it owns, over the whole image -- is counts[counts_off[i] .. + counts_len[i]), the lists back to back in instance order,
+ *     each exactly what amp_rle_encode gives for the dense labels == i + 1 (column-major, the first count is the run of zeros and may be 0,
+ *     runs joined across column ends); an instance that owns nothing is the single run h * w.
+ *   stats [n][2] = {the area of the input mask, the pixels owned}; boxes [n][4] = {r0, c0, r1, c1} the tight box of the owned pixels with
+ *     exclusive ends, zeros when nothing is owned; pixels [3] = the pixels covered by no instance, by exactly one, by two or more.
+ * With valid arguments and counts != NULL need[0] = the counts of all visible lists is always written; with counts_cap below it the call
+ * returns AMP_ERR_NOMEM naming both and writes nothing else.  counts_cap = 2 x the sum of len[i] always suffices: the owner changes only at
+ * a position where some input mask changes, such a position is a boundary of at most two visible lists, and the one further count every
+ * list has is paid by its mask's own.  Arguments are checked on the host before any device work (AMP_ERR_ARG naming the
+ * offender, nothing written): the sizes, n < 0, NULL pointers that are not optional, counts_cap without counts, every run list non-empty
+ * and summing to h * w.  n == 0 is valid: labels all zero, pixels = {h * w, 0, 0}.
+ * ctx == NULL: computed on the host (flatten_host.hip: one sweep over the sorted run ends with the set of covering instances).  Otherwise
+ * on ctx's device and stream (flatten.hip): upload, a fixed list of launches whatever n is, download; no dense mask per instance, integer
+ * arithmetic only, the bytes do not depend on the device's scheduling and equal the host's. */
+int amp_flatten_instances(amp_ctx* ctx, const uint32_t* pool, const unsigned long long* off, const int* len, int n, int h, int w,
+                          const uint32_t* rank /* [n] or NULL */, int* labels /* [h][w] or NULL */, uint32_t* counts,
+                          unsigned long long counts_cap, unsigned long long* counts_off /* [n] */, int* counts_len /* [n] */,
+                          unsigned long long* stats /* [n][2] */, int* boxes /* [n][4] */, unsigned long long* pixels /* [3] */,
+                          unsigned long long* need /* [1] */);
 
 /* The model: DefaultPredictor(cfg) / predictor(img) ---------------------------------------------- */
 typedef struct amp_model amp_model;
