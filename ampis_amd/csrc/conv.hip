@@ -3197,6 +3197,16 @@ extern "C" int amp_conv2d_grouped_nhwc_fmt(amp_ctx* ctx, const amp_conv_desc* d,
     return amp::conv_run(ctx, d, groups, x, w_win, nullptr, 0, scale, shift, res, nullptr, y, 0, fmt);
 }
 
+// Tests (tests/test_conv_exact_gpu.py): conv_run as the model's training step calls it -- a ReLU mask (fp32, or split rows with AMP_FMT_MASK_SPLIT),
+// a scaled input (in_shift), force_f32 and weights split beforehand (w_split: amp_split_weights / amp_dgrad_weights_split of w, or null for the per-call
+// split) have no entry in the public header.  No fused tail.
+extern "C" int amp_debug_conv_run(amp_ctx* ctx, const amp_conv_desc* d, int groups, const float* x, const float* w, const float* w_split, const float* scale,
+                                  const float* shift, const float* res, const float* mask, float* y, int in_shift, int fmt, int force_f32) {
+    AMP_REQUIRE(d && groups >= 1 && fmt >= 0 && fmt < 16 && in_shift >= 0 && in_shift <= 24, "amp_debug_conv_run: bad argument");
+    AMP_REQUIRE(fmt == 0 || (ctx && ctx->conv_mode == AMP_CONV_F16X3), "amp_debug_conv_run: split formats exist in AMP_CONV_F16X3 only");
+    return amp::conv_run(ctx, d, groups, x, w, w_split, force_f32, scale, shift, res, mask, y, in_shift, fmt);
+}
+
 namespace {
 __global__ void group_expand_kernel(const float* __restrict__ w, int Cout, int taps, int cpg, float* __restrict__ out) {
     const size_t total = (size_t)Cout * taps * 64;

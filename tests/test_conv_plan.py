@@ -1,6 +1,7 @@
 """Which kernel conv_run gives a layer (csrc/conv.hip conv_plan), without a GPU: tests/golden/conv_plan_table.json holds one row per distinct
 combination of selection inputs and switch state that the benchmark (default and --full) and tests/test_{conv,conv_modes,x101,backward}_gpu.py
-reach, with the launch the if / else chain of conv_run chose for it BEFORE conv_plan existed (recorded from that commit, not from this code).
+reach, with the launch the if / else chain of conv_run chose for it BEFORE conv_plan existed (recorded from that commit, not from this code);
+the rows of the cases of tests/test_conv_exact_gpu.py came later and were recorded from the rules current then (the table's "what" field).
 amp_debug_conv_plan must give exactly that: kernel, epilogue, N tiles, grid, stagger, dominant flag.  A pull request that changes a rule
 regenerates the table (tools/conv_plan_table.py) and shows the moved layers as its diff."""
 import os
@@ -9,10 +10,9 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-# values of amp::ConvKernel without a row: no recorded run reaches them at the recording commit
-UNREACHED = {
-    "F16X3S_256": "a split input on 256-wide tiles with the ring kernel switched off (AMP_SPLIT_RING=0): the tests that flip that switch run layers below the 256-wide rule",
-}
+# values of amp::ConvKernel without a row (none since the cases of tests/test_conv_exact_gpu.py have rows: F16X3S_256 -- a split input on 256-wide
+# tiles with the ring kernel switched off -- was the last one)
+UNREACHED = {}
 
 
 def test_every_recorded_choice_is_reproduced():
