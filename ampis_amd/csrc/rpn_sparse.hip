@@ -218,6 +218,10 @@ int rpn_sparse_backward(amp_ctx* ctx, const RpnSparseArgs& A) {
     const size_t g_need = std::max((size_t)R * 9 * A.C, sums_floats);
     AMP_REQUIRE(A.G_floats >= g_need, "rpn_sparse_backward: G holds %zu floats, needs %zu (max of %d rows x %d and the head sums' %zu partials)",
                 A.G_floats, g_need, R, 9 * A.C, sums_floats);
+    // dW_conv: the weight gradient of a 1x1 layer 2304 -> 256 over a 1 x R image (its scratch is checked here, before anything is launched: a refused call writes nothing)
+    amp_conv_desc dw;
+    dw.B = 1; dw.H = 1; dw.W = R; dw.Cin = 9 * A.C; dw.Cout = A.C; dw.KH = 1; dw.KW = 1; dw.stride = 1; dw.pad = 0; dw.relu = 0; dw.res_mode = 0; dw.out_mode = 0;
+    AMP_REQUIRE(amp_conv_wgrad_scratch_floats(&dw) <= A.wg_scratch_floats, "rpn_sparse_backward: wgrad scratch too small");
     hipLaunchKernelGGL(rpn_nz_rows_kernel, dim3(A.B), dim3(512), 0, ctx->stream, g, A.sampled, A.counts, A.batch, A.rows, A.nrows);
     GatherArgs ga;
     ga.g = g; ga.rows = A.rows; ga.batch = A.batch; ga.feat_split = A.feat_split; ga.xg = A.xg;
@@ -241,10 +245,7 @@ int rpn_sparse_backward(amp_ctx* ctx, const RpnSparseArgs& A) {
     // (the partial sums live in G, which the data-gradient GEMM overwrites further down: RPN_SPARSE_SUMS_FLOATS, more than R x 2304 when R < 64)
     hipLaunchKernelGGL(rpn_head_sums_kernel, dim3(A.ld + 2, SUM_SLICES), dim3(1024), 0, ctx->stream, A.dpred_rows, A.act_rows, A.dt_rows, R, A.K, A.ld, A.G);
     hipLaunchKernelGGL(rpn_head_sums_final_kernel, dim3(A.ld + 2), dim3(256), 0, ctx->stream, A.G, A.K, A.ld, A.gw_pred, A.gb_pred, A.gb_conv);
-    // dW_conv[n][tap][c] = sum_r d_t[r][n] * X[r][tap][c]: the weight gradient of a 1x1 layer 2304 -> 256 over a 1 x R image (gradients of 1e-9 .. 1e-4: * 2^16 in front of the f16 split)
-    amp_conv_desc dw;
-    dw.B = 1; dw.H = 1; dw.W = R; dw.Cin = 9 * A.C; dw.Cout = A.C; dw.KH = 1; dw.KW = 1; dw.stride = 1; dw.pad = 0; dw.relu = 0; dw.res_mode = 0; dw.out_mode = 0;
-    AMP_REQUIRE(amp_conv_wgrad_scratch_floats(&dw) <= A.wg_scratch_floats, "rpn_sparse_backward: wgrad scratch too small");
+    // dW_conv[n][tap][c] = sum_r d_t[r][n] * X[r][tap][c] (gradients of 1e-9 .. 1e-4: * 2^16 in front of the f16 split)
     AMP_TRY_STATUS(amp_conv2d_wgrad_scaled(ctx, &dw, A.xg, A.dt_rows, A.conv_scale, A.wg_scratch, A.gw_conv, 0, 16, 0));
     // G = d_t . Wt: a 1x1 layer 256 -> 2304 over the same image
     hipLaunchKernelGGL(rpn_wt_kernel, dim3(9 * A.C), dim3(256), 0, ctx->stream, A.w_conv, A.conv_scale, A.wt, A.C, A.C);
@@ -263,3 +264,38 @@ int rpn_sparse_backward(amp_ctx* ctx, const RpnSparseArgs& A) {
 }
 
 }  // namespace amp
+
+// Tests (tests/test_rpn_sparse_exact_gpu.py): the sparse pass has no entry in the public header.  The struct is amp::RpnSparseArgs in plain C, field for field.
+extern "C" {
+struct amp_debug_rpn_sparse_args {
+    int B, batch, ld, K, C, A;
+    int fh[5], fw[5];
+    const int* sampled; const int* counts;
+    const float* dpred[5]; const float* t[5]; const float* feat[5];
+    int t_split, feat_split, recompute_t;
+    const float* w_conv_split; const float* conv_shift; const float* w_pred; const float* w_conv; const float* conv_scale;
+    float* gw_pred; float* gb_pred; float* gw_conv; float* gb_conv;
+    float* dfeat[5];
+    unsigned int* rows; int* nrows;
+    float* dpred_rows; float* act_rows; float* dt_rows;
+    float* xg; float* G; float* wt;
+    size_t G_floats;
+    float* wg_scratch; size_t wg_scratch_floats;
+};
+int amp_debug_rpn_sparse_backward(amp_ctx* ctx, const amp_debug_rpn_sparse_args* d) {
+    AMP_REQUIRE(ctx && d, "amp_debug_rpn_sparse_backward: null argument");
+    amp::RpnSparseArgs a;
+    a.B = d->B; a.batch = d->batch; a.ld = d->ld; a.K = d->K; a.C = d->C; a.A = d->A;
+    for (int l = 0; l < 5; ++l) {
+        a.fh[l] = d->fh[l]; a.fw[l] = d->fw[l];
+        a.dpred[l] = d->dpred[l]; a.t[l] = d->t[l]; a.feat[l] = d->feat[l]; a.dfeat[l] = d->dfeat[l];
+    }
+    a.sampled = d->sampled; a.counts = d->counts;
+    a.t_split = d->t_split; a.feat_split = d->feat_split; a.recompute_t = d->recompute_t;
+    a.w_conv_split = d->w_conv_split; a.conv_shift = d->conv_shift; a.w_pred = d->w_pred; a.w_conv = d->w_conv; a.conv_scale = d->conv_scale;
+    a.gw_pred = d->gw_pred; a.gb_pred = d->gb_pred; a.gw_conv = d->gw_conv; a.gb_conv = d->gb_conv;
+    a.rows = d->rows; a.nrows = d->nrows; a.dpred_rows = d->dpred_rows; a.act_rows = d->act_rows; a.dt_rows = d->dt_rows;
+    a.xg = d->xg; a.G = d->G; a.wt = d->wt; a.G_floats = d->G_floats; a.wg_scratch = d->wg_scratch; a.wg_scratch_floats = d->wg_scratch_floats;
+    return amp::rpn_sparse_backward(ctx, a);
+}
+}  // extern "C"

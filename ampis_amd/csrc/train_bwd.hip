@@ -851,6 +851,12 @@ int amp_roi_align_bwd_batched(amp_ctx* ctx, float* const dfeat[4], const int fh[
     return amp::roi_align_bwd_run(ctx, dfeat, fh, fw, stride, C, rois, batch_idx, R, P, dout, B, 0);
 }
 
+// Tests (tests/test_roi_bwd_exact_gpu.py): the first-writer mode the training step uses (init = 1) has no entry in the public header.
+int amp_debug_roi_align_bwd(amp_ctx* ctx, float* const dfeat[4], const int fh[4], const int fw[4], const int stride[4], int C, const float* rois,
+                            const int* batch_idx, int R, int P, const float* dout, int B, int init) {
+    return amp::roi_align_bwd_run(ctx, dfeat, fh, fw, stride, C, rois, batch_idx, R, P, dout, B, init);
+}
+
 }  // extern "C"
 
 // init = 1: the gradient maps are uninitialised and this call is their first writer (B > 0 required): the owner-computes kernel visits
