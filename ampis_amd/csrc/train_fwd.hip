@@ -593,9 +593,11 @@ __global__ __launch_bounds__(64) void mask_target_loss_kernel(const MaskLossArgs
     } else {
         for (int i = lane; i < MS * MS; i += 64) bits[i] = 0;
     }
-    // detectron2 rasterize_polygons_within_box: box arithmetic in fp32, polygon in fp64
+    // detectron2 rasterize_polygons_within_box: the box sides are fp32 differences, everything after them is fp64.  The ratio too: the oracle
+    // (and detectron2 under the NumPy 1.x of its pinned environment) divides 28 by max(side, 0.1) in double, with the double 0.1 as the floor.
+    // An fp32 quotient moves a vertex across a rounding boundary of rleFrPoly's 5x grid once in a few thousand instances.
     const float w32 = __fsub_rn(r[2], r[0]), h32 = __fsub_rn(r[3], r[1]);
-    const double rw = (double)__fdiv_rn((float)MS, fmaxf(w32, 0.1f)), rh = (double)__fdiv_rn((float)MS, fmaxf(h32, 0.1f));
+    const double rw = (double)MS / fmax((double)w32, 0.1), rh = (double)MS / fmax((double)h32, 0.1);
     const double bx = (double)r[0], by = (double)r[1];
     // polygons_to_bitmask: frPyObjects of every polygon of the instance, merged (union), decoded
     const int q0 = from_bitmask ? 0 : (a.inst_poly_off ? a.inst_poly_off[pid] : pid);
