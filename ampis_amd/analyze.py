@@ -39,6 +39,11 @@ pycocotools:
     as canonical run lists, the int32 label image, the visible areas and boxes; one wave per 64 x 64 tile claims the pixels in priority
     order on the device (csrc/flatten.hip), a sweep over the sorted run ends on the host; no mask is decoded.  It is the inverse of
     `label_image_to_rle`.
+  * `mask_contours` and `masks_to_polygons` (what users do today with cv2.findContours / detectron2's GenericMask.mask_to_polygons on one
+    decoded array per mask): ONE `amp_mask_contours` call gives the boundary rings of every mask of an image from the run lists as exact
+    crack rings on pixel corners -- the cycles of a successor permutation over the top and bottom edges of vertical pieces, found by pointer
+    jumping on the device (csrc/contours.hip) or by a sequential walk on the host --; no mask is decoded.  It is the inverse of
+    `masks_to_rle(PolygonMasks, ...)`.
 With no prediction at all the detection precision is 0/0: like the reference this raises ZeroDivisionError.
 The independent checker is oracle/matcher.py (a loop-for-loop restatement of the reference, pinned by its known-answer test)."""
 import numpy as np
@@ -359,6 +364,47 @@ def clean_masks(masks, min_size=0, area_threshold=0, keep_largest=False, connect
         pool, off, ln = rle._pool(counts)
         rles = [{"size": list(r["size"]), "counts": c} for r, c in zip(rles, rle.counts_to_strings(pool, off, ln))]
     return (rles, stats) if return_stats else rles
+
+
+# ---- boundary rings: masks back to polygons (cv2.findContours / detectron2's GenericMask.mask_to_polygons on one decoded array per mask) --------
+
+def _contours_call(who, masks, connectivity, size, device):
+    """(rle.mask_contours' arrays, the number of masks) of a mask_contours / masks_to_polygons call"""
+    rles, ctx = _parts_input(who, masks, connectivity, size, device)
+    if not rles:                                                     # no mask: no ring, whatever the size
+        z = np.zeros(0, np.int64)
+        return (np.zeros(1, np.int64), z, z, z, z, np.zeros((0, 2), np.int32)), 0
+    return rle.mask_contours(rles, connectivity, ctx=ctx), len(rles)
+
+
+def mask_contours(masks, connectivity=2, size=None, device='auto'):
+    """The boundary rings of every mask: a list with, per mask, the list of its rings as dicts {'xy': int32 [k, 2] corners (x, y), 'hole': bool,
+    'area': int, 'length': int}.  Exact crack rings on pixel corners: pixel (r, c) is the square [c, c + 1] x [r, r + 1], a vertex an integer
+    corner 0 <= x <= w, 0 <= y <= h -- the coordinates PolygonMasks and polygons_to_rle use, no half-pixel shift --, every ring has the mask on
+    its right hand (outer rings clockwise on screen, hole rings the other way) and lists its corners only, from its smallest corner by x, then
+    y; the rings of a mask are ordered by that corner.  connectivity 2 joins diagonal ones into one ring (and keeps diagonal zeros apart), 1
+    the other way round, so the outer rings are mask_topology's parts and the hole rings its holes (an island in a hole is a part).  'area' is
+    the pixels the ring encloses, 'length' its crack length.  The parity (XOR) of all rings through polygons_to_rle is the mask again, bit for
+    bit.  UNPINNED PARITY with cv2.findContours, which is not part of this environment and returns pixel-centre chains, not cracks.
+
+    masks: anything masks_to_rle accepts (size=(h, w) for polygons); device: 'cpu' (host), 'cuda' (HIP device, an error without one) or 'auto'
+    (the device when one is visible).  One amp_mask_contours call on the run lists (csrc/contours.hip, or contours_host.hip on the host:
+    identical bytes), no mask is decoded.  ValueError for a bad connectivity or device and for masks of different sizes."""
+    (first, off, ln, area2, length, xy), n = _contours_call("mask_contours", masks, connectivity, size, device)
+    return [[{"xy": xy[off[r]: off[r] + ln[r]].copy(), "hole": bool(area2[r] < 0), "area": abs(int(area2[r])) // 2, "length": int(length[r])}
+             for r in range(first[i], first[i + 1])] for i in range(n)]
+
+
+def masks_to_polygons(masks, connectivity=2, size=None, device='auto', return_has_holes=False):
+    """Every mask as polygons: per mask the list of its outer rings as flat float64 arrays [x0, y0, x1, y1, ...] -- what structures.PolygonMasks
+    and a dataset dict's 'segmentation' hold, so masks_to_rle(PolygonMasks(result), size) gives the masks back with their holes filled.  Holes
+    are dropped, as in detectron2's GenericMask.mask_to_polygons; return_has_holes: also a bool [N] array that says which masks had one.  An
+    empty mask has no polygon.  Rings, coordinates, masks, connectivity and device as in mask_contours (one amp_mask_contours call)."""
+    (first, off, ln, area2, length, xy), n = _contours_call("masks_to_polygons", masks, connectivity, size, device)
+    polys = [[xy[off[r]: off[r] + ln[r]].astype(np.float64).reshape(-1) for r in range(first[i], first[i + 1]) if area2[r] > 0] for i in range(n)]
+    if not return_has_holes:
+        return polys
+    return polys, np.array([bool((area2[first[i]: first[i + 1]] < 0).any()) for i in range(n)], dtype=bool)
 
 
 # ---- overlap-free instances: the owner of every pixel (the labels[mask_i] = i + 1 loop over decoded masks) ---------------------------------------

@@ -495,6 +495,42 @@ def flatten_instances(masks, rank=None, ctx=None, emit=True, return_labels=False
     return res + (labels,) if return_labels else res
 
 
+def mask_contours(masks, connectivity=2, ctx=None, size=None):
+    """The boundary rings of RLE dicts of one image size as flat arrays, one C call (amp_mask_contours; a second one when the first reports
+    that the capacity guess was too small).  Vertices are integer pixel corners (x, y) -- pixel (r, c) is the square [c, c + 1] x [r, r + 1],
+    the coordinates of polygons_to_rle --, a ring is its corners only, the one on its right hand (outer rings clockwise on screen), starting
+    at its smallest corner by x, then y; connectivity 2 joins diagonal ones into one ring, 1 keeps them apart.  Returns (ring_first, ring_off,
+    ring_len, ring_area2, ring_length, xy): the rings of mask i are ring_first[i] .. ring_first[i + 1] - 1 (int64 [n + 1]), ring r's corners
+    are xy[ring_off[r] : ring_off[r] + ring_len[r]] (xy int32 [vertices, 2]), ring_area2 int64 is the signed shoelace sum (positive: outer ring,
+    twice the enclosed pixels; negative: hole), ring_length int64 the crack length.  size=(h, w) is needed only when there is no mask.
+    ValueError for masks of different sizes.  ctx: a _lib.Context (computed on its device) or None (on the host): the same bytes."""
+    n = len(masks)
+    sizes = {tuple(int(v) for v in r["size"]) for r in masks}
+    if size is not None:
+        sizes.add((int(size[0]), int(size[1])))
+    if len(sizes) > 1:
+        raise ValueError(f"mask_contours: masks of different sizes {sorted(sizes)}")
+    if not sizes:
+        raise ValueError("mask_contours: size=(height, width) is required when there is no mask to take it from")
+    h, w = sizes.pop()
+    pool, off, ln = _pool([_counts(x) for x in masks])
+    first, need = np.zeros(n + 1, dtype=np.uint64), np.zeros(2, dtype=np.uint64)
+    vcap, rcap = 4 * int(ln.sum()) + 64, int(ln.sum()) + 16        # a guess: a run of ones that stays in its column is one piece
+    for attempt in range(2):
+        xy = np.empty((vcap, 2), dtype=np.int32)
+        r_off, r_len = np.empty(rcap, dtype=np.uint64), np.empty(rcap, dtype=np.int32)
+        r_a2, r_length = np.empty(rcap, dtype=np.int64), np.empty(rcap, dtype=np.int64)
+        st = lib().amp_mask_contours(_handle(ctx), _vp(pool), _vp(off), _vp(ln), n, h, w, int(connectivity), _vp(first), _vp(r_off), _vp(r_len),
+                                     _vp(r_a2), _vp(r_length), rcap, _vp(xy), vcap, _vp(need))
+        if st != -3 or attempt:                                     # AMP_ERR_NOMEM the first time: the need is known now
+            check(st, "amp_mask_contours")
+            break
+        vcap, rcap = max(int(need[0]), 1), max(int(need[1]), 1)
+    nv, nr = int(need[0]), int(need[1])
+    return (first.astype(np.int64), r_off[:nr].astype(np.int64), r_len[:nr].astype(np.int64), r_a2[:nr].copy(), r_length[:nr].copy(),
+            xy[:nv].copy())
+
+
 def merge(rles, intersect=False):
     assert len(rles) >= 1
     h, w = rles[0]["size"]

@@ -686,6 +686,33 @@ int amp_flatten_instances(amp_ctx* ctx, const uint32_t* pool, const unsigned lon
                           unsigned long long counts_cap, unsigned long long* counts_off /* [n] */, int* counts_len /* [n] */,
                           unsigned long long* stats /* [n][2] */, int* boxes /* [n][4] */, unsigned long long* pixels /* [3] */,
                           unsigned long long* need /* [1] */);
+/* Boundary rings: the polygons of the n run lists pool[off[i] : off[i] + len[i]] of one h x w image size (1 <= h, w <= 32768, h * w <= 2^30)
+ * in one call -- the way back from amp_polygons_to_rle, what users get from a contour tracer on one decoded array per mask.  ALL POINTERS ARE
+ * HOST POINTERS.  Pixel (r, c) is the square [c, c + 1] x [r, r + 1]; vertices are integer pixel corners (x, y), 0 <= x <= w, 0 <= y <= h, the
+ * coordinates of amp_polygons_to_rle, no half-pixel shift.  A boundary edge is a unit pixel side with a one on one side and a zero (or the
+ * outside of the image) on the other, directed with the one on its right hand, y down: outer boundaries run clockwise on screen.  Following
+ * successors partitions the edges into closed rings; at a saddle vertex (ones on one diagonal, zeros on the other) the walk turns left on to
+ * the diagonal pixel for connectivity 2 (ones 8-connected) and right for connectivity 1.  A ring is stored as its corners only -- a saddle
+ * visited twice appears twice --, starting at its smallest corner by x, then y; the rings of a mask are ordered by that corner.
+ *   ring_first [n + 1]: the rings of mask i are ring_first[i] .. ring_first[i + 1] - 1; an empty mask has none.
+ *   per ring r: its corners are xy[2 * ring_off[r] .. 2 * (ring_off[r] + ring_len[r])) as int32 x, y pairs, the rings back to back;
+ *     ring_area2[r] = sum(x_i * y_(i+1) - x_(i+1) * y_i), positive for the outer ring of a part (twice the pixels it encloses), negative
+ *     for a hole ring; ring_length[r] = the crack length, the sum of the segment lengths.
+ * With valid arguments need[0] = the vertices and need[1] = the rings of all masks are always written; with xy_cap (in vertices) or ring_cap
+ * below them the call returns AMP_ERR_NOMEM and writes nothing else.  Four vertices and two rings per vertical piece of ones always suffice,
+ * and the pieces of a mask are at most its runs of ones plus the columns of its tight box, so xy_cap = 4 * sum(len[i] / 2 + box width of mask
+ * i) and ring_cap = half of that do: a piece (a maximal vertical run of ones within one column; a run of the list is cut only at the column
+ * ends it crosses) has two horizontal boundary edges that start a vertical segment, its top and its bottom side; every vertical segment
+ * follows exactly one such edge, has two corners, and a ring has at least two of them.  Arguments are checked on the host before
+ * any device work (AMP_ERR_ARG naming the offender, nothing written): the sizes, n < 0, connectivity, NULL pointers, every run list
+ * non-empty and summing to h * w.  n == 0 is valid.
+ * ctx == NULL: computed on the host (contours_host.hip: a sequential walk of the successor function).  Otherwise on ctx's device and stream
+ * (contours.hip): upload, a list of launches that depends only on the largest piece count of one mask, download; no dense mask, integer
+ * arithmetic only, the bytes do not depend on the device's scheduling and equal the host's. */
+int amp_mask_contours(amp_ctx* ctx, const uint32_t* pool, const unsigned long long* off, const int* len, int n, int h, int w, int connectivity,
+                      unsigned long long* ring_first /* [n + 1] */, unsigned long long* ring_off, int* ring_len, long long* ring_area2,
+                      long long* ring_length, unsigned long long ring_cap, int* xy, unsigned long long xy_cap,
+                      unsigned long long* need /* [2] */);
 
 /* The model: DefaultPredictor(cfg) / predictor(img) ---------------------------------------------- */
 typedef struct amp_model amp_model;
