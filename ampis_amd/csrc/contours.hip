@@ -27,19 +27,15 @@
 
 #include "common.h"
 #include "contours.h"
+#include "mask_parts_dev.h"
 
 namespace {
 
-using amp::MpMask;
 using amp::u64;
 using amp::wave_sum;
 
-struct CtArgs {
-    const unsigned int *S, *E, *col;
-    const unsigned char* T;
-    const MpMask* masks;
-    const unsigned long long* first;             // [n + 1], in items
-    int n, h, k;
+struct CtArgs : amp::MpItemsView {
+    int h, k;
     unsigned int N;                              // nodes: two an item
 };
 
@@ -176,13 +172,9 @@ int contours_device(amp_ctx* ctx, const amp::MpItems& it, int h, int connectivit
     AMP_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
 
-    amp::DevBuf d_S, d_E, d_T, d_col, d_first, d_masks, d_succ, d_stp, d_j0, d_j1, d_l0, d_l1, d_min, d_area, d_vlen, d_tot;
-    AMP_TRY_STATUS(amp::dev_upload(ctx, d_S, it.S));
-    AMP_TRY_STATUS(amp::dev_upload(ctx, d_E, it.E));
-    AMP_TRY_STATUS(amp::dev_upload(ctx, d_T, it.T));
-    AMP_TRY_STATUS(amp::dev_upload(ctx, d_col, it.col));
-    AMP_TRY_STATUS(amp::dev_upload(ctx, d_first, it.first));
-    AMP_TRY_STATUS(amp::dev_upload(ctx, d_masks, it.m));
+    amp::MpItemsDev d_items;
+    amp::DevBuf d_succ, d_stp, d_j0, d_j1, d_l0, d_l1, d_min, d_area, d_vlen, d_tot;
+    AMP_TRY_STATUS(d_items.upload(ctx, it));
     AMP_TRY_STATUS(amp::dev_alloc(d_succ, (size_t)N * 4));
     AMP_TRY_STATUS(amp::dev_alloc(d_stp, (size_t)N * 16));
     AMP_TRY_STATUS(amp::dev_alloc(d_j0, (size_t)N * 8));
@@ -194,8 +186,7 @@ int contours_device(amp_ctx* ctx, const amp::MpItems& it, int h, int connectivit
     AMP_TRY_STATUS(amp::dev_alloc(d_vlen, (size_t)N * 8));
     AMP_TRY_STATUS(amp::dev_alloc(d_tot, 16));
     AMP_HIP_CHECK(hipMemsetAsync(d_tot.p, 0, 16, st));
-    const CtArgs g{d_S.as<unsigned int>(), d_E.as<unsigned int>(), d_col.as<unsigned int>(), d_T.as<unsigned char>(), d_masks.as<MpMask>(),
-                   d_first.as<unsigned long long>(), n, h, connectivity, N};
+    const CtArgs g{d_items.view(), h, connectivity, N};
     unsigned long long *ringmin = d_min.as<unsigned long long>(), *area = d_area.as<unsigned long long>(), *vlen = d_vlen.as<unsigned long long>(),
                        *tot = d_tot.as<unsigned long long>();
     uint2 *ja = d_j0.as<uint2>(), *jb = d_j1.as<uint2>();

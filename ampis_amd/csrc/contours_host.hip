@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "common.h"
+#include "mask_analysis.h"
 #include "contours.h"
 
 namespace amp {
@@ -15,23 +16,13 @@ int contours_check(const uint32_t* pool, const unsigned long long* off, const in
                    const unsigned long long* ring_first, const unsigned long long* ring_off, const int* ring_len, const long long* ring_area2,
                    const long long* ring_length, const int* xy, const unsigned long long* need, RunPlan& runs) {
     AMP_REQUIRE(n >= 0, "amp_mask_contours: n = %d", n);
-    AMP_REQUIRE(h >= 1 && w >= 1 && h <= 32768 && w <= 32768 && (unsigned long long)h * w <= (1ull << 30),
-                "amp_mask_contours: image size %d x %d (1 .. 32768 a side, at most 2^30 pixels)", h, w);
+    AMP_TRY_STATUS(require_image_size("amp_mask_contours", h, w));
     AMP_REQUIRE(connectivity == 1 || connectivity == 2, "amp_mask_contours: connectivity = %d (1: 4 neighbours, 2: 8 neighbours)", connectivity);
     AMP_REQUIRE(n == 0 || (pool && off && len), "amp_mask_contours: null argument %s", !pool ? "pool" : !off ? "off" : "len");
     AMP_REQUIRE(ring_first && ring_off && ring_len && ring_area2 && ring_length && xy && need, "amp_mask_contours: null argument %s",
                 !ring_first ? "ring_first" : !ring_off ? "ring_off" : !ring_len ? "ring_len" : !ring_area2 ? "ring_area2"
                 : !ring_length ? "ring_length" : !xy ? "xy" : "need");
-    const unsigned long long area = (unsigned long long)h * w;
-    runs.reset((size_t)n);
-    for (int p = 0; p < n; ++p) {
-        u64 covered = 0;
-        const RunListFault f = plan_add_mask(runs, (size_t)p, pool + off[p], len[p], h, w, false, &covered);
-        AMP_REQUIRE(f != RUNS_EMPTY, "amp_mask_contours: mask %d has an empty run list", p);
-        AMP_REQUIRE(f != RUNS_OVER, "amp_mask_contours: the runs of mask %d cover more than the image's %llu pixels", p, area);
-        AMP_REQUIRE(f != RUNS_SHORT, "amp_mask_contours: the runs of mask %d cover %llu pixels, the image has %llu", p, covered, area);
-        AMP_REQUIRE(f == RUNS_OK, "amp_mask_contours: the masks of one call have more than 2^31 runs");
-    }
+    AMP_TRY_STATUS(plan_pool("amp_mask_contours", pool, off, len, n, h, w, runs));
     return AMP_OK;
 }
 

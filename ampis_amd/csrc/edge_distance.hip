@@ -14,10 +14,12 @@
 // Five launches and one memset per call whatever the number of pairs; scratch is two bit planes and two 8-byte words per crop row.  Integer
 // arithmetic only: h, w <= 32768 keeps every squared distance below 2^31.  Work is cut into host-built tile lists -- (pair, mask, 256 runs of
 // ones) for the decoder, (pair, 64 rows) for the row kernels -- so a full-image crop spreads over the chip like three hundred small ones.  The
-// runs come from the plan the argument checks build (run_list.h, mask_analysis_host.hip); the painter and the scan are run_list.h's.
+// runs come from the plan the argument checks build (run_list.h, mask_analysis_host.hip); the painter and the scan are run_list.h's, the
+// chunked scan of an array in one workgroup is compaction.h's.
 #include <vector>
 
 #include "common.h"
+#include "compaction.h"
 #include "mask_analysis.h"
 
 namespace {
@@ -85,20 +87,12 @@ __global__ __launch_bounds__(1024) void ed_scan_kernel(unsigned long long* rows_
                                                        unsigned long long* __restrict__ off_fn) {
     __shared__ unsigned long long s[1024];
     const int tid = threadIdx.x;
-    const long long per = (nrows + 1023) / 1024;
-    const long long i0 = min((long long)tid * per, nrows), i1 = min(i0 + per, nrows);
-    unsigned long long a = 0, b = 0;
-    for (long long i = i0; i < i1; ++i) { a += rows_fp[i]; b += rows_fn[i]; }
-    unsigned long long ra = amp::block_scan_1024(s, a) - a;          // exclusive
+    const auto nothing = [](unsigned long long, unsigned long long) {};
+    scan_sums_in_place(rows_fp, (unsigned long long)nrows, s, nothing);
     const unsigned long long ta = s[1023];
-    __syncthreads();
-    unsigned long long rb = amp::block_scan_1024(s, b) - b;
+    __syncthreads();                                                 // s is read before the second scan writes it
+    scan_sums_in_place(rows_fn, (unsigned long long)nrows, s, nothing);
     const unsigned long long tb = s[1023];
-    for (long long i = i0; i < i1; ++i) {
-        const unsigned long long ca = rows_fp[i], cb = rows_fn[i];
-        rows_fp[i] = ra; rows_fn[i] = rb;
-        ra += ca; rb += cb;
-    }
     __syncthreads();
     for (int p = tid; p <= n; p += 1024) {
         const int t0 = p < n ? pairs[p].tile0 : ntiles;

@@ -10,9 +10,10 @@
 //                        tile and instance; the tile then writes its rows of the int32 label image coalesced (zeros where nothing is);
 //   a statistics / label-image call (counts NULL) ends here.  The visible lists are the per-id column-major runs of the label image,
 //   exactly what amp_label_runs computes for AMP_LABEL_IDS, so the stages of label_runs_kernels.h run on the device's label image:
-//   2. lr_planes_kernel, 3. lr_count_kernel, 4. lr_scan_kernel (the host reads the number of runs), 5. lr_write_kernel, 6. lr_keys_kernel,
-//   7. rocprim::radix_sort_pairs (stable; its own launches depend on the number of runs only), 8. lr_heads_kernel, 9. lr_scan_kernel (the
-//   host reads the owners and the counts, reports the need and refuses a capacity that is too small), 10. lr_emit_kernel;
+//   2. lr_planes_kernel, 3. lr_count_kernel, 4. scan_sums_kernel (the host reads the number of runs), 5. lr_write_kernel (lr_cut),
+//   6. lr_keys_kernel, 7. rocprim::radix_sort_pairs (stable; its own launches depend on the number of runs only), 8. lr_heads_kernel,
+//   9. scan_sums_kernel (lr_group; the host reads the owners and the counts, reports the need and refuses a capacity that is too small),
+//  10. lr_emit_kernel (lr_emit);
 //  11. fl_diff_kernel    one lane per count of the result, all n instances back to back: boundary minus the boundary before it, or the single
 //                        run h * w of an instance that owns nothing.
 // LDS: the owner of pixel (r, c) of the tile at c * 65 + r -- a lane walks its own column, the odd dword stride keeps the lanes on distinct
@@ -23,8 +24,6 @@
 
 #include <vector>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
 #include "common.h"
 #include "flatten.h"
 #include "label_runs_kernels.h"
@@ -33,6 +32,7 @@
 namespace {
 
 using amp::RunMask;
+using amp::wave_sum;
 
 constexpr int FL_STRIDE = 65;                     // dwords of one tile column in LDS: 64 rows + 1
 
@@ -161,92 +161,27 @@ int flatten_device(amp_ctx* ctx, const amp::RunPlan& runs, const std::vector<int
     };
     if (!counts) return finish();
 
-    // the runs of the label image, as in label_runs.hip
-    const int pitch = (h + 63) >> 6;
-    const unsigned long long units = (unsigned long long)w * pitch;
-    const unsigned int nblk = (unsigned int)((units + 255) / 256);
-    amp::DevBuf d_planes, d_sums, d_base;
-    AMP_TRY_STATUS(amp::dev_alloc(d_planes, (size_t)units * 16));
-    AMP_TRY_STATUS(amp::dev_alloc(d_sums, (size_t)nblk * 16));
-    AMP_TRY_STATUS(amp::dev_alloc(d_base, 3 * 8));
-    unsigned long long *planes = d_planes.as<unsigned long long>(), *sums = d_sums.as<unsigned long long>(), *base = d_base.as<unsigned long long>();
-    hipLaunchKernelGGL(lr_planes_kernel, lr_grid(units), dim3(256), 0, st, d_labels.p, h, w, (int)AMP_LABEL_IDS, 1, pitch, units, planes);
-    AMP_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(lr_count_kernel, lr_grid(units), dim3(256), 0, st, planes, units, nblk, sums);
-    AMP_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(lr_scan_kernel, dim3(1), dim3(1024), 0, st, sums, nblk, base);
-    AMP_HIP_CHECK(hipGetLastError());
-    unsigned long long hb[3];
-    AMP_HIP_CHECK(hipMemcpyAsync(hb, base, sizeof(hb), hipMemcpyDeviceToHost, st));
-    AMP_HIP_CHECK(hipStreamSynchronize(st));
-    const unsigned long long nruns = hb[1] - hb[0];
-    if (hb[2] - hb[1] != nruns || nruns > image) {                   // cannot happen: every run has one first and one last pixel
-        amp::set_error("amp_flatten_instances: %llu run starts and %llu run ends on the device", nruns, hb[2] - hb[1]);
-        return AMP_ERR_HIP;
-    }
+    // the runs of the label image, by the stages of amp_label_runs
+    LrStages g;
+    AMP_TRY_STATUS(lr_cut("amp_flatten_instances", st, d_labels.p, h, w, (int)AMP_LABEL_IDS, 1, g));
     std::vector<unsigned long long> foff((size_t)n), src((size_t)n, ~0ull);
     unsigned long long total = (unsigned long long)n;               // nothing is owned: the single run h * w for every instance
-    amp::DevBuf d_S2, d_E2, d_V, d_parent, d_col, d_keys, d_idx, d_skeys, d_sidx, d_tmp, d_sums2, d_base2, d_rank, d_ids, d_off, d_bnd, d_mins2,
-        d_maxs2, d_areas, d_foff, d_src, d_counts;
-    if (nruns) {
-        const unsigned int R = (unsigned int)nruns, nblk2 = (R + 255) / 256;
-        AMP_TRY_STATUS(amp::dev_alloc(d_S2, (size_t)R * 4));
-        AMP_TRY_STATUS(amp::dev_alloc(d_E2, (size_t)R * 4));
-        AMP_TRY_STATUS(amp::dev_alloc(d_V, (size_t)R * 4));
-        AMP_TRY_STATUS(amp::dev_alloc(d_parent, (size_t)R * 4));
-        AMP_TRY_STATUS(amp::dev_alloc(d_col, ((size_t)w + 1) * 4));
-        AMP_TRY_STATUS(amp::dev_alloc(d_keys, (size_t)R * 4));
-        AMP_TRY_STATUS(amp::dev_alloc(d_idx, (size_t)R * 4));
-        AMP_TRY_STATUS(amp::dev_alloc(d_skeys, (size_t)R * 4));
-        AMP_TRY_STATUS(amp::dev_alloc(d_sidx, (size_t)R * 4));
-        AMP_TRY_STATUS(amp::dev_alloc(d_sums2, (size_t)nblk2 * 16));
-        AMP_TRY_STATUS(amp::dev_alloc(d_base2, 3 * 8));
-        unsigned int *S2 = d_S2.as<unsigned int>(), *E2 = d_E2.as<unsigned int>();
-        hipLaunchKernelGGL(lr_write_kernel, lr_grid(units), dim3(256), 0, st, planes, units, h, w, pitch, nblk, sums, base, d_labels.p,
-                           (int)AMP_LABEL_IDS, S2, E2, d_V.as<int>(), d_parent.as<unsigned int>(), d_col.as<unsigned int>());
-        AMP_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(lr_keys_kernel, lr_grid(R), dim3(256), 0, st, (const unsigned int*)nullptr, (const unsigned int*)nullptr, d_V.as<int>(),
-                           (int)AMP_LABEL_IDS, R, d_keys.as<unsigned int>(), d_idx.as<unsigned int>());
-        AMP_HIP_CHECK(hipGetLastError());
-        size_t tmp_bytes = 0;
-        AMP_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_keys.as<unsigned int>(), d_skeys.as<unsigned int>(), d_idx.as<unsigned int>(),
-                                                d_sidx.as<unsigned int>(), (size_t)R, 0u, 32u, st));
-        AMP_TRY_STATUS(amp::dev_alloc(d_tmp, tmp_bytes));
-        AMP_HIP_CHECK(rocprim::radix_sort_pairs(d_tmp.p, tmp_bytes, d_keys.as<unsigned int>(), d_skeys.as<unsigned int>(), d_idx.as<unsigned int>(),
-                                                d_sidx.as<unsigned int>(), (size_t)R, 0u, 32u, st));
-        const unsigned int *SK = d_skeys.as<unsigned int>(), *SI = d_sidx.as<unsigned int>();
-        unsigned long long *sums2 = d_sums2.as<unsigned long long>(), *base2 = d_base2.as<unsigned long long>();
-        hipLaunchKernelGGL(lr_heads_kernel, lr_grid(R), dim3(256), 0, st, SK, SI, S2, E2, R, area, nblk2, sums2);
-        AMP_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(lr_scan_kernel, dim3(1), dim3(1024), 0, st, sums2, nblk2, base2);
-        AMP_HIP_CHECK(hipGetLastError());
-        AMP_HIP_CHECK(hipMemcpyAsync(hb, base2, sizeof(hb), hipMemcpyDeviceToHost, st));
-        AMP_HIP_CHECK(hipStreamSynchronize(st));
-        const unsigned long long N = hb[1] - hb[0], listed = hb[2] - hb[1];
+    amp::DevBuf d_foff, d_src, d_counts;
+    if (g.R) {
+        const unsigned int R = g.R;
+        AMP_TRY_STATUS(lr_group(st, nullptr, nullptr, g));
+        const unsigned long long N = g.N, listed = g.listed;
         if (N == 0 || N > (unsigned long long)n || listed < 2 * N || listed > 3ull * R) {            // cannot happen: an owner is one of the n instances
             amp::set_error("amp_flatten_instances: %llu owners and %llu counts from %u runs of %d instances on the device", N, listed, R, n);
             return AMP_ERR_HIP;
         }
         total = listed + ((unsigned long long)n - N);
         AMP_TRY_STATUS(amp::flatten_capacity(total, counts_cap, need));
-        AMP_TRY_STATUS(amp::dev_alloc(d_rank, (size_t)R * 4));
-        AMP_TRY_STATUS(amp::dev_alloc(d_ids, (size_t)N * 4));
-        AMP_TRY_STATUS(amp::dev_alloc(d_off, (size_t)N * 8));
-        AMP_TRY_STATUS(amp::dev_alloc(d_bnd, (size_t)listed * 4));
-        AMP_TRY_STATUS(amp::dev_alloc(d_mins2, (size_t)N * 8));
-        AMP_TRY_STATUS(amp::dev_alloc(d_maxs2, (size_t)N * 8));
-        AMP_TRY_STATUS(amp::dev_alloc(d_areas, (size_t)N * 4));
-        AMP_HIP_CHECK(hipMemsetAsync(d_mins2.p, 0x7f, (size_t)N * 8, st));
-        AMP_HIP_CHECK(hipMemsetAsync(d_maxs2.p, 0, (size_t)N * 8, st));
-        AMP_HIP_CHECK(hipMemsetAsync(d_areas.p, 0, (size_t)N * 4, st));
-        hipLaunchKernelGGL(lr_emit_kernel, lr_grid(R), dim3(256), 0, st, SK, SI, S2, E2, R, area, h, (int)AMP_LABEL_IDS, nblk2, sums2, base2,
-                           d_rank.as<unsigned int>(), d_ids.as<int>(), d_off.as<unsigned long long>(), d_bnd.as<unsigned int>(), d_mins2.as<int>(),
-                           d_maxs2.as<int>(), d_areas.as<unsigned int>());
-        AMP_HIP_CHECK(hipGetLastError());
+        AMP_TRY_STATUS(lr_emit(st, g));
         std::vector<int> ids((size_t)N);
         std::vector<unsigned long long> off((size_t)N);
-        AMP_HIP_CHECK(hipMemcpyAsync(ids.data(), d_ids.p, (size_t)N * 4, hipMemcpyDeviceToHost, st));
-        AMP_HIP_CHECK(hipMemcpyAsync(off.data(), d_off.p, (size_t)N * 8, hipMemcpyDeviceToHost, st));
+        AMP_HIP_CHECK(hipMemcpyAsync(ids.data(), g.ids.p, (size_t)N * 4, hipMemcpyDeviceToHost, st));
+        AMP_HIP_CHECK(hipMemcpyAsync(off.data(), g.off.p, (size_t)N * 8, hipMemcpyDeviceToHost, st));
         AMP_HIP_CHECK(hipStreamSynchronize(st));
         for (size_t k = 0; k < (size_t)N; ++k) {                     // the owners come in ascending id order
             if (ids[k] < 1 || ids[k] > n || off[k] >= listed || (k && ids[k] <= ids[k - 1])) {       // cannot happen
@@ -274,7 +209,7 @@ int flatten_device(amp_ctx* ctx, const amp::RunPlan& runs, const std::vector<int
         AMP_TRY_STATUS(amp::dev_upload(ctx, d_foff, foff));
         AMP_TRY_STATUS(amp::dev_upload(ctx, d_src, src));
         AMP_TRY_STATUS(amp::dev_alloc(d_counts, (size_t)total * 4));
-        hipLaunchKernelGGL(fl_diff_kernel, lr_grid(total), dim3(256), 0, st, d_bnd.as<unsigned int>(), d_foff.as<unsigned long long>(),
+        hipLaunchKernelGGL(fl_diff_kernel, grid_256(total), dim3(256), 0, st, g.bnd.as<unsigned int>(), d_foff.as<unsigned long long>(),
                            d_src.as<unsigned long long>(), n, total, area, d_counts.as<unsigned int>());
         AMP_HIP_CHECK(hipGetLastError());
         AMP_HIP_CHECK(hipMemcpyAsync(counts, d_counts.p, (size_t)total * 4, hipMemcpyDeviceToHost, st));

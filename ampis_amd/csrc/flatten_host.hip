@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "common.h"
+#include "mask_analysis.h"
 #include "flatten.h"
 
 namespace amp {
@@ -23,8 +24,7 @@ int flatten_check(const uint32_t* pool, const unsigned long long* off, const int
                   const unsigned long long* stats, const int* boxes, const unsigned long long* pixels, const unsigned long long* need,
                   RunPlan& runs, std::vector<int>& order) {
     AMP_REQUIRE(n >= 0, "amp_flatten_instances: n = %d", n);
-    AMP_REQUIRE(h >= 1 && w >= 1 && h <= 32768 && w <= 32768 && (unsigned long long)h * w <= (1ull << 30),
-                "amp_flatten_instances: image size %d x %d (1 .. 32768 a side, at most 2^30 pixels)", h, w);
+    AMP_TRY_STATUS(require_image_size("amp_flatten_instances", h, w));
     AMP_REQUIRE(pixels, "amp_flatten_instances: null argument pixels");
     AMP_REQUIRE(n == 0 || (pool && off && len && stats && boxes), "amp_flatten_instances: null argument %s",
                 !pool ? "pool" : !off ? "off" : !len ? "len" : !stats ? "stats" : "boxes");
@@ -32,27 +32,13 @@ int flatten_check(const uint32_t* pool, const unsigned long long* off, const int
                 !counts_off ? "counts_off" : "counts_len");
     AMP_REQUIRE(!counts || need, "amp_flatten_instances: null argument need");
     AMP_REQUIRE(counts || counts_cap == 0, "amp_flatten_instances: counts_cap = %llu with counts NULL (no list is emitted)", counts_cap);
-    const unsigned long long area = (unsigned long long)h * w;
-    runs.reset((size_t)n);
-    for (int p = 0; p < n; ++p) {
-        u64 covered = 0;
-        const RunListFault f = plan_add_mask(runs, (size_t)p, pool + off[p], len[p], h, w, false, &covered);
-        AMP_REQUIRE(f != RUNS_EMPTY, "amp_flatten_instances: mask %d has an empty run list", p);
-        AMP_REQUIRE(f != RUNS_OVER, "amp_flatten_instances: the runs of mask %d cover more than the image's %llu pixels", p, area);
-        AMP_REQUIRE(f != RUNS_SHORT, "amp_flatten_instances: the runs of mask %d cover %llu pixels, the image has %llu", p, covered, area);
-        AMP_REQUIRE(f == RUNS_OK, "amp_flatten_instances: the masks of one call have more than 2^31 runs");
-    }
+    AMP_TRY_STATUS(plan_pool("amp_flatten_instances", pool, off, len, n, h, w, runs));
     flatten_order(rank, n, order);
     return AMP_OK;
 }
 
 int flatten_capacity(unsigned long long counts, unsigned long long counts_cap, unsigned long long* need) {
-    need[0] = counts;
-    if (counts > counts_cap) {
-        set_error("amp_flatten_instances: counts_cap = %llu; %llu counts are needed", counts_cap, counts);
-        return AMP_ERR_NOMEM;
-    }
-    return AMP_OK;
+    return counts_capacity("amp_flatten_instances", "counts_cap", counts, counts_cap, need);
 }
 
 int flatten_host(const RunPlan& runs, const std::vector<int>& order, int h, int w, int* labels, uint32_t* counts, unsigned long long counts_cap,

@@ -6,7 +6,7 @@
 //   lr_planes_kernel   one lane per (64 rows, column), columns fastest so a wave reads rows of the row-major image: two column-major bit
 //                      planes (64 rows a word), START = the pixel opens a run, END = it closes one;
 //   lr_count_kernel    one lane per plane word in column-major order: the set bits of both planes, a workgroup sum each;
-//   lr_scan_kernel     one workgroup: the exclusive scan of the sums;
+//   scan_sums_kernel   one workgroup: the exclusive scan of the sums (compaction.h, as the workgroup sums and scans of the kernels here);
 //   lr_write_kernel    as lr_count_kernel with a workgroup scan: run k's start S[k], end E[k], id V[k] (LABEL), parent[k] = k, and the first
 //                      run of every column;
 //   lr_keys_kernel     the sort key of every run -- its root's smallest position, or the id with the sign bit flipped -- and the run's index
@@ -15,18 +15,24 @@
 //                      neighbour across a column end; the closing h * w after an instance's last run), a workgroup sum each;
 //   lr_emit_kernel     as lr_heads_kernel with a workgroup scan: boundary positions, id and offset of every instance, box and area by atomic
 //                      min / max / add.
+// The host drives them in three steps over one LrStages, which both entry points call in this order: lr_cut (planes, count, scan, the
+// number of runs read back, write), lr_group (keys, the stable radix sort, heads, scan, the instances and counts read back) and lr_emit.
+// Between them an entry point does what is its own: amp_label_runs unites the runs of a BINARY image, each judges the numbers read back
+// by its own bound and reports its own capacity.
 // Integer arithmetic only; nothing is placed through a counter, so the bytes repeat.  Every loop states why it ends; none waits for
 // another lane.  For hipcc only; every file that includes this header gets kernels of its own.
 #pragma once
 #include <algorithm>
 
+#include <rocprim/device/device_radix_sort.hpp>
+
 #include "common.h"
+#include "compaction.h"
 #include "mask_analysis.h"
 
 namespace {
 
 using amp::u64;
-using amp::wave_sum;
 
 __global__ __launch_bounds__(256) void lr_planes_kernel(const void* __restrict__ img, int h, int w, int kind, int zero_bg, int pitch,
                                                         unsigned long long units, unsigned long long* __restrict__ planes) {
@@ -53,50 +59,10 @@ __global__ __launch_bounds__(256) void lr_planes_kernel(const void* __restrict__
 // workgroup b owns plane words [256 b, 256 b + 256) in column-major order; sums[k * nblk + b] = the set bits of plane k in them
 __global__ __launch_bounds__(256) void lr_count_kernel(const unsigned long long* __restrict__ planes, unsigned long long units, unsigned int nblk,
                                                        unsigned long long* __restrict__ sums) {
-    __shared__ unsigned long long part[4][2];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (unsigned int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {                  // ends: blk grows by the grid; uniform over the workgroup
         const unsigned long long u = (unsigned long long)blk * 256 + threadIdx.x;
-        for (int k = 0; k < 2; ++k) {
-            const unsigned long long s = wave_sum((unsigned long long)(u < units ? amp::popc(planes[k * units + u]) : 0));
-            if (lane == 0) part[wave][k] = s;
-        }
-        __syncthreads();
-        if (threadIdx.x < 2) sums[(size_t)threadIdx.x * nblk + blk] = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
-        __syncthreads();
+        block_sums_256<2>(2, nblk, blk, sums, [&](int k) { return u < units ? amp::popc(planes[k * units + u]) : 0; });
     }
-}
-
-// one workgroup of 1024: sums[0 .. 2 nblk) becomes its exclusive scan; base[k] = where quantity k starts in it, base[2] = the total
-__global__ __launch_bounds__(1024) void lr_scan_kernel(unsigned long long* __restrict__ sums, unsigned int nblk, unsigned long long* __restrict__ base) {
-    __shared__ unsigned long long tot[1024];
-    const unsigned long long m = 2ull * nblk, chunk = (m + 1023) / 1024, first = chunk * threadIdx.x, last = min(first + chunk, m);
-    unsigned long long s = 0;
-    for (unsigned long long i = first; i < last; ++i) s += sums[i];                      // ends: i grows to last
-    unsigned long long run = amp::block_scan_1024(tot, s) - s;
-    for (unsigned long long i = first; i < last; ++i) {                                  // ends: i grows to last
-        const unsigned long long v = sums[i];
-        sums[i] = run;
-        if (i == 0 || i == nblk) base[i / nblk] = run;
-        run += v;
-    }
-    if (threadIdx.x == 0) base[2] = tot[1023];
-}
-
-// what lies in front of this lane in its workgroup (exclusive scan of c over 256 threads); every thread calls it
-__device__ __forceinline__ unsigned int lr_block_before(unsigned int c, unsigned int* wtot) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned int inc = c;
-    for (int o = 1; o < 64; o <<= 1) {                                                   // ends: six steps
-        const unsigned int v = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += v;
-    }
-    __syncthreads();                                                                     // wtot of the call before has been read
-    if (lane == 63) wtot[wave] = inc;
-    __syncthreads();
-    unsigned int before = inc - c;
-    for (int v = 0; v < wave; ++v) before += wtot[v];                                    // ends: at most three waves
-    return before;
 }
 
 __global__ __launch_bounds__(256) void lr_write_kernel(const unsigned long long* __restrict__ planes, unsigned long long units, int h, int w,
@@ -111,7 +77,7 @@ __global__ __launch_bounds__(256) void lr_write_kernel(const unsigned long long*
         const int c = in ? (int)(u / (unsigned)pitch) : 0, wv = in ? (int)(u % (unsigned)pitch) : 0;
         const unsigned int pos = (unsigned)c * (unsigned)h + ((unsigned)wv << 6);
         const u64 start = in ? planes[u] : 0ull, end = in ? planes[units + u] : 0ull;
-        unsigned int at = (unsigned int)(sums[blk] - base[0]) + lr_block_before((unsigned)amp::popc(start), wtot);
+        unsigned int at = (unsigned int)(sums[blk] - base[0]) + block_before_256((unsigned)amp::popc(start), wtot);
         if (in && wv == 0) colstart[c] = at;
         for (u64 x = start; x; x &= x - 1) {                                             // ends: one set bit fewer each time
             const int b = amp::ctz(x);
@@ -121,7 +87,7 @@ __global__ __launch_bounds__(256) void lr_write_kernel(const unsigned long long*
             ++at;
         }
         if (in && u == units - 1) colstart[w] = at;
-        at = (unsigned int)(sums[(size_t)nblk + blk] - base[1]) + lr_block_before((unsigned)amp::popc(end), wtot);
+        at = (unsigned int)(sums[(size_t)nblk + blk] - base[1]) + block_before_256((unsigned)amp::popc(end), wtot);
         for (u64 x = end; x; x &= x - 1) E[at++] = pos + (unsigned)amp::ctz(x) + 1u;     // ends: one set bit fewer each time
     }
 }
@@ -158,15 +124,9 @@ __device__ __forceinline__ LrItem lr_item(const unsigned int* __restrict__ SK, c
 __global__ __launch_bounds__(256) void lr_heads_kernel(const unsigned int* __restrict__ SK, const unsigned int* __restrict__ SI,
                                                        const unsigned int* __restrict__ S, const unsigned int* __restrict__ E, unsigned int R,
                                                        unsigned int area, unsigned int nblk, unsigned long long* __restrict__ sums) {
-    __shared__ unsigned long long part[4][2];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (unsigned int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {                  // ends: blk grows by the grid; uniform over the workgroup
         const LrItem it = lr_item(SK, SI, S, E, R, blk * 256 + threadIdx.x, area);
-        const unsigned long long a = wave_sum((unsigned long long)it.head), b = wave_sum((unsigned long long)it.bounds());
-        if (lane == 0) { part[wave][0] = a; part[wave][1] = b; }
-        __syncthreads();
-        if (threadIdx.x < 2) sums[(size_t)threadIdx.x * nblk + blk] = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
-        __syncthreads();
+        block_sums_256<2>(2, nblk, blk, sums, [&](int k) { return k ? it.bounds() : (unsigned)it.head; });
     }
 }
 
@@ -182,8 +142,8 @@ __global__ __launch_bounds__(256) void lr_emit_kernel(const unsigned int* __rest
     for (unsigned int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {                  // ends: blk grows by the grid; uniform over the workgroup
         const unsigned int j = blk * 256 + threadIdx.x;
         const LrItem it = lr_item(SK, SI, S, E, R, j, area);
-        const unsigned int inst = (unsigned int)(sums[blk] - base[0]) + lr_block_before((unsigned)it.head, wtot) + (unsigned)it.head - 1u;
-        unsigned long long at = sums[(size_t)nblk + blk] - base[1] + lr_block_before(it.bounds(), wtot);
+        const unsigned int inst = (unsigned int)(sums[blk] - base[0]) + block_before_256((unsigned)it.head, wtot) + (unsigned)it.head - 1u;
+        unsigned long long at = sums[(size_t)nblk + blk] - base[1] + block_before_256(it.bounds(), wtot);
         if (j >= R) continue;                                                            // after the barriers
         rank[j] = inst;
         if (it.head) {
@@ -202,6 +162,103 @@ __global__ __launch_bounds__(256) void lr_emit_kernel(const unsigned int* __rest
     }
 }
 
-dim3 lr_grid(unsigned long long items) { return dim3((unsigned)std::min<unsigned long long>(std::max<unsigned long long>((items + 255) / 256, 1ull), 1ull << 16)); }
+// what the three steps below hand from one to the next
+struct LrStages {
+    int h, w, kind, pitch;
+    unsigned long long units;
+    unsigned int area, nblk, R, nblk2;            // R runs; 0: the image holds none, and lr_cut has written nothing
+    unsigned long long N, listed;                 // after lr_group: the instances, the counts of their lists
+    amp::DevBuf planes, sums, base, S, E, V, parent, col, keys, idx, skeys, sidx, tmp, sums2, base2, rank, ids, off, bnd, mins, maxs, areas;
+};
+
+// The h x w image d_img (on the device) cut into runs: S, E, V (LABEL), parent, col.  The host reads the number of runs back in between.
+int lr_cut(const char* api, hipStream_t st, const void* d_img, int h, int w, int kind, int zero_bg, LrStages& g) {
+    g.h = h; g.w = w; g.kind = kind; g.pitch = (h + 63) >> 6;
+    g.units = (unsigned long long)w * g.pitch;
+    const unsigned long long pixels = (unsigned long long)h * w;
+    g.area = (unsigned int)pixels; g.nblk = (unsigned int)((g.units + 255) / 256);
+    g.R = 0;
+    AMP_TRY_STATUS(amp::dev_alloc(g.planes, (size_t)g.units * 16));
+    AMP_TRY_STATUS(amp::dev_alloc(g.sums, (size_t)g.nblk * 16));
+    AMP_TRY_STATUS(amp::dev_alloc(g.base, 3 * 8));
+    unsigned long long *planes = g.planes.as<unsigned long long>(), *sums = g.sums.as<unsigned long long>(), *base = g.base.as<unsigned long long>();
+    hipLaunchKernelGGL(lr_planes_kernel, grid_256(g.units), dim3(256), 0, st, d_img, h, w, kind, zero_bg, g.pitch, g.units, planes);
+    AMP_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(lr_count_kernel, grid_256(g.units), dim3(256), 0, st, planes, g.units, g.nblk, sums);
+    AMP_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(1024), 0, st, sums, g.nblk, 2, base);
+    AMP_HIP_CHECK(hipGetLastError());
+    unsigned long long hb[3];
+    AMP_HIP_CHECK(hipMemcpyAsync(hb, base, sizeof(hb), hipMemcpyDeviceToHost, st));
+    AMP_HIP_CHECK(hipStreamSynchronize(st));
+    const unsigned long long runs = hb[1] - hb[0];
+    if (hb[2] - hb[1] != runs || runs > pixels) {                    // cannot happen: every run has one first and one last pixel
+        amp::set_error("%s: %llu run starts and %llu run ends on the device", api, runs, hb[2] - hb[1]);
+        return AMP_ERR_HIP;
+    }
+    if (runs == 0) return AMP_OK;
+    const unsigned int R = (unsigned int)runs;
+    g.R = R; g.nblk2 = (R + 255) / 256;
+    AMP_TRY_STATUS(amp::dev_alloc(g.S, (size_t)R * 4));
+    AMP_TRY_STATUS(amp::dev_alloc(g.E, (size_t)R * 4));
+    AMP_TRY_STATUS(amp::dev_alloc(g.V, kind == AMP_LABEL_BINARY ? 0 : (size_t)R * 4));
+    AMP_TRY_STATUS(amp::dev_alloc(g.parent, (size_t)R * 4));
+    AMP_TRY_STATUS(amp::dev_alloc(g.col, ((size_t)w + 1) * 4));
+    AMP_TRY_STATUS(amp::dev_alloc(g.keys, (size_t)R * 4));
+    AMP_TRY_STATUS(amp::dev_alloc(g.idx, (size_t)R * 4));
+    AMP_TRY_STATUS(amp::dev_alloc(g.skeys, (size_t)R * 4));
+    AMP_TRY_STATUS(amp::dev_alloc(g.sidx, (size_t)R * 4));
+    AMP_TRY_STATUS(amp::dev_alloc(g.sums2, (size_t)g.nblk2 * 16));
+    AMP_TRY_STATUS(amp::dev_alloc(g.base2, 3 * 8));
+    hipLaunchKernelGGL(lr_write_kernel, grid_256(g.units), dim3(256), 0, st, planes, g.units, h, w, g.pitch, g.nblk, sums, base, d_img, kind,
+                       g.S.as<unsigned int>(), g.E.as<unsigned int>(), g.V.as<int>(), g.parent.as<unsigned int>(), g.col.as<unsigned int>());
+    AMP_HIP_CHECK(hipGetLastError());
+    return AMP_OK;
+}
+
+// The runs grouped into instances: sorted by key (root_of, first: the roots of a BINARY image and their smallest positions; a LABEL image
+// sorts by V), skeys / sidx, and the workgroup sums of the heads scanned.  The host reads N and listed back; the caller judges them.
+int lr_group(hipStream_t st, const unsigned int* root_of, const unsigned int* first, LrStages& g) {
+    const unsigned int R = g.R;
+    unsigned int *keys = g.keys.as<unsigned int>(), *idx = g.idx.as<unsigned int>(), *skeys = g.skeys.as<unsigned int>(), *sidx = g.sidx.as<unsigned int>();
+    hipLaunchKernelGGL(lr_keys_kernel, grid_256(R), dim3(256), 0, st, root_of, first, g.V.as<int>(), g.kind, R, keys, idx);
+    AMP_HIP_CHECK(hipGetLastError());
+    size_t tmp_bytes = 0;
+    AMP_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys, skeys, idx, sidx, (size_t)R, 0u, 32u, st));
+    AMP_TRY_STATUS(amp::dev_alloc(g.tmp, tmp_bytes));
+    AMP_HIP_CHECK(rocprim::radix_sort_pairs(g.tmp.p, tmp_bytes, keys, skeys, idx, sidx, (size_t)R, 0u, 32u, st));
+    unsigned long long *sums2 = g.sums2.as<unsigned long long>(), *base2 = g.base2.as<unsigned long long>();
+    hipLaunchKernelGGL(lr_heads_kernel, grid_256(R), dim3(256), 0, st, skeys, sidx, g.S.as<unsigned int>(), g.E.as<unsigned int>(), R, g.area, g.nblk2,
+                       sums2);
+    AMP_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(1024), 0, st, sums2, g.nblk2, 2, base2);
+    AMP_HIP_CHECK(hipGetLastError());
+    unsigned long long hb[3];
+    AMP_HIP_CHECK(hipMemcpyAsync(hb, base2, sizeof(hb), hipMemcpyDeviceToHost, st));
+    AMP_HIP_CHECK(hipStreamSynchronize(st));
+    g.N = hb[1] - hb[0]; g.listed = hb[2] - hb[1];
+    return AMP_OK;
+}
+
+// rank of every sorted run, ids / off / bnd / mins / maxs / areas of the N instances
+int lr_emit(hipStream_t st, LrStages& g) {
+    const size_t N = (size_t)g.N;
+    AMP_TRY_STATUS(amp::dev_alloc(g.rank, (size_t)g.R * 4));
+    AMP_TRY_STATUS(amp::dev_alloc(g.ids, N * 4));
+    AMP_TRY_STATUS(amp::dev_alloc(g.off, N * 8));
+    AMP_TRY_STATUS(amp::dev_alloc(g.bnd, (size_t)g.listed * 4));
+    AMP_TRY_STATUS(amp::dev_alloc(g.mins, N * 8));
+    AMP_TRY_STATUS(amp::dev_alloc(g.maxs, N * 8));
+    AMP_TRY_STATUS(amp::dev_alloc(g.areas, N * 4));
+    AMP_HIP_CHECK(hipMemsetAsync(g.mins.p, 0x7f, N * 8, st));                            // 0x7f7f7f7f: above every row and column
+    AMP_HIP_CHECK(hipMemsetAsync(g.maxs.p, 0, N * 8, st));
+    AMP_HIP_CHECK(hipMemsetAsync(g.areas.p, 0, N * 4, st));
+    hipLaunchKernelGGL(lr_emit_kernel, grid_256(g.R), dim3(256), 0, st, g.skeys.as<unsigned int>(), g.sidx.as<unsigned int>(), g.S.as<unsigned int>(),
+                       g.E.as<unsigned int>(), g.R, g.area, g.h, g.kind, g.nblk2, g.sums2.as<unsigned long long>(), g.base2.as<unsigned long long>(),
+                       g.rank.as<unsigned int>(), g.ids.as<int>(), g.off.as<unsigned long long>(), g.bnd.as<unsigned int>(), g.mins.as<int>(),
+                       g.maxs.as<int>(), g.areas.as<unsigned int>());
+    AMP_HIP_CHECK(hipGetLastError());
+    return AMP_OK;
+}
 
 }  // namespace

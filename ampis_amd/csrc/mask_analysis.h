@@ -5,9 +5,47 @@
 // at the end; amp_mask_parts, the components of every mask and their repair (mask_parts.hip, mask_parts_host.hip), has its shared arithmetic and
 // its declarations in mask_parts.h, included below.  Plain C++: the host-only sanitizer builds include this header.
 #pragma once
+#include "../../include/ampis_hip.h"
 #include "run_list.h"
 
 namespace amp {
+
+void set_error(const char* fmt, ...);            // context.hip; the sanitizer programs bring their own
+
+// What the argument checks of the entry points share.  api is the entry point's name, the first word of every message.
+// Every mask of a pool planned (nothing when pool is NULL: the plan stays empty), or the first malformed run list refused.
+inline int plan_pool(const char* api, const uint32_t* pool, const unsigned long long* off, const int* len, int n, int h, int w, RunPlan& runs) {
+    const unsigned long long area = (unsigned long long)h * w;
+    runs.reset(pool && n > 0 ? (size_t)n : 0);
+    for (int p = 0; pool && p < n; ++p) {
+        u64 covered = 0;
+        const RunListFault f = plan_add_mask(runs, (size_t)p, pool + off[p], len[p], h, w, false, &covered);
+        if (f == RUNS_OK) continue;
+        if (f == RUNS_EMPTY) set_error("%s: mask %d has an empty run list", api, p);
+        else if (f == RUNS_OVER) set_error("%s: the runs of mask %d cover more than the image's %llu pixels", api, p, area);
+        else if (f == RUNS_SHORT) set_error("%s: the runs of mask %d cover %llu pixels, the image has %llu", api, p, covered, area);
+        else set_error("%s: the masks of one call have more than 2^31 runs", api);
+        return AMP_ERR_ARG;
+    }
+    return AMP_OK;
+}
+
+// the image size of the analyses that index pixels and sides in 32 bits
+inline int require_image_size(const char* api, int h, int w) {
+    if (h >= 1 && w >= 1 && h <= 32768 && w <= 32768 && (unsigned long long)h * w <= (1ull << 30)) return AMP_OK;
+    set_error("%s: image size %d x %d (1 .. 32768 a side, at most 2^30 pixels)", api, h, w);
+    return AMP_ERR_ARG;
+}
+
+// the capacity report of a call whose need is one number: need[0] = counts, refused when the capacity cap_name = cap is smaller
+inline int counts_capacity(const char* api, const char* cap_name, unsigned long long counts, unsigned long long cap, unsigned long long* need) {
+    need[0] = counts;
+    if (counts > cap) {
+        set_error("%s: %s = %llu; %llu counts are needed", api, cap_name, cap, counts);
+        return AMP_ERR_NOMEM;
+    }
+    return AMP_OK;
+}
 
 // amp_mask_edge_distance.  One plan for both pools: mask g of the ground truths is runs.m[g], mask q of the predictions runs.m[ng + q];
 // planned are the masks the pairs name.  crop = the boxes clamped to the image, [n][4] {r1, r2, c1, c2}.

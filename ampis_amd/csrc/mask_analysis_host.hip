@@ -143,16 +143,7 @@ int region_props_check(const uint32_t* pool, const unsigned long long* off, cons
     AMP_REQUIRE(n == 0 || (pool && off && len && bbox && vals), "amp_mask_region_props: null argument");
     AMP_REQUIRE(h >= 1 && w >= 1 && h <= 32768 && w <= 32768 && (unsigned long long)h * w <= (1ull << 30),
                 "amp_mask_region_props: image size %d x %d (1 .. 32768 a side, at most 2^30 pixels: the moment sums are 64-bit)", h, w);
-    const unsigned long long area = (unsigned long long)h * w;
-    runs.reset((size_t)std::max(n, 0));
-    for (int p = 0; p < n; ++p) {
-        u64 covered = 0;
-        const RunListFault f = plan_add_mask(runs, (size_t)p, pool + off[p], len[p], h, w, false, &covered);
-        AMP_REQUIRE(f != RUNS_EMPTY, "amp_mask_region_props: mask %d has an empty run list", p);
-        AMP_REQUIRE(f != RUNS_OVER, "amp_mask_region_props: the runs of mask %d cover more than the image's %llu pixels", p, area);
-        AMP_REQUIRE(f != RUNS_SHORT, "amp_mask_region_props: the runs of mask %d cover %llu pixels, the image has %llu", p, covered, area);
-        AMP_REQUIRE(f == RUNS_OK, "amp_mask_region_props: the masks of one call have more than 2^31 runs");
-    }
+    AMP_TRY_STATUS(plan_pool("amp_mask_region_props", pool, off, len, n, h, w, runs));
     return AMP_OK;
 }
 
@@ -299,8 +290,7 @@ int seg_class_map_check(const uint32_t* gpool, const unsigned long long* goff, c
     AMP_REQUIRE(mode == 0 || mode == 1, "amp_seg_class_map: mode = %d (0 reduced, 1 all)", mode);
     AMP_REQUIRE(counts && counts_off && pixels, "amp_seg_class_map: null argument");
     AMP_REQUIRE(n == 0 || (gpool && goff && glen && ppool && poff && plen && pair_g && pair_p), "amp_seg_class_map: null argument");
-    AMP_REQUIRE(h >= 1 && w >= 1 && h <= 32768 && w <= 32768 && (unsigned long long)h * w <= (1ull << 30),
-                "amp_seg_class_map: image size %d x %d (1 .. 32768 a side, at most 2^30 pixels)", h, w);
+    AMP_TRY_STATUS(require_image_size("amp_seg_class_map", h, w));
     g.reset((size_t)ng);
     p.reset((size_t)np);
     unsigned long long bounds = 0;                                               // every boundary of a class is a boundary of a named run list
@@ -401,16 +391,7 @@ int render_check(const uint8_t* image, int h, int w, const uint32_t* pool, const
     AMP_REQUIRE(h >= 1 && w >= 1 && (unsigned long long)h * w <= (1ull << 30), "amp_render_instances: image size %d x %d (at most 2^30 pixels)", h, w);
     AMP_REQUIRE(n == 0 || !pool || (off && len && fill_tab), "amp_render_instances: null argument (off, len and fill_tab go with pool)");
     AMP_REQUIRE(n == 0 || !boxes || box_rgb, "amp_render_instances: null argument (box_rgb goes with boxes)");
-    const unsigned long long area = (unsigned long long)h * w;
-    runs.reset(pool ? (size_t)n : 0);
-    for (int p = 0; pool && p < n; ++p) {
-        u64 covered = 0;
-        const RunListFault f = plan_add_mask(runs, (size_t)p, pool + off[p], len[p], h, w, false, &covered);
-        AMP_REQUIRE(f != RUNS_EMPTY, "amp_render_instances: mask %d has an empty run list", p);
-        AMP_REQUIRE(f != RUNS_OVER, "amp_render_instances: the runs of mask %d cover more than the image's %llu pixels", p, area);
-        AMP_REQUIRE(f != RUNS_SHORT, "amp_render_instances: the runs of mask %d cover %llu pixels, the image has %llu", p, covered, area);
-        AMP_REQUIRE(f == RUNS_OK, "amp_render_instances: the masks of one call have more than 2^31 runs");
-    }
+    AMP_TRY_STATUS(plan_pool("amp_render_instances", pool, off, len, n, h, w, runs));
     rects.assign(boxes ? (size_t)n * 16 : 0, 0);
     for (int p = 0; boxes && p < n; ++p) {
         const int x0 = boxes[4 * (size_t)p], y0 = boxes[4 * (size_t)p + 1], x1 = boxes[4 * (size_t)p + 2], y1 = boxes[4 * (size_t)p + 3];

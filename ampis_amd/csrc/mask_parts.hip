@@ -14,17 +14,20 @@
 //                         root, which is the set's first item and so the tie rule of the definition);
 //   5. mp_count_kernel    one lane per item: is its component flipped, its value in the result and those of its neighbours, the boundaries
 //                         it writes (none where it meets a neighbour of the same value); the flipped pixels per mask; a workgroup sum each;
-//   6. mp_scan_kernel     one workgroup: the exclusive scan of the sums.  The host reads the total, reports the need and refuses a capacity
+//   6. scan_sums_kernel   one workgroup: the exclusive scan of the sums.  The host reads the total, reports the need and refuses a capacity
 //                         that is too small;
 //   7. mp_emit_kernel     as 5 with a workgroup scan: the boundary positions and where every mask's list starts;
-//   8. mp_diff_kernel     one lane per count: boundary minus the boundary before it (0 in front of a mask's first).
+//   8. diff_counts_kernel one lane per count: boundary minus the boundary before it (0 in front of a mask's first).
+// The workgroup sums and scans, 6 and 8 are compaction.h's; the items reach the device through MpItemsDev (mask_parts_dev.h).
 // A stats-only call (out_pool NULL) ends after 5.  Integer arithmetic only.  The atomics are integer add / or / max and the compare-and-swap
 // on the parents: the partition into sets does not depend on the order of the unions, nothing is placed through a counter.  So the bytes
 // repeat and equal the host's (mask_parts_host.hip).  Every loop in a kernel states why it ends; none waits for another lane.
 #include <vector>
 
 #include "common.h"
+#include "compaction.h"
 #include "mask_parts.h"
+#include "mask_parts_dev.h"
 #include "union_find.h"
 
 namespace {
@@ -33,13 +36,9 @@ using amp::MpMask;
 using amp::u64;
 using amp::wave_sum;
 
-struct MpArgs {
-    const unsigned int *S, *E, *col;
-    const unsigned char* T;
-    const MpMask* masks;
-    const unsigned long long* first;             // [n + 1]
-    int n, h, colour, keep_largest;
-    unsigned int R, threshold;
+struct MpArgs : amp::MpItemsView {
+    int h, colour, keep_largest;
+    unsigned int threshold;
 };
 
 __global__ __launch_bounds__(256) void mp_init_kernel(unsigned int R, unsigned int* __restrict__ parent, unsigned int* __restrict__ area,
@@ -131,8 +130,6 @@ __device__ __forceinline__ amp::MpBounds mp_item_bounds(const MpArgs& g, const M
 // workgroup b owns items [256 b, 256 b + 256): sums[b] = the boundaries they write
 __global__ __launch_bounds__(256) void mp_count_kernel(MpArgs g, MpRoots r, unsigned int nblk, unsigned long long* __restrict__ sums,
                                                        unsigned long long* __restrict__ stats) {
-    __shared__ unsigned long long part[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (unsigned int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {                  // ends: blk grows by the grid; uniform over the workgroup
         const unsigned int j = blk * 256 + threadIdx.x;
         unsigned int nb = 0;
@@ -143,43 +140,8 @@ __global__ __launch_bounds__(256) void mp_count_kernel(MpArgs g, MpRoots r, unsi
             nb = (unsigned)b.s + (unsigned)b.e;
             if (flip && r.root_of[j] == j) atomicAdd(&stats[4 * (size_t)m + 3], (unsigned long long)r.area[j]);
         }
-        const unsigned long long s = wave_sum((unsigned long long)nb);
-        if (lane == 0) part[wave] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) sums[blk] = part[0] + part[1] + part[2] + part[3];
-        __syncthreads();
+        block_sums_256<1>(1, nblk, blk, sums, [&](int) { return nb; });
     }
-}
-
-// one workgroup of 1024: sums[0 .. nblk) becomes its exclusive scan; *total = the sum
-__global__ __launch_bounds__(1024) void mp_scan_kernel(unsigned long long* __restrict__ sums, unsigned int nblk, unsigned long long* __restrict__ total) {
-    __shared__ unsigned long long tot[1024];
-    const unsigned long long m = nblk, chunk = (m + 1023) / 1024, first = min(chunk * threadIdx.x, m), last = min(first + chunk, m);
-    unsigned long long s = 0;
-    for (unsigned long long i = first; i < last; ++i) s += sums[i];                      // ends: i grows to last
-    unsigned long long run = amp::block_scan_1024(tot, s) - s;
-    for (unsigned long long i = first; i < last; ++i) {                                  // ends: i grows to last
-        const unsigned long long v = sums[i];
-        sums[i] = run;
-        run += v;
-    }
-    if (threadIdx.x == 0) *total = tot[1023];
-}
-
-// what lies in front of this lane in its workgroup (exclusive scan of c over 256 threads); every thread calls it
-__device__ __forceinline__ unsigned int mp_block_before(unsigned int c, unsigned int* wtot) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned int inc = c;
-    for (int o = 1; o < 64; o <<= 1) {                                                   // ends: six steps
-        const unsigned int v = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += v;
-    }
-    __syncthreads();                                                                     // wtot of the round before has been read
-    if (lane == 63) wtot[wave] = inc;
-    __syncthreads();
-    unsigned int before = inc - c;
-    for (int v = 0; v < wave; ++v) before += wtot[v];                                    // ends: at most three waves
-    return before;
 }
 
 __global__ __launch_bounds__(256) void mp_emit_kernel(MpArgs g, MpRoots r, unsigned int nblk, const unsigned long long* __restrict__ sums,
@@ -191,23 +153,13 @@ __global__ __launch_bounds__(256) void mp_emit_kernel(MpArgs g, MpRoots r, unsig
         bool flip;
         amp::MpBounds b{false, false};
         if (j < g.R) b = mp_item_bounds(g, r, j, &m, &flip);
-        unsigned long long at = sums[blk] + mp_block_before((unsigned)b.s + (unsigned)b.e, wtot);
+        unsigned long long at = sums[blk] + block_before_256((unsigned)b.s + (unsigned)b.e, wtot);
         if (j >= g.R) continue;                                                          // after the barriers
         if ((u64)j == g.first[m]) off[m] = at;
         if (b.s) bnd[at++] = g.S[j];
         if (b.e) bnd[at++] = g.E[j];
     }
 }
-
-__global__ __launch_bounds__(256) void mp_diff_kernel(const unsigned int* __restrict__ bnd, const unsigned long long* __restrict__ off, int n,
-                                                      unsigned long long total, unsigned int* __restrict__ counts) {
-    for (unsigned long long t = (unsigned long long)blockIdx.x * 256 + threadIdx.x; t < total; t += (unsigned long long)gridDim.x * 256) {   // ends: t grows by the grid
-        const int lo = amp::owner_of(off, n, t);                                         // off[0] = 0 <= t, every mask has a count: the mask that owns count t
-        counts[t] = bnd[t] - (off[lo] == t ? 0u : bnd[t - 1]);
-    }
-}
-
-dim3 mp_grid(unsigned long long items) { return dim3((unsigned)std::min<unsigned long long>(std::max<unsigned long long>((items + 255) / 256, 1ull), 1ull << 16)); }
 
 int mask_parts_device(amp_ctx* ctx, const amp::MpItems& it, int h, int colour, int connectivity, unsigned int threshold, int keep_largest,
                       unsigned long long* stats, uint32_t* out_pool, unsigned long long out_cap, unsigned long long* out_off, int* out_len,
@@ -217,13 +169,9 @@ int mask_parts_device(amp_ctx* ctx, const amp::MpItems& it, int h, int colour, i
     AMP_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
 
-    amp::DevBuf d_S, d_E, d_T, d_col, d_first, d_masks, d_parent, d_root, d_area, d_touch, d_stats, d_best, d_sums, d_total;
-    AMP_TRY_STATUS(amp::dev_upload(ctx, d_S, it.S));
-    AMP_TRY_STATUS(amp::dev_upload(ctx, d_E, it.E));
-    AMP_TRY_STATUS(amp::dev_upload(ctx, d_T, it.T));
-    AMP_TRY_STATUS(amp::dev_upload(ctx, d_col, it.col));
-    AMP_TRY_STATUS(amp::dev_upload(ctx, d_first, it.first));
-    AMP_TRY_STATUS(amp::dev_upload(ctx, d_masks, it.m));
+    amp::MpItemsDev d_items;
+    amp::DevBuf d_parent, d_root, d_area, d_touch, d_stats, d_best, d_sums, d_total;
+    AMP_TRY_STATUS(d_items.upload(ctx, it));
     AMP_TRY_STATUS(amp::dev_alloc(d_parent, (size_t)R * 4));
     AMP_TRY_STATUS(amp::dev_alloc(d_root, (size_t)R * 4));
     AMP_TRY_STATUS(amp::dev_alloc(d_area, (size_t)R * 4));
@@ -231,24 +179,23 @@ int mask_parts_device(amp_ctx* ctx, const amp::MpItems& it, int h, int colour, i
     AMP_TRY_STATUS(amp::dev_alloc(d_stats, (size_t)n * 32));
     AMP_TRY_STATUS(amp::dev_alloc(d_best, (size_t)n * 8));
     AMP_TRY_STATUS(amp::dev_alloc(d_sums, (size_t)nblk * 8));
-    AMP_TRY_STATUS(amp::dev_alloc(d_total, 8));
+    AMP_TRY_STATUS(amp::dev_alloc(d_total, 2 * 8));
     AMP_HIP_CHECK(hipMemsetAsync(d_stats.p, 0, (size_t)n * 32, st));
     AMP_HIP_CHECK(hipMemsetAsync(d_best.p, 0, (size_t)n * 8, st));
-    const MpArgs g{d_S.as<unsigned int>(), d_E.as<unsigned int>(), d_col.as<unsigned int>(), d_T.as<unsigned char>(), d_masks.as<MpMask>(),
-                   d_first.as<unsigned long long>(), n, h, colour, keep_largest, R, threshold};
+    const MpArgs g{d_items.view(), h, colour, keep_largest, threshold};
     const MpRoots r{d_root.as<unsigned int>(), d_area.as<unsigned int>(), d_touch.as<unsigned int>(), d_best.as<unsigned long long>()};
     unsigned int* parent = d_parent.as<unsigned int>();
     unsigned long long *dstats = d_stats.as<unsigned long long>(), *sums = d_sums.as<unsigned long long>();
-    hipLaunchKernelGGL(mp_init_kernel, mp_grid(R), dim3(256), 0, st, R, parent, d_area.as<unsigned int>(), d_touch.as<unsigned int>());
+    hipLaunchKernelGGL(mp_init_kernel, grid_256(R), dim3(256), 0, st, R, parent, d_area.as<unsigned int>(), d_touch.as<unsigned int>());
     AMP_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(mp_union_kernel, mp_grid(R), dim3(256), 0, st, g, amp::mp_reach(colour, connectivity), parent);
+    hipLaunchKernelGGL(mp_union_kernel, grid_256(R), dim3(256), 0, st, g, amp::mp_reach(colour, connectivity), parent);
     AMP_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(mp_flatten_kernel, mp_grid(R), dim3(256), 0, st, g, parent, d_root.as<unsigned int>(), d_area.as<unsigned int>(),
+    hipLaunchKernelGGL(mp_flatten_kernel, grid_256(R), dim3(256), 0, st, g, parent, d_root.as<unsigned int>(), d_area.as<unsigned int>(),
                        d_touch.as<unsigned int>());
     AMP_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(mp_roots_kernel, mp_grid(R), dim3(256), 0, st, g, r.root_of, r.area, r.touch, dstats, d_best.as<unsigned long long>());
+    hipLaunchKernelGGL(mp_roots_kernel, grid_256(R), dim3(256), 0, st, g, r.root_of, r.area, r.touch, dstats, d_best.as<unsigned long long>());
     AMP_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(mp_count_kernel, mp_grid(R), dim3(256), 0, st, g, r, nblk, sums, dstats);
+    hipLaunchKernelGGL(mp_count_kernel, grid_256(R), dim3(256), 0, st, g, r, nblk, sums, dstats);
     AMP_HIP_CHECK(hipGetLastError());
 
     std::vector<unsigned long long> hstats(4 * (size_t)n), hbest((size_t)n);
@@ -263,10 +210,10 @@ int mask_parts_device(amp_ctx* ctx, const amp::MpItems& it, int h, int colour, i
         finish_stats();
         return AMP_OK;
     }
-    hipLaunchKernelGGL(mp_scan_kernel, dim3(1), dim3(1024), 0, st, sums, nblk, d_total.as<unsigned long long>());
+    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(1024), 0, st, sums, nblk, 1, d_total.as<unsigned long long>());      // {0, the total}
     AMP_HIP_CHECK(hipGetLastError());
     unsigned long long total = 0;
-    AMP_HIP_CHECK(hipMemcpyAsync(&total, d_total.p, 8, hipMemcpyDeviceToHost, st));
+    AMP_HIP_CHECK(hipMemcpyAsync(&total, d_total.as<unsigned long long>() + 1, 8, hipMemcpyDeviceToHost, st));
     AMP_HIP_CHECK(hipStreamSynchronize(st));
     if (total < (unsigned long long)n || total > 2ull * R) {         // cannot happen: a mask has a count, an item writes at most two boundaries
         amp::set_error("amp_mask_parts: %llu counts from %u items of %d masks on the device", total, R, n);
@@ -278,9 +225,9 @@ int mask_parts_device(amp_ctx* ctx, const amp::MpItems& it, int h, int colour, i
     AMP_TRY_STATUS(amp::dev_alloc(d_off, (size_t)n * 8));
     AMP_TRY_STATUS(amp::dev_alloc(d_bnd, (size_t)total * 4));
     AMP_TRY_STATUS(amp::dev_alloc(d_counts, (size_t)total * 4));
-    hipLaunchKernelGGL(mp_emit_kernel, mp_grid(R), dim3(256), 0, st, g, r, nblk, sums, d_off.as<unsigned long long>(), d_bnd.as<unsigned int>());
+    hipLaunchKernelGGL(mp_emit_kernel, grid_256(R), dim3(256), 0, st, g, r, nblk, sums, d_off.as<unsigned long long>(), d_bnd.as<unsigned int>());
     AMP_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(mp_diff_kernel, mp_grid(total), dim3(256), 0, st, d_bnd.as<unsigned int>(), d_off.as<unsigned long long>(), n, total,
+    hipLaunchKernelGGL(diff_counts_kernel, grid_256(total), dim3(256), 0, st, d_bnd.as<unsigned int>(), d_off.as<unsigned long long>(), n, total,
                        d_counts.as<unsigned int>());
     AMP_HIP_CHECK(hipGetLastError());
     std::vector<unsigned long long> hoff((size_t)n);

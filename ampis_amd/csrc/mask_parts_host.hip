@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "common.h"
+#include "mask_analysis.h"
 #include "mask_parts.h"
 
 namespace amp {
@@ -20,8 +21,7 @@ int mask_parts_check(const uint32_t* pool, const unsigned long long* off, const 
                      int keep_largest, const unsigned long long* stats, const uint32_t* out_pool, const unsigned long long* out_off,
                      const int* out_len, const unsigned long long* need, RunPlan& runs) {
     AMP_REQUIRE(n >= 0, "amp_mask_parts: n = %d", n);
-    AMP_REQUIRE(h >= 1 && w >= 1 && h <= 32768 && w <= 32768 && (unsigned long long)h * w <= (1ull << 30),
-                "amp_mask_parts: image size %d x %d (1 .. 32768 a side, at most 2^30 pixels)", h, w);
+    AMP_TRY_STATUS(require_image_size("amp_mask_parts", h, w));
     AMP_REQUIRE(colour == 0 || colour == 1, "amp_mask_parts: colour = %d (1: parts of the ones, 0: holes of the zeros)", colour);
     AMP_REQUIRE(connectivity == 1 || connectivity == 2, "amp_mask_parts: connectivity = %d (1: 4 neighbours, 2: 8 neighbours)", connectivity);
     AMP_REQUIRE(keep_largest == 0 || (keep_largest == 1 && colour == 1), "amp_mask_parts: keep_largest = %d with colour = %d (0 or 1, parts only)",
@@ -30,26 +30,12 @@ int mask_parts_check(const uint32_t* pool, const unsigned long long* off, const 
                 !pool ? "pool" : !off ? "off" : !len ? "len" : "stats");
     AMP_REQUIRE(!out_pool || n == 0 || (out_off && out_len), "amp_mask_parts: null argument %s", !out_off ? "out_off" : "out_len");
     AMP_REQUIRE(!out_pool || need, "amp_mask_parts: null argument need");
-    const unsigned long long area = (unsigned long long)h * w;
-    runs.reset((size_t)n);
-    for (int p = 0; p < n; ++p) {
-        u64 covered = 0;
-        const RunListFault f = plan_add_mask(runs, (size_t)p, pool + off[p], len[p], h, w, false, &covered);
-        AMP_REQUIRE(f != RUNS_EMPTY, "amp_mask_parts: mask %d has an empty run list", p);
-        AMP_REQUIRE(f != RUNS_OVER, "amp_mask_parts: the runs of mask %d cover more than the image's %llu pixels", p, area);
-        AMP_REQUIRE(f != RUNS_SHORT, "amp_mask_parts: the runs of mask %d cover %llu pixels, the image has %llu", p, covered, area);
-        AMP_REQUIRE(f == RUNS_OK, "amp_mask_parts: the masks of one call have more than 2^31 runs");
-    }
+    AMP_TRY_STATUS(plan_pool("amp_mask_parts", pool, off, len, n, h, w, runs));
     return AMP_OK;
 }
 
 int mask_parts_capacity(unsigned long long counts, unsigned long long out_cap, unsigned long long* need) {
-    need[0] = counts;
-    if (counts > out_cap) {
-        set_error("amp_mask_parts: out_cap = %llu; %llu counts are needed", out_cap, counts);
-        return AMP_ERR_NOMEM;
-    }
-    return AMP_OK;
+    return counts_capacity("amp_mask_parts", "out_cap", counts, out_cap, need);
 }
 
 int mask_parts_host(const MpItems& it, int h, int colour, int connectivity, unsigned int threshold, int keep_largest,

@@ -8,7 +8,7 @@
 //   2. exclusive scan      of the steps (rocprim): where the steps of every edge start among the T items;
 //   3. pg_cross_kernel     COUNT: a fixed grid, every workgroup a contiguous slice of the items, one lane per (edge, step): is it a crossing;
 //   4. exclusive scan      of the workgroup sums.  The host reads C and sizes the arrays;
-//   5. pg_cross_kernel     EMIT: the same walk with a workgroup scan: the key (polygon, position) of every crossing;
+//   5. pg_cross_kernel     EMIT: the same walk with a workgroup scan (compaction.h): the key (polygon, position) of every crossing;
 //   6. radix sort          of the keys (rocprim): equal keys are indistinguishable, so any order among them gives the same array;
 //   7. pg_polystart_kernel one lane per polygon: where its crossings start;
 //   8. pg_toggle_kernel    one lane per sorted crossing: the first of a group of equal keys survives when the group is odd and lies inside the
@@ -37,6 +37,7 @@
 #include <rocprim/functional.hpp>
 
 #include "common.h"
+#include "compaction.h"
 #include "mask_analysis.h"
 
 namespace {
@@ -48,8 +49,6 @@ constexpr int PG_POS_BITS = 31;                   // a position is at most h * w
 
 struct PgEdge { int xs, ys, xe, ye, poly; };      // an edge's end points on the 5x grid as the polygon lists them, and its polygon
 
-dim3 pg_grid(unsigned long long items) { return dim3((unsigned)std::min<unsigned long long>(std::max<unsigned long long>((items + 255) / 256, 1ull), 1ull << 16)); }
-
 // the first of the n ascending keys that is >= x (n when there is none)
 __device__ __forceinline__ unsigned int pg_lower_bound(const u64* __restrict__ a, unsigned int n, u64 x) {
     unsigned int lo = 0, hi = n;
@@ -58,23 +57,6 @@ __device__ __forceinline__ unsigned int pg_lower_bound(const u64* __restrict__ a
         if (a[mid] < x) lo = mid + 1; else hi = mid;
     }
     return lo;
-}
-
-// what lies in front of this lane in its workgroup of 256 (exclusive scan of c) and the workgroup's sum; every thread calls it
-__device__ __forceinline__ unsigned int pg_block_before(unsigned int c, unsigned int* wtot, unsigned int* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned int inc = c;
-    for (int o = 1; o < 64; o <<= 1) {                                                   // ends: six steps
-        const unsigned int v = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += v;
-    }
-    __syncthreads();                                                                     // wtot of the call before has been read
-    if (lane == 63) wtot[wave] = inc;
-    __syncthreads();
-    unsigned int before = inc - c;
-    for (int v = 0; v < wave; ++v) before += wtot[v];                                    // ends: at most three waves
-    *total = wtot[0] + wtot[1] + wtot[2] + wtot[3];
-    return before;
 }
 
 // voff: the first vertex of every polygon, [P + 1] ascending, no polygon empty; elen[V] = 0 closes the array the scan reads
@@ -115,7 +97,7 @@ __global__ __launch_bounds__(256) void pg_cross_kernel(const PgEdge* __restrict_
             poly = (unsigned)ed.poly;
         }
         unsigned int total;
-        const unsigned int before = pg_block_before((unsigned)hit, wtot, &total);
+        const unsigned int before = block_before_256((unsigned)hit, wtot, &total);
         if (EMIT && hit) keys[at + before] = ((u64)poly << PG_POS_BITS) | pos;
         at += total;
     }
@@ -250,7 +232,7 @@ int polygons_device(amp_ctx* ctx, const double* xy, const unsigned long long* po
     AMP_HIP_CHECK(hipMemcpyAsync(g_xy, xy + d0, (size_t)V * 16, hipMemcpyHostToDevice, st));
     AMP_HIP_CHECK(hipMemcpyAsync(g_voff, voff.data(), ((size_t)P + 1) * 8, hipMemcpyHostToDevice, st));
     AMP_HIP_CHECK(hipMemcpyAsync(g_pinst, pinst.data(), (size_t)P * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(pg_edge_kernel, pg_grid((u64)V + 1), dim3(256), 0, st, g_xy, g_voff, P, V, g_edges, g_elen);
+    hipLaunchKernelGGL(pg_edge_kernel, grid_256((u64)V + 1), dim3(256), 0, st, g_xy, g_voff, P, V, g_edges, g_elen);
     AMP_HIP_CHECK(hipGetLastError());
     q = tmp_a;
     AMP_HIP_CHECK(rocprim::exclusive_scan(A + o_tmpa, q, g_elen, g_eoff, 0ull, (size_t)V + 1, rocprim::plus<u64>(), st));
@@ -299,21 +281,21 @@ int polygons_device(amp_ctx* ctx, const double* xy, const unsigned long long* po
     AMP_HIP_CHECK(hipGetLastError());
     q = tmp_b;
     AMP_HIP_CHECK(rocprim::radix_sort_keys(B + o_tmpb, q, g_k1, g_k2, (size_t)C, 0u, bits1, st));              // g_k2: the crossings by (polygon, position)
-    hipLaunchKernelGGL(pg_polystart_kernel, pg_grid((u64)P + 1), dim3(256), 0, st, g_k2, C, P, g_pstart);
+    hipLaunchKernelGGL(pg_polystart_kernel, grid_256((u64)P + 1), dim3(256), 0, st, g_k2, C, P, g_pstart);
     AMP_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(pg_toggle_kernel, pg_grid(C), dim3(256), 0, st, g_k2, C, g_pstart, g_pinst, n, area, g_k1);
+    hipLaunchKernelGGL(pg_toggle_kernel, grid_256(C), dim3(256), 0, st, g_k2, C, g_pstart, g_pinst, n, area, g_k1);
     AMP_HIP_CHECK(hipGetLastError());
     q = tmp_b;
     AMP_HIP_CHECK(rocprim::radix_sort_keys(B + o_tmpb, q, g_k1, g_k2, (size_t)C, 0u, bits2, st));              // g_k2: the toggles by (instance, position)
-    hipLaunchKernelGGL(pg_delta_kernel, pg_grid(std::max<u64>(C, (u64)n + 1)), dim3(256), 0, st, g_k2, C, n, g_delta, g_ioff);
+    hipLaunchKernelGGL(pg_delta_kernel, grid_256(std::max<u64>(C, (u64)n + 1)), dim3(256), 0, st, g_k2, C, n, g_delta, g_ioff);
     AMP_HIP_CHECK(hipGetLastError());
     q = tmp_b;
     AMP_HIP_CHECK(rocprim::inclusive_scan(B + o_tmpb, q, g_delta, g_cover, (size_t)C, rocprim::plus<int>(), st));
-    hipLaunchKernelGGL(pg_bound_kernel, pg_grid((u64)C + 1), dim3(256), 0, st, g_k2, C, n, g_cover, g_ioff, g_flags);
+    hipLaunchKernelGGL(pg_bound_kernel, grid_256((u64)C + 1), dim3(256), 0, st, g_k2, C, n, g_cover, g_ioff, g_flags);
     AMP_HIP_CHECK(hipGetLastError());
     q = tmp_b;
     AMP_HIP_CHECK(rocprim::exclusive_scan(B + o_tmpb, q, g_flags, g_bidx, 0u, (size_t)C + 1, rocprim::plus<unsigned int>(), st));
-    hipLaunchKernelGGL(pg_instoff_kernel, pg_grid((u64)n + 1), dim3(256), 0, st, g_bidx, g_ioff, n, g_coff, g_mins, g_maxs, g_areas);
+    hipLaunchKernelGGL(pg_instoff_kernel, grid_256((u64)n + 1), dim3(256), 0, st, g_bidx, g_ioff, n, g_coff, g_mins, g_maxs, g_areas);
     AMP_HIP_CHECK(hipGetLastError());
     std::vector<u64> coff((size_t)n + 1);
     AMP_HIP_CHECK(hipMemcpyAsync(coff.data(), g_coff, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, st));
@@ -331,9 +313,9 @@ int polygons_device(amp_ctx* ctx, const double* xy, const unsigned long long* po
     amp::DevBuf d_c;
     AMP_TRY_STATUS(amp::dev_alloc(d_c, ac.total));
     unsigned int *g_bnd = (unsigned int*)(d_c.as<char>() + o_bnd), *g_counts = (unsigned int*)(d_c.as<char>() + o_counts);
-    hipLaunchKernelGGL(pg_place_kernel, pg_grid(C), dim3(256), 0, st, g_k2, C, g_flags, g_bidx, g_bnd);
+    hipLaunchKernelGGL(pg_place_kernel, grid_256(C), dim3(256), 0, st, g_k2, C, g_flags, g_bidx, g_bnd);
     AMP_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(pg_counts_kernel, pg_grid(total), dim3(256), 0, st, g_bnd, g_coff, n, (u64)total, h, area, g_counts, g_mins, g_maxs, g_areas);
+    hipLaunchKernelGGL(pg_counts_kernel, grid_256(total), dim3(256), 0, st, g_bnd, g_coff, n, (u64)total, h, area, g_counts, g_mins, g_maxs, g_areas);
     AMP_HIP_CHECK(hipGetLastError());
     std::vector<int> mins(2 * (size_t)n), maxs(2 * (size_t)n);
     std::vector<unsigned int> ar((size_t)n);

@@ -44,12 +44,7 @@ int polygons_check(const double* xy, const unsigned long long* poly_off, const i
 }
 
 int polygons_capacity(unsigned long long counts, unsigned long long counts_cap, unsigned long long* need) {
-    need[0] = counts;
-    if (counts > counts_cap) {
-        set_error("amp_polygons_to_rle: counts_cap = %llu; %llu counts are needed", counts_cap, counts);
-        return AMP_ERR_NOMEM;
-    }
-    return AMP_OK;
+    return counts_capacity("amp_polygons_to_rle", "counts_cap", counts, counts_cap, need);
 }
 
 int polygons_host(const double* xy, const unsigned long long* poly_off, const int* inst_first, int n, int h, int w, uint32_t* counts,

@@ -14,6 +14,7 @@
 //                        lists and the closing boundary h * w of each;
 //   4. sc_write_kernel   as 2, with a workgroup scan: every transition writes its pixel position where the scan says;
 //   5. sc_diff_kernel    one lane per count: boundary minus the boundary before it (0 in front of a class's first).
+// The workgroup sums of 2, the scan loop of 3 and the workgroup scan of 4 are compaction.h's.
 // Five launches and one memset per call whatever the number of pairs.  Integer arithmetic only; the atomics are 64-bit ORs and adds, whose
 // results do not depend on the order, and every other word is written once by the lane that owns it: the bytes repeat and equal the host's
 // (mask_analysis_host.hip paints the planes by one walk over the two run lists of a pair and reads the same words).  Scratch: the plan, three planes of
@@ -21,6 +22,7 @@
 #include <vector>
 
 #include "common.h"
+#include "compaction.h"
 #include "mask_analysis.h"
 #include "seg_class_map.h"
 
@@ -75,8 +77,7 @@ __device__ __forceinline__ bool sc_word_transitions(const unsigned long long* __
 __global__ __launch_bounds__(256) void sc_count_kernel(const unsigned long long* __restrict__ planes, unsigned long long units, int h, int pitch,
                                                        int mode, int K, unsigned int nblk, unsigned long long* __restrict__ sums,
                                                        unsigned long long* __restrict__ px) {
-    __shared__ unsigned long long part[4][7];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
     for (unsigned int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {          // uniform over the workgroup: every thread meets every barrier
         const unsigned long long u = (unsigned long long)blk * 256 + threadIdx.x;
         u64 t[7], tp = 0, fn = 0, fp = 0, valid = 0;
@@ -85,13 +86,7 @@ __global__ __launch_bounds__(256) void sc_count_kernel(const unsigned long long*
             const unsigned long long s = wave_sum((unsigned long long)amp::popc(amp::sc_code_word(tp, fn, fp, c) & valid));
             if (lane == 0 && s) atomicAdd(&px[c], s);
         }
-        for (int k = 0; k < K; ++k) {
-            const unsigned long long s = wave_sum((unsigned long long)amp::popc(t[k]));
-            if (lane == 0) part[wave][k] = s;
-        }
-        __syncthreads();
-        if ((int)threadIdx.x < K) sums[(size_t)threadIdx.x * nblk + blk] = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
-        __syncthreads();
+        block_sums_256<7>(K, nblk, blk, sums, [&](int k) { return amp::popc(t[k]); });
     }
 }
 
@@ -101,16 +96,9 @@ __global__ __launch_bounds__(1024) void sc_scan_kernel(unsigned long long* __res
                                                        unsigned int area, unsigned long long* __restrict__ coff, unsigned int* __restrict__ bnd) {
     __shared__ unsigned long long tot[1024];
     __shared__ unsigned long long start[7];
-    const unsigned long long chunk = (m + 1023) / 1024, first = chunk * threadIdx.x, last = min(first + chunk, m);
-    unsigned long long s = 0;
-    for (unsigned long long i = first; i < last; ++i) s += sums[i];
-    unsigned long long run = amp::block_scan_1024(tot, s) - s;       // what lies in front of this thread's chunk
-    for (unsigned long long i = first; i < last; ++i) {
-        const unsigned long long v = sums[i];
-        sums[i] = run;
+    scan_sums_in_place(sums, m, tot, [&](unsigned long long i, unsigned long long run) {
         if (i % nblk == 0) start[i / nblk] = run;                    // the first workgroup of a class: where the class's boundaries start
-        run += v;
-    }
+    });
     __syncthreads();
     if ((int)threadIdx.x <= K) {
         const int k = threadIdx.x;
@@ -125,26 +113,14 @@ __global__ __launch_bounds__(256) void sc_write_kernel(const unsigned long long*
                                                        int mode, int K, unsigned int nblk, const unsigned long long* __restrict__ sums,
                                                        unsigned int* __restrict__ bnd) {
     __shared__ unsigned int wtot[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (unsigned int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+    for (unsigned int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {          // uniform over the workgroup: every thread meets every barrier
         const unsigned long long u = (unsigned long long)blk * 256 + threadIdx.x;
         u64 t[7], tp = 0, fn = 0, fp = 0, valid = 0;
         sc_word_transitions(planes, units, u, h, pitch, mode, K, t, &tp, &fn, &fp, &valid);
         const unsigned int base = (unsigned int)(u / (unsigned)pitch) * (unsigned)h + ((unsigned int)(u % (unsigned)pitch) << 6);
-        for (int k = 0; k < K; ++k) {
-            const unsigned int c = (unsigned)amp::popc(t[k]);
-            unsigned int inc = c;                                    // inclusive scan over the wave
-            for (int o = 1; o < 64; o <<= 1) {
-                const unsigned int v = __shfl_up(inc, o, 64);
-                if (lane >= o) inc += v;
-            }
-            if (lane == 63) wtot[wave] = inc;
-            __syncthreads();
-            unsigned int before = inc - c;
-            for (int v = 0; v < wave; ++v) before += wtot[v];
-            unsigned long long at = sums[(size_t)k * nblk + blk] + (unsigned long long)k + before;
+        for (int k = 0; k < K; ++k) {                                // the barrier that opens a scan protects the wtot of the class before
+            unsigned long long at = sums[(size_t)k * nblk + blk] + (unsigned long long)k + block_before_256((unsigned)amp::popc(t[k]), wtot);
             for (u64 x = t[k]; x; x &= x - 1) bnd[at++] = base + (unsigned)amp::ctz(x);
-            __syncthreads();                                         // wtot is rewritten for the next class
         }
     }
 }

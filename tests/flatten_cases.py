@@ -84,6 +84,15 @@ def _hand():
     board = np.add.outer(np.arange(66), np.arange(3)) % 2 == 0
     c["checkerboard_66x3"] = _case(np.stack([board, ~board]))                           # the most runs per pixel
     c["checkerboard_66x3_full_under"] = _case(np.stack([np.ones((66, 3), bool), board]), [1, 0])
+    # 257 x 26300, the label image in horizontal bands of three owners, six or seven vertical runs a column: 131 500 plane words in 514
+    # workgroups, so the first scan of the workgroup sums runs over 1028 entries, and 7 x 26300 - 15000 = 169 100 runs in 661 workgroups, so
+    # the second runs over 1322 -- both past the 1024 entries that one round of the one-workgroup scan takes, neither a multiple of it; the
+    # last band is the single row of the ragged fifth plane word, one band crosses the word edge 63 | 64
+    bands = np.zeros((3, 257, 26300), bool)
+    for k, (a, b) in enumerate(((0, 1), (2, 4), (62, 66), (100, 128), (130, 131), (200, 201), (256, 257))):
+        bands[k % 2, a:b, :] = True
+    bands[2, 90:140, 5000:20000] = True                                                 # on top by rank: it swallows two bands where it lies
+    c["two_round_scans"] = _case(bands, [1, 2, 0])
     return c
 
 

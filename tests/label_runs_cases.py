@@ -110,7 +110,20 @@ def _hand():
     c["label_near_both_ends"] = _label(far)
     c["label_all_zero"] = _label(np.zeros((5, 4)))
     c["label_wrap"] = _label(np.array([[1, 2, 2], [1, 1, 2], [2, 1, 1]]))
+    c["two_round_scans"] = _binary(_bands(257, 26300), 1)
     return c
+
+
+def _bands(h, w):
+    """Seven horizontal bands, so seven vertical runs in every column but one: the last band in the single row of the ragged fifth plane word,
+    one across the word edge 63 | 64, one cut in two (eight instances).  At 257 x 26300: 131 500 plane words in 514 workgroups, so the first
+    scan of the workgroup sums runs over 1028 entries, and 184 099 runs in 720 workgroups, so the second runs over 1440 -- both past the 1024
+    entries that one round of the one-workgroup scan takes, neither a multiple of it."""
+    m = np.zeros((h, w), np.uint8)
+    for a, b in ((0, 1), (2, 4), (62, 66), (100, 128), (130, 131), (200, 201), (h - 1, h)):
+        m[a:b, :] = 1
+    m[130, w // 2] = 0                            # two instances from one band
+    return m
 
 
 HAND_CASES = _hand()

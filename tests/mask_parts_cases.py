@@ -104,6 +104,15 @@ def _hand():
     c["twelve_masks"] = _case(mix, 2, 0, None)
     c["twelve_masks_4"] = _case(mix, 1, 2, 10, True)
     c["twelve_masks_thresholds"] = _case(mix, 2, 9, 26)
+    # one mask of alternating rows, 257 x 1100, closed by its first and last column so that the rows of zeros are 128 holes, the upper 100 of
+    # them cut in two by a bar: as holes 2 + 57 + 1097 x 257 + 1 = 281 989 items in 1102 workgroups -- the scan of the workgroup sums runs
+    # over more than the 1024 entries one round takes and no multiple of it --, as parts 141 545 items in 553; 257 rows: the last 64-row
+    # word of a column holds one row.  The threshold fills the holes of 499 pixels and leaves those of 598 and 1098
+    rows = np.zeros((257, 1100), bool)
+    rows[::2, :] = True
+    rows[:, 0] = rows[:, 1099] = True
+    rows[:200, 500] = True
+    c["two_round_scan"] = _case(rows, 1, 0, 550)
     return c
 
 

@@ -6,7 +6,6 @@
 // segments left of a pixel is the pixel, the areas sum to twice the mask's and the lengths to its crack perimeter --, every buffer has exactly
 // the capacity asked for, one element less is refused with nothing written, and bad arguments are refused.  Built and run by
 // tests/test_mask_contours_sanitize.py like the flatten run beside it.
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -16,21 +15,7 @@
 
 #include "../../ampis_amd/csrc/contours.h"
 #include "../../include/ampis_hip.h"
-
-namespace amp {
-static char g_err[1024];
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-}  // namespace amp
-
-static unsigned long long rng_state = 0x9E3779B97F4A7C15ull;
-static unsigned int rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return (unsigned int)(rng_state >> 11); }
-
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "CHECK failed line %d: %s (%s)\n", __LINE__, #cond, amp::g_err); return 1; } } while (0)
+#include "sanitize_common.h"
 
 // what amp_mask_contours does with a NULL context
 static int call(const uint32_t* pool, const unsigned long long* off, const int* len, int n, int h, int w, int connectivity,
@@ -43,22 +28,6 @@ static int call(const uint32_t* pool, const unsigned long long* off, const int* 
     amp::MpItems items;
     if (!amp::mp_build_items(plan, h, w, 1, items)) return AMP_ERR_ARG;
     return amp::contours_host(items, h, connectivity, ring_first, ring_off, ring_len, ring_area2, ring_length, ring_cap, xy, xy_cap, need);
-}
-
-// a dense row-major mask as COCO counts (column-major, zeros first); loose: zero-length runs are put in here and there
-static std::vector<uint32_t> encode(const std::vector<int>& m, int h, int w, bool loose) {
-    std::vector<uint32_t> c;
-    int cur = 0;
-    uint32_t run = 0;
-    for (int x = 0; x < w; ++x)
-        for (int y = 0; y < h; ++y) {
-            const int v = m[(size_t)y * w + x];
-            if (v != cur) { c.push_back(run); run = 0; cur = v; }
-            if (loose && run == 2) { c.push_back(2); c.push_back(0); run = 0; }          // the same colour goes on behind an empty run of the other
-            ++run;
-        }
-    c.push_back(run);
-    return c;
 }
 
 typedef std::vector<std::vector<int>> Masks;

@@ -4,7 +4,6 @@
 // cut at column ends, empty masks, no mask, equal / descending / extreme ranks, many masks on one block, single pixels, a checkerboard) and
 // random masks, every result compared with a per-pixel evaluation written here, every buffer of exactly the capacity asked for, and the
 // refusals.  Built and run by tests/test_flatten_sanitize.py like the mask-parts run beside it.
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -14,21 +13,7 @@
 
 #include "../../ampis_amd/csrc/flatten.h"
 #include "../../include/ampis_hip.h"
-
-namespace amp {
-static char g_err[1024];
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-}  // namespace amp
-
-static unsigned long long rng_state = 0x9E3779B97F4A7C15ull;
-static unsigned int rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return (unsigned int)(rng_state >> 11); }
-
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "CHECK failed line %d: %s (%s)\n", __LINE__, #cond, amp::g_err); return 1; } } while (0)
+#include "sanitize_common.h"
 
 // what amp_flatten_instances does with a NULL context
 static int call(const uint32_t* pool, const unsigned long long* off, const int* len, int n, int h, int w, const uint32_t* rank, int* labels,
@@ -39,22 +24,6 @@ static int call(const uint32_t* pool, const unsigned long long* off, const int* 
     int st = amp::flatten_check(pool, off, len, n, h, w, rank, counts, counts_cap, counts_off, counts_len, stats, boxes, pixels, need, plan, order);
     if (st != AMP_OK) return st;
     return amp::flatten_host(plan, order, h, w, labels, counts, counts_cap, counts_off, counts_len, stats, boxes, pixels, need);
-}
-
-// a dense row-major mask as COCO counts (column-major, zeros first); loose: zero-length runs are put in here and there
-static std::vector<uint32_t> encode(const std::vector<int>& m, int h, int w, bool loose) {
-    std::vector<uint32_t> c;
-    int cur = 0;
-    uint32_t run = 0;
-    for (int x = 0; x < w; ++x)
-        for (int y = 0; y < h; ++y) {
-            const int v = m[(size_t)y * w + x];
-            if (v != cur) { c.push_back(run); run = 0; cur = v; }
-            if (loose && run == 2) { c.push_back(2); c.push_back(0); run = 0; }          // the same colour goes on behind an empty run of the other
-            ++run;
-        }
-    c.push_back(run);
-    return c;
 }
 
 typedef std::vector<std::vector<int>> Masks;

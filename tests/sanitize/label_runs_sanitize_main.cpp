@@ -3,7 +3,6 @@
 // pixel, one row, one column, 63 / 64 / 65 / 129 rows, empty, full, checkerboard, serpentine, comb) and random images of both kinds and both
 // connectivities, every instance compared with a per-pixel flood fill written here, every buffer of exactly the capacity asked for, and the
 // refusals.  Built and run by tests/test_label_runs_sanitize.py like the class-map run beside it.
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -14,21 +13,7 @@
 
 #include "../../ampis_amd/csrc/mask_analysis.h"
 #include "../../include/ampis_hip.h"
-
-namespace amp {
-static char g_err[1024];
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-}  // namespace amp
-
-static unsigned long long rng_state = 0x9E3779B97F4A7C15ull;
-static unsigned int rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return (unsigned int)(rng_state >> 11); }
-
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "CHECK failed line %d: %s (%s)\n", __LINE__, #cond, amp::g_err); return 1; } } while (0)
+#include "sanitize_common.h"
 
 // the instance number (1 ..) of every pixel by definition: flood fill in row-major order of the first pixel (BINARY), rank of the id (LABEL)
 static std::vector<int> reference_labels(const std::vector<int>& img, int h, int w, int kind, int conn, int zero_bg, std::vector<int>* ids) {

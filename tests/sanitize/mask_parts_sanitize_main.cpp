@@ -4,7 +4,6 @@
 // the border, a hole that meets the outside by a corner, checkerboards, serpentine and its complement, a mask on all four borders) and random
 // masks at both colours and connectivities, every result compared with a per-pixel flood fill written here, every buffer of exactly the
 // capacity asked for, and the refusals.  Built and run by tests/test_mask_parts_sanitize.py like the label-runs run beside it.
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -14,21 +13,7 @@
 
 #include "../../ampis_amd/csrc/mask_analysis.h"
 #include "../../include/ampis_hip.h"
-
-namespace amp {
-static char g_err[1024];
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-}  // namespace amp
-
-static unsigned long long rng_state = 0x9E3779B97F4A7C15ull;
-static unsigned int rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return (unsigned int)(rng_state >> 11); }
-
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "CHECK failed line %d: %s (%s)\n", __LINE__, #cond, amp::g_err); return 1; } } while (0)
+#include "sanitize_common.h"
 
 // what amp_mask_parts does with a NULL context
 static int call(const uint32_t* pool, const unsigned long long* off, const int* len, int n, int h, int w, int colour, int conn,
@@ -41,22 +26,6 @@ static int call(const uint32_t* pool, const unsigned long long* off, const int* 
     amp::MpItems items;
     if (!amp::mp_build_items(plan, h, w, colour, items)) return AMP_ERR_ARG;
     return amp::mask_parts_host(items, h, colour, conn, threshold, keep_largest, stats, out_pool, out_cap, out_off, out_len, need);
-}
-
-// a dense row-major mask as COCO counts (column-major, zeros first); loose: zero-length runs are put in here and there
-static std::vector<uint32_t> encode(const std::vector<int>& m, int h, int w, bool loose) {
-    std::vector<uint32_t> c;
-    int cur = 0;
-    uint32_t run = 0;
-    for (int x = 0; x < w; ++x)
-        for (int y = 0; y < h; ++y) {
-            const int v = m[(size_t)y * w + x];
-            if (v != cur) { c.push_back(run); run = 0; cur = v; }
-            if (loose && run == 2) { c.push_back(2); c.push_back(0); run = 0; }          // the same colour goes on behind an empty run of the other
-            ++run;
-        }
-    c.push_back(run);
-    return c;
 }
 
 // by definition: the components of colour `colour` by flood fill, holes = components of the zeros with no pixel on the image border; the rule;

@@ -4,7 +4,6 @@
 // amp_rle_from_polygon and amp_rle_merge2 written here, every output buffer of exactly the capacity asked for, the closed-form edge walk of
 // mask_analysis.h against the crossings the routine collects, and the refusals.  Built and run by tests/test_polygons_sanitize.py.
 #include <math.h>
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -14,22 +13,9 @@
 
 #include "../../ampis_amd/csrc/mask_analysis.h"
 #include "../../include/ampis_hip.h"
+#include "sanitize_common.h"
 
-namespace amp {
-static char g_err[1024];
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-}  // namespace amp
-
-static unsigned long long rng_state = 0x9E3779B97F4A7C15ull;
-static unsigned int rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return (unsigned int)(rng_state >> 11); }
 static double uni(double lo, double hi) { return lo + (hi - lo) * (double)(rnd() % 1000003u) / 1000003.0; }
-
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "CHECK failed line %d: %s (%s)\n", __LINE__, #cond, amp::g_err); return 1; } } while (0)
 
 // the run list of one instance from the public entry points
 static int composed(const std::vector<std::vector<double>>& polys, int h, int w, std::vector<uint32_t>* out) {

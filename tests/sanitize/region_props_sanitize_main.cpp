@@ -2,7 +2,6 @@
 // amp::region_props_check / amp::region_props_host, what amp_mask_region_props runs with a NULL context, and through them the word arithmetic
 // of region_props.h that the kernels share), on random masks up to three 64-row words tall -- every integer compared with a per-pixel
 // evaluation -- and on hostile input.  Built and run by tests/test_region_props_sanitize.py like the edge-distance run beside it.
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -13,21 +12,7 @@
 
 #include "../../ampis_amd/csrc/mask_analysis.h"
 #include "../../include/ampis_hip.h"
-
-namespace amp {
-static char g_err[1024];
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-}  // namespace amp
-
-static unsigned long long rng_state = 0x9E3779B97F4A7C15ull;
-static unsigned int rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return (unsigned int)(rng_state >> 11); }
-
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "CHECK failed line %d: %s (%s)\n", __LINE__, #cond, amp::g_err); return 1; } } while (0)
+#include "sanitize_common.h"
 
 typedef std::pair<long long, long long> Pt;
 static long long cross(const Pt& o, const Pt& a, const Pt& b) { return (a.first - o.first) * (b.second - o.second) - (a.second - o.second) * (b.first - o.first); }

@@ -3,7 +3,6 @@
 // 1, 2, 63, 64, 65, 130; empty and full masks, masks owning the corners, noise; boxes on the border, inverted and thinner than the line) against
 // a per-pixel evaluation written here, the image and output buffers of exactly h * w * 3 bytes, and hostile input.  Built and run by
 // tests/test_render_sanitize.py like the runs beside it.  The device kernel indexes only what these checks let through.
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -14,21 +13,7 @@
 
 #include "../../ampis_amd/csrc/mask_analysis.h"
 #include "../../include/ampis_hip.h"
-
-namespace amp {
-static char g_err[1024];
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-}  // namespace amp
-
-static unsigned long long rng_state = 0x9E3779B97F4A7C15ull;
-static unsigned int rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return (unsigned int)(rng_state >> 11); }
-
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "CHECK failed line %d: %s (%s)\n", __LINE__, #cond, amp::g_err); return 1; } } while (0)
+#include "sanitize_common.h"
 
 struct Pool {
     std::vector<uint32_t> pool;

@@ -2,7 +2,6 @@
 // amp::overlap_groups_check / amp::overlap_groups_host, what the call runs with a NULL context): random groups of random masks, every count
 // compared with a per-pixel evaluation, output buffers of exactly the needed size, and hostile input.  Built and run by
 // tests/test_rle_overlap_sanitize.py like the region-property run beside it.  The device kernel indexes only what these checks let through.
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -11,21 +10,7 @@
 
 #include "../../ampis_amd/csrc/mask_analysis.h"
 #include "../../include/ampis_hip.h"
-
-namespace amp {
-static char g_err[1024];
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-}  // namespace amp
-
-static unsigned long long rng_state = 0x9E3779B97F4A7C15ull;
-static unsigned int rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return (unsigned int)(rng_state >> 11); }
-
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "CHECK failed line %d: %s (%s)\n", __LINE__, #cond, amp::g_err); return 1; } } while (0)
+#include "sanitize_common.h"
 
 struct Pool {
     std::vector<uint32_t> pool;

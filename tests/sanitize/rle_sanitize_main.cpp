@@ -2,7 +2,6 @@
 // with valid round trips and with hostile input (the reference has no sanitizer run; GPU sanitizers are not available on
 // the pool, so the host codec is what can be covered).  Built and run by tests/test_sanitize.py:
 //   g++ -x c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I<rocm>/include rle_sanitize_main.cpp rle_host.hip
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -12,21 +11,8 @@
 #include <vector>
 
 #include "../../include/ampis_hip.h"
-
-namespace amp {   // the library defines these in context.hip (which needs the HIP runtime); the codec only reports through them
-static char g_err[1024];
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-}  // namespace amp
-
-static unsigned long long rng_state = 88172645463325252ull;
-static unsigned int rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return (unsigned int)(rng_state >> 11); }
-
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "CHECK failed line %d: %s (%s)\n", __LINE__, #cond, amp::g_err); return 1; } } while (0)
+#define SANITIZE_SEED 88172645463325252ull
+#include "sanitize_common.h"      // amp::set_error: the library defines it in context.hip (which needs the HIP runtime); the codec only reports through it
 
 int main() {
     // 1. round trips on random masks of awkward sizes: encode -> string -> from_string -> decode, area, iou, merge

@@ -4,7 +4,6 @@
 // hostile lengths that must be refused before anything is read), and the hostile `off / len` that the four argument checks of
 // ampis_amd/csrc/mask_analysis_host.hip must refuse without reading a run.  Built and run by tests/test_run_list_sanitize.py like the other
 // five sanitizer programs.
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -14,21 +13,7 @@
 
 #include "../../ampis_amd/csrc/mask_analysis.h"
 #include "../../include/ampis_hip.h"
-
-namespace amp {
-static char g_err[1024];
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-}  // namespace amp
-
-static unsigned long long rng_state = 0x9E3779B97F4A7C15ull;
-static unsigned int rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return (unsigned int)(rng_state >> 11); }
-
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "CHECK failed line %d: %s (%s)\n", __LINE__, #cond, amp::g_err); return 1; } } while (0)
+#include "sanitize_common.h"
 
 // pixels [s, e) into the plane (r0, c0, H, W), bit by bit; the plane has exactly W * pitch words: a word too far is a heap overflow
 static std::vector<amp::u64> paint_by_pixel(unsigned int s, unsigned int e, int h, int r0, int c0, int H, int W) {

@@ -95,11 +95,22 @@ def hand_cases():
     c["pairs_64_same_words"] = case(g64, q64, [(i % 8, i // 8) for i in range(64)], (H, W))
     # an empty mask (the single run h * w) inside a pair, on either side and on both
     c["empty_in_pair"] = case([z(), disc(H, W, 8, 8, 5), z()], [disc(H, W, 12, 20, 5), z(), z()], [(0, 0), (1, 1), (2, 2)], (H, W))
+    # 257 x 13500: 67 500 plane words in 264 workgroups, so the scan of the classes x workgroups sums runs over 1056 entries (reduced) and
+    # 1848 (all) -- past the 1024 entries that one round of the one-workgroup scan takes, neither a multiple of it.  Bands of rows against the
+    # same bands one row lower (TP, FN and FP in every column, one band across the word edge 63 | 64, one in the single row of the ragged
+    # fifth word), and a second pair whose boxes overlap the bands (the mixed codes)
+    h2, w2 = 257, 13500
+    g2, q2 = np.zeros((h2, w2), bool), np.zeros((h2, w2), bool)
+    for a, b in ((0, 2), (62, 66), (100, 128), (200, 202), (255, 257)):
+        g2[a:b, :] = True
+        q2[a + 1:b + 1, :] = True
+    c["two_round_scan"] = case([g2, rect(h2, w2, 90, 140, 3000, 9000)], [q2, rect(h2, w2, 110, 210, 5000, 12000)], [(0, 0), (1, 1)], (h2, w2))
     return c
 
 
 HAND = ("all_codes_8x8", "first_pixel", "last_pixel", "full_columns", "full_image", "w1", "h1", "one_pixel_image", "h63_seam", "h64_seam",
-        "h65_seam", "h129_seam", "no_pairs", "identical", "disjoint", "two_gt_one_pred", "pair_twice", "pairs_64_same_words", "empty_in_pair")
+        "h65_seam", "h129_seam", "no_pairs", "identical", "disjoint", "two_gt_one_pred", "pair_twice", "pairs_64_same_words", "empty_in_pair",
+        "two_round_scan")
 N_SEEDED = 200
 
 
