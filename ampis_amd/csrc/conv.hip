@@ -16,16 +16,15 @@
 // or nearest-x2-upsampled for the FPN top-down path), optional ReLU, optional ConvTranspose2x2 scatter.
 #include "common.h"
 #include <type_traits>
+#include "lds_ring.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-constexpr float LO_SCALE = 2048.0f;      // AMP_CONV_F16X3: lo' = (x - hi) * 2^11 (see conv_f16x3_kernel)
 
 constexpr int BK = 32;      // K-slice per step (floats)
 constexpr int LDS_LD = 36;  // padded row length in LDS (floats): 144 B rows -> conflict-free ds_read_b128
@@ -73,6 +72,14 @@ struct ConvArgs {
 
 __device__ __forceinline__ unsigned int fastdiv(unsigned int x, unsigned int mul, int shr) {
     return (unsigned int)(((unsigned long long)x * mul) >> shr);
+}
+
+// GEMM row m -> output pixel (image b, row oy, column ox) through the two multiply-shift divisions conv_run prepared
+__device__ __forceinline__ void conv_pixel(const ConvArgs& a, unsigned int m, unsigned int& b, unsigned int& oy, unsigned int& ox) {
+    b = fastdiv(m, a.div_howo_mul, a.div_howo_shr);
+    const unsigned int rem = m - b * (unsigned int)(a.Ho * a.Wo);
+    oy = fastdiv(rem, a.div_wo_mul, a.div_wo_shr);
+    ox = rem - oy * (unsigned int)a.Wo;
 }
 
 // Epilogue shared by both kernels: accumulators -> LDS (per-wave tile, [m][n]) -> row-wise float4 residual loads + stores.
@@ -214,7 +221,7 @@ __device__ __forceinline__ void conv_epilogue_generic_rows(const ConvArgs& a, fl
             const f16x4 mh = *reinterpret_cast<const f16x4*>(mb);
             const f16x4 ml = *reinterpret_cast<const f16x4*>(mb + 64);
 #pragma unroll
-            for (int q = 0; q < 4; ++q) o[q] = __fadd_rn((float)mh[q], __fmul_rn((float)ml[q], 1.0f / LO_SCALE)) > 0.f ? o[q] : 0.f;
+            for (int q = 0; q < 4; ++q) o[q] = fold((float)mh[q], (float)ml[q]) > 0.f ? o[q] : 0.f;
         } else if (a.mask) {
             if (vec) {
                 const f32x4 mk = *reinterpret_cast<const f32x4*>(a.mask + yoff[it]);
@@ -374,10 +381,8 @@ __device__ __forceinline__ void conv_epilogue_rows8(const ConvArgs& a, float* st
             yrow[t] = (size_t)m * a.Cout;
             rrow[t] = yrow[t];
             if (SPATIAL && a.res_mode == 2) {
-                const unsigned int b = fastdiv(m, a.div_howo_mul, a.div_howo_shr);
-                const unsigned int rem = m - b * (unsigned int)(a.Ho * a.Wo);
-                const unsigned int oy = fastdiv(rem, a.div_wo_mul, a.div_wo_shr);
-                const unsigned int ox = rem - oy * (unsigned int)a.Wo;
+                unsigned int b, oy, ox;
+                conv_pixel(a, m, b, oy, ox);
                 rrow[t] = ((size_t)(b * (a.Ho >> 1) + (oy >> 1)) * (a.Wo >> 1) + (ox >> 1)) * a.Cout;
             }
         }
@@ -412,7 +417,7 @@ __device__ __forceinline__ void conv_epilogue_rows8(const ConvArgs& a, float* st
                     float r;
                     if (a.res_split) {
                         const f16x8 rh = __builtin_bit_cast(f16x8, r0[t]), rl = __builtin_bit_cast(f16x8, r1[t]);
-                        r = __fadd_rn((float)rh[q], __fmul_rn((float)rl[q], 1.0f / LO_SCALE));
+                        r = fold((float)rh[q], (float)rl[q]);
                     } else {
                         r = q < 4 ? r0[t][q] : r1[t][q - 4];
                     }
@@ -504,10 +509,8 @@ __device__ __forceinline__ void conv_epilogue_direct_rows(const ConvArgs& a, f32
             const unsigned int m = min((unsigned int)mrow_in[i], (unsigned int)(a.M - 1));
             size_t rrow = (size_t)m * a.Cout;
             if (SPATIAL && a.res_mode == 2) {
-                const unsigned int b = fastdiv(m, a.div_howo_mul, a.div_howo_shr);
-                const unsigned int rem = m - b * (unsigned int)(a.Ho * a.Wo);
-                const unsigned int oy = fastdiv(rem, a.div_wo_mul, a.div_wo_shr);
-                const unsigned int ox = rem - oy * (unsigned int)a.Wo;
+                unsigned int b, oy, ox;
+                conv_pixel(a, m, b, oy, ox);
                 rrow = ((size_t)(b * (a.Ho >> 1) + (oy >> 1)) * (a.Wo >> 1) + (ox >> 1)) * a.Cout;
             }
 #pragma unroll
@@ -544,10 +547,8 @@ __device__ __forceinline__ void conv_epilogue_direct_rows(const ConvArgs& a, f32
         const unsigned int m = min((unsigned int)mrow, (unsigned int)(a.M - 1));
         size_t yrow = (size_t)m * a.Cout;
         if (deconv) {
-            const unsigned int b = fastdiv(m, a.div_howo_mul, a.div_howo_shr);
-            const unsigned int rem = m - b * (unsigned int)(a.Ho * a.Wo);
-            const unsigned int oy = fastdiv(rem, a.div_wo_mul, a.div_wo_shr);
-            const unsigned int ox = rem - oy * (unsigned int)a.Wo;
+            unsigned int b, oy, ox;
+            conv_pixel(a, m, b, oy, ox);
             yrow = (((size_t)b * 2 * a.Ho + 2 * oy + (tap >> 1)) * (2 * a.Wo) + 2 * ox + (tap & 1)) * (size_t)yld;
         }
         f16x8 rh[2], rl[2], mh[2], ml[2];
@@ -656,10 +657,8 @@ __device__ __forceinline__ void conv_epilogue_rows(const ConvArgs& a, float* sta
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             const unsigned int m = min((unsigned int)(mw0 + it * RPI + erow), (unsigned int)(a.M - 1));   // clamped rows are never stored
-            const unsigned int b = fastdiv(m, a.div_howo_mul, a.div_howo_shr);
-            const unsigned int rem = m - b * (unsigned int)(a.Ho * a.Wo);
-            const unsigned int oy = fastdiv(rem, a.div_wo_mul, a.div_wo_shr);
-            const unsigned int ox = rem - oy * (unsigned int)a.Wo;
+            unsigned int b, oy, ox;
+            conv_pixel(a, m, b, oy, ox);
             roff[it] = (a.res_mode == 2) ? ((size_t)(b * (a.Ho >> 1) + (oy >> 1)) * (a.Wo >> 1) + (ox >> 1)) * a.Cout + n
                                          : (size_t)m * a.Cout + n;
             if (a.out_mode == 1) {
@@ -689,7 +688,7 @@ __device__ __forceinline__ void conv_epilogue_rows(const ConvArgs& a, float* sta
                     const f16x4 rh = *reinterpret_cast<const f16x4*>(rb);
                     const f16x4 rl = *reinterpret_cast<const f16x4*>(rb + 64);
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) rres[it][q] = __fadd_rn((float)rh[q], __fmul_rn((float)rl[q], 1.0f / LO_SCALE));
+                    for (int q = 0; q < 4; ++q) rres[it][q] = fold((float)rh[q], (float)rl[q]);
                 }
         } else if (has_res) {
 #pragma unroll
@@ -706,7 +705,7 @@ __device__ __forceinline__ void conv_epilogue_rows(const ConvArgs& a, float* sta
                     const f16x4 mh = *reinterpret_cast<const f16x4*>(mb);
                     const f16x4 ml = *reinterpret_cast<const f16x4*>(mb + 64);
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) mk[it][q] = __fadd_rn((float)mh[q], __fmul_rn((float)ml[q], 1.0f / LO_SCALE));
+                    for (int q = 0; q < 4; ++q) mk[it][q] = fold((float)mh[q], (float)ml[q]);
                 }
         } else if (has_mask) {
 #pragma unroll
@@ -912,8 +911,6 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvArgs a) {
 // XOR swizzle applied to the per-lane SOURCE chunk and again on the fragment reads (chunk ^ ((row >> 1) & 7):
 // conflict-free for the 16-lane groups of ds_read_b128).
 // ------------------------------------------------------------------------------------------------------------------
-constexpr unsigned int OOB_VOFF = 0x80000000u;   // >= num_records of every buffer this kernel accepts (< 2 GiB)
-
 // STEM = true: the 7x7 stride-2 stem on the [B,H,W,4] input with weights [64][7][8][4]: a K-step is one kernel row ky, whose
 // 8 taps x 4 channels are 128 contiguous bytes; the 16-B chunk index IS the tap kx, so validity is per chunk.
 // EPI: 0 = generic epilogue (any Cout), 1 = fast (Cout % 4 == 0, out_mode 0, res_mode 0/1), 2 = fast with per-row (b,oy,ox).
@@ -961,16 +958,16 @@ __global__ __launch_bounds__(BN == 256 ? 512 : 256, BN == 256 ? 1 : 2) void conv
     const int n0 = tile_n * BN;
     const int HoWo = a.Ho * a.Wo;
 
-    const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_x = buffer_rsrc(a.x, x_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_w = buffer_rsrc(a.w, w_bytes);
 
     // ---- staging geometry: instruction g of this wave fills rows wave*R + 8g + (lane>>3), 16-B position lane&7 ----
-    const int srow = lane >> 3, spos = lane & 7;
+    const int srow = dma_row(lane), spos = dma_pos(lane);
     int a_iy0[GA], a_ix0[GA], a_pb[GA], a_chunk[GA];
 #pragma unroll
     for (int g = 0; g < GA; ++g) {
         const int r = wave * (BM / NW) + 8 * g + srow;
-        a_chunk[g] = 4 * (spos ^ ((r >> 1) & 7));      // source chunk (floats) = 4 * (pos ^ swz(row))
+        a_chunk[g] = dma_chunk(spos, r);      // source chunk (floats) = 4 * (pos ^ swz(row))
         const int m = m0 + r;
         if (m < a.M) {
             const int b = m / HoWo;
@@ -991,7 +988,7 @@ __global__ __launch_bounds__(BN == 256 ? 512 : 256, BN == 256 ? 1 : 2) void conv
     for (int g = 0; g < GB; ++g) {
         const int r = wave * (BN / NW) + 8 * g + srow;
         const int n = n0 + r;
-        b_voff[g] = (n < a.Cout) ? (unsigned int)(((size_t)n * a.K + (G32 ? 32 * ((n >> 5) & 1) : 0) + 4 * (spos ^ ((r >> 1) & 7))) * 4) : OOB_VOFF;
+        b_voff[g] = (n < a.Cout) ? (unsigned int)(((size_t)n * a.K + (G32 ? 32 * ((n >> 5) & 1) : 0) + dma_chunk(spos, r)) * 4) : OOB_VOFF;
     }
     unsigned int a_voff[GA];              // byte offset of the input pixel of the current tap (+ swizzled chunk), or OOB
 
@@ -1060,23 +1057,15 @@ __global__ __launch_bounds__(BN == 256 ? 512 : 256, BN == 256 ? 1 : 2) void conv
 
     if constexpr (RING) {
         constexpr int NDMA = NPL * GA + GB;     // LDS-DMA requests of this wave per tile
-        static_assert(NDMA < 16, "vmcnt immediate");
         stage(0);
         if (nsteps > 1) stage(1);
         int cur = 0, nxt = 2;
         for (int step = 0; step < nsteps; ++step) {
-            // tile `step` has landed once all but the youngest tile's requests of this wave are done (in-order vmcnt); bare s_barrier: the
-            // fence of __syncthreads() would wait for vmcnt(0), i.e. for the tile the ring keeps in flight (see conv_split_kernel)
-            if (step + 1 < nsteps) __builtin_amdgcn_s_waitcnt(0x0070 | NDMA);
-            else __builtin_amdgcn_s_waitcnt(0x0070);
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_s_barrier();       // every wave's share of tile `step` is in LDS; everyone is done with tile step-1
-            asm volatile("" ::: "memory");
+            ring_open<NDMA>(step + 1 < nsteps);
             if (step + 2 < nsteps) stage(nxt);  // into the buffer tile step-1 occupied
             f16x3_step16<MB, NB>(lds + cur * TILE_FLOATS + (G32 ? wn * BM * BK : 0) + (wm * WTM + l15) * BK,
                                  lds + cur * TILE_FLOATS + NPL * BM * BK + (wn * WTN + l15) * BK, fo16_hi, fo16_lo, acc16, acx16);
-            cur = (cur == 2) ? 0 : cur + 1;
-            nxt = (nxt == 2) ? 0 : nxt + 1;
+            ring_next<3>(cur, nxt);
         }
         __syncthreads();                        // all operand reads done: the epilogue re-uses the buffers as its staging tile
     } else {
@@ -1121,8 +1110,7 @@ __global__ __launch_bounds__(BN == 256 ? 512 : 256, BN == 256 ? 1 : 2) void conv
 #pragma unroll
             for (int j = 0; j < NB; ++j)
 #pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    acc16[i][j][e] = __fadd_rn(acc16[i][j][e], __fmul_rn(acx16[i][j][e], 1.0f / LO_SCALE));
+                for (int e = 0; e < 4; ++e) acc16[i][j][e] = fold(acc16[i][j][e], acx16[i][j][e]);
         if (EPI == 0) conv_epilogue16<WTM, WTN, MB, NB, true>(a, acc16, lds, wave, lane, m0 + wm * WTM, n0 + wn * WTN, HoWo);
         else conv_epilogue_fast16<WTM, WTN, MB, NB, EPI == 2, true>(a, acc16, lds, wave, lane, m0 + wm * WTM, n0 + wn * WTN);
     } else {
@@ -1209,10 +1197,8 @@ __device__ __forceinline__ void conv_epilogue_predict(const ConvArgs& a, f32x4 (
         const int rl = wm * WTM + lane;
         const int m = m0 + rl;
         if (m < a.M) {
-            const unsigned int b = fastdiv((unsigned int)m, a.div_howo_mul, a.div_howo_shr);
-            const unsigned int rem = (unsigned int)m - b * (unsigned int)(a.Ho * a.Wo);
-            const unsigned int oy = fastdiv(rem, a.div_wo_mul, a.div_wo_shr);
-            const unsigned int ox = rem - oy * (unsigned int)a.Wo;
+            unsigned int b, oy, ox;
+            conv_pixel(a, (unsigned int)m, b, oy, ox);
             float x = __fadd_rn(__fadd_rn(__fadd_rn(red[rl], red[128 + rl]), red[256 + rl]), red[384 + rl]);
             x = __fadd_rn(x, (b == pf.b0) ? pf.pb0 : pf.pb1);
             const float p = __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-x)));
@@ -1284,7 +1270,7 @@ __device__ __forceinline__ void conv_epilogue_rpn_rows(const ConvArgs& a, f32x4 
                 d = __builtin_amdgcn_mfma_f32_16x16x32_f16(hi, wh[g], d, 0, 0, 0);
             }
 #pragma unroll
-            for (int e = 0; e < 4; ++e) d[e] = __fadd_rn(d[e], __fmul_rn(dx[e], 1.0f / LO_SCALE));
+            for (int e = 0; e < 4; ++e) d[e] = fold(d[e], dx[e]);
             red[((wm * 4 + wn) * 4 + i) * 64 + lane] = d;
         }
         if (j == 0) { if (!(chk[0] == 0.f) || !(chk[1] == 0.f)) atomicOr(a.range_flag, 1); }
@@ -1372,22 +1358,20 @@ __global__ __launch_bounds__((BM / 64) * (BN / 64) * 64, NSTAGE == 2 ? 2 : 1) vo
     const int m0 = tile_m * BM;
     const int n0 = tile_n * BN;
 
-    const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_x = buffer_rsrc(a.x, x_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_w = buffer_rsrc(a.w, w_bytes);
 
     // ---- staging geometry (as conv_glds_kernel): instruction g of this wave fills rows wave*R + 8g + (lane>>3), 16-B position lane&7 ----
-    const int srow = lane >> 3, spos = lane & 7;
+    const int srow = dma_row(lane), spos = dma_pos(lane);
     int a_iy0[GA], a_ix0[GA], a_pb[GA], a_chunk[GA];
 #pragma unroll
     for (int g = 0; g < GA; ++g) {
         const int r = wave * (BM / NW) + 8 * g + srow;
-        a_chunk[g] = 4 * (spos ^ ((r >> 1) & 7));
+        a_chunk[g] = dma_chunk(spos, r);
         const int m = m0 + r;
         if (m < a.M) {
-            const unsigned int b = fastdiv((unsigned int)m, a.div_howo_mul, a.div_howo_shr);
-            const unsigned int rem = (unsigned int)m - b * (unsigned int)(a.Ho * a.Wo);
-            const unsigned int oy = fastdiv(rem, a.div_wo_mul, a.div_wo_shr);
-            const unsigned int ox = rem - oy * (unsigned int)a.Wo;
+            unsigned int b, oy, ox;
+            conv_pixel(a, (unsigned int)m, b, oy, ox);
             a_iy0[g] = (int)oy * a.stride - a.pad;
             a_ix0[g] = (int)ox * a.stride - a.pad;
             a_pb[g] = (int)b * a.H * a.W;
@@ -1402,7 +1386,7 @@ __global__ __launch_bounds__((BM / 64) * (BN / 64) * 64, NSTAGE == 2 ? 2 : 1) vo
     for (int g = 0; g < GB; ++g) {
         const int r = wave * (BN / NW) + 8 * g + srow;               // LDS row; its weight row follows swap_channel (see conv_epilogue_direct)
         const int n = n0 + (r & ~63) + swap_channel(r & 63);
-        b_voff[g] = (n < a.Cout) ? (unsigned int)(((size_t)n * a.K + 4 * (spos ^ ((r >> 1) & 7))) * 4) : OOB_VOFF;
+        b_voff[g] = (n < a.Cout) ? (unsigned int)(((size_t)n * a.K + dma_chunk(spos, r)) * 4) : OOB_VOFF;
     }
     unsigned int a_voff[GA];
 
@@ -1466,23 +1450,9 @@ __global__ __launch_bounds__((BM / 64) * (BN / 64) * 64, NSTAGE == 2 ? 2 : 1) vo
         if (NBP == 1 && a.out_mode == 3) ppf = predict_prefetch(a, wave, lane, m0);
     }
     int cur = 0, nxt = 2;                      // ring positions of the tile being computed / staged
-    auto open_step = [&](int step) {
-        // tile `step` has landed once all but the youngest tile's requests of this wave are done (LDS-DMA counts in vmcnt, in order);
-        // lgkmcnt(0): this wave's fragment reads of tile step-1 have returned (the staggered half issues them last in its step)
-        if (step + 1 < a.nsteps) __builtin_amdgcn_s_waitcnt(0x0070 | NDMA);
-        else __builtin_amdgcn_s_waitcnt(0x0070);
-        // Bare s_barrier: __syncthreads() is fence + barrier, and the workgroup-release fence waits for vmcnt(0) -- it would drain the
-        // very requests this ring keeps in flight.  Nothing a fence orders is needed here: the tiles are written by LDS-DMA (covered by
-        // the vmcnt above) and read by ds_read whose data has returned (lgkmcnt above).  The empty asm statements keep the compiler
-        // from moving LDS accesses across the barrier.
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_barrier();          // every wave's share of tile `step` is in LDS; everyone is done with tile step-1
-        asm volatile("" ::: "memory");
-    };
-    auto advance = [&]() {
-        cur = (cur == NSTAGE - 1) ? 0 : cur + 1;
-        nxt = (nxt == NSTAGE - 1) ? 0 : nxt + 1;
-    };
+    // (lgkmcnt(0) in ring_open: the staggered half issues its fragment reads of tile step-1 last in its step)
+    auto open_step = [&](int step) { ring_open<NDMA>(step + 1 < a.nsteps); };
+    auto advance = [&]() { ring_next<NSTAGE>(cur, nxt); };
     // Ping-pong between the two waves of a SIMD (MI355X_MICROARCH.md, "Two waves per SIMD"): waves w and w + NW/2 share a SIMD, and run
     // in lockstep they first both issue LDS-DMA and fragment reads (matrix pipe idle) and then both issue MFMAs (pipe contended) -- the
     // in-kernel stamps (tools/stamp_conv.py) gave 2400-2540 cycles per K-step against 1536 of MFMA work.  So the second half of the
@@ -1512,9 +1482,7 @@ __global__ __launch_bounds__((BM / 64) * (BN / 64) * 64, NSTAGE == 2 ? 2 : 1) vo
                 // two buffers: tile step+2 goes into the buffer of tile `step` itself, once every wave holds its fragments in registers
                 if (step + 2 < a.nsteps) {
                     __builtin_amdgcn_s_waitcnt(0xc07f);          // lgkmcnt(0): this wave's fragment reads have returned
-                    asm volatile("" ::: "memory");
-                    __builtin_amdgcn_s_barrier();
-                    asm volatile("" ::: "memory");
+                    ring_barrier();
                     stage(cur);
                 }
             } else
@@ -1573,7 +1541,7 @@ __global__ __launch_bounds__((BM / 64) * (BN / 64) * 64, NSTAGE == 2 ? 2 : 1) vo
         for (int j = 0; j < NB; ++j)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                acc[i][j][e] = __fadd_rn(acc[i][j][e], __fmul_rn(acx[i][j][e], 1.0f / LO_SCALE));
+                acc[i][j][e] = fold(acc[i][j][e], acx[i][j][e]);
                 if (scaled_in) acc[i][j][e] *= a.out_scale;      // x arrived as split rows of x * 2^shift (a scaled loss gradient): exact power of two
             }
     if constexpr (BM == 128 && BN == 256 && EPI == 3) {          // the fused tails have an instantiation of their own: no row epilogue, no spills
@@ -1618,21 +1586,21 @@ __global__ __launch_bounds__(512, 1) void mask_tail_kernel(const ConvArgs a, con
     const int wm = wave >> 2, wn = wave & 3;
     const int l15 = lane & 15, lq = lane >> 4;
     const int m0 = amp::xcd_remap(blockIdx.x, a.nblk) * BM;
-    const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, w_bytes, 0x00020000);
-    const int srow = lane >> 3, spos = lane & 7;
+    const __amdgpu_buffer_rsrc_t rsrc_x = buffer_rsrc(a.x, x_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_w = buffer_rsrc(a.w, w_bytes);
+    const int srow = dma_row(lane), spos = dma_pos(lane);
     unsigned int a_voff[GA], b_voff[GB];
 #pragma unroll
     for (int g = 0; g < GA; ++g) {
         const int r = wave * (BM / NW) + 8 * g + srow;
         const int m = m0 + r;
-        a_voff[g] = (m < a.M) ? (unsigned int)(((size_t)m * a.Cin + 4 * (spos ^ ((r >> 1) & 7))) * 4) : OOB_VOFF;
+        a_voff[g] = (m < a.M) ? (unsigned int)(((size_t)m * a.Cin + dma_chunk(spos, r)) * 4) : OOB_VOFF;
     }
 #pragma unroll
     for (int g = 0; g < GB; ++g) {
         const int r = wave * (BN / NW) + 8 * g + srow;
         const int n = (r & ~63) + swap_channel(r & 63);
-        b_voff[g] = (unsigned int)(((size_t)n * a.K + 4 * (spos ^ ((r >> 1) & 7))) * 4);
+        b_voff[g] = (unsigned int)(((size_t)n * a.K + dma_chunk(spos, r)) * 4);
     }
     const int csteps = a.Cin / BK;                 // K-steps per tap (8)
     const int total = NTAP * csteps;
@@ -1652,15 +1620,7 @@ __global__ __launch_bounds__(512, 1) void mask_tail_kernel(const ConvArgs a, con
         if (++s_cs == csteps) { s_cs = 0; ++s_tap; }
     };
     f32x4 acc[4][4], acx[4][4];
-    auto zero_acc = [&]() {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { acc[i][j][e] = 0.f; acx[i][j][e] = 0.f; }
-    };
-    zero_acc();
+    zero_acc(acc, acx);
     const int fo16_hi = 4 * (lq ^ (l15 >> 1)), fo16_lo = 4 * ((4 + lq) ^ (l15 >> 1));
     stage(0);
     stage(1);
@@ -1696,7 +1656,7 @@ __global__ __launch_bounds__(512, 1) void mask_tail_kernel(const ConvArgs a, con
                 float sg = 0.f;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float v = __fadd_rn(acc[i][j][e], __fmul_rn(acx[i][j][e], 1.0f / LO_SCALE));
+                    const float v = fold(acc[i][j][e], acx[i][j][e]);
                     bad = bad || !(fabsf(v) <= 3.0e38f);
                     const float o = fmaxf(__fadd_rn(v, bias[j][e]), 0.f);
                     sg = __fadd_rn(sg, __fmul_rn(o, wp[e]));
@@ -1715,10 +1675,8 @@ __global__ __launch_bounds__(512, 1) void mask_tail_kernel(const ConvArgs a, con
         const int rl = wm * 64 + lane;
         const int m = m0 + rl;
         if (m < a.M) {
-            const unsigned int b = fastdiv((unsigned int)m, a.div_howo_mul, a.div_howo_shr);
-            const unsigned int rem = (unsigned int)m - b * (unsigned int)(a.Ho * a.Wo);
-            const unsigned int oy = fastdiv(rem, a.div_wo_mul, a.div_wo_shr);
-            const unsigned int ox = rem - oy * (unsigned int)a.Wo;
+            unsigned int b, oy, ox;
+            conv_pixel(a, (unsigned int)m, b, oy, ox);
             float x = __fadd_rn(__fadd_rn(__fadd_rn(red[rl], red[BM + rl]), red[2 * BM + rl]), red[3 * BM + rl]);
             x = __fadd_rn(x, pbs[(b == b_first) ? 0 : 1]);
             const float p = __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-x)));
@@ -1726,16 +1684,9 @@ __global__ __launch_bounds__(512, 1) void mask_tail_kernel(const ConvArgs a, con
         }
     };
     int cur = 0, nxt = 2, c_cs = 0, c_tap = 0;      // ring positions; the step being COMPUTED
-    auto open_step = [&](int step) {
-        if (step + 1 < total) __builtin_amdgcn_s_waitcnt(0x0070 | NDMA);
-        else __builtin_amdgcn_s_waitcnt(0x0070);
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    };
+    auto open_step = [&](int step) { ring_open<NDMA>(step + 1 < total); };
     auto advance = [&]() {
-        cur = (cur == 2) ? 0 : cur + 1;
-        nxt = (nxt == 2) ? 0 : nxt + 1;
+        ring_next<3>(cur, nxt);
         if (++c_cs == csteps) { c_cs = 0; ++c_tap; }
     };
     F16x3Frags<4, 4> fr;
@@ -1754,7 +1705,7 @@ __global__ __launch_bounds__(512, 1) void mask_tail_kernel(const ConvArgs a, con
             f16x3_mfma16<4, 4, true>(fr, acc, acx);
             __builtin_amdgcn_s_setprio(0);
             __builtin_amdgcn_sched_barrier(0);
-            if (c_cs == csteps - 1) { partial_sums(c_tap); zero_acc(); }
+            if (c_cs == csteps - 1) { partial_sums(c_tap); zero_acc(acc, acx); }
             advance();
         }
     } else {
@@ -1765,7 +1716,7 @@ __global__ __launch_bounds__(512, 1) void mask_tail_kernel(const ConvArgs a, con
             __builtin_amdgcn_s_setprio(0);
             __builtin_amdgcn_sched_barrier(0);
             const bool tap_done = c_cs == 0 && c_tap > 0;                         // the MFMAs above finished tap c_tap - 1
-            if (tap_done) { partial_sums(c_tap - 1); zero_acc(); __builtin_amdgcn_s_waitcnt(0xc07f); }
+            if (tap_done) { partial_sums(c_tap - 1); zero_acc(acc, acx); __builtin_amdgcn_s_waitcnt(0xc07f); }
             __builtin_amdgcn_s_barrier();
             if (tap_done && wn == 0) finish_rows(c_tap - 1);
             f16x3_load16<4, 4>(As0 + cur * TILE_FLOATS, Bs0 + cur * TILE_FLOATS, fo16_hi, fo16_lo, fr);
@@ -1814,9 +1765,9 @@ __global__ __launch_bounds__(512, 1) void conv1x1_nloop_kernel(const ConvArgs a,
     const int m0 = (wg / ngrp) * BM;
     const int n_first = grp * NT * BN;
     const bool full = m0 + BM <= a.M;
-    const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, w_bytes, 0x00020000);
-    const int srow = lane >> 3, spos = lane & 7;
+    const __amdgpu_buffer_rsrc_t rsrc_x = buffer_rsrc(a.x, x_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_w = buffer_rsrc(a.w, w_bytes);
+    const int srow = dma_row(lane), spos = dma_pos(lane);
     unsigned int a_voff[GA], b_voff[GB];
 #pragma unroll
     for (int g = 0; g < GA; ++g) {
@@ -1824,18 +1775,16 @@ __global__ __launch_bounds__(512, 1) void conv1x1_nloop_kernel(const ConvArgs a,
         const int m = m0 + r;
         a_voff[g] = OOB_VOFF;
         if (m < a.M) {                             // 1x1, pad 0: output pixel (b, oy, ox) reads input pixel (oy, ox) * stride
-            const unsigned int b = fastdiv((unsigned int)m, a.div_howo_mul, a.div_howo_shr);
-            const unsigned int rem = (unsigned int)m - b * (unsigned int)(a.Ho * a.Wo);
-            const unsigned int oy = fastdiv(rem, a.div_wo_mul, a.div_wo_shr);
-            const unsigned int ox = rem - oy * (unsigned int)a.Wo;
-            a_voff[g] = (unsigned int)((((size_t)(b * a.H + oy * a.stride) * a.W + ox * a.stride) * a.Cin + 4 * (spos ^ ((r >> 1) & 7))) * 4);
+            unsigned int b, oy, ox;
+            conv_pixel(a, (unsigned int)m, b, oy, ox);
+            a_voff[g] = (unsigned int)((((size_t)(b * a.H + oy * a.stride) * a.W + ox * a.stride) * a.Cin + dma_chunk(spos, r)) * 4);
         }
     }
 #pragma unroll
     for (int g = 0; g < GB; ++g) {
         const int r = wave * (BN / NW) + 8 * g + srow;
         const int n = n_first + (r & ~63) + swap_channel(r & 63);
-        b_voff[g] = (unsigned int)(((size_t)n * a.K + 4 * (spos ^ ((r >> 1) & 7))) * 4);
+        b_voff[g] = (unsigned int)(((size_t)n * a.K + dma_chunk(spos, r)) * 4);
     }
     const int csteps = a.Cin / BK;                 // K-steps per tile
     const int total = NT * csteps;
@@ -1855,15 +1804,7 @@ __global__ __launch_bounds__(512, 1) void conv1x1_nloop_kernel(const ConvArgs a,
         if (++s_cs == csteps) { s_cs = 0; ++s_tile; }
     };
     f32x4 acc[4][4], acx[4][4];
-    auto zero_acc = [&]() {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { acc[i][j][e] = 0.f; acx[i][j][e] = 0.f; }
-    };
-    zero_acc();
+    zero_acc(acc, acx);
     const int fo16_hi = 4 * (lq ^ (l15 >> 1)), fo16_lo = 4 * ((4 + lq) ^ (l15 >> 1));
     stage(0);
     stage(1);
@@ -1881,7 +1822,7 @@ __global__ __launch_bounds__(512, 1) void conv1x1_nloop_kernel(const ConvArgs a,
             for (int j = 0; j < 4; ++j)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    acc[i][j][e] = __fadd_rn(acc[i][j][e], __fmul_rn(acx[i][j][e], 1.0f / LO_SCALE));
+                    acc[i][j][e] = fold(acc[i][j][e], acx[i][j][e]);
                     if (scaled_in) acc[i][j][e] *= a.out_scale;
                 }
         // one 16-row block at a time: the loop's state stays live across this epilogue, and two blocks' hoisted residual / mask rows beside it spill
@@ -1899,13 +1840,10 @@ __global__ __launch_bounds__(512, 1) void conv1x1_nloop_kernel(const ConvArgs a,
         if (step + 1 >= total) __builtin_amdgcn_s_waitcnt(0x0070);
         else if (behind_epilogue) __builtin_amdgcn_s_waitcnt(0x0070 | ((NDMA + NST) & 15) | (((NDMA + NST) >> 4) << 14));
         else __builtin_amdgcn_s_waitcnt(0x0070 | NDMA);
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        ring_barrier();
     };
     auto advance = [&]() {
-        cur = (cur == 2) ? 0 : cur + 1;
-        nxt = (nxt == 2) ? 0 : nxt + 1;
+        ring_next<3>(cur, nxt);
         if (++c_cs == csteps) { c_cs = 0; ++c_tile; }
     };
     F16x3Frags<4, 4> fr;
@@ -1923,7 +1861,7 @@ __global__ __launch_bounds__(512, 1) void conv1x1_nloop_kernel(const ConvArgs a,
             f16x3_mfma16<4, 4, true>(fr, acc, acx);
             __builtin_amdgcn_s_setprio(0);
             __builtin_amdgcn_sched_barrier(0);
-            if (c_cs == csteps - 1) { tile_epilogue(c_tile); zero_acc(); __builtin_amdgcn_sched_barrier(0); }
+            if (c_cs == csteps - 1) { tile_epilogue(c_tile); zero_acc(acc, acx); __builtin_amdgcn_sched_barrier(0); }
             advance();
         }
     } else {
@@ -1933,7 +1871,7 @@ __global__ __launch_bounds__(512, 1) void conv1x1_nloop_kernel(const ConvArgs a,
             if (step > 0) f16x3_mfma16<4, 4, true>(fr, acc, acx);
             __builtin_amdgcn_s_setprio(0);
             __builtin_amdgcn_sched_barrier(0);
-            if (c_cs == 0 && c_tile > 0) { tile_epilogue(c_tile - 1); zero_acc(); __builtin_amdgcn_sched_barrier(0); }      // the MFMAs above finished tile c_tile - 1
+            if (c_cs == 0 && c_tile > 0) { tile_epilogue(c_tile - 1); zero_acc(acc, acx); __builtin_amdgcn_sched_barrier(0); }      // the MFMAs above finished tile c_tile - 1
             __builtin_amdgcn_s_barrier();
             f16x3_load16<4, 4>(As0 + cur * TILE_FLOATS, Bs0 + cur * TILE_FLOATS, fo16_hi, fo16_lo, fr);
             __builtin_amdgcn_sched_barrier(0);
@@ -1983,9 +1921,9 @@ __global__ __launch_bounds__(512, 1) void conv3x3_patch_kernel(const ConvArgs a,
     const int ty = t % tiles_y;
     const int b = t / tiles_y;
     const int oy0 = ty * TH, ox0 = tx * TW, n0 = tile_n * 256;
-    const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, w_bytes, 0x00020000);
-    const int srow = lane >> 3, spos = lane & 7;      // weight DMA: lane = (row of 8, 16-B position)
+    const __amdgpu_buffer_rsrc_t rsrc_x = buffer_rsrc(a.x, x_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_w = buffer_rsrc(a.w, w_bytes);
+    const int srow = dma_row(lane), spos = dma_pos(lane);      // weight DMA: lane = (row of 8, 16-B position)
     // ---- patch layout in LDS: CHUNK-MAJOR -- the 16-B piece p (0..7: hi 0-7, .., hi 24-31, lo' 0-7, ..) of patch pixel q at p * 3072 + q * 16 bytes
     // (192 pixel slots per plane).  The 16 consecutive pixels a lane group reads for one fragment are then 256 contiguous bytes -- every bank once,
     // whatever the alignment of the first pixel -- and a lane's address is (its own base) + (tap, tile row) * constant: the nine taps and four tile
@@ -2009,7 +1947,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_patch_kernel(const ConvArgs a,
     for (int g = 0; g < GB; ++g) {
         const int r = wave * 32 + 8 * g + srow;
         const int n = n0 + (r & ~63) + swap_channel(r & 63);
-        b_voff[g] = (n < a.Cout) ? (unsigned int)(((size_t)n * a.K + 4 * (spos ^ ((r >> 1) & 7))) * 4) : OOB_VOFF;
+        b_voff[g] = (n < a.Cout) ? (unsigned int)(((size_t)n * a.K + dma_chunk(spos, r)) * 4) : OOB_VOFF;
     }
     const int csteps = a.Cin / BK;
     int s_c = 0, s_tap = 0;                  // the step being STAGED
@@ -2054,9 +1992,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_patch_kernel(const ConvArgs a,
 #ifdef AMP_STAMP
         st_vm = clock64();
 #endif
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        ring_barrier();
     };
     F16x3Frags<4, 4> fr;
     const float* Pl = patch + qb * 4 + lq * 768;
@@ -2079,8 +2015,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_patch_kernel(const ConvArgs a,
         if (c_tap < 3 && c_c + 1 < csteps) stage_patch(c_tap, c_c + 1);
     };
     auto advance = [&]() {
-        cur = (cur == 2) ? 0 : cur + 1;
-        nxt = (nxt == 2) ? 0 : nxt + 1;
+        ring_next<3>(cur, nxt);
         ++c_tap; ++c_toff;
         if (c_tap == 3 || c_tap == 6) c_toff += PW - 3;
         if (c_tap == 9) { c_tap = 0; c_toff = 0; ++c_c; }
@@ -2160,7 +2095,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_patch_kernel(const ConvArgs a,
         for (int j = 0; j < 4; ++j)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                acc[i][j][e] = __fadd_rn(acc[i][j][e], __fmul_rn(acx[i][j][e], 1.0f / LO_SCALE));
+                acc[i][j][e] = fold(acc[i][j][e], acx[i][j][e]);
                 if (scaled_in) acc[i][j][e] *= a.out_scale;
             }
     const int oyw = oy0 + 4 * wm;
@@ -2241,8 +2176,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(const ConvArgs a, c
     const int b = t / tiles_y;
     const int oy0 = ty * TH, ox0 = tx * TW, n0 = tile_n * 64;
     const int cwin = a.grouped ? n0 : 0;                                            // first input channel of the window
-    const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_x = buffer_rsrc(a.x, x_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_w = buffer_rsrc(a.w, w_bytes);
     const int sub = lane >> 4, chunk = lane & 15;                                   // DMA: lane = (row sub of 4, 16-B chunk)
     // ---- the patch, once ----
     for (int it = wave; it < NINST; it += 4) {
@@ -2265,12 +2200,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(const ConvArgs a, c
     };
     stage_w(0, 0);
     f32x4 acc[2][4], acx[2][4];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { acc[i][j][e] = 0.f; acx[i][j][e] = 0.f; }
+    zero_acc(acc, acx);
     for (int tap = 0; tap < 9; ++tap) {
         __syncthreads();                        // (vmcnt(0) + barrier) the patch and this tap's weights have landed; everyone is done with the other weight buffer
         if (tap + 1 < 9) stage_w(tap + 1, (tap + 1) & 1);
@@ -2318,7 +2248,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(const ConvArgs a, c
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) acc[i][j][e] = __fadd_rn(acc[i][j][e], __fmul_rn(acx[i][j][e], 1.0f / LO_SCALE));
+            for (int e = 0; e < 4; ++e) acc[i][j][e] = fold(acc[i][j][e], acx[i][j][e]);
     int mrows[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -2361,7 +2291,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(const ConvArgs a, c
         if (!(chk[0] == 0.f) || !(chk[1] == 0.f)) atomicOr(a.range_flag, 1);
         // ---- conv3's weights: C3 rows x 256 B into the LDS of the patch + tap buffers (everyone is past its last tap) ----
         __syncthreads();
-        const __amdgpu_buffer_rsrc_t rsrc_w3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(f3.w3), 0, f3.w3_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsrc_w3 = buffer_rsrc(f3.w3, f3.w3_bytes);
         float* w3s = lds;
         const int ninst3 = f3.C3 / 4;                    // 4 rows per DMA instruction
         for (int it = wave; it < ninst3; it += 4) {
@@ -2376,12 +2306,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(const ConvArgs a, c
         a3.Cout = f3.C3; a3.relu = 1; a3.res_mode = 1; a3.res_split = 1; a3.y_split = 1; a3.out_mode = 0; a3.mask_split = 0;
         for (int c = 0; c < f3.C3 / 64; ++c) {
             f32x4 acc3[2][4], acx3[2][4];
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { acc3[i][j][e] = 0.f; acx3[i][j][e] = 0.f; }
+            zero_acc(acc3, acx3);
             const float* wc = w3s + c * 64 * ROWF;
 #pragma unroll
             for (int g = 0; g < 2; ++g) {
@@ -2401,7 +2326,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_kernel(const ConvArgs a, c
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) acc3[i][j][e] = __fadd_rn(acc3[i][j][e], __fmul_rn(acx3[i][j][e], 1.0f / LO_SCALE));
+                    for (int e = 0; e < 4; ++e) acc3[i][j][e] = fold(acc3[i][j][e], acx3[i][j][e]);
             conv_epilogue_direct_rows<false, true, 2>(a3, acc3, lane, mrows, 64 * c);
         }
     }
@@ -2467,8 +2392,8 @@ __global__ __launch_bounds__(BN == 256 ? 512 : 256, BN == 256 ? 1 : 2) void conv
     const int n0 = tile_n * BN;
     const int HoWo = a.Ho * a.Wo;
 
-    const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_x = buffer_rsrc(a.x, x_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_w = buffer_rsrc(a.w, w_bytes);
 
     // ---- A (activations): lane = 4 * (row in a 16-row group) + kg; a lane owns 8 consecutive k (32 B) of rows ra[0], ra[1] ----
     const int arow = lane >> 2, akg = lane & 3;
@@ -2493,13 +2418,13 @@ __global__ __launch_bounds__(BN == 256 ? 512 : 256, BN == 256 ? 1 : 2) void conv
         }
     }
     // ---- B (split weights): LDS-DMA, 8 rows x 128 B per wave-instruction, source chunk XOR-swizzled ----
-    const int srow = lane >> 3, spos = lane & 7;
+    const int srow = dma_row(lane), spos = dma_pos(lane);
     unsigned int b_voff[GB];
 #pragma unroll
     for (int g = 0; g < GB; ++g) {
         const int r = wave * (BN / NW) + 8 * g + srow;
         const int n = n0 + r;
-        b_voff[g] = (n < a.Cout) ? (unsigned int)(((size_t)n * a.K + 4 * (spos ^ ((r >> 1) & 7))) * 4) : OOB_VOFF;
+        b_voff[g] = (n < a.Cout) ? (unsigned int)(((size_t)n * a.K + dma_chunk(spos, r)) * 4) : OOB_VOFF;
     }
 
     const int csteps = STEM ? 1 : a.cin_win / BK;
@@ -2600,7 +2525,7 @@ __global__ __launch_bounds__(BN == 256 ? 512 : 256, BN == 256 ? 1 : 2) void conv
         for (int j = 0; j < NB; ++j)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                acc[i][j][e] = __fadd_rn(acc[i][j][e], __fmul_rn(acx[i][j][e], 1.0f / LO_SCALE));
+                acc[i][j][e] = fold(acc[i][j][e], acx[i][j][e]);
                 if (SCALED) acc[i][j][e] *= a.out_scale;
             }
     if (EPI == 0) conv_epilogue16<WTM, WTN, MB, NB, true>(a, acc, lds, wave, lane, m0 + wm * WTM, n0 + wn * WTN, HoWo);
@@ -2645,8 +2570,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const int ty = tyb % sp.tiles_y, b = tyb / sp.tiles_y;
     const int oy_first = 2 * ty * SP_PH - 1, ox_first = 2 * tx * SP_PW - 1;      // conv pixel of patch row 0 / column 0
 
-    const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_x = buffer_rsrc(a.x, x_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_w = buffer_rsrc(a.w, w_bytes);
 
     // ---- A: lane = 4 * (row in a 16-row group) + kg; a lane owns 8 consecutive k (two taps x 4 channels) of rows ra[0], ra[1] ----
     const int arow = lane >> 2, akg = lane & 3;
@@ -2663,11 +2588,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         a_ix0[p] = v ? ox * a.stride - a.pad : 0;
     }
     // ---- B (split weights): LDS-DMA, 8 rows x 128 B per wave-instruction, source chunk XOR-swizzled ----
-    const int srow = lane >> 3, spos = lane & 7;
+    const int srow = dma_row(lane), spos = dma_pos(lane);
     unsigned int b_voff;
     {
         const int r = wave * 8 + srow;
-        b_voff = (r < a.Cout) ? (unsigned int)(((size_t)r * a.K + 4 * (spos ^ ((r >> 1) & 7))) * 4) : OOB_VOFF;
+        b_voff = (r < a.Cout) ? (unsigned int)(((size_t)r * a.K + dma_chunk(spos, r)) * 4) : OOB_VOFF;
     }
     int kstep = 0;
     u32x4 ra[RPT][2];
@@ -2709,12 +2634,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 
     constexpr int MB = WTM / 16, NB = WTN / 16;
     f32x4 acc[MB][NB], acx[MB][NB];
-#pragma unroll
-    for (int i = 0; i < MB; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { acc[i][j][e] = 0.f; acx[i][j][e] = 0.f; }
+    zero_acc(acc, acx);
 
     const int l15 = lane & 15, lq = lane >> 4;
     const int fo16_hi = 4 * (lq ^ (l15 >> 1)), fo16_lo = 4 * ((4 + lq) ^ (l15 >> 1));
@@ -2748,7 +2668,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                 const int r = wm * WTM + i * 16 + 4 * lq + e;
                 const int pr = r / SP_CW, pc = r - pr * SP_CW;
                 const bool v = pr < SP_CH && (unsigned)(oy_first + pr) < (unsigned)a.Ho && (unsigned)(ox_first + pc) < (unsigned)a.Wo;
-                const float s = __fadd_rn(acc[i][j][e], __fmul_rn(acx[i][j][e], 1.0f / LO_SCALE));
+                const float s = fold(acc[i][j][e], acx[i][j][e]);
                 bad = bad || !(fabsf(s) <= 3.0e38f);
                 float t = __fadd_rn(__fmul_rn(s, sc), sh);
                 if (a.relu) t = fmaxf(t, 0.f);
@@ -2906,87 +2826,27 @@ __global__ __launch_bounds__(256) void weight_jobs_kernel(const amp::WeightJob* 
     }
 }
 
-template <int BN, bool STEM>
-void launch_glds(const ConvArgs& a, int epi, hipStream_t st, unsigned int xb, unsigned int wb) {
-    switch (epi) {
-        case 1: AMP_TIMED_LAUNCH((conv_glds_kernel<BN, STEM, 1>), dim3(a.nblk), dim3(256), 0, st, a, xb, wb); break;
-        case 2: AMP_TIMED_LAUNCH((conv_glds_kernel<BN, STEM, 2>), dim3(a.nblk), dim3(256), 0, st, a, xb, wb); break;
-        default: AMP_TIMED_LAUNCH((conv_glds_kernel<BN, STEM, 0>), dim3(a.nblk), dim3(256), 0, st, a, xb, wb);
-    }
+// epi -> template argument of a launch: f(std::integral_constant<int, E>()) for the first E of E0, Es... that equals epi, for the last otherwise
+template <int E0, int... Es, class F>
+void with_epi(int epi, F f) {
+    if (sizeof...(Es) == 0 || epi == E0) f(std::integral_constant<int, E0>());
+    else if constexpr (sizeof...(Es) > 0) with_epi<Es...>(epi, f);
 }
-
-template <int BN>
-void launch_f16x3s(const ConvArgs& a, int epi, hipStream_t st, unsigned int xb, unsigned int wb) {
-    constexpr int NT_ = (BN == 256) ? 512 : 256;
-    switch (epi) {
-        case 1: AMP_TIMED_LAUNCH((conv_glds_kernel<BN, false, 1, true>), dim3(a.nblk), dim3(NT_), 0, st, a, xb, wb); break;
-        case 2: AMP_TIMED_LAUNCH((conv_glds_kernel<BN, false, 2, true>), dim3(a.nblk), dim3(NT_), 0, st, a, xb, wb); break;
-        default: AMP_TIMED_LAUNCH((conv_glds_kernel<BN, false, 0, true>), dim3(a.nblk), dim3(NT_), 0, st, a, xb, wb);
-    }
-}
-
-void launch_f16x3s_g32(const ConvArgs& a, int epi, hipStream_t st, unsigned int xb, unsigned int wb) {     // grouped, <= 32 channels per group: one K-step per tap
-    switch (epi) {
-        case 1: AMP_TIMED_LAUNCH((conv_glds_kernel<64, false, 1, true, true>), dim3(a.nblk), dim3(256), 0, st, a, xb, wb); break;
-        case 2: AMP_TIMED_LAUNCH((conv_glds_kernel<64, false, 2, true, true>), dim3(a.nblk), dim3(256), 0, st, a, xb, wb); break;
-        default: AMP_TIMED_LAUNCH((conv_glds_kernel<64, false, 0, true, true>), dim3(a.nblk), dim3(256), 0, st, a, xb, wb);
-    }
-}
-
-template <int BM, int BN>
-void launch_split(const ConvArgs& a, int epi, hipStream_t st, unsigned int xb, unsigned int wb) {
-    constexpr int NT_ = (BM / 64) * (BN / 64) * 64;
-    if constexpr (BM == 128 && BN == 256) {
-        if (a.korder) {      // EXPERIMENT (AMP_KORDER=1): channel-major K order
-            if (epi == 3) AMP_TIMED_LAUNCH((conv_split_kernel<128, 256, 3, 3, true>), dim3(a.nblk), dim3(NT_), 0, st, a, xb, wb);
-            else if (epi == 2) AMP_TIMED_LAUNCH((conv_split_kernel<128, 256, 2, 3, true>), dim3(a.nblk), dim3(NT_), 0, st, a, xb, wb);
-            else AMP_TIMED_LAUNCH((conv_split_kernel<128, 256, 1, 3, true>), dim3(a.nblk), dim3(NT_), 0, st, a, xb, wb);
-            return;
-        }
-        if (epi == 3) { AMP_TIMED_LAUNCH((conv_split_kernel<128, 256, 3>), dim3(a.nblk), dim3(NT_), 0, st, a, xb, wb); return; }
-        if (epi == 4) { AMP_TIMED_LAUNCH((conv_split_kernel<128, 256, 3, 3, false, 2>), dim3(a.nblk), dim3(NT_), 0, st, a, xb, wb); return; }      // the RPN tail with 32 ...
-        if (epi == 5) { AMP_TIMED_LAUNCH((conv_split_kernel<128, 256, 3, 3, false, 3>), dim3(a.nblk), dim3(NT_), 0, st, a, xb, wb); return; }      // ... and 48 predictor rows
-    }
-    if (epi == 2) AMP_TIMED_LAUNCH((conv_split_kernel<BM, BN, 2>), dim3(a.nblk), dim3(NT_), 0, st, a, xb, wb);
-    else AMP_TIMED_LAUNCH((conv_split_kernel<BM, BN, 1>), dim3(a.nblk), dim3(NT_), 0, st, a, xb, wb);
-}
+struct ConvLaunch {       // one convolution launch: the kernel's arguments behind (a, x bytes, w bytes) follow the thread count
+    const ConvArgs& a; hipStream_t st; unsigned int xb, wb;
+    template <class K, class... More>
+    void operator()(K kernel, int threads, More... more) const { AMP_TIMED_LAUNCH(kernel, dim3(a.nblk), dim3(threads), 0, st, a, xb, wb, more...); }
+};
+// Four launches as functions of their own, in front of the stem launches: templates are instantiated in the order of their first use, and the
+// listing has had these kernels first.
+// grouped, <= 32 channels per group: one K-step per tap
+void launch_f16x3s_g32(const ConvLaunch& launch, int epi) { with_epi<1, 2, 0>(epi, [&](auto E) { launch(conv_glds_kernel<64, false, E(), true, true>, 256); }); }
 // the two-workgroups-per-CU form (two buffers, no ping-pong: the SIMD partner is the other workgroup's wave)
-static void launch_split_short(const ConvArgs& a, int epi, hipStream_t st, unsigned int xb, unsigned int wb) {
-    if (epi == 2) AMP_TIMED_LAUNCH((conv_split_kernel<128, 128, 2, 2>), dim3(a.nblk), dim3(256), 0, st, a, xb, wb);
-    else AMP_TIMED_LAUNCH((conv_split_kernel<128, 128, 1, 2>), dim3(a.nblk), dim3(256), 0, st, a, xb, wb);
-}
-
+void launch_split_short(const ConvLaunch& launch, int epi) { with_epi<2, 1>(epi, [&](auto E) { launch(conv_split_kernel<128, 128, E(), 2>, 256); }); }
 // Cout = 64 (res2's 3x3 and 1x1 layers): 256 x 64 tiles, four waves of 64 x 64 (one wave spans all 64 output channels: 2/3 of the LDS bytes per
 // MFMA of the 128 x 64 tiles' 64 x 32 wave tiles), two buffers, two workgroups per CU
-static void launch_split_tall64(const ConvArgs& a, hipStream_t st, unsigned int xb, unsigned int wb) {
-    AMP_TIMED_LAUNCH((conv_split_kernel<256, 64, 1, 2>), dim3(a.nblk), dim3(256), 0, st, a, xb, wb);
-}
-
-void launch_f16x3_stem(const ConvArgs& a, int epi, hipStream_t st, unsigned int xb, unsigned int wb) {
-    if (epi == 1) AMP_TIMED_LAUNCH((conv_f16x3_kernel<64, 1, true>), dim3(a.nblk), dim3(256), 0, st, a, xb, wb);
-    else AMP_TIMED_LAUNCH((conv_f16x3_kernel<64, 0, true>), dim3(a.nblk), dim3(256), 0, st, a, xb, wb);
-}
-
-template <int BN>
-void launch_f16x3_scaled(const ConvArgs& a, int epi, hipStream_t st, unsigned int xb, unsigned int wb) {
-    constexpr int NT_ = (BN == 256) ? 512 : 256;
-    switch (epi) {
-        case 1: AMP_TIMED_LAUNCH((conv_f16x3_kernel<BN, 1, false, true>), dim3(a.nblk), dim3(NT_), 0, st, a, xb, wb); break;
-        case 2: AMP_TIMED_LAUNCH((conv_f16x3_kernel<BN, 2, false, true>), dim3(a.nblk), dim3(NT_), 0, st, a, xb, wb); break;
-        default: AMP_TIMED_LAUNCH((conv_f16x3_kernel<BN, 0, false, true>), dim3(a.nblk), dim3(NT_), 0, st, a, xb, wb);
-    }
-}
-
-template <int BN>
-void launch_f16x3(const ConvArgs& a, int epi, hipStream_t st, unsigned int xb, unsigned int wb) {
-    if (a.in_scale != 1.0f) { launch_f16x3_scaled<BN>(a, epi, st, xb, wb); return; }
-    constexpr int NT_ = (BN == 256) ? 512 : 256;
-    switch (epi) {
-        case 1: AMP_TIMED_LAUNCH((conv_f16x3_kernel<BN, 1>), dim3(a.nblk), dim3(NT_), 0, st, a, xb, wb); break;
-        case 2: AMP_TIMED_LAUNCH((conv_f16x3_kernel<BN, 2>), dim3(a.nblk), dim3(NT_), 0, st, a, xb, wb); break;
-        default: AMP_TIMED_LAUNCH((conv_f16x3_kernel<BN, 0>), dim3(a.nblk), dim3(NT_), 0, st, a, xb, wb);
-    }
-}
+void launch_split_tall64(const ConvLaunch& launch) { launch(conv_split_kernel<256, 64, 1, 2>, 256); }
+void launch_f16x3_stem(const ConvLaunch& launch, int epi) { with_epi<1, 0>(epi, [&](auto E) { launch(conv_f16x3_kernel<64, E(), true>, 256); }); }
 
 void set_fastdiv(unsigned int d, unsigned int* mul, int* shr) {
     int l = 0;
@@ -3115,7 +2975,7 @@ __global__ void unsplit_rows_kernel(const unsigned int* __restrict__ in, size_t 
         for (int q = 0; q < 2; ++q) {
             const _Float16 h = __builtin_bit_cast(_Float16, (unsigned short)(hw >> (16 * q)));
             const _Float16 l = __builtin_bit_cast(_Float16, (unsigned short)(lw >> (16 * q)));
-            out[r * C + 2 * kp + q] = __fadd_rn((float)h, __fmul_rn((float)l, 1.0f / LO_SCALE));
+            out[r * C + 2 * kp + q] = fold((float)h, (float)l);
         }
     }
 }
@@ -3273,12 +3133,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const int oy_first = 2 * ty * SP_PH - 1, ox_first = 2 * tx * SP_PW - 1;      // conv pixel of patch row 0 / column 0
     const int iy_first = 2 * oy_first - 3, ix_first = 2 * ox_first - 3;           // input pixel of plane row 0 / column 0
 
-    const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.w), 0, w_bytes, 0x00020000);
-    const int srow = lane >> 3, spos = lane & 7;
+    const __amdgpu_buffer_rsrc_t rsrc_w = buffer_rsrc(a.w, w_bytes);
+    const int srow = dma_row(lane), spos = dma_pos(lane);
     unsigned int b_voff;
     {
         const int r = wave * 8 + srow;
-        b_voff = (r < a.Cout) ? (unsigned int)(((size_t)r * a.K + 4 * (spos ^ ((r >> 1) & 7))) * 4) : OOB_VOFF;
+        b_voff = (r < a.Cout) ? (unsigned int)(((size_t)r * a.K + dma_chunk(spos, r)) * 4) : OOB_VOFF;
     }
     // (no lambda here: AMP_NO_PK changes the kernel's target features, and a closure compiled with the default ones is then CALLED, not inlined)
 #pragma unroll
@@ -3327,12 +3187,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 
     constexpr int MB = WTM / 16, NB = WTN / 16;
     f32x4 acc[MB][NB], acx[MB][NB];
-#pragma unroll
-    for (int i = 0; i < MB; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { acc[i][j][e] = 0.f; acx[i][j][e] = 0.f; }
+    zero_acc(acc, acx);
     const int l15 = lane & 15, lq = lane >> 4;
     const int fo16_hi = 4 * (lq ^ (l15 >> 1)), fo16_lo = 4 * ((4 + lq) ^ (l15 >> 1));
     int a_off[MB];                                   // byte offset of this lane's A fragment inside a plane, kernel row 0
@@ -3379,7 +3234,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                 const int r = wm * WTM + i * 16 + 4 * lq + e;
                 const int pr = r / SP_CW, pc = r - pr * SP_CW;
                 const bool v = pr < SP_CH && (unsigned)(oy_first + pr) < (unsigned)a.Ho && (unsigned)(ox_first + pc) < (unsigned)a.Wo;
-                const float s_ = __fadd_rn(acc[i][j][e], __fmul_rn(acx[i][j][e], 1.0f / LO_SCALE));
+                const float s_ = fold(acc[i][j][e], acx[i][j][e]);
                 bad = bad || !(fabsf(s_) <= 3.0e38f);
                 float t = __fadd_rn(__fmul_rn(s_, sc), sh);
                 if (a.relu) t = fmaxf(t, 0.f);
@@ -3766,39 +3621,44 @@ int amp::conv_run(amp_ctx* ctx, const amp_conv_desc* d, int groups, const float*
     const unsigned int xb = (unsigned int)p.x_bytes, wb = (unsigned int)p.w_bytes;
     hipStream_t st = ctx->stream;
     using amp::ConvKernel;
-    // (templates are instantiated in the order of their first use, so the cases stand in the order the listing has had its kernels in)
+    // (templates are instantiated in the order of their first use, depth first, so the cases stand in the order the listing has had its kernels in)
+    const ConvLaunch launch{a, st, xb, wb};
+    auto launch_f16x3 = [&](auto BN_) {      // activations split in the kernel; in_scale != 1: multiplied by that power of two first (SCALED)
+        constexpr int BN = decltype(BN_)::value, NT_ = (BN == 256) ? 512 : 256;
+        if (a.in_scale != 1.0f) with_epi<1, 2, 0>(p.epi, [&](auto E) { launch(conv_f16x3_kernel<BN, E(), false, true>, NT_); });
+        else with_epi<1, 2, 0>(p.epi, [&](auto E) { launch(conv_f16x3_kernel<BN, E()>, NT_); });
+    };
     switch (p.kernel) {
-        case ConvKernel::C64_PATCH_DIAG: AMP_TIMED_LAUNCH(conv3x3_c64_kernel<true>, dim3(a.nblk), dim3(256), 0, st, a, xb, wb, p.tiles_x, p.tiles_y, Fuse3Args()); break;
-        case ConvKernel::C64_PATCH: AMP_TIMED_LAUNCH(conv3x3_c64_kernel<false>, dim3(a.nblk), dim3(256), 0, st, a, xb, wb, p.tiles_x, p.tiles_y, Fuse3Args()); break;
-        case ConvKernel::PATCH256:
-            if (p.epi == 5) AMP_TIMED_LAUNCH(conv3x3_patch_kernel<5>, dim3(a.nblk), dim3(512), 0, st, a, xb, wb, p.tiles_x, p.tiles_y);
-            else if (p.epi == 4) AMP_TIMED_LAUNCH(conv3x3_patch_kernel<4>, dim3(a.nblk), dim3(512), 0, st, a, xb, wb, p.tiles_x, p.tiles_y);
-            else if (p.epi == 3) AMP_TIMED_LAUNCH(conv3x3_patch_kernel<3>, dim3(a.nblk), dim3(512), 0, st, a, xb, wb, p.tiles_x, p.tiles_y);
-            else AMP_TIMED_LAUNCH(conv3x3_patch_kernel<1>, dim3(a.nblk), dim3(512), 0, st, a, xb, wb, p.tiles_x, p.tiles_y);
+        case ConvKernel::C64_PATCH_DIAG: launch(conv3x3_c64_kernel<true>, 256, p.tiles_x, p.tiles_y, Fuse3Args()); break;
+        case ConvKernel::C64_PATCH: launch(conv3x3_c64_kernel<false>, 256, p.tiles_x, p.tiles_y, Fuse3Args()); break;
+        case ConvKernel::PATCH256: with_epi<5, 4, 3, 1>(p.epi, [&](auto E) { launch(conv3x3_patch_kernel<E()>, 512, p.tiles_x, p.tiles_y); }); break;
+        case ConvKernel::MASK_TAIL: launch(mask_tail_kernel, 512); break;
+        case ConvKernel::SPLIT_128x256:
+            if (a.korder)      // EXPERIMENT (AMP_KORDER=1): channel-major K order
+                with_epi<3, 2, 1>(p.epi, [&](auto E) { launch(conv_split_kernel<128, 256, E(), 3, true>, 512); });
+            else if (p.epi >= 3 && p.epi <= 5)      // the fused tails: the mask head's, or the RPN tail with 16, 32 or 48 predictor rows
+                with_epi<3, 4, 5>(p.epi, [&](auto E) { launch(conv_split_kernel<128, 256, 3, 3, false, E() - 2>, 512); });
+            else
+                with_epi<2, 1>(p.epi, [&](auto E) { launch(conv_split_kernel<128, 256, E()>, 512); });
             break;
-        case ConvKernel::MASK_TAIL: AMP_TIMED_LAUNCH(mask_tail_kernel, dim3(a.nblk), dim3(512), 0, st, a, xb, wb); break;
-        case ConvKernel::SPLIT_128x256: launch_split<128, 256>(a, p.epi, st, xb, wb); break;
-        case ConvKernel::SPLIT_SHORT_128x128: launch_split_short(a, p.epi, st, xb, wb); break;
-        case ConvKernel::NLOOP_SCATTER: AMP_TIMED_LAUNCH(conv1x1_nloop_kernel<true>, dim3(a.nblk), dim3(512), 0, st, a, xb, wb, p.nloop_nt); break;
-        case ConvKernel::NLOOP: AMP_TIMED_LAUNCH(conv1x1_nloop_kernel<false>, dim3(a.nblk), dim3(512), 0, st, a, xb, wb, p.nloop_nt); break;
-        case ConvKernel::SPLIT_256x128: launch_split<256, 128>(a, p.epi, st, xb, wb); break;
-        case ConvKernel::SPLIT_TALL64: launch_split_tall64(a, st, xb, wb); break;
-        case ConvKernel::F16X3S_256: launch_f16x3s<256>(a, p.epi, st, xb, wb); break;
-        case ConvKernel::F16X3S_128: launch_f16x3s<128>(a, p.epi, st, xb, wb); break;
-        case ConvKernel::F16X3S_G32: launch_f16x3s_g32(a, p.epi, st, xb, wb); break;
-        case ConvKernel::F16X3S_64: launch_f16x3s<64>(a, p.epi, st, xb, wb); break;
-        case ConvKernel::F16X3_STEM: launch_f16x3_stem(a, p.epi, st, xb, wb); break;
-        case ConvKernel::F16X3_64: launch_f16x3<64>(a, p.epi, st, xb, wb); break;
-        case ConvKernel::F16X3_256: launch_f16x3<256>(a, p.epi, st, xb, wb); break;
-        case ConvKernel::F16X3_128: launch_f16x3<128>(a, p.epi, st, xb, wb); break;
-        case ConvKernel::GLDS_STEM: launch_glds<64, true>(a, p.epi, st, xb, wb); break;
-        case ConvKernel::GLDS_128: launch_glds<128, false>(a, p.epi, st, xb, wb); break;
-        case ConvKernel::GLDS_64: launch_glds<64, false>(a, p.epi, st, xb, wb); break;
+        case ConvKernel::SPLIT_SHORT_128x128: launch_split_short(launch, p.epi); break;
+        case ConvKernel::NLOOP_SCATTER: launch(conv1x1_nloop_kernel<true>, 512, p.nloop_nt); break;
+        case ConvKernel::NLOOP: launch(conv1x1_nloop_kernel<false>, 512, p.nloop_nt); break;
+        case ConvKernel::SPLIT_256x128: with_epi<2, 1>(p.epi, [&](auto E) { launch(conv_split_kernel<256, 128, E()>, 512); }); break;
+        case ConvKernel::SPLIT_TALL64: launch_split_tall64(launch); break;
+        case ConvKernel::F16X3S_256: with_epi<1, 2, 0>(p.epi, [&](auto E) { launch(conv_glds_kernel<256, false, E(), true>, 512); }); break;
+        case ConvKernel::F16X3S_128: with_epi<1, 2, 0>(p.epi, [&](auto E) { launch(conv_glds_kernel<128, false, E(), true>, 256); }); break;
+        case ConvKernel::F16X3S_G32: launch_f16x3s_g32(launch, p.epi); break;
+        case ConvKernel::F16X3S_64: with_epi<1, 2, 0>(p.epi, [&](auto E) { launch(conv_glds_kernel<64, false, E(), true>, 256); }); break;
+        case ConvKernel::F16X3_STEM: launch_f16x3_stem(launch, p.epi); break;
+        case ConvKernel::F16X3_64: launch_f16x3(std::integral_constant<int, 64>()); break;
+        case ConvKernel::F16X3_256: launch_f16x3(std::integral_constant<int, 256>()); break;
+        case ConvKernel::F16X3_128: launch_f16x3(std::integral_constant<int, 128>()); break;
+        case ConvKernel::GLDS_STEM: with_epi<1, 2, 0>(p.epi, [&](auto E) { launch(conv_glds_kernel<64, true, E()>, 256); }); break;
+        case ConvKernel::GLDS_128: with_epi<1, 2, 0>(p.epi, [&](auto E) { launch(conv_glds_kernel<128, false, E()>, 256); }); break;
+        case ConvKernel::GLDS_64: with_epi<1, 2, 0>(p.epi, [&](auto E) { launch(conv_glds_kernel<64, false, E()>, 256); }); break;
         case ConvKernel::MFMA_128:
-            if (g_sw.ablate == 1) AMP_TIMED_LAUNCH((conv_mfma_kernel<128, 128, 1>), dim3(a.nblk), dim3(256), 0, st, a);
-            else if (g_sw.ablate == 2) AMP_TIMED_LAUNCH((conv_mfma_kernel<128, 128, 2>), dim3(a.nblk), dim3(256), 0, st, a);
-            else if (g_sw.ablate == 3) AMP_TIMED_LAUNCH((conv_mfma_kernel<128, 128, 3>), dim3(a.nblk), dim3(256), 0, st, a);
-            else AMP_TIMED_LAUNCH((conv_mfma_kernel<128, 128, 0>), dim3(a.nblk), dim3(256), 0, st, a);
+            with_epi<1, 2, 3, 0>(g_sw.ablate, [&](auto ABL) { AMP_TIMED_LAUNCH((conv_mfma_kernel<128, 128, ABL()>), dim3(a.nblk), dim3(256), 0, st, a); });
             break;
         case ConvKernel::MFMA_64: AMP_TIMED_LAUNCH((conv_mfma_kernel<128, 64>), dim3(a.nblk), dim3(256), 0, st, a); break;
         case ConvKernel::COUNT: break;

@@ -12,11 +12,11 @@
 #include <string.h>
 
 #include "common.h"
+#include "lds_ring.h"
 
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-constexpr unsigned int OOB = 0x80000000u;
 constexpr int BKW = 32;     // pixels per step
 constexpr int TN = 128;     // output-channel tile
 constexpr int TC = 128;     // (tap, c) tile
@@ -68,8 +68,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(const WgradArgs a) {
     const int m_end = min(a.M, m_begin + a.rows_per_split);
     const int nsteps = (m_end > m_begin) ? (m_end - m_begin + BKW - 1) / BKW : 0;
 
-    const __amdgpu_buffer_rsrc_t rsrc_dy = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.dy), 0, a.dy_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, a.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_dy = buffer_rsrc(a.dy, a.dy_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_x = buffer_rsrc(a.x, a.x_bytes);
 
     // staging: DMA instruction g (0..3) of this wave fills tile rows 8*wave + 2g + (lane>>5), 16-B chunk lane&31.
     // dY: the row byte offset is linear in m -> the step part rides in the scalar soffset, the lane part is constant.  Rows past
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(const WgradArgs a) {
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
         const int n = n0 + 4 * chunk;               // N % 4 == 0: a chunk is all-in or all-out
-        p_voff[g] = (n < a.N) ? (unsigned int)(((8 * wave + 2 * g + lh) * a.N + n) * 4) : OOB;
+        p_voff[g] = (n < a.N) ? (unsigned int)(((8 * wave + 2 * g + lh) * a.N + n) * 4) : OOB_VOFF;
     }
     const unsigned int q_lane = (unsigned int)((c0 + 4 * chunk) * 4);
     const unsigned int* tab = a.rowtab + (size_t)tap * a.Mpad + m_begin + 8 * wave + lh;   // + 32*step + 2g
@@ -188,7 +188,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(const WgradArgs a) {
 // which raises *range_flag (the caller redoes the step on the fp32 MFMA).
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-constexpr float LO_SCALE = 2048.0f;
 constexpr int WPITCH = 144;                 // bytes per tile column
 // A tile of C columns is two regions, even columns then odd columns, each C/2 columns of WPITCH bytes plus 128 B: a lane's two
 // columns go to the same slot of the two regions, so the 8 lanes of a ds_write_b128 group hit 8 consecutive slots (pitch 9 x 16 B:
@@ -226,12 +225,12 @@ __global__ __launch_bounds__(256, 2) void wgrad_f16x3_kernel(const WgradArgs a, 
     const int m_end = min(a.M, m_begin + a.rows_per_split);
     const int nsteps = (m_end > m_begin) ? (m_end - m_begin + BKW - 1) / BKW : 0;
 
-    const __amdgpu_buffer_rsrc_t rsrc_dy = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.dy), 0, a.dy_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, a.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_dy = buffer_rsrc(a.dy, a.dy_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_x = buffer_rsrc(a.x, a.x_bytes);
 
     const int pcol = 2 * lane;                     // tile column pair of this lane
     const int pc = n0 + pcol;
-    const unsigned int p_voff = (pc < a.N) ? (PS ? (unsigned int)((pc >> 5) * 128 + (pc & 31) * 2) : (unsigned int)(pc * 4)) : OOB;   // N even: a pair is all-in or all-out
+    const unsigned int p_voff = (pc < a.N) ? (PS ? (unsigned int)((pc >> 5) * 128 + (pc & 31) * 2) : (unsigned int)(pc * 4)) : OOB_VOFF;   // N even: a pair is all-in or all-out
     const int qc = c0 + 2 * lane;                  // this lane's channel pair of X
     const unsigned int q_lane = XS ? (unsigned int)((qc >> 5) * 128 + (qc & 31) * 2) : (unsigned int)(qc * 4);
     const unsigned int* tab = a.rowtab + (size_t)tap * a.Mpad + m_begin + 8 * mg;   // wave-uniform: scalar loads
@@ -392,7 +391,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_f16x3_kernel(const WgradArgs a, 
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const int n = n0 + wm * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
-                float v = __fadd_rn(acc[i][j][e], __fmul_rn(acx[i][j][e], 1.0f / LO_SCALE));
+                float v = fold(acc[i][j][e], acx[i][j][e]);
                 bad |= !(fabsf(v) <= 3.0e38f);
                 if (SC != 0) v *= out_scale;
                 if (n < a.N && kp < a.Kp) out[(size_t)n * a.Kp + kp] = v;
@@ -467,8 +466,8 @@ __global__ __launch_bounds__(512, 1) void wgrad_split_kernel(const WgradArgs a, 
     const int m_end = min(a.M, m_begin + a.rows_per_split);
     const int nsteps = (m_end > m_begin) ? (m_end - m_begin + BKW - 1) / BKW : 0;
 
-    const __amdgpu_buffer_rsrc_t rsrc_dy = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.dy), 0, a.dy_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x), 0, a.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_dy = buffer_rsrc(a.dy, a.dy_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_x = buffer_rsrc(a.x, a.x_bytes);
     auto swz = [](int R) { return ((R & 3) | (((R >> 3) & 1) << 2)) << 1; };
 
     // ---- staging: dY, 2 requests per wave and step, each 2 rows x 512 B; lane -> (row, chunk position), source chunk swizzled ----
@@ -478,7 +477,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_split_kernel(const WgradArgs a, 
         const int R = 2 * (2 * wave + i) + (lane >> 5);
         const int src = (lane & 31) ^ swz(R);
         // the tile's 128 channels are 4 groups of 128 B, contiguous in a split row; the row offset (pixel * N * 4) is added per step
-        p_voff[i] = (n0 < a.N) ? (unsigned int)((size_t)(m_begin + R) * a.N * 4 + (size_t)(n0 >> 5) * 128 + 16 * src) : OOB;
+        p_voff[i] = (n0 < a.N) ? (unsigned int)((size_t)(m_begin + R) * a.N * 4 + (size_t)(n0 >> 5) * 128 + 16 * src) : OOB_VOFF;
     }
     const unsigned int p_step = (unsigned int)(BKW * a.N * 4);
     // ---- X: 4 requests per wave and step, one row of 1 KiB each; the 256 (tap, c) of the tile are one run of a tap's channels, or (Cin =
@@ -517,7 +516,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_split_kernel(const WgradArgs a, 
     };
     auto take_tab = [&]() {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) { qt0[i] = tap0_ok ? qn0[i] : OOB; qt1[i] = tap1_ok ? qn1[i] : OOB; }
+        for (int i = 0; i < 4; ++i) { qt0[i] = tap0_ok ? qn0[i] : OOB_VOFF; qt1[i] = tap1_ok ? qn1[i] : OOB_VOFF; }
     };
 
     int staged = 0;                                                  // next K-step to stage
@@ -553,12 +552,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_split_kernel(const WgradArgs a, 
         }
 
     f32x4w acc[4][4], acx[4][4];                                    // [c block][n block]
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { acc[i][j][e] = 0.f; acx[i][j][e] = 0.f; }
+    zero_acc(acc, acx);
     f16x8 xh[4], xl[4], yh[4], yl[4];
 
     const unsigned int lds_base = (unsigned int)(size_t)lds;          // LDS byte address of the ring (low half of the generic address)
@@ -597,14 +591,8 @@ __global__ __launch_bounds__(512, 1) void wgrad_split_kernel(const WgradArgs a, 
         if (nsteps > 1) { load_tab(1); take_tab(); stage(1); }
         if (nsteps > 2) { load_tab(2); take_tab(); }                 // qt: the rows of K-step 2, staged in step 0
         int cur = 0, nxt = 2;
-        auto open_step = [&](int step) {
-            if (step + 1 < nsteps) __builtin_amdgcn_s_waitcnt(0x0070 | 6);     // all but the youngest tile's 6 requests; lgkmcnt(0)
-            else __builtin_amdgcn_s_waitcnt(0x0070);
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-        };
-        auto advance = [&]() { cur = (cur == 2) ? 0 : cur + 1; nxt = (nxt == 2) ? 0 : nxt + 1; };
+        auto open_step = [&](int step) { ring_open<6>(step + 1 < nsteps); };      // 2 dY + 4 X requests per tile
+        auto advance = [&]() { ring_next<3>(cur, nxt); };
         if (wave < 4) {
             for (int step = 0; step < nsteps; ++step) {
                 open_step(step);
@@ -654,7 +642,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_split_kernel(const WgradArgs a, 
             f32x4w v;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                v[e] = __fadd_rn(acc[i][j][e], __fmul_rn(acx[i][j][e], 1.0f / LO_SCALE));
+                v[e] = fold(acc[i][j][e], acx[i][j][e]);
                 bad |= !(fabsf(v[e]) <= 3.0e38f);
                 v[e] *= out_scale;
             }
@@ -696,7 +684,7 @@ __global__ void wgrad_rowtab_kernel(const WgradArgs a, unsigned int* __restrict_
         const unsigned int ox = rem - oy * (unsigned int)a.Wo;
         const int iy = (int)oy * a.stride - a.pad + ky, ix = (int)ox * a.stride - a.pad + kx;
         const bool v = (int)m < a.M && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-        tab[i] = v ? (unsigned int)(((b * a.H + iy) * a.W + ix) * a.Cin) * 4u : OOB;
+        tab[i] = v ? (unsigned int)(((b * a.H + iy) * a.W + ix) * a.Cin) * 4u : OOB_VOFF;
     }
 }
 
@@ -834,7 +822,7 @@ __global__ __launch_bounds__(256) void colsum_of_split_kernel(const float* __res
                 const char* ib = reinterpret_cast<const char*>(dy_split + (size_t)r * N) + col_b;
                 const cs_h8 hi = *reinterpret_cast<const cs_h8*>(ib), lo = *reinterpret_cast<const cs_h8*>(ib + 64);
 #pragma unroll
-                for (int q = 0; q < 8; ++q) acc[q] = __fadd_rn(acc[q], __fmul_rn(__fadd_rn((float)hi[q], __fmul_rn((float)lo[q], 1.0f / LO_SCALE)), inv_scale));
+                for (int q = 0; q < 8; ++q) acc[q] = __fadd_rn(acc[q], __fmul_rn(fold((float)hi[q], (float)lo[q]), inv_scale));
             }
         }
         __syncthreads();
@@ -989,7 +977,7 @@ int amp_conv2d_wgrad_fmt(amp_ctx* ctx, const amp_conv_desc* d, const float* x, c
     a.nsplit = pick_nsplit(M, tiles);
     a.rows_per_split = amp::cdiv(amp::cdiv(a.M, a.nsplit), BKW) * BKW;
     const size_t dyb = (size_t)M * a.N * 4, xb = (size_t)a.B * a.H * a.W * a.Cin * 4;
-    AMP_REQUIRE(dyb < (size_t)OOB && xb < (size_t)OOB, "amp_conv2d_wgrad: operand larger than 2 GiB (split the batch)");
+    AMP_REQUIRE(dyb < (size_t)OOB_VOFF && xb < (size_t)OOB_VOFF, "amp_conv2d_wgrad: operand larger than 2 GiB (split the batch)");
     a.dy_bytes = (unsigned int)dyb; a.x_bytes = (unsigned int)xb;
     AMP_REQUIRE(M + 64 < (1ll << 29), "amp_conv2d_wgrad: too many output pixels for the multiply-shift division");
     set_fastdiv((unsigned int)(a.Ho * a.Wo), &a.div_howo_mul, &a.div_howo_shr);
