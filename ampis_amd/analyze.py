@@ -44,6 +44,11 @@ pycocotools:
     crack rings on pixel corners -- the cycles of a successor permutation over the top and bottom edges of vertical pieces, found by pointer
     jumping on the device (csrc/contours.hip) or by a sequential walk on the host --; no mask is decoded.  It is the inverse of
     `masks_to_rle(PolygonMasks, ...)`.
+  * `dilate_masks`, `erode_masks`, `open_masks`, `close_masks`, `boundary_bands`, `boundary_iou` and `near_pairs` (what users do today with
+    scipy.ndimage.binary_dilation / binary_erosion / binary_opening / binary_closing or cv2.erode on one decoded array per mask): ONE
+    `amp_mask_morphology` call changes the shape of every mask of an image by a distance on its run list -- every vertical piece sends a
+    grown or shrunk interval to the columns within the radius, and a pixel's class follows from the integer cover of those intervals, found
+    by a sort and a scan of +1 / -1 events on the device (csrc/morphology.hip) or by a sweep per column on the host --; no mask is decoded.
 With no prediction at all the detection precision is 0/0: like the reference this raises ZeroDivisionError.
 The independent checker is oracle/matcher.py (a loop-for-loop restatement of the reference, pinned by its known-answer test)."""
 import numpy as np
@@ -405,6 +410,135 @@ def masks_to_polygons(masks, connectivity=2, size=None, device='auto', return_ha
     if not return_has_holes:
         return polys
     return polys, np.array([bool((area2[first[i]: first[i + 1]] < 0).any()) for i in range(n)], dtype=bool)
+
+
+# ---- morphology: a mask's shape changed by a distance (scipy.ndimage.binary_dilation / binary_erosion / binary_opening / binary_closing on one
+# ---- decoded array per mask; Boundary IoU's cv2.erode) -------------------------------------------------------------------------------------------
+
+def _morphology(who, masks, op, shape, radius, border_value, size, device, return_stats):
+    """One rle.morphology call for a public function; every argument is checked before anything else happens"""
+    if shape not in rle.MORPH_SHAPES:
+        raise ValueError(f"{who}: shape = {shape!r} ('square', 'diamond' or 'disk')")
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= int(radius) <= rle.MORPH_MAX_RADIUS:
+        raise ValueError(f"{who}: radius = {radius!r} (an integer 0 .. {rle.MORPH_MAX_RADIUS})")
+    if isinstance(border_value, bool) or border_value not in (0, 1):
+        raise ValueError(f"{who}: border_value = {border_value!r} (0 or 1)")
+    if str(device).lower() not in ("auto", "cpu", "cuda"):
+        raise ValueError(f"{who}: device = {device!r} ('auto', 'cpu' or 'cuda')")
+    masks, size = _unwrap_masks(masks, size)
+    rles = masks_to_rle(masks, size, device)
+    sizes = {tuple(int(v) for v in r["size"]) for r in rles}
+    if len(sizes) > 1:
+        raise ValueError(f"{who}: masks of different sizes {sorted(sizes)}")
+    out, boxes, areas = rle.morphology(rles, op, shape, int(radius), int(border_value), ctx=_device_context(who, device, len(rles)),
+                                       size=size if not rles else None, return_stats=True)
+    return (out, {"area": areas, "bbox": boxes}) if return_stats else out
+
+
+def dilate_masks(masks, shape='disk', radius=1, border_value=0, size=None, device='auto', return_stats=False):
+    """Every mask grown by `radius` pixels: a pixel is set where a pixel of the mask lies within the structuring element -- 'square': Chebyshev
+    distance <= radius (the 3 x 3 ones element iterated radius times), 'diamond': city-block distance (the 3 x 3 cross iterated), 'disk':
+    Euclidean distance, dx^2 + dy^2 <= radius^2 (skimage.morphology.disk).  What scipy.ndimage.binary_dilation gives per decoded mask; the image
+    clips the result and border_value plays no part.  Returns the list of RLE dicts in canonical form (what rle.encode gives for the dense
+    result), length and order unchanged; return_stats: also a dict of 'area' int64 [N] and 'bbox' int64 [N, 4] = {r0, c0, r1, c1}, ends
+    exclusive, zeros for an empty result.
+
+    masks: anything masks_to_rle accepts (size=(h, w) for polygons), an Instances or an InstanceSet; radius: an integer 0 .. 1024, 0 returns the
+    canonical form of the input; device: 'cpu' (host), 'cuda' (HIP device, an error without one) or 'auto' (the device when one is visible).
+    One amp_mask_morphology call on the run lists (csrc/morphology.hip, or morphology_host.hip on the host: identical bytes), no mask is
+    decoded.  ValueError before any device work for a bad shape, radius, border value or device and for masks of different sizes."""
+    return _morphology("dilate_masks", masks, "dilate", shape, radius, border_value, size, device, return_stats)
+
+
+def erode_masks(masks, shape='disk', radius=1, border_value=0, size=None, device='auto', return_stats=False):
+    """Every mask shrunk by `radius` pixels: a pixel stays where the whole structuring element around it lies in the mask.  border_value is
+    what the outside of the image counts as: 0 (scipy.ndimage.binary_erosion's default) erodes a mask from the image's sides, 1 (cv2.erode's
+    default) does not.  A mask may come back empty.  Shapes, masks, radius, device, result and errors as in dilate_masks."""
+    return _morphology("erode_masks", masks, "erode", shape, radius, border_value, size, device, return_stats)
+
+
+def open_masks(masks, shape='disk', radius=1, border_value=0, size=None, device='auto', return_stats=False):
+    """The opening of every mask, the dilation of its erosion: what the structuring element cannot enter is removed -- specks, spurs and the
+    thin bridge that joins two particles predicted as one (mask_topology then counts two parts).  border_value is the erosion's.  Both passes
+    run inside one amp_mask_morphology call; on the device the eroded masks never leave it.  Shapes, masks, radius, device, result and errors
+    as in dilate_masks."""
+    return _morphology("open_masks", masks, "open", shape, radius, border_value, size, device, return_stats)
+
+
+def close_masks(masks, shape='disk', radius=1, border_value=1, size=None, device='auto', return_stats=False):
+    """The closing of every mask, the erosion of its dilation: gaps the structuring element cannot enter are filled -- cracks, pinholes, narrow
+    bays.  border_value is the erosion's and defaults to 1 HERE, unlike everywhere else: the dilation is clipped by the image, and an erosion
+    that took the outside for background would then eat into a mask that touches the image's side; with 1 the closing is extensive, every
+    mask is contained in its closing, at the border too.  border_value=0 is scipy.ndimage.binary_closing's default.  Both passes run inside
+    one amp_mask_morphology call.  Shapes, masks, radius, device, result and errors as in dilate_masks."""
+    return _morphology("close_masks", masks, "close", shape, radius, border_value, size, device, return_stats)
+
+
+def boundary_bands(masks, width, side='inner', shape='square', border_value=0, size=None, device='auto', return_stats=False):
+    """The band of `width` pixels along every mask's outline: side 'inner' = the mask minus its erosion (the pixels of the mask within `width`
+    of a pixel outside it; with border_value 0 the outside of the image counts), 'outer' = its dilation minus the mask.  One pass of one
+    amp_mask_morphology call.  width is the radius of dilate_masks; shapes, masks, device, result and errors as there."""
+    if side not in ("inner", "outer"):
+        raise ValueError(f"boundary_bands: side = {side!r} ('inner' or 'outer')")
+    return _morphology("boundary_bands", masks, "band_in" if side == "inner" else "band_out", shape, width, border_value, size, device, return_stats)
+
+
+def boundary_iou(gt, pred, matches=None, dilation_ratio=0.02, distance=None, size=None, device='auto'):
+    """Boundary IoU (Cheng et al. 2021) of every matched pair: |band(g) AND band(p)| / |band(g) OR band(p)|, band(M) = M minus its erosion by the
+    3 x 3 ones element iterated d times with the outside of the image as background -- boundary_bands(M, d, 'inner', 'square', 0), the published
+    definition -- at d = `distance`, or max(1, round(dilation_ratio * sqrt(h^2 + w^2))).  Large instances score well on mask IoU whatever
+    their outline; this score looks at the outline only.  matches: the dict of rle_instance_matcher or an [n, 2] array of (gt, pred) index
+    pairs, None to take the true positives at IoU 0.5.  Returns {'boundary_iou': float64 [n] (NaN for a pair whose bands are both empty),
+    'inter': int64 [n], 'union': int64 [n], 'distance': d}.
+
+    gt, pred: anything masks_to_rle accepts (size=(h, w) for polygons and when both sides are empty), an Instances or an InstanceSet; device:
+    'cpu', 'cuda' or 'auto'.  One amp_mask_morphology call for the matched ground-truth masks, one for the matched predictions, one
+    amp_rle_pair_overlap; no mask is decoded.  ValueError for a bad distance, ratio, pair or device and for masks of different sizes."""
+    if str(device).lower() not in ("auto", "cpu", "cuda"):
+        raise ValueError(f"boundary_iou: device = {device!r} ('auto', 'cpu' or 'cuda')")
+    if distance is not None and (isinstance(distance, bool) or not isinstance(distance, (int, np.integer)) or not 1 <= int(distance) <= rle.MORPH_MAX_RADIUS):
+        raise ValueError(f"boundary_iou: distance = {distance!r} (an integer 1 .. {rle.MORPH_MAX_RADIUS}, or None for the ratio)")
+    if distance is None and not (isinstance(dilation_ratio, (int, float, np.integer, np.floating)) and 0 <= float(dilation_ratio) < float("inf")):
+        raise ValueError(f"boundary_iou: dilation_ratio = {dilation_ratio!r} (a finite share of the image diagonal, not negative)")
+    gm, size = _unwrap_masks(gt, size)
+    pm, size = _unwrap_masks(pred, size)
+    g, p = masks_to_rle(gm, size, device), masks_to_rle(pm, size, device)
+    h, w = _image_size("boundary_iou", g + p, size)
+    d = int(distance) if distance is not None else max(1, int(round(float(dilation_ratio) * float(np.sqrt(float(h * h + w * w))))))
+    if d > rle.MORPH_MAX_RADIUS:
+        raise ValueError(f"boundary_iou: the band width {d} of a {h} x {w} image at ratio {dilation_ratio!r} exceeds {rle.MORPH_MAX_RADIUS}; pass distance=")
+    if matches is None:
+        matches = match_instances(iou_matrix(g, p), 0.5)
+    pairs = np.asarray(matches["tp"] if isinstance(matches, dict) else matches, dtype=np.int64).reshape(-1, 2)
+    for i, (a, b) in enumerate(pairs.tolist()):
+        if not (0 <= a < len(g) and 0 <= b < len(p)):
+            raise ValueError(f"boundary_iou: pair {i} = ({a}, {b}) is outside the {len(g)} ground-truth and {len(p)} predicted masks")
+    n = len(pairs)
+    ctx = _device_context("boundary_iou", device, n)
+    bg = rle.morphology([g[a] for a in pairs[:, 0].tolist()], "band_in", "square", d, 0, ctx=ctx, size=(h, w))
+    bp = rle.morphology([p[b] for b in pairs[:, 1].tolist()], "band_in", "square", d, 0, ctx=ctx, size=(h, w))
+    inter, g_only, p_only = rle.pair_overlap(bg, bp, np.stack([np.arange(n), np.arange(n)], axis=1))
+    union = inter + g_only + p_only
+    with np.errstate(divide="ignore", invalid="ignore"):
+        biou = inter.astype(np.float64) / union.astype(np.float64)
+    return {"boundary_iou": biou, "inter": inter, "union": union, "distance": d}
+
+
+def near_pairs(masks, gap=1, shape='disk', size=None, device='auto'):
+    """Which instances touch or lie close together: the int64 [k, 2] index pairs i < j, in lexicographic order, of masks with a pixel of one
+    within `gap` of a pixel of the other -- Euclidean distance for 'disk', Chebyshev for 'square', city-block for 'diamond'; exact for integer
+    pixel offsets.  gap = 1 with 'square' is 8-touching, with 'diamond' 4-touching, gap = 0 overlapping.  The contact graph of a powder image,
+    the near-neighbour graph of a set of carbides.  Pair (i, j) is reported where dilate(masks[i], gap) meets masks[j]; the distance is
+    symmetric, so nothing is lost by looking at i < j only.
+
+    One amp_mask_morphology call (the dilation) and one amp_rle_overlap_groups call (overlap_matrix) on the run lists.  masks, shape, device
+    and errors as in dilate_masks; gap is its radius."""
+    grown = _morphology("near_pairs", masks, "dilate", shape, gap, 0, size, device, False)
+    if len(grown) < 2:
+        return np.zeros((0, 2), np.int64)
+    masks, size = _unwrap_masks(masks, size)
+    meets = overlap_matrix(grown, masks_to_rle(masks, size, device), device=device) > 0
+    return np.argwhere(np.triu(meets, 1)).astype(np.int64).reshape(-1, 2)
 
 
 # ---- overlap-free instances: the owner of every pixel (the labels[mask_i] = i + 1 loop over decoded masks) ---------------------------------------

@@ -6,7 +6,9 @@
 //   scan_sums_in_place one workgroup of 1024: an array becomes its exclusive scan, the caller notes what it needs on the way;
 //   scan_sums_kernel   that scan as a kernel for K quantities of nblk sums each: where each starts, and the total;
 //   block_before_256   what lies in front of a lane in its workgroup;
-//   diff_counts_kernel boundaries to counts.
+//   diff_counts_kernel boundaries to counts;
+//   count_offsets_kernel / run_counts_kernel  the last two stages of the ops that find a pool's boundaries among sorted events
+//                      (polygon_runs.hip, morphology.hip): where every mask's counts start, and the counts with box and area.
 // Fixed trees and no atomics: the order is fixed and the bytes repeat.  Every loop states why it ends; none waits for another lane.  For hipcc
 // only; every file that includes this header gets kernels of its own.
 #pragma once
@@ -90,6 +92,39 @@ __global__ __launch_bounds__(256) void diff_counts_kernel(const unsigned int* __
     for (unsigned long long t = (unsigned long long)blockIdx.x * 256 + threadIdx.x; t < total; t += (unsigned long long)gridDim.x * 256) {   // ends: t grows by the grid
         const int lo = amp::owner_of(off, n, t);                                         // off[0] = 0 <= t, every list has a count: the list that owns count t
         counts[t] = bnd[t] - (off[lo] == t ? 0u : bnd[t - 1]);
+    }
+}
+
+// coff[i] = where mask i's counts start: the boundaries of the masks before it and one closing count each (bidx: the exclusive scan of the
+// boundary flags over the sorted events, ioff[i]: mask i's first event); the box and the area of every mask preset for the atomics of
+// run_counts_kernel
+__global__ __launch_bounds__(256) void count_offsets_kernel(const unsigned int* __restrict__ bidx, const unsigned int* __restrict__ ioff, int n,
+                                                            unsigned long long* __restrict__ coff, int* __restrict__ mins, int* __restrict__ maxs,
+                                                            unsigned int* __restrict__ areas) {
+    for (int i = blockIdx.x * 256 + threadIdx.x; i <= n; i += gridDim.x * 256) {         // ends: i grows by the grid
+        coff[i] = (unsigned long long)bidx[ioff[i]] + (unsigned long long)i;
+        if (i < n) { mins[2 * i] = 0x7fffffff; mins[2 * i + 1] = 0x7fffffff; maxs[2 * i] = 0; maxs[2 * i + 1] = 0; areas[i] = 0; }
+    }
+}
+
+// one lane per count: boundary minus the boundary before, the closing count up to area = h * w; the runs of ones give box {row, column} and
+// area by atomic min / max / add.  bnd: the boundaries of all masks back to back, mask i's behind the coff[i] - i of the masks before it
+__global__ __launch_bounds__(256) void run_counts_kernel(const unsigned int* __restrict__ bnd, const unsigned long long* __restrict__ coff, int n,
+                                                         unsigned long long total, int h, unsigned int area, unsigned int* __restrict__ counts,
+                                                         int* __restrict__ mins, int* __restrict__ maxs, unsigned int* __restrict__ areas) {
+    for (unsigned long long t = (unsigned long long)blockIdx.x * 256 + threadIdx.x; t < total; t += (unsigned long long)gridDim.x * 256) {   // ends: t grows by the grid
+        const int i = amp::owner_of(coff, n, t);                                         // coff[0] = 0 <= t < coff[n] = total, every mask has a count
+        const unsigned long long j = t - coff[i], nb = coff[i + 1] - coff[i] - 1, b0 = coff[i] - (unsigned long long)i;
+        const unsigned int s = j > 0 ? bnd[b0 + j - 1] : 0u, e = j < nb ? bnd[b0 + j] : area;
+        counts[t] = e - s;
+        if (!(j & 1ull) || e == s) continue;                                             // pixels [s, e) are a run of ones
+        const int cf = (int)(s / (unsigned)h), cl = (int)((e - 1) / (unsigned)h);
+        const int ra = cf == cl ? (int)(s - (unsigned)cf * (unsigned)h) : 0, rb = cf == cl ? (int)(e - (unsigned)cf * (unsigned)h) : h;
+        atomicMin(&mins[2 * (size_t)i], ra);
+        atomicMin(&mins[2 * (size_t)i + 1], cf);
+        atomicMax(&maxs[2 * (size_t)i], rb);
+        atomicMax(&maxs[2 * (size_t)i + 1], cl + 1);
+        atomicAdd(&areas[i], e - s);
     }
 }
 

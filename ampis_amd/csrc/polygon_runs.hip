@@ -19,10 +19,10 @@
 //  11. inclusive scan      of the deltas: the number of polygons that cover the pixels behind each toggle;
 //  12. pg_bound_kernel     one lane per group of equal (instance, position): a boundary where the cover leaves or reaches 0 over the group;
 //  13. exclusive scan      of the boundary flags;
-//  14. pg_instoff_kernel   where every instance's counts start (its boundaries and the closing count).  The host reads the total, reports the
+//  14. count_offsets_kernel where every instance's counts start (its boundaries and the closing count).  The host reads the total, reports the
 //                          need and refuses a capacity that is too small;
 //  15. pg_place_kernel     the boundary positions, in order;
-//  16. pg_counts_kernel    one lane per count: boundary minus the boundary before; the runs of ones give box and area by atomic min / max / add.
+//  16. run_counts_kernel   one lane per count: boundary minus the boundary before; the runs of ones give box and area by atomic min / max / add.
 // No buffer has a size fixed at compile time: one long edge or one polygon with tens of thousands of crossings is spread over lanes like any
 // other, and memory is linear in vertices + crossings + counts.  Double arithmetic as on the host (-ffp-contract=off, IEEE division); the
 // atomics are integer min / max / add whose order cannot show; every other word is written once by the lane that owns it.  So the bytes repeat
@@ -153,40 +153,10 @@ __global__ __launch_bounds__(256) void pg_bound_kernel(const u64* __restrict__ s
     }
 }
 
-// coff[i] = where instance i's counts start: the boundaries of the instances before it and one closing count each; the box and the area of
-// every instance preset for the atomics of pg_counts_kernel
-__global__ __launch_bounds__(256) void pg_instoff_kernel(const unsigned int* __restrict__ bidx, const unsigned int* __restrict__ ioff, int n,
-                                                         u64* __restrict__ coff, int* __restrict__ mins, int* __restrict__ maxs,
-                                                         unsigned int* __restrict__ areas) {
-    for (int i = blockIdx.x * 256 + threadIdx.x; i <= n; i += gridDim.x * 256) {         // ends: i grows by the grid
-        coff[i] = (u64)bidx[ioff[i]] + (u64)i;
-        if (i < n) { mins[2 * i] = 0x7fffffff; mins[2 * i + 1] = 0x7fffffff; maxs[2 * i] = 0; maxs[2 * i + 1] = 0; areas[i] = 0; }
-    }
-}
-
 __global__ __launch_bounds__(256) void pg_place_kernel(const u64* __restrict__ skeys2, unsigned int C, const unsigned int* __restrict__ flags,
                                                        const unsigned int* __restrict__ bidx, unsigned int* __restrict__ bnd) {
     for (unsigned int i = blockIdx.x * 256 + threadIdx.x; i < C; i += gridDim.x * 256)   // ends: i grows by the grid
         if (flags[i]) bnd[bidx[i]] = (unsigned int)((skeys2[i] >> 1) & 0x7fffffffull);
-}
-
-__global__ __launch_bounds__(256) void pg_counts_kernel(const unsigned int* __restrict__ bnd, const u64* __restrict__ coff, int n, u64 total, int h,
-                                                        unsigned int area, unsigned int* __restrict__ counts, int* __restrict__ mins,
-                                                        int* __restrict__ maxs, unsigned int* __restrict__ areas) {
-    for (u64 t = (u64)blockIdx.x * 256 + threadIdx.x; t < total; t += (u64)gridDim.x * 256) {   // ends: t grows by the grid
-        const int i = amp::owner_of(coff, n, t);                                         // coff[0] = 0 <= t < coff[n] = total, every instance has a count
-        const u64 j = t - coff[i], nb = coff[i + 1] - coff[i] - 1, b0 = coff[i] - (u64)i;
-        const unsigned int s = j > 0 ? bnd[b0 + j - 1] : 0u, e = j < nb ? bnd[b0 + j] : area;
-        counts[t] = e - s;
-        if (!(j & 1ull) || e == s) continue;                                             // pixels [s, e) are a run of ones
-        const int cf = (int)(s / (unsigned)h), cl = (int)((e - 1) / (unsigned)h);
-        const int ra = cf == cl ? (int)(s - (unsigned)cf * (unsigned)h) : 0, rb = cf == cl ? (int)(e - (unsigned)cf * (unsigned)h) : h;
-        atomicMin(&mins[2 * (size_t)i], ra);
-        atomicMin(&mins[2 * (size_t)i + 1], cf);
-        atomicMax(&maxs[2 * (size_t)i], rb);
-        atomicMax(&maxs[2 * (size_t)i + 1], cl + 1);
-        atomicAdd(&areas[i], e - s);
-    }
 }
 
 // one allocation cut into aligned pieces
@@ -295,7 +265,7 @@ int polygons_device(amp_ctx* ctx, const double* xy, const unsigned long long* po
     AMP_HIP_CHECK(hipGetLastError());
     q = tmp_b;
     AMP_HIP_CHECK(rocprim::exclusive_scan(B + o_tmpb, q, g_flags, g_bidx, 0u, (size_t)C + 1, rocprim::plus<unsigned int>(), st));
-    hipLaunchKernelGGL(pg_instoff_kernel, grid_256((u64)n + 1), dim3(256), 0, st, g_bidx, g_ioff, n, g_coff, g_mins, g_maxs, g_areas);
+    hipLaunchKernelGGL(count_offsets_kernel, grid_256((u64)n + 1), dim3(256), 0, st, g_bidx, g_ioff, n, g_coff, g_mins, g_maxs, g_areas);
     AMP_HIP_CHECK(hipGetLastError());
     std::vector<u64> coff((size_t)n + 1);
     AMP_HIP_CHECK(hipMemcpyAsync(coff.data(), g_coff, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, st));
@@ -315,7 +285,7 @@ int polygons_device(amp_ctx* ctx, const double* xy, const unsigned long long* po
     unsigned int *g_bnd = (unsigned int*)(d_c.as<char>() + o_bnd), *g_counts = (unsigned int*)(d_c.as<char>() + o_counts);
     hipLaunchKernelGGL(pg_place_kernel, grid_256(C), dim3(256), 0, st, g_k2, C, g_flags, g_bidx, g_bnd);
     AMP_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(pg_counts_kernel, grid_256(total), dim3(256), 0, st, g_bnd, g_coff, n, (u64)total, h, area, g_counts, g_mins, g_maxs, g_areas);
+    hipLaunchKernelGGL(run_counts_kernel, grid_256(total), dim3(256), 0, st, g_bnd, g_coff, n, (u64)total, h, area, g_counts, g_mins, g_maxs, g_areas);
     AMP_HIP_CHECK(hipGetLastError());
     std::vector<int> mins(2 * (size_t)n), maxs(2 * (size_t)n);
     std::vector<unsigned int> ar((size_t)n);

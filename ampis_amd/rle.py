@@ -531,6 +531,54 @@ def mask_contours(masks, connectivity=2, ctx=None, size=None):
             xy[:nv].copy())
 
 
+MORPH_OPS = {"dilate": 0, "erode": 1, "open": 2, "close": 3, "band_in": 4, "band_out": 5}
+MORPH_SHAPES = {"square": 0, "diamond": 1, "disk": 2}
+MORPH_MAX_RADIUS = 1024
+
+
+def morphology(masks, op, shape='disk', radius=1, border_value=0, ctx=None, size=None, return_stats=False):
+    """Mask morphology on RLE dicts of one image size, one C call (amp_mask_morphology; a second one when the first reports that the capacity
+    guess was too small).  op: 'dilate', 'erode', 'open' (the dilation of the erosion), 'close' (the erosion of the dilation), 'band_in' (the
+    mask minus its erosion) or 'band_out' (its dilation minus the mask); shape: 'square' (Chebyshev distance), 'diamond' (city-block) or 'disk'
+    (Euclidean, dx^2 + dy^2 <= radius^2); radius: an integer 0 .. 1024; border_value: what an erosion takes the outside of the image for, 0
+    (scipy's default: a mask erodes from the image's sides) or 1 (cv2's default).  Returns the list of RLE dicts in canonical form -- what
+    encode gives for the dense result --, length and order unchanged; with return_stats also the int64 [n, 4] tight boxes {r0, c0, r1, c1}
+    (ends exclusive, zeros for an empty result) and the int64 [n] areas of the results.  radius 0 gives the canonical form of the input (empty
+    masks for the bands).  size=(h, w) is needed only when there is no mask.  ValueError for an unknown op or shape, a radius or border value
+    out of range and masks of different sizes.  ctx: a _lib.Context (computed on its device) or None (on the host): the same bytes."""
+    if op not in MORPH_OPS:
+        raise ValueError(f"morphology: op = {op!r} (one of {sorted(MORPH_OPS)})")
+    if shape not in MORPH_SHAPES:
+        raise ValueError(f"morphology: shape = {shape!r} (one of {sorted(MORPH_SHAPES)})")
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= int(radius) <= MORPH_MAX_RADIUS:
+        raise ValueError(f"morphology: radius = {radius!r} (an integer 0 .. {MORPH_MAX_RADIUS})")
+    if isinstance(border_value, bool) or border_value not in (0, 1):
+        raise ValueError(f"morphology: border_value = {border_value!r} (0 or 1)")
+    n = len(masks)
+    sizes = {tuple(int(v) for v in r["size"]) for r in masks}
+    if size is not None:
+        sizes.add((int(size[0]), int(size[1])))
+    if len(sizes) > 1:
+        raise ValueError(f"morphology: masks of different sizes {sorted(sizes)}")
+    boxes, areas = np.zeros((n, 4), dtype=np.int64), np.zeros(n, dtype=np.uint64)
+    if n == 0:
+        return ([], boxes, areas.astype(np.int64)) if return_stats else []
+    h, w = sizes.pop()
+    pool, off, ln = _pool([_counts(x) for x in masks])
+    out_off, out_len, need = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.int32), np.zeros(1, dtype=np.uint64)
+    cap = 2 * int(ln.sum()) + 64                                    # a guess: a result has about as many runs as its input
+    for attempt in range(2):
+        out = np.empty(cap, dtype=np.uint32)
+        st = lib().amp_mask_morphology(_handle(ctx), _vp(pool), _vp(off), _vp(ln), n, h, w, MORPH_OPS[op], MORPH_SHAPES[shape], int(radius),
+                                       int(border_value), _vp(out), cap, _vp(out_off), _vp(out_len), _vp(boxes), _vp(areas), _vp(need))
+        if st != -3 or attempt:                                     # AMP_ERR_NOMEM the first time: the need is known now
+            check(st, "amp_mask_morphology")
+            break
+        cap = max(int(need[0]), 1)
+    res = [{"size": [h, w], "counts": c} for c in counts_to_strings(out[: int(need[0])], out_off, out_len)]
+    return (res, boxes, areas.astype(np.int64)) if return_stats else res
+
+
 def merge(rles, intersect=False):
     assert len(rles) >= 1
     h, w = rles[0]["size"]

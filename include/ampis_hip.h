@@ -713,6 +713,40 @@ int amp_mask_contours(amp_ctx* ctx, const uint32_t* pool, const unsigned long lo
                       unsigned long long* ring_first /* [n + 1] */, unsigned long long* ring_off, int* ring_len, long long* ring_area2,
                       long long* ring_length, unsigned long long ring_cap, int* xy, unsigned long long xy_cap,
                       unsigned long long* need /* [2] */);
+/* Mask morphology on run lists: the n run lists pool[off[i] : off[i] + len[i]] of one h x w image size (1 <= h, w <= 32768, h * w <= 2^30)
+ * dilated, eroded, opened, closed or reduced to a boundary band in one call, without a dense mask.  ALL POINTERS ARE HOST POINTERS.  The
+ * structuring element is the set of offsets (dx, dy) with |dx| <= radius and |dy| <= hh(dx):
+ *   AMP_MORPH_SQUARE   hh = radius                             Chebyshev distance, the 3 x 3 ones element iterated radius times;
+ *   AMP_MORPH_DIAMOND  hh = radius - |dx|                      city-block distance, the 3 x 3 cross iterated radius times;
+ *   AMP_MORPH_DISK     hh = isqrt(radius^2 - dx^2)             Euclidean distance, dx^2 + dy^2 <= radius^2.
+ * A piece is a maximal vertical run of ones [s, e) of one column x; it sends to every output column x + dx inside the image
+ *   dilation: the rows [max(s - hh, 0), min(e + hh, h)) with weight 1; a pixel is set where the weights covering it sum to at least 1;
+ *   erosion:  the rows [s + hh, e - hh), empty ones dropped; with border_value 1 an end on the image's first row (s == 0) or behind its last
+ *             (e == h) is not moved.  A pixel of column x is set where the cover equals K(x): 2 * radius + 1 with border_value 0 (the outside
+ *             of the image is background, a mask erodes from the image's sides), the number of columns x - dx inside the image with
+ *             border_value 1 (the outside counts as mask).
+ *   AMP_MORPH_OPEN = dilation of the erosion, AMP_MORPH_CLOSE = erosion of the dilation, border_value used by the erosion; AMP_MORPH_BAND_IN =
+ *   the mask minus its erosion, AMP_MORPH_BAND_OUT = its dilation minus the mask (the mask's own pieces enter with weight 2^32).
+ * Mask i's result is the canonical run list of the dense result, what amp_rle_encode gives (the first count may be 0), at
+ * out_pool[out_off[i] : out_off[i] + out_len[i]]; boxes[i] = its tight box {r0, c0, r1, c1}, ends exclusive, as amp_polygons_to_rle reports
+ * it (zeros for an empty result), areas[i] its pixels.  radius == 0 gives the canonical form of the input (an empty mask for the bands).
+ * With valid arguments need[0] = the counts of all results is always written; with out_cap below it the call returns AMP_ERR_NOMEM and writes
+ * nothing else.  No closed form bounds the need: a result can have more runs than its input as well as fewer; call again with need[0].
+ * Checked on the host before any device work (AMP_ERR_ARG naming the offender, nothing written): the sizes, n < 0, op, shape, border_value
+ * (0 or 1), radius (0 .. 1024), NULL pointers, every run list non-empty and summing to h * w, and the events of the call: summed over the
+ * pieces, 2 x the output columns inside the image (one more for a band) must stay below 2^31.  The second pass of an opening or closing is
+ * held to the same limit on the events it really emits, once the first pass is known.  n == 0, empty masks, full masks and zero-length
+ * runs are valid.
+ * ctx == NULL: computed on the host (morphology_host.hip: a sweep per mask and output column).  Otherwise on ctx's device and stream
+ * (morphology.hip): upload, a fixed list of launches whatever the masks hold (twice for an opening or closing, the intermediate stays on the
+ * device), download; integer arithmetic only, the bytes do not depend on the device's scheduling and equal the host's. */
+enum { AMP_MORPH_DILATE = 0, AMP_MORPH_ERODE = 1, AMP_MORPH_OPEN = 2, AMP_MORPH_CLOSE = 3, AMP_MORPH_BAND_IN = 4, AMP_MORPH_BAND_OUT = 5 };
+enum { AMP_MORPH_SQUARE = 0, AMP_MORPH_DIAMOND = 1, AMP_MORPH_DISK = 2 };
+#define AMP_MORPH_MAX_RADIUS 1024
+int amp_mask_morphology(amp_ctx* ctx, const uint32_t* pool, const unsigned long long* off, const int* len, int n, int h, int w, int op,
+                        int shape, int radius, int border_value, uint32_t* out_pool, unsigned long long out_cap,
+                        unsigned long long* out_off /* [n] */, int* out_len /* [n] */, long long* boxes /* [n][4] */,
+                        unsigned long long* areas /* [n] */, unsigned long long* need /* [1] */);
 
 /* The model: DefaultPredictor(cfg) / predictor(img) ---------------------------------------------- */
 typedef struct amp_model amp_model;
