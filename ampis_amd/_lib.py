@@ -278,6 +278,7 @@ def _declare(L):
         "amp_box_loss_ex": ([vp, i, i, i, vp, i, vp, vp, vp, vp, vp, vp, C.POINTER(f), i, vp, C.POINTER(LossOpts)], i),
         "amp_model_set_loss_opts": ([vp, C.POINTER(LossOpts)], i),
         "amp_model_get_loss_opts": ([vp, C.POINTER(LossOpts)], i),
+        "amp_model_f32_reruns": ([vp, C.POINTER(C.c_int)], i),
         "amp_mask_target_loss": ([vp, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp], i),
         "amp_grouped_wgrad_scratch_floats": ([C.POINTER(ConvDesc)], C.c_size_t),
         "amp_conv2d_grouped_wgrad": ([vp, C.POINTER(ConvDesc), i, vp, vp, vp, vp, vp], i),

@@ -1260,6 +1260,9 @@ __device__ __forceinline__ void conv_epilogue_rpn_rows(const ConvArgs& a, f32x4 
                     o[0] = fmaxf(o[0], 0.f); o[1] = fmaxf(o[1], 0.f);
                     const f16x2 h = __builtin_convertvector(o, f16x2);
                     const f32x2 hf = {(float)h[0], (float)h[1]};
+                    // the hidden value is an OPERAND of the product below, never stored: finite sums whose FrozenBN + ReLU leave the f16 range
+                    // (hi = inf) have no consumer that would notice, so the half itself is checked
+                    if (j == 0) chk = __builtin_elementwise_fma(hf, f32x2{0.f, 0.f}, chk);
                     const f32x2 l = __builtin_elementwise_fma(hf, f32x2{-LO_SCALE, -LO_SCALE}, o * LO_SCALE);
                     const f16x2 lh = __builtin_convertvector(l, f16x2);
                     hi[2 * p] = h[0]; hi[2 * p + 1] = h[1];

@@ -2234,6 +2234,8 @@ int amp_model_infer(amp_model* m, const uint8_t* imgs_bgr, int imgs_on_host, int
     if (out_h_h && out_w_h) { oh.assign(out_h_h, out_h_h + B); ow.assign(out_w_h, out_w_h + B); }
     AMP_HIP_CHECK(hipSetDevice(m->ctx->device));
     AMP_HIP_CHECK(hipMemsetAsync(m->d_flags, 0, 4 * sizeof(int), m->ctx->stream));
+    // the range flag this call reads is the one ITS kernels raise: a flag an earlier op-level call left on the context is dropped here, in stream order
+    if (m->ctx->conv_mode == AMP_CONV_F16X3) AMP_HIP_CHECK(hipMemsetAsync(m->ctx->d_conv_flag, 0, sizeof(int), m->ctx->stream));
     const uint8_t* imgs_d = imgs_bgr;
     if (imgs_on_host) {
         AMP_TRY(stage_images(m, imgs_bgr, (size_t)B * H * W * 3));
@@ -2465,6 +2467,9 @@ static int train_entry(amp_model* m, const uint8_t* imgs_bgr, int imgs_on_host, 
         return AMP_OK;
     };
     std::string first_error;
+    // the verdict is about THIS step: a range flag an earlier op-level call left on the context is dropped first, in stream order, by every rank
+    // at the same point (before anything of the step can fail, so before the first agree())
+    AMP_HIP_CHECK(hipMemsetAsync(m->ctx->d_conv_flag, 0, sizeof(int), m->ctx->stream));
     int st = prepare();
     if (st == AMP_OK) st = run_train(m, imgs_d, B, H, W, gt, seed, losses_h, backward != 0);
     m->ctx->conv_mode = mode;
@@ -2500,6 +2505,12 @@ static int train_entry(amp_model* m, const uint8_t* imgs_bgr, int imgs_on_host, 
         }
     }
     return st;
+}
+
+int amp_model_f32_reruns(amp_model* m, int* count) {
+    AMP_REQUIRE(m && count, "amp_model_f32_reruns: null argument");
+    *count = m->f32_reruns;
+    return AMP_OK;
 }
 
 int amp_model_set_loss_opts(amp_model* m, const amp_loss_opts* opts) {

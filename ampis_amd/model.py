@@ -461,6 +461,13 @@ class MaskRCNN:
         names = {v: k for k, v in _lib.BOXLOSS_TYPES.items()}
         return {k: names[getattr(o, k)] if k.endswith("_loss_type") else float(getattr(o, k)) for k in _lib.LOSS_OPT_KEYS}
 
+    @property
+    def f32_reruns(self):
+        """How many infer batches / training steps of this model were run again in AMP_CONV_F32 after a split kernel raised the range flag."""
+        n = C.c_int(0)
+        check(lib().amp_model_f32_reruns(self._h, C.byref(n)), "amp_model_f32_reruns")
+        return int(n.value)
+
     def set_image_sizes(self, sizes):
         """sizes: list of (h, w) valid extents inside the common frame for the next batches, or None."""
         if sizes is None:

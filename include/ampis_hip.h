@@ -853,6 +853,10 @@ int  amp_model_forward_backward(amp_model* m, const uint8_t* imgs_bgr, int imgs_
 int  amp_model_set_loss_opts(amp_model* m, const amp_loss_opts* opts);
 int  amp_model_get_loss_opts(amp_model* m, amp_loss_opts* opts);
 int  amp_model_grad_arena(amp_model* m, float** grads_dev, size_t* nfloats);
+/* How many amp_model_infer batches / training steps of this model were run a second time in AMP_CONV_F32 because a split kernel raised the
+ * range flag (amp_conv_range_flag) during the call.  A model call clears the context's flag on entry, in stream order: only its own kernels
+ * decide, never a flag an earlier op-level call left behind. */
+int  amp_model_f32_reruns(amp_model* m, int* count);
 /* the SGD momentum buffers: one arena with the parameters' offsets (like amp_model_grad_arena).  The layout depends on the model
  * configuration only (classes, backbone), not on the capacity: a host can carry it over to a re-created model or into a checkpoint. */
 int  amp_model_momentum_arena(amp_model* m, float** vel_dev, size_t* nfloats);

@@ -86,6 +86,20 @@ def assert_sum_bound(amax_a, amax_b, K, what):
     assert float(amax_a) * float(amax_b) * K < 2.0 ** 24, f"{what}: sum |a||b| may reach 2^24 ({amax_a} x {amax_b} x {K})"
 
 
+def assert_conv_sum_bound(x, w, in_shift, stride, pad, groups, check=True):
+    """sum |x||w| < 2^24 at every output: from the largest |x| and |w| and K where that already shows it, else from the convolution of the
+    magnitudes (a single element near the edge of the f16 range among small ones).  A non-finite operand (check=False only: a poisoned
+    tensor has no exact sum) is left out of the bound."""
+    ax, aw = np.abs(np.asarray(x, F64)) * 2.0 ** in_shift, np.abs(np.asarray(w, F64))
+    if not check:
+        ax, aw = np.where(np.isfinite(ax), ax, 0.0), np.where(np.isfinite(aw), aw, 0.0)
+    assert np.isfinite(ax).all() and np.isfinite(aw).all(), "conv: a non-finite operand has no exact reference"
+    if ax.max() * aw.max() * (w.shape[1] * w.shape[2] * w.shape[3]) < 2.0 ** 24:
+        return
+    worst = conv_sum(ax, aw, stride, pad, groups).max()
+    assert worst < 2.0 ** 24, f"conv: sum |x||w| reaches {worst} >= 2^24 at some output"
+
+
 def out_hw(H, W, KH, KW, stride, pad):
     return (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
 
@@ -138,10 +152,9 @@ def conv_ref(x, w, scale=None, shift=None, res=None, mask=None, *, stride=1, pad
     mask is indexed like y.  low: None (class I), 'x' or 'w' (class L: which operand carries the low half).  check=False skips the
     representability assertions (a reference with a seeded defect).  Returns float32."""
     x, w = np.asarray(x, F32), np.asarray(w, F32)
-    Cout, KH, KW, cpg = w.shape
-    K = KH * KW * cpg
+    Cout = w.shape[0]
     f32_check = assert_f32 if check else (lambda a, what: None)
-    assert_sum_bound(np.abs(x).max() * 2.0 ** in_shift, np.abs(w).max(), K, "conv")
+    assert_conv_sum_bound(x, w, in_shift, stride, pad, groups, check)
     xs, ws = x, w
     if defect == "cross_term":
         assert low in ("x", "w")
@@ -232,7 +245,10 @@ def wgrad_ref(x, dy, KH, KW, scale=None, grad=None, bias_grad=None, *, stride=1,
     f32_check = assert_f32 if check else (lambda a, what: None)      # check=False: a reference with a seeded defect
     M = dy.shape[0] * dy.shape[1] * dy.shape[2]
     # the bound is on the values the kernel multiplies: dy * 2^dy_shift
-    assert_sum_bound(np.abs(x).max(), np.abs(dy).max() * 2.0 ** dy_shift, M, "wgrad slab")
+    if not float(np.abs(x).max()) * float(np.abs(dy).max()) * 2.0 ** dy_shift * M < 2.0 ** 24:
+        # a single element near the edge of the f16 range among small ones: the bound from the sums of the magnitudes themselves
+        worst = wgrad_sum(np.abs(x), np.abs(dy) * 2.0 ** dy_shift, KH, KW, stride, pad).max()
+        assert worst < 2.0 ** 24, f"wgrad slab: sum |x||dy| reaches {worst} >= 2^24"
     xs, ds = x, dy
     if defect == "cross_term":
         assert low in ("x", "dy")

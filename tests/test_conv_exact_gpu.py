@@ -291,47 +291,71 @@ def set_switches(L, sw):
         getattr(L, SW_SETTER[k])(int(v))
 
 
-def run_case(ctx, c, cls):
+def planned(c):
+    """(the 22 plan inputs, the kernel name the rules give): the case must get the kernel and the epilogue it is meant for"""
+    import conv_plan_table as T
+    inputs, switches = plan_inputs(c)
+    chosen = T.plan(inputs, switches)
+    assert (chosen[0], chosen[1]) == (c["kernel"], c["epi"]), f"{c['name']}: the plan gives {chosen}, the case is meant for {c['kernel']} with epilogue {c['epi']}"
+    return inputs, chosen[0]
+
+
+def upload(c, d, kernel):
+    """the operands on the device in the formats of the case, and the weight forms it is launched with: split by conv_run per call (the public
+    entries), and -- the split arithmetic only -- split beforehand as amp_model_finalize keeps them (here by the CPU reference of the format, so
+    that no device split kernel stands between the operands and the convolution)"""
+    import torch
+    fmt = c["fmt"]
+    dev = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
+    t = dict(x=dev(R.split_rows_ref(d["x"], c["in_shift"]) if fmt & X_SPLIT else d["x"]),
+             w=dev(R.group_window_weights(d["w"], c["Cin"] // c["groups"]) if c["groups"] > 1 else d["w"]),
+             res=dev(R.split_rows_ref(d["res"]) if (fmt & RES_SPLIT) else d["res"]),
+             mask=dev(R.split_rows_ref(d["mask"]) if (fmt & MASK_SPLIT) else d["mask"]), scale=dev(d["scale"]), shift=dev(d["shift"]))
+    w_np = np.ascontiguousarray(t["w"].cpu().numpy())
+    t["w_forms"] = [("split per call", None)]
+    if kernel.startswith(("F16X3", "SPLIT", "NLOOP", "C64", "PATCH")):
+        t["w_forms"].append(("weights split beforehand", dev(R.split_rows_ref(w_np.reshape(c["Cout"], -1)))))
+    return t
+
+
+def launch(ctx, c, inputs, t, w_split, y):
+    """one amp_debug_conv_run of the case under its switches and mode; amp_debug_conv_plan is asked first (the process's current state, what
+    conv_run is about to read), so the case cannot drift to another kernel"""
     import torch
     import conv_plan_table as T
     from ampis_amd._lib import ConvDesc, check, ptr
     L = _lib()
-    inputs, switches = plan_inputs(c)
-    chosen = T.plan(inputs, switches)
-    assert (chosen[0], chosen[1]) == (c["kernel"], c["epi"]), f"{c['name']}: the plan gives {chosen}, the case is meant for {c['kernel']} with epilogue {c['epi']}"
-    d = operands(c, cls)
-    want = reference(c, cls, d)
-    fmt = c["fmt"]
-    dev = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
-    x = dev(R.split_rows_ref(d["x"], c["in_shift"]) if fmt & X_SPLIT else d["x"])
-    w = dev(R.group_window_weights(d["w"], c["Cin"] // c["groups"]) if c["groups"] > 1 else d["w"])
-    res = dev(R.split_rows_ref(d["res"]) if (fmt & RES_SPLIT) else d["res"])
-    mask = dev(R.split_rows_ref(d["mask"]) if (fmt & MASK_SPLIT) else d["mask"])
-    scale, shift = dev(d["scale"]), dev(d["shift"])
-    # the weights: split by conv_run per call (the public entries), and -- the split arithmetic only -- split beforehand as amp_model_finalize keeps them
-    # (here by the CPU reference of the format, so that no device split kernel stands between the operands and the convolution)
-    w_np = np.ascontiguousarray(w.cpu().numpy())
-    w_forms = [("split per call", None)]
-    if chosen[0].startswith(("F16X3", "SPLIT", "NLOOP", "C64", "PATCH")):
-        w_forms.append(("weights split beforehand", dev(R.split_rows_ref(w_np.reshape(c["Cout"], -1)))))
     desc = ConvDesc(c["B"], c["H"], c["W"], c["Cin"], c["Cout"], c["KH"], c["KW"], c["stride"], c["pad"], c["relu"], c["res_mode"], c["out_mode"])
-    want_bits = R.split_rows_ref(want) if fmt & Y_SPLIT else want
+    ctx.conv_mode = c["mode"]
+    try:
+        set_switches(L, c["sw"])
+        now = T.PlanOut()      # a null switch vector: the process's current state
+        assert T._lib().amp_debug_conv_plan((C.c_int * 22)(*inputs), None, C.byref(now)) == 0
+        assert T.kernel_names()[now.kernel] == c["kernel"] and now.epi == c["epi"], "the process's switch state gives another launch than the case's switch vector"
+        check(L.amp_debug_conv_run(ctx.handle, C.byref(desc), c["groups"], ptr(t["x"]), ptr(t["w"]), ptr(w_split), ptr(t["scale"]), ptr(t["shift"]), ptr(t["res"]),
+                                   ptr(t["mask"]), ptr(y), c["in_shift"], c["fmt"], c["force_f32"]), "amp_debug_conv_run")
+        torch.cuda.synchronize()
+    finally:
+        set_switches(L, {k: SW_DEFAULT[k] for k in c["sw"]})
+        ctx.conv_mode = "f16x3"
+
+
+def case_tile_m(c):
+    return 256 if c["kernel"] in ("SPLIT_256x128", "SPLIT_TALL64") else 128
+
+
+def run_case(ctx, c, cls, d=None):
+    """d: other operands than the case's own (tests/test_range_guard_gpu.py: the in-range edge)"""
+    inputs, kernel = planned(c)
+    d = operands(c, cls) if d is None else d
+    want = reference(c, cls, d)
+    t = upload(c, d, kernel)
+    want_bits = R.split_rows_ref(want) if c["fmt"] & Y_SPLIT else want
     ctx.conv_range_flag()
-    for form, w_split in w_forms:
+    for form, w_split in t["w_forms"]:
         buf, y, g = guarded(want.shape, zero_fill=c["out_mode"] == 2)
-        ctx.conv_mode = c["mode"]
-        try:
-            set_switches(L, c["sw"])
-            now = T.PlanOut()      # a null switch vector: the process's current state, what conv_run is about to read
-            assert T._lib().amp_debug_conv_plan((C.c_int * 22)(*inputs), None, C.byref(now)) == 0
-            assert T.kernel_names()[now.kernel] == c["kernel"] and now.epi == c["epi"], "the process's switch state gives another launch than the case's switch vector"
-            check(L.amp_debug_conv_run(ctx.handle, C.byref(desc), c["groups"], ptr(x), ptr(w), ptr(w_split), ptr(scale), ptr(shift), ptr(res), ptr(mask), ptr(y),
-                                       c["in_shift"], fmt, c["force_f32"]), "amp_debug_conv_run")
-            torch.cuda.synchronize()
-        finally:
-            set_switches(L, {k: SW_DEFAULT[k] for k in c["sw"]})
-            ctx.conv_mode = "f16x3"
-        check_guarded(buf, g, want_bits, want.shape[-1], f"{c['name']} [{cls}] {c['kernel']}, {form}", 256 if c["kernel"] in ("SPLIT_256x128", "SPLIT_TALL64") else 128)
+        launch(ctx, c, inputs, t, w_split, y)
+        check_guarded(buf, g, want_bits, want.shape[-1], f"{c['name']} [{cls}] {c['kernel']}, {form}", case_tile_m(c))
     assert not ctx.conv_range_flag(), "the range flag must stay clear"
     assert np.abs(want).max() > 0
 
