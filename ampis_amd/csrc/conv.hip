@@ -1,4 +1,8 @@
-// Implicit-GEMM convolution, fp32 in / fp32 accumulate on the gfx950 f32 MFMA (v_mfma_f32_32x32x2_f32).
+// Convolution as implicit GEMM on the gfx950 matrix pipe: every kernel family, the launch table (conv_run) and the C entry points, one translation
+// unit.  The pieces the families share are headers: conv_args.h (types, ConvArgs), conv_epilogue.h (the epilogues, the f16x3 MFMA step); so are the
+// pure kernel selection, conv_plan.h, and the first family cut out, conv_nloop.h.  The other families and the weight-layout kernels stand below in
+// the order the listing has them (which orders are part of the machine code); the tiling paragraph that follows describes the fp32
+// kernel, conv_mfma_kernel.
 //
 // Replaces the cuDNN convolutions detectron2 runs for AMPIS:
 // ResNet-50 stem+res2..res5, FPN lateral/output convs, the RPN head, the box-head FCs (as 1x1 convs over
@@ -17,740 +21,12 @@
 #include "common.h"
 #include <type_traits>
 #include "lds_ring.h"
+#include "conv_args.h"          // types, BK, ConvArgs, fastdiv, conv_pixel
+#include "conv_epilogue.h"      // the epilogues and the f16x3 MFMA step
+#include "conv_nloop.h"         // conv1x1_nloop_kernel (experiment, default off)
+#include "conv_plan.h"          // ConvSwitches, conv_plan (host only)
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int BK = 32;      // K-slice per step (floats)
-constexpr int LDS_LD = 36;  // padded row length in LDS (floats): 144 B rows -> conflict-free ds_read_b128
-
-struct ConvArgs {
-    const float* x;
-    const float* w;
-    const float* scale;
-    const float* shift;
-    const float* res;
-    const float* mask;   // optional, indexed like y: y = mask > 0 ? y : 0 (ReLU backward of the tensor the gradient belongs to)
-    float* y;
-    int B, H, W, Cin;
-    int Ho, Wo, Cout;
-    int KH, KW, stride, pad;
-    int M, K, nsteps;
-    int relu, res_mode, out_mode;
-    int ntn;  // number of N tiles
-    float in_scale, out_scale;   // f16x3 kernels: activations are multiplied by in_scale (a power of two) before the split, the sum by out_scale
-    int y_split;            // 1: y is written in the split hi|lo' row format (out_mode 0, Cout % 32 == 0): the next conv's operand
-    // out_mode 3 (conv_split_kernel<128,256> only): the ConvTranspose 2x2 of the mask head with its consumers fused into the epilogue --
-    // ReLU, the 1x1 predictor row of the detection's class, sigmoid -- so the [N,28,28,256] tensor never exists (see conv_epilogue_predict)
-    const float* pred_w;    // [K][C2] predictor weights (fp32), C2 = Cout / 4 = 256
-    const float* pred_b;    // [K]
-    const int* pred_cls;    // [B] class of each RoI (row b of the input)
-    int pred_K;
-    // out_mode 4 (conv_split_kernel<128,256> only): the RPN head's tail -- ReLU, then the 16 predictor rows (3 objectness + 12 deltas + pad) as a
-    // second f16x3 product in the epilogue (conv_epilogue_rpn); the 256-channel hidden tensor is never written
-    const float* rpn_w;     // [16][Cout] split rows
-    const float* rpn_b;     // [16]
-    float* rpn_pred;        // [M][16 NBP], NBP = 1, 2, 3 blocks of 16 predictor rows (the epilogue's template argument; amp::rpn_ld)
-    float* prob;            // [B][2Ho][2Wo] mask probabilities
-    int res_split;          // 1: res is in that format too (decoded in the epilogue: hi + lo' * 2^-11, exact in fp32)
-    int mask_split;         // 1: the ReLU mask tensor (training: the forward activation) is in that format (AMP_FMT_MASK_SPLIT)
-    int direct_epi;         // conv_split_kernel: split rows written straight from the accumulators (0: staged through LDS, the form before it; always 1 now)
-    int stagger;            // conv_split_kernel: the two halves of the workgroup ping-pong between loading and multiplying (0: lockstep; EXPERIMENT switch AMP_STAGGER)
-    int* range_flag;        // f16x3 kernels: set to 1 when an accumulator is not finite (operand beyond fp16 range)
-    int cin_win, grouped;   // K runs over KH*KW*cin_win input channels; grouped: the window of N-tile n0 starts at channel n0
-    int nblk;
-    int korder;             // conv_split_kernel: 0 = K runs tap-major (ky, kx, then the 32-channel slices), 1 = channel-major (slice, then the KH*KW taps:
-                            // the nine taps of a slice re-read the same cache lines within nine K-steps, while they are still in the XCD's L2)
-    unsigned int div_howo_mul, div_wo_mul;   // x / d == (x * mul) >> shr for every x < 2^29 (Granlund-Montgomery, mul = ceil(2^shr / d))
-    int div_howo_shr, div_wo_shr;
-};
-
-__device__ __forceinline__ unsigned int fastdiv(unsigned int x, unsigned int mul, int shr) {
-    return (unsigned int)(((unsigned long long)x * mul) >> shr);
-}
-
-// GEMM row m -> output pixel (image b, row oy, column ox) through the two multiply-shift divisions conv_run prepared
-__device__ __forceinline__ void conv_pixel(const ConvArgs& a, unsigned int m, unsigned int& b, unsigned int& oy, unsigned int& ox) {
-    b = fastdiv(m, a.div_howo_mul, a.div_howo_shr);
-    const unsigned int rem = m - b * (unsigned int)(a.Ho * a.Wo);
-    oy = fastdiv(rem, a.div_wo_mul, a.div_wo_shr);
-    ox = rem - oy * (unsigned int)a.Wo;
-}
-
-// Epilogue shared by both kernels: accumulators -> LDS (per-wave tile, [m][n]) -> row-wise float4 residual loads + stores.
-// The MFMA C layout puts one n per lane and 16 m in registers: stored directly that is 64 dword stores per lane and,
-// with a residual, 64 dependent dword loads.  Transposed through LDS every lane owns 4 consecutive n of one row per step:
-// 16-B coalesced residual loads (all issued before the first store) and 16-B stores.  Callers pass the wave's tile origin
-// (mw0, nw0) and must have synchronised the workgroup after the last operand reads.
-template <int WTM, int WTN>
-__device__ __forceinline__ void conv_epilogue_generic_rows(const ConvArgs& a, float* stage, int lane, int mw0, int nw0, int HoWo);
-
-template <int WTM, int WTN, int MT, int NT, bool CHECK = false>
-__device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[MT][NT], float* lds, int wave, int lane,
-                                              int mw0, int nw0, int HoWo) {
-    if (CHECK) {
-        bool bad = false;
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < NT; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) bad = bad || !(fabsf(acc[i][j][e]) <= 3.0e38f);
-        if (bad) atomicOr(a.range_flag, 1);
-    }
-    const int l31 = lane & 31, lh = lane >> 5;
-    constexpr int SLD = WTN + 4;                       // padded row of the staging tile (floats)
-    float* stage = lds + wave * (WTM * SLD);
-    // (the loop's last __syncthreads() already ordered every wave's operand reads before these writes)
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e)
-                stage[(i * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh) * SLD + j * 32 + l31] = acc[i][j][e];
-    conv_epilogue_generic_rows<WTM, WTN>(a, stage, lane, mw0, nw0, HoWo);
-}
-
-// the same from MB x NB blocks of 16x16 MFMA accumulators
-template <int WTM, int WTN, int MB, int NB, bool CHECK = false>
-__device__ __forceinline__ void conv_epilogue16(const ConvArgs& a, f32x4 (&acc)[MB][NB], float* lds, int wave, int lane,
-                                                int mw0, int nw0, int HoWo) {
-    if (CHECK) {
-        bool bad = false;
-#pragma unroll
-        for (int i = 0; i < MB; ++i)
-#pragma unroll
-            for (int j = 0; j < NB; ++j)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) bad = bad || !(fabsf(acc[i][j][e]) <= 3.0e38f);
-        if (bad) atomicOr(a.range_flag, 1);
-    }
-    const int l15 = lane & 15, lq = lane >> 4;
-    constexpr int SLD = WTN + 4;
-    float* stage = lds + wave * (WTM * SLD);
-#pragma unroll
-    for (int i = 0; i < MB; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                stage[(i * 16 + 4 * lq + e) * SLD + j * 16 + l15] = acc[i][j][e];
-    conv_epilogue_generic_rows<WTM, WTN>(a, stage, lane, mw0, nw0, HoWo);
-}
-
-template <int WTM, int WTN>
-__device__ __forceinline__ void conv_epilogue_generic_rows(const ConvArgs& a, float* stage, int lane, int mw0, int nw0, int HoWo) {
-    constexpr int SLD = WTN + 4;                       // padded row of the staging tile (floats)
-    constexpr int F4R = WTN / 4;                       // float4 per row
-    constexpr int RPI = 64 / F4R;                      // rows per iteration (one wave)
-    constexpr int NIT = WTM / RPI;
-
-    const int erow = lane / F4R;                       // row within an iteration
-    const int ec4 = lane % F4R;
-    const int n = nw0 + ec4 * 4;
-    const bool vec = (a.Cout & 3) == 0;                // rows of y / res are 16-B aligned
-    const bool nv = n < a.Cout;
-    f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        if (n + q < a.Cout) {
-            if (a.scale) sc[q] = a.scale[n + q];
-            if (a.shift) sh[q] = a.shift[n + q];
-        }
-    }
-    const int C2 = a.Cout >> 2;                        // deconv scatter only
-
-    size_t yoff[NIT];
-    f32x4 rres[NIT];
-    bool mv[NIT];
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int m = mw0 + it * RPI + erow;
-        mv[it] = nv && m < a.M;
-        yoff[it] = (size_t)m * a.Cout + n;
-        rres[it] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (!mv[it]) continue;
-        if (a.res_mode != 0 || a.out_mode != 0) {
-            const int b = m / HoWo;
-            const int rem = m - b * HoWo;
-            const int oy = rem / a.Wo;
-            const int ox = rem - oy * a.Wo;
-            size_t roff = yoff[it];
-            if (a.res_mode == 2)
-                roff = ((size_t)(b * (a.Ho >> 1) + (oy >> 1)) * (a.Wo >> 1) + (ox >> 1)) * a.Cout + n;
-            if (a.res_mode != 0) {
-                if (vec) {
-                    rres[it] = *reinterpret_cast<const f32x4*>(a.res + roff);
-                } else {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        if (n + q < a.Cout) rres[it][q] = a.res[roff + q];
-                }
-            }
-            if (a.out_mode == 1) {
-                const int kk = n / C2;
-                const int co = n - kk * C2;
-                const int oy2 = 2 * oy + (kk >> 1), ox2 = 2 * ox + (kk & 1);
-                yoff[it] = ((size_t)(b * 2 * a.Ho + oy2) * (2 * a.Wo) + ox2) * C2 + co;
-            } else if (a.out_mode == 2) {   // stride-2 scatter into a [B,2Ho,2Wo,Cout] tensor (data gradient of a strided 1x1 conv)
-                yoff[it] = ((size_t)(b * 2 * a.Ho + 2 * oy) * (2 * a.Wo) + 2 * ox) * a.Cout + n;
-            }
-        }
-    }
-    __builtin_amdgcn_wave_barrier();                   // staging writes of this wave precede its reads (same-wave LDS order)
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(stage + (it * RPI + erow) * SLD + ec4 * 4);
-        if (!mv[it]) continue;
-        f32x4 o;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            float t = __fadd_rn(__fmul_rn(v[q], sc[q]), sh[q]);
-            if (a.res_mode != 0) t = __fadd_rn(t, rres[it][q]);
-            if (a.relu) t = fmaxf(t, 0.f);
-            o[q] = t;
-        }
-        if (a.mask && a.mask_split) {                  // the gating activation in the split row format (Cout % 32 == 0, out_mode 0)
-            const char* mb = reinterpret_cast<const char*>(a.mask + (yoff[it] - (size_t)n)) + (n >> 5) * 128 + (n & 31) * 2;
-            const f16x4 mh = *reinterpret_cast<const f16x4*>(mb);
-            const f16x4 ml = *reinterpret_cast<const f16x4*>(mb + 64);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) o[q] = fold((float)mh[q], (float)ml[q]) > 0.f ? o[q] : 0.f;
-        } else if (a.mask) {
-            if (vec) {
-                const f32x4 mk = *reinterpret_cast<const f32x4*>(a.mask + yoff[it]);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) o[q] = mk[q] > 0.f ? o[q] : 0.f;
-            } else {
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    if (n + q < a.Cout) o[q] = a.mask[yoff[it] + q] > 0.f ? o[q] : 0.f;
-            }
-        }
-        if (vec) {
-            *reinterpret_cast<f32x4*>(a.y + yoff[it]) = o;
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if (n + q < a.Cout) a.y[yoff[it] + q] = o[q];
-        }
-    }
-}
-
-// One K-step (32 k) of the AMP_CONV_F16X3 product on a wave tile of MB x NB blocks of 16 x 16, operands in the LDS row format
-// (per row 64 B of hi halves, 64 B of lo' halves, 16-B chunks XOR-swizzled by (row >> 1) & 7).  v_mfma_f32_16x16x32_f16: lane =
-// (row l15 of a block, k group lq), so the hi halves of k 8lq.. are chunk lq of the row and their lo' halves chunk 4 + lq: one
-// ds_read_b128 each, conflict-free over the 16 rows of a lane group.  Every AMP_CONV_F16X3 forward kernel computes through this
-// function, whoever staged the tiles: that is what makes "split in the kernel" and "split by the producer" the same arithmetic.
-// (Shape: the 16x16x32 MFMA does the flops of the 32x32x16 one in the same cycles with the same LDS bytes, but on random operands
-// the chip holds a higher clock under it -- MI355X_MICROARCH.md -- measured here: +2..9 % on the 3x3 / fc layers.)
-template <int MB, int NB>
-struct F16x3Frags {
-    f16x8 ah[MB], al[MB], bh[NB], bl[NB];
-};
-template <int MB, int NB>
-__device__ __forceinline__ void f16x3_load16(const float* As, const float* Bs, int fo_hi, int fo_lo, F16x3Frags<MB, NB>& f) {
-#pragma unroll
-    for (int i = 0; i < MB; ++i) {
-        f.ah[i] = *reinterpret_cast<const f16x8*>(As + i * 16 * BK + fo_hi);
-        f.al[i] = *reinterpret_cast<const f16x8*>(As + i * 16 * BK + fo_lo);
-    }
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-        f.bh[j] = *reinterpret_cast<const f16x8*>(Bs + j * 16 * BK + fo_hi);
-        f.bl[j] = *reinterpret_cast<const f16x8*>(Bs + j * 16 * BK + fo_lo);
-    }
-}
-// SWAP = true: the weights are the MFMA's A operand (rows) and the activations its B operand (columns): the same exact products
-// summed in the same order into acc[i][j] / acx[i][j] (i: 16 tile rows m, j: 16 channels n), but a lane now holds, per block, FOUR
-// CHANNELS (4 lq + e) of ONE tile row (l15) instead of four rows of one channel -- what conv_epilogue_direct needs.
-template <int MB, int NB, bool SWAP = false>
-__device__ __forceinline__ void f16x3_mfma16(const F16x3Frags<MB, NB>& f, f32x4 (&acc)[MB][NB], f32x4 (&acx)[MB][NB]) {
-    // per accumulator the order is lo'*hi, hi*lo' (cross sums), hi*hi; consecutive MFMAs never share an accumulator (NB apart)
-#pragma unroll
-    for (int i = 0; i < MB; ++i) {
-        if (SWAP) {
-#pragma unroll
-            for (int j = 0; j < NB; ++j) acx[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f.bh[j], f.al[i], acx[i][j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NB; ++j) acx[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f.bl[j], f.ah[i], acx[i][j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NB; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f.bh[j], f.ah[i], acc[i][j], 0, 0, 0);
-        } else {
-#pragma unroll
-            for (int j = 0; j < NB; ++j) acx[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f.al[i], f.bh[j], acx[i][j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NB; ++j) acx[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f.ah[i], f.bl[j], acx[i][j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NB; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f.ah[i], f.bh[j], acc[i][j], 0, 0, 0);
-        }
-    }
-}
-template <int MB, int NB>
-__device__ __forceinline__ void f16x3_step16(const float* As, const float* Bs, int fo_hi, int fo_lo, f32x4 (&acc)[MB][NB], f32x4 (&acx)[MB][NB]) {
-    F16x3Frags<MB, NB> f;
-    f16x3_load16<MB, NB>(As, Bs, fo_hi, fo_lo, f);
-    f16x3_mfma16<MB, NB>(f, acc, acx);
-}
-
-// Fast epilogue for the layouts the model actually uses (Cout % 4 == 0): same LDS transposition and the same arithmetic as
-// conv_epilogue, but straight-line: the row offsets advance by additions (SPATIAL = false: out_mode 0, res_mode 0/1) or come from
-// two multiply-shift divisions per row (SPATIAL = true: upsampled residual, deconv / stride-2 scatter); residual and mask loads of
-// all rows are issued before the first store; a block-uniform `full` flag removes the per-row bounds predicates from every tile
-// but the last one.  (Measured on gfx950: the generic epilogue's per-row branches cost 13-55 % of the short-K layers.)
-template <int WTM, int WTN, bool SPATIAL, bool CHECK>
-__device__ __forceinline__ void conv_epilogue_rows(const ConvArgs& a, float* stage, int lane, int mw0, int nw0);
-template <int WTM, int WTN, bool SPATIAL, bool CHECK>
-__device__ __forceinline__ void conv_epilogue_rows8(const ConvArgs& a, float* stage, int lane, int mw0, int nw0);
-
-template <int WTM, int WTN, int MT, int NT, bool SPATIAL, bool CHECK = false>
-__device__ __forceinline__ void conv_epilogue_fast(const ConvArgs& a, f32x16 (&acc)[MT][NT], float* lds, int wave, int lane,
-                                                   int mw0, int nw0) {
-    const int l31 = lane & 31, lh = lane >> 5;
-    constexpr int SLD = WTN + 4;
-    float* stage = lds + wave * (WTM * SLD);
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e)
-                stage[(i * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh) * SLD + j * 32 + l31] = acc[i][j][e];
-    if (a.y_split && !a.mask && a.out_mode == 0) conv_epilogue_rows8<WTM, WTN, SPATIAL, CHECK>(a, stage, lane, mw0, nw0);
-    else conv_epilogue_rows<WTM, WTN, SPATIAL, CHECK>(a, stage, lane, mw0, nw0);
-}
-
-// the same from 16x16 MFMA accumulators (v_mfma_f32_16x16x32_f16: lane = column, 4 consecutive rows per lane group of 16)
-template <int WTM, int WTN, int MT, int NT, bool SPATIAL, bool CHECK = false>
-__device__ __forceinline__ void conv_epilogue_fast16(const ConvArgs& a, f32x4 (&acc)[MT][NT], float* lds, int wave, int lane,
-                                                     int mw0, int nw0) {
-    const int l15 = lane & 15, lq = lane >> 4;
-    constexpr int SLD = WTN + 4;
-    float* stage = lds + wave * (WTM * SLD);
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                stage[(i * 16 + 4 * lq + e) * SLD + j * 16 + l15] = acc[i][j][e];
-    if (a.y_split && !a.mask && a.out_mode == 0) conv_epilogue_rows8<WTM, WTN, SPATIAL, CHECK>(a, stage, lane, mw0, nw0);
-    else conv_epilogue_rows<WTM, WTN, SPATIAL, CHECK>(a, stage, lane, mw0, nw0);
-}
-
-// Split-format output (the trunk's native activation format), 8 channels per lane: a lane's share of an output row is 16 B of hi
-// halves and 16 B of lo' halves (and the same of a split residual), so every global access is a full dwordx4 -- with 4 channels per
-// lane (conv_epilogue_rows) they were 8-B accesses and the memory-bound 1x1 layers ran 10 % slower than with fp32 rows.
-// out_mode 0, no mask (inference), Cout % 32 == 0; same arithmetic, same order as conv_epilogue_rows.
-template <int WTM, int WTN, bool SPATIAL, bool CHECK>
-__device__ __forceinline__ void conv_epilogue_rows8(const ConvArgs& a, float* stage, int lane, int mw0, int nw0) {
-    constexpr int SLD = WTN + 4;
-    constexpr int L8R = WTN / 8;                       // lanes per row
-    constexpr int RPI = 64 / L8R;                      // rows per iteration
-    constexpr int NIT = WTM / RPI;
-    const int erow = lane / L8R;
-    const int ec8 = lane % L8R;
-    const int n = nw0 + ec8 * 8;
-    const bool nv = n < a.Cout;                        // Cout % 32 == 0
-    float sc[8], sh[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        sc[q] = (nv && a.scale) ? a.scale[n + q] : 1.f;
-        sh[q] = (nv && a.shift) ? a.shift[n + q] : 0.f;
-    }
-    const bool has_res = a.res_mode != 0;
-    const size_t col_b = (size_t)(n >> 5) * 128 + (size_t)(n & 31) * 2;   // byte offset of this lane's hi halves inside a split row
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {                      // two passes of NIT / 2 rows: bounds the live registers
-        constexpr int HN = NIT / 2;
-        size_t yrow[HN], rrow[HN];                     // float index of the row start in y / res
-        bool mv[HN];
-        f32x4 r0[HN], r1[HN];
-#pragma unroll
-        for (int t = 0; t < HN; ++t) {
-            const int it = h * HN + t;
-            const int mrow = mw0 + it * RPI + erow;
-            mv[t] = nv && mrow < a.M;
-            const unsigned int m = min((unsigned int)mrow, (unsigned int)(a.M - 1));
-            yrow[t] = (size_t)m * a.Cout;
-            rrow[t] = yrow[t];
-            if (SPATIAL && a.res_mode == 2) {
-                unsigned int b, oy, ox;
-                conv_pixel(a, m, b, oy, ox);
-                rrow[t] = ((size_t)(b * (a.Ho >> 1) + (oy >> 1)) * (a.Wo >> 1) + (ox >> 1)) * a.Cout;
-            }
-        }
-        if (has_res) {
-#pragma unroll
-            for (int t = 0; t < HN; ++t) {
-                if (!mv[t]) continue;
-                if (a.res_split) {
-                    const char* rb = reinterpret_cast<const char*>(a.res + rrow[t]) + col_b;
-                    r0[t] = *reinterpret_cast<const f32x4*>(rb);          // 8 hi halves
-                    r1[t] = *reinterpret_cast<const f32x4*>(rb + 64);     // 8 lo' halves
-                } else {
-                    r0[t] = *reinterpret_cast<const f32x4*>(a.res + rrow[t] + n);
-                    r1[t] = *reinterpret_cast<const f32x4*>(a.res + rrow[t] + n + 4);
-                }
-            }
-        }
-        if (h == 0) __builtin_amdgcn_wave_barrier();   // staging writes of this wave precede its reads (same-wave LDS order)
-        bool bad = false;
-#pragma unroll
-        for (int t = 0; t < HN; ++t) {
-            const int it = h * HN + t;
-            const float* sp = stage + (it * RPI + erow) * SLD + ec8 * 8;
-            const f32x4 v0 = *reinterpret_cast<const f32x4*>(sp), v1 = *reinterpret_cast<const f32x4*>(sp + 4);
-            f16x8 hi, lo;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const float v = q < 4 ? v0[q] : v1[q - 4];
-                if (CHECK) bad = bad || !(fabsf(v) <= 3.0e38f);
-                float o = __fadd_rn(__fmul_rn(v, sc[q]), sh[q]);
-                if (has_res) {
-                    float r;
-                    if (a.res_split) {
-                        const f16x8 rh = __builtin_bit_cast(f16x8, r0[t]), rl = __builtin_bit_cast(f16x8, r1[t]);
-                        r = fold((float)rh[q], (float)rl[q]);
-                    } else {
-                        r = q < 4 ? r0[t][q] : r1[t][q - 4];
-                    }
-                    o = __fadd_rn(o, r);
-                }
-                if (a.relu) o = fmaxf(o, 0.f);
-                const _Float16 hh = (_Float16)o;
-                hi[q] = hh;
-                lo[q] = (_Float16)((o - (float)hh) * LO_SCALE);
-            }
-            if (mv[t]) {
-                char* base = reinterpret_cast<char*>(a.y + yrow[t]) + col_b;
-                *reinterpret_cast<f16x8*>(base) = hi;
-                *reinterpret_cast<f16x8*>(base + 64) = lo;
-            }
-        }
-        if (CHECK && bad) atomicOr(a.range_flag, 1);
-    }
-}
-
-// ---- epilogues of conv_split_kernel (role-swapped MFMA, see f16x3_mfma16<.., SWAP = true>) ---------------------------------------
-// Channel order inside a wave's 64 channels: LDS weight row w = 16 j + 4 q + e (block j, MFMA row 4 q + e) holds channel
-// swap_channel(w) = 32 (j >> 1) + 8 q + 4 (j & 1) + e, so that lane (l15, lq = q) owns, per tile row, channels [8 lq, 8 lq + 8) of
-// each of the two 32-channel groups: 16 B of hi halves and 16 B of lo' halves per group in the split row format.
-__device__ __forceinline__ int swap_channel(int w) {
-    const int j = w >> 4, q = (w >> 2) & 3, e = w & 3;
-    return 32 * (j >> 1) + 8 * q + 4 * (j & 1) + e;
-}
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// Straight from the accumulators to split rows -- no LDS staging (the staged epilogue moves 128 KB per tile through ds_write_b32 at
-// 64 B/clk: ~2000 cycles, plus the read-back) and packed arithmetic: per pair of outputs v_pk_mul/add (affine), 2 v_max (ReLU),
-// v_cvt_pk_f16_f32 (hi), v_pk_mul (x 2^11), v_pk_fma (hi * -2^11 + o * 2^11: the exact difference, already scaled), v_cvt_pk (lo').
-// Same values as conv_epilogue_rows8, bit for bit: o - hi and the scaling by 2^11 are exact in fp32, so the fused form rounds once,
-// where the unfused one did not round at all.  Range check: s = fma(v, 0, s) stays 0 unless an accumulator is inf or NaN.
-// out_mode 0, split output; residual none or in the split format (res_mode 1: same row; 2: the coarser level's row); ReLU mask
-// (training: the data gradient gated by the forward activation) none or in the split format.
-// out_mode 1 (SPATIAL instantiation; round 4): the ConvTranspose 2x2 s2 of the mask head as a 1x1 conv to (tap, co) = 4 x C2 channels -- a wave's
-// 64 columns lie inside ONE tap (C2 % 64 == 0), tile row m = input pixel (b, oy, ox) goes to output pixel (b, 2 oy + ky, 2 ox + kx), a row of C2
-// channels: the same 16-B stores at another row address, so the 1.6-GB tensor of a training step no longer takes the staged epilogue's trip
-// through LDS (1048 us at 1.96 TB/s before).
-// MBR row blocks of 16 per wave tile (4: the 64 x 64 wave tiles of conv_split_kernel; 2: conv3x3_c64_kernel); mrow_in[i] + (nothing): the GEMM row of
-// this lane in row block i (any value >= a.M: not stored) -- consecutive rows for the GEMM tiles, rows of a 2-D pixel patch for the patch kernel
-// AFFINE_LDS: scale / shift come from LDS copies indexed by the channel relative to nrel0 (conv1x1_nloop_kernel: a global load between two K-steps
-// would wait for the ring's prefetched tiles -- vector-memory operations retire in order)
-// PLAIN: the layer has neither residual nor mask, known at compile time -- behind a RUN-TIME "has residual" branch the compiler waits for the branch's
-// loads with vmcnt(0) at the join, on both paths, which inside conv1x1_nloop_kernel's loop would drain the ring at every tile
-template <bool SPATIAL, bool CHECK, int MBR, bool AFFINE_LDS = false, bool PLAIN = false>
-__device__ __forceinline__ void conv_epilogue_direct_rows(const ConvArgs& a, f32x4 (&acc)[MBR][4], int lane, const int (&mrow_in)[MBR], int nw0,
-                                                          const float* lsc = nullptr, const float* lsh = nullptr, int nrel0 = 0) {
-    const int lq = lane >> 4;
-    const bool has_res = !PLAIN && a.res_mode != 0, has_mask = !PLAIN && a.mask != nullptr;
-    const bool deconv = SPATIAL && a.out_mode == 1;
-    const int C2 = a.Cout >> 2;
-    const int tap = deconv ? nw0 / C2 : 0, ncol0 = deconv ? nw0 - tap * C2 : nw0;      // column of this wave inside an output row
-    const int yld = deconv ? C2 : a.Cout;                                              // floats per output row
-    f32x2 sc[2][4], sh[2][4];
-    size_t colb[2];
-#pragma unroll
-    for (int g = 0; g < 2; ++g) {
-        const int n = nw0 + 32 * g + 8 * lq;
-        const int nc = ncol0 + 32 * g + 8 * lq;
-        colb[g] = (size_t)(nc >> 5) * 128 + (size_t)(nc & 31) * 2;
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            if constexpr (AFFINE_LDS) {
-                const int nr = nrel0 + 32 * g + 8 * lq + 2 * p;
-                sc[g][p] = f32x2{lsc[nr], lsc[nr + 1]};
-                sh[g][p] = f32x2{lsh[nr], lsh[nr + 1]};
-            } else {
-                sc[g][p] = a.scale ? f32x2{a.scale[n + 2 * p], a.scale[n + 2 * p + 1]} : f32x2{1.f, 1.f};
-                sh[g][p] = a.shift ? f32x2{a.shift[n + 2 * p], a.shift[n + 2 * p + 1]} : f32x2{0.f, 0.f};
-            }
-        }
-    }
-    f32x2 chk = {0.f, 0.f};
-    // The residual rows of ALL four row groups are requested before the first store: y and res may alias as far as the compiler knows, so
-    // it keeps a group's loads behind the previous group's stores -- and loads return in order BEHIND older stores (one vmcnt queue), so
-    // every group paid a store round trip plus a load round trip.  The 64 registers are the cross-term accumulators', dead since the fold.
-    f16x8 rha[MBR][2], rla[MBR][2];
-#ifdef AMP_NO_HOIST
-    constexpr bool HOIST = false;
-#else
-    constexpr bool HOIST = true;
-#endif
-    auto load_res = [&](int i) {
-        {
-            const unsigned int m = min((unsigned int)mrow_in[i], (unsigned int)(a.M - 1));
-            size_t rrow = (size_t)m * a.Cout;
-            if (SPATIAL && a.res_mode == 2) {
-                unsigned int b, oy, ox;
-                conv_pixel(a, m, b, oy, ox);
-                rrow = ((size_t)(b * (a.Ho >> 1) + (oy >> 1)) * (a.Wo >> 1) + (ox >> 1)) * a.Cout;
-            }
-#pragma unroll
-            for (int g = 0; g < 2; ++g) {
-                const char* rb = reinterpret_cast<const char*>(a.res + rrow) + colb[g];
-                rha[i][g] = *reinterpret_cast<const f16x8*>(rb);
-                rla[i][g] = *reinterpret_cast<const f16x8*>(rb + 64);
-            }
-        }
-    };
-    if (has_res && HOIST) {
-#pragma unroll
-        for (int i = 0; i < MBR; ++i) load_res(i);
-    }
-    // the same for the gating activation (training: data gradients): all four row groups up front
-    f16x8 mha[MBR][2], mla[MBR][2];
-    auto load_mask = [&](int i) {
-        const unsigned int m = min((unsigned int)mrow_in[i], (unsigned int)(a.M - 1));
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-            const char* mb = reinterpret_cast<const char*>(a.mask + (size_t)m * a.Cout) + colb[g];
-            mha[i][g] = *reinterpret_cast<const f16x8*>(mb);
-            mla[i][g] = *reinterpret_cast<const f16x8*>(mb + 64);
-        }
-    };
-    if (has_mask && HOIST) {
-#pragma unroll
-        for (int i = 0; i < MBR; ++i) load_mask(i);
-    }
-#pragma unroll
-    for (int i = 0; i < MBR; ++i) {
-        const int mrow = mrow_in[i];
-        const bool mv = mrow < a.M;
-        const unsigned int m = min((unsigned int)mrow, (unsigned int)(a.M - 1));
-        size_t yrow = (size_t)m * a.Cout;
-        if (deconv) {
-            unsigned int b, oy, ox;
-            conv_pixel(a, m, b, oy, ox);
-            yrow = (((size_t)b * 2 * a.Ho + 2 * oy + (tap >> 1)) * (2 * a.Wo) + 2 * ox + (tap & 1)) * (size_t)yld;
-        }
-        f16x8 rh[2], rl[2], mh[2], ml[2];
-        if (has_res) {
-            if (!HOIST) load_res(i);
-#pragma unroll
-            for (int g = 0; g < 2; ++g) { rh[g] = rha[i][g]; rl[g] = rla[i][g]; }
-        }
-        if (has_mask) {                                  // the gating activation (training), split rows indexed like y
-            if (!HOIST) load_mask(i);
-#pragma unroll
-            for (int g = 0; g < 2; ++g) { mh[g] = mha[i][g]; ml[g] = mla[i][g]; }
-        }
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-            f16x8 hi, lo;
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                const f32x4& blk = acc[i][2 * g + (p >> 1)];
-                const f32x2 v = {blk[2 * (p & 1)], blk[2 * (p & 1) + 1]};
-                if (CHECK) chk = __builtin_elementwise_fma(v, f32x2{0.f, 0.f}, chk);
-                f32x2 o = v * sc[g][p] + sh[g][p];
-                if (has_res) {
-                    const f32x2 r1 = {(float)rh[g][2 * p], (float)rh[g][2 * p + 1]};
-                    const f32x2 r2 = {(float)rl[g][2 * p], (float)rl[g][2 * p + 1]};
-                    o = o + (r1 + r2 * (1.0f / LO_SCALE));
-                }
-                if (a.relu) { o[0] = fmaxf(o[0], 0.f); o[1] = fmaxf(o[1], 0.f); }
-                if (has_mask) {
-                    const f32x2 mk = f32x2{(float)mh[g][2 * p], (float)mh[g][2 * p + 1]} + f32x2{(float)ml[g][2 * p], (float)ml[g][2 * p + 1]} * (1.0f / LO_SCALE);
-                    o[0] = mk[0] > 0.f ? o[0] : 0.f;
-                    o[1] = mk[1] > 0.f ? o[1] : 0.f;
-                }
-                const f16x2 h = __builtin_convertvector(o, f16x2);
-                const f32x2 hf = {(float)h[0], (float)h[1]};
-                const f32x2 l = __builtin_elementwise_fma(hf, f32x2{-LO_SCALE, -LO_SCALE}, o * LO_SCALE);
-                const f16x2 lh = __builtin_convertvector(l, f16x2);
-                hi[2 * p] = h[0]; hi[2 * p + 1] = h[1];
-                lo[2 * p] = lh[0]; lo[2 * p + 1] = lh[1];
-            }
-            if (mv) {
-                char* base = reinterpret_cast<char*>(a.y + yrow) + colb[g];
-                *reinterpret_cast<f16x8*>(base) = hi;
-                *reinterpret_cast<f16x8*>(base + 64) = lo;
-            }
-        }
-    }
-    if (CHECK && (!(chk[0] == 0.f) || !(chk[1] == 0.f))) atomicOr(a.range_flag, 1);
-}
-
-template <bool SPATIAL, bool CHECK>
-__device__ __forceinline__ void conv_epilogue_direct(const ConvArgs& a, f32x4 (&acc)[4][4], int lane, int mw0, int nw0) {
-    const int l15 = lane & 15;
-    const int mrows[4] = {mw0 + l15, mw0 + 16 + l15, mw0 + 32 + l15, mw0 + 48 + l15};
-    conv_epilogue_direct_rows<SPATIAL, CHECK, 4>(a, acc, lane, mrows, nw0);
-}
-
-// The staged epilogues (fp32 output, mask, scatter modes) behind the role-swapped MFMA: only the staging indices differ.
-template <int WTM, int WTN, bool SPATIAL, bool CHECK>
-__device__ __forceinline__ void conv_epilogue_swapped(const ConvArgs& a, f32x4 (&acc)[4][4], float* lds, int wave, int lane, int mw0, int nw0) {
-    const int l15 = lane & 15, lq = lane >> 4;
-    constexpr int SLD = WTN + 4;
-    float* stage = lds + wave * (WTM * SLD);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            *reinterpret_cast<f32x4*>(stage + (i * 16 + l15) * SLD + 32 * (j >> 1) + 8 * lq + 4 * (j & 1)) = acc[i][j];
-    if (a.y_split && !a.mask && a.out_mode == 0) conv_epilogue_rows8<WTM, WTN, SPATIAL, CHECK>(a, stage, lane, mw0, nw0);
-    else conv_epilogue_rows<WTM, WTN, SPATIAL, CHECK>(a, stage, lane, mw0, nw0);
-}
-
-// rows of a wave's staged [WTM][WTN] tile -> affine, residual, ReLU, mask -> y (fp32 or split rows)
-template <int WTM, int WTN, bool SPATIAL, bool CHECK>
-__device__ __forceinline__ void conv_epilogue_rows(const ConvArgs& a, float* stage, int lane, int mw0, int nw0) {
-    constexpr int SLD = WTN + 4;
-    constexpr int F4R = WTN / 4;
-    constexpr int RPI = 64 / F4R;
-    constexpr int NIT = WTM / RPI;
-
-    const int erow = lane / F4R;
-    const int ec4 = lane % F4R;
-    const int n = nw0 + ec4 * 4;
-    const bool nv = n < a.Cout;                        // Cout % 4 == 0: the whole float4 is in range or none of it
-    f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
-    if (nv) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (a.scale) sc[q] = a.scale[n + q];
-            if (a.shift) sh[q] = a.shift[n + q];
-        }
-    }
-    const bool full = __builtin_amdgcn_readfirstlane(mw0) + WTM <= a.M && __builtin_amdgcn_readfirstlane(nw0) + WTN <= a.Cout;
-    const bool has_res = a.res_mode != 0, has_mask = a.mask != nullptr;
-
-    size_t yoff[NIT], roff[NIT];
-    if (!SPATIAL) {
-        const size_t step = (size_t)RPI * a.Cout;
-        yoff[0] = (size_t)(mw0 + erow) * a.Cout + n;
-#pragma unroll
-        for (int it = 1; it < NIT; ++it) yoff[it] = yoff[it - 1] + step;
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) roff[it] = yoff[it];
-    } else {
-        const int C2 = a.Cout >> 2;
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const unsigned int m = min((unsigned int)(mw0 + it * RPI + erow), (unsigned int)(a.M - 1));   // clamped rows are never stored
-            unsigned int b, oy, ox;
-            conv_pixel(a, m, b, oy, ox);
-            roff[it] = (a.res_mode == 2) ? ((size_t)(b * (a.Ho >> 1) + (oy >> 1)) * (a.Wo >> 1) + (ox >> 1)) * a.Cout + n
-                                         : (size_t)m * a.Cout + n;
-            if (a.out_mode == 1) {
-                const int kk = n / C2;
-                const int co = n - kk * C2;
-                yoff[it] = ((size_t)(b * 2 * a.Ho + 2 * oy + (kk >> 1)) * (2 * a.Wo) + 2 * ox + (kk & 1)) * C2 + co;
-            } else if (a.out_mode == 2) {
-                yoff[it] = ((size_t)(b * 2 * a.Ho + 2 * oy) * (2 * a.Wo) + 2 * ox) * a.Cout + n;
-            } else {
-                yoff[it] = (size_t)m * a.Cout + n;
-            }
-        }
-    }
-
-    auto body = [&](auto full_tag) {
-        constexpr bool FULL = decltype(full_tag)::value;
-        bool mv[NIT];
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) mv[it] = FULL || (nv && mw0 + it * RPI + erow < a.M);
-        f32x4 rres[NIT], mk[NIT];
-        if (has_res && a.res_split) {
-            // the residual tensor lives in the split row format: this lane's 4 channels are 8 B of hi halves and 8 B of lo' halves
-#pragma unroll
-            for (int it = 0; it < NIT; ++it)
-                if (mv[it]) {
-                    const char* rb = reinterpret_cast<const char*>(a.res + (roff[it] - (size_t)n)) + (n >> 5) * 128 + (n & 31) * 2;
-                    const f16x4 rh = *reinterpret_cast<const f16x4*>(rb);
-                    const f16x4 rl = *reinterpret_cast<const f16x4*>(rb + 64);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) rres[it][q] = fold((float)rh[q], (float)rl[q]);
-                }
-        } else if (has_res) {
-#pragma unroll
-            for (int it = 0; it < NIT; ++it)
-                if (mv[it]) rres[it] = *reinterpret_cast<const f32x4*>(a.res + roff[it]);
-        }
-        if (has_mask && a.mask_split) {
-            // the activation whose sign gates the gradient lives in the split row format (training on the native trunk): decoded like a
-            // split residual; hi + lo' * 2^-11 > 0 exactly when the stored activation was (down to 2^-35, below which both halves are 0)
-#pragma unroll
-            for (int it = 0; it < NIT; ++it)
-                if (mv[it]) {
-                    const char* mb = reinterpret_cast<const char*>(a.mask + (yoff[it] - (size_t)n)) + (n >> 5) * 128 + (n & 31) * 2;
-                    const f16x4 mh = *reinterpret_cast<const f16x4*>(mb);
-                    const f16x4 ml = *reinterpret_cast<const f16x4*>(mb + 64);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) mk[it][q] = fold((float)mh[q], (float)ml[q]);
-                }
-        } else if (has_mask) {
-#pragma unroll
-            for (int it = 0; it < NIT; ++it)
-                if (mv[it]) mk[it] = *reinterpret_cast<const f32x4*>(a.mask + yoff[it]);
-        }
-        __builtin_amdgcn_wave_barrier();               // staging writes of this wave precede its reads (same-wave LDS order)
-        bool bad = false;
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(stage + (it * RPI + erow) * SLD + ec4 * 4);
-            if (CHECK) bad = bad || !(fabsf(v[0]) <= 3.0e38f) || !(fabsf(v[1]) <= 3.0e38f) || !(fabsf(v[2]) <= 3.0e38f) || !(fabsf(v[3]) <= 3.0e38f);
-            f32x4 o;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float t = __fadd_rn(__fmul_rn(v[q], sc[q]), sh[q]);
-                if (has_res) t = __fadd_rn(t, rres[it][q]);
-                if (a.relu) t = fmaxf(t, 0.f);
-                if (has_mask) t = mk[it][q] > 0.f ? t : 0.f;
-                o[q] = t;
-            }
-            if (a.y_split) {
-                // row-relative: 32 channels = 64 B of hi halves + 64 B of lo' halves; this lane's 4 channels -> 8 B in each
-                if (mv[it]) {
-                    f16x4 hi, lo;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const _Float16 h = (_Float16)o[q];
-                        hi[q] = h;
-                        lo[q] = (_Float16)((o[q] - (float)h) * LO_SCALE);
-                    }
-                    const size_t row = yoff[it] - (size_t)n;                     // float index of the row start
-                    char* base = reinterpret_cast<char*>(a.y + row) + (n >> 5) * 128 + (n & 31) * 2;
-                    *reinterpret_cast<f16x4*>(base) = hi;
-                    *reinterpret_cast<f16x4*>(base + 64) = lo;
-                }
-            } else if (mv[it]) {
-                *reinterpret_cast<f32x4*>(a.y + yoff[it]) = o;
-            }
-        }
-        if (CHECK && bad) atomicOr(a.range_flag, 1);
-    };
-    if (full) body(std::true_type{});
-    else body(std::false_type{});
-}
 
 // ABL (ablation, tools/bench_conv_ablate.py only; results wrong for ABL != 0): 1 = no global loads in the K loop,
 // 2 = also no LDS writes / barriers, 3 = MFMA only (fragments read once).
@@ -1737,157 +1013,6 @@ __global__ __launch_bounds__(512, 1) void mask_tail_kernel(const ConvArgs a, con
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// conv1x1_nloop_kernel (round 4): the short-K 1x1 layers that run one 128 x 256 tile per CU (stride-2 shortcuts, conv1 of a stage's first block, their
-// data gradients, the mask head's deconv in a training step: K = 64 ... 512, two to sixteen K-steps) with SEVERAL N tiles of a 128-pixel block in one
-// workgroup -- mask_tail_kernel's loop with conv_epilogue_direct_rows as the tile epilogue.  A workgroup of conv_split_kernel pays a cold ring, a prologue and
-// an epilogue per tile for 5 us of MFMA work (K = 256); here the ring runs on across the tiles (tile t + 1's first weight tiles and the pixel block's rows,
-// now in the L2, are requested during tile t's last steps) and a half's epilogue -- loads of residual / mask, 16 stores per wave -- sits between two steps.
-// Those stores are YOUNGER than the requests already in flight, so the counted wait in front of a step allows for them exactly where they are in the queue:
-//   early half (epilogue after the last MFMAs of step e):   step e + 1 needs D(e+1); younger: D(e+2), E      -> vmcnt(6 + 16)
-//                                                            step e + 2 needs D(e+2); younger: E, D(e+3)      -> vmcnt(6 + 16)
-//   late half  (epilogue in step e + 1, before its requests): step e + 1 needs D(e+1); younger: D(e+2)         -> vmcnt(6)
-//                                                            step e + 2 needs D(e+2); younger: E, D(e+3)      -> vmcnt(6 + 16)
-// and vmcnt(6) from then on (which also retires E).  16 is a LOWER bound on a full tile's stores (more younger operations only make the wait stricter);
-// a partial tile (rows beyond M: stores skipped) waits with vmcnt(6).  Same products, same order, same epilogue: bit-identical to conv_split_kernel.
-// ------------------------------------------------------------------------------------------------------------------
-template <bool SPATIAL>
-__global__ __launch_bounds__(512, 1) void conv1x1_nloop_kernel(const ConvArgs a, const unsigned int x_bytes, const unsigned int w_bytes, const int NT) {
-    constexpr int BM = 128, BN = 256, NW = 8, GA = 2, GB = 4, NDMA = GA + GB, NST = 16;
-    constexpr int TILE_FLOATS = (BM + BN) * BK;
-    constexpr int NT_MAX = 8;                      // scale + shift of NT_MAX * 256 channels: the 16 KB behind the ring
-    __shared__ __attribute__((aligned(16))) float lds[3 * TILE_FLOATS + 2 * NT_MAX * BN];
-    float* lsc = lds + 3 * TILE_FLOATS;
-    float* lsh = lsc + NT_MAX * BN;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 2, wn = wave & 3;
-    const int l15 = lane & 15, lq = lane >> 4;
-    const int ngrp = a.ntn / NT;                   // groups of NT consecutive N tiles
-    const int wg = amp::xcd_remap(blockIdx.x, a.nblk);
-    const int grp = wg % ngrp;
-    const int m0 = (wg / ngrp) * BM;
-    const int n_first = grp * NT * BN;
-    const bool full = m0 + BM <= a.M;
-    const __amdgpu_buffer_rsrc_t rsrc_x = buffer_rsrc(a.x, x_bytes);
-    const __amdgpu_buffer_rsrc_t rsrc_w = buffer_rsrc(a.w, w_bytes);
-    const int srow = dma_row(lane), spos = dma_pos(lane);
-    unsigned int a_voff[GA], b_voff[GB];
-#pragma unroll
-    for (int g = 0; g < GA; ++g) {
-        const int r = wave * (BM / NW) + 8 * g + srow;
-        const int m = m0 + r;
-        a_voff[g] = OOB_VOFF;
-        if (m < a.M) {                             // 1x1, pad 0: output pixel (b, oy, ox) reads input pixel (oy, ox) * stride
-            unsigned int b, oy, ox;
-            conv_pixel(a, (unsigned int)m, b, oy, ox);
-            a_voff[g] = (unsigned int)((((size_t)(b * a.H + oy * a.stride) * a.W + ox * a.stride) * a.Cin + dma_chunk(spos, r)) * 4);
-        }
-    }
-#pragma unroll
-    for (int g = 0; g < GB; ++g) {
-        const int r = wave * (BN / NW) + 8 * g + srow;
-        const int n = n_first + (r & ~63) + swap_channel(r & 63);
-        b_voff[g] = (unsigned int)(((size_t)n * a.K + dma_chunk(spos, r)) * 4);
-    }
-    const int csteps = a.Cin / BK;                 // K-steps per tile
-    const int total = NT * csteps;
-    const int tile_bytes = BN * a.K * 4;           // weight rows of one N tile
-    int s_cs = 0, s_tile = 0;                      // the step being STAGED
-    auto stage = [&](int buf) {
-        float* As = lds + buf * TILE_FLOATS;
-        float* Bs = As + BM * BK;
-        const int a_soff = s_cs * (BK * 4);
-        const int b_soff = s_tile * tile_bytes + s_cs * (BK * 4);
-#pragma unroll
-        for (int g = 0; g < GA; ++g)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_x, (__attribute__((address_space(3))) void*)(As + (wave * (BM / NW) + 8 * g) * BK), 16, (int)a_voff[g], a_soff, 0, 0);
-#pragma unroll
-        for (int g = 0; g < GB; ++g)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, (__attribute__((address_space(3))) void*)(Bs + (wave * (BN / NW) + 8 * g) * BK), 16, (int)b_voff[g], b_soff, 0, 0);
-        if (++s_cs == csteps) { s_cs = 0; ++s_tile; }
-    };
-    f32x4 acc[4][4], acx[4][4];
-    zero_acc(acc, acx);
-    const int fo16_hi = 4 * (lq ^ (l15 >> 1)), fo16_lo = 4 * ((4 + lq) ^ (l15 >> 1));
-    stage(0);
-    stage(1);
-    // FrozenBN scale / shift (or 1 / bias) of the group's channels: once, into LDS (visible behind the first step's barrier)
-    for (int c = tid; c < NT * BN; c += 512) {
-        lsc[c] = a.scale ? a.scale[n_first + c] : 1.0f;
-        lsh[c] = a.shift ? a.shift[n_first + c] : 0.0f;
-    }
-    const int mw0 = m0 + wm * 64;
-    const bool scaled_in = a.out_scale != 1.0f;
-    auto tile_epilogue = [&](int tile) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    acc[i][j][e] = fold(acc[i][j][e], acx[i][j][e]);
-                    if (scaled_in) acc[i][j][e] *= a.out_scale;
-                }
-        // one 16-row block at a time: the loop's state stays live across this epilogue, and two blocks' hoisted residual / mask rows beside it spill
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int mrows[1] = {mw0 + 16 * i + l15};
-            conv_epilogue_direct_rows<SPATIAL, true, 1, true, true>(a, reinterpret_cast<f32x4 (&)[1][4]>(acc[i]), lane, mrows, n_first + tile * BN + wn * 64, lsc, lsh, tile * BN + wn * 64);
-        }
-    };
-    int cur = 0, nxt = 2, c_cs = 0, c_tile = 0;    // ring positions; the step being COMPUTED
-    const bool early = wave < NW / 2;
-    auto open_step = [&](int step) {
-        // the stores of the previous tile's epilogue in the queue (see the table above); exact for full tiles only
-        const bool behind_epilogue = full && c_tile > 0 && (early ? c_cs <= 1 : c_cs == 1);
-        if (step + 1 >= total) __builtin_amdgcn_s_waitcnt(0x0070);
-        else if (behind_epilogue) __builtin_amdgcn_s_waitcnt(0x0070 | ((NDMA + NST) & 15) | (((NDMA + NST) >> 4) << 14));
-        else __builtin_amdgcn_s_waitcnt(0x0070 | NDMA);
-        ring_barrier();
-    };
-    auto advance = [&]() {
-        ring_next<3>(cur, nxt);
-        if (++c_cs == csteps) { c_cs = 0; ++c_tile; }
-    };
-    F16x3Frags<4, 4> fr;
-    const float* As0 = lds + (wm * 64 + l15) * BK;
-    const float* Bs0 = lds + BM * BK + (wn * 64 + l15) * BK;
-    if (early) {
-        for (int step = 0; step < total; ++step) {
-            open_step(step);
-            f16x3_load16<4, 4>(As0 + cur * TILE_FLOATS, Bs0 + cur * TILE_FLOATS, fo16_hi, fo16_lo, fr);
-            __builtin_amdgcn_sched_barrier(0);
-            if (step + 2 < total) stage(nxt);
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_s_setprio(1);
-            f16x3_mfma16<4, 4, true>(fr, acc, acx);
-            __builtin_amdgcn_s_setprio(0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (c_cs == csteps - 1) { tile_epilogue(c_tile); zero_acc(acc, acx); __builtin_amdgcn_sched_barrier(0); }
-            advance();
-        }
-    } else {
-        for (int step = 0; step < total; ++step) {
-            open_step(step);
-            __builtin_amdgcn_s_setprio(1);
-            if (step > 0) f16x3_mfma16<4, 4, true>(fr, acc, acx);
-            __builtin_amdgcn_s_setprio(0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (c_cs == 0 && c_tile > 0) { tile_epilogue(c_tile - 1); zero_acc(acc, acx); __builtin_amdgcn_sched_barrier(0); }      // the MFMAs above finished tile c_tile - 1
-            __builtin_amdgcn_s_barrier();
-            f16x3_load16<4, 4>(As0 + cur * TILE_FLOATS, Bs0 + cur * TILE_FLOATS, fo16_hi, fo16_lo, fr);
-            __builtin_amdgcn_sched_barrier(0);
-            if (step + 2 < total) stage(nxt);
-            __builtin_amdgcn_sched_barrier(0);
-            advance();
-        }
-        f16x3_mfma16<4, 4, true>(fr, acc, acx);
-        tile_epilogue(NT - 1);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------------------
 // conv3x3_patch_kernel (round 4): the 3x3 stride-1 pad-1 convolutions of the FPN / RPN / res4 / res5 (Cin % 32 == 0, Cout % 256 == 0) with both
 // operands in the split row format -- conv_split_kernel<128, 256>'s loop (ring of three weight tiles filled by LDS-DMA two steps ahead, counted
 // vmcnt, bare barriers, the two halves of the workgroup one half-step apart), but the 128 GEMM rows of a workgroup are an 8 x 16 PIXEL tile and
@@ -2860,32 +1985,6 @@ void set_fastdiv(unsigned int d, unsigned int* mul, int* shr) {
 
 }  // namespace
 
-// The switches conv_plan reads: one instance (g_sw), written by the amp_debug_set_* entries below; the environment gives the initial values.
-struct ConvSwitches {
-    int f16x3_bn256 = 1;   // EXPERIMENT switch: 256-wide 8-wave tiles where Cout % 256 == 0
-    int short_k = getenv("AMP_NO_SHORT_K") ? 0 : 1;      // EXPERIMENT switch: K <= 64 layers on 128 x 128 tiles, two workgroups per CU (0: the 128 x 256 ring tiles)
-    int tall64 = getenv("AMP_TALL64") ? atoi(getenv("AMP_TALL64")) : 1;      // Cout = 64 layers on 256 x 64 tiles of conv_split_kernel, two workgroups per CU (0: the 128 x 64 ring tiles of conv_glds_kernel): res2 3x3 160 -> 145 us, 1x1 256 -> 64 148 -> 140 us, bit-identical
-    int split_ring = getenv("AMP_SPLIT_RING") ? atoi(getenv("AMP_SPLIT_RING")) : 1;    // EXPERIMENT switch: the 3-buffer conv_split_kernel for pre-split inputs (0: the 2-buffer conv_glds_kernel<.., F16>)
-    int korder = getenv("AMP_KORDER") ? atoi(getenv("AMP_KORDER")) : 0;     // EXPERIMENT switch: 1 = channel-major K order in conv_split_kernel (ConvArgs::korder)
-    // EXPERIMENT switch, default OFF: 1 = conv3x3_patch_kernel for the wide 3x3 layers (0: conv_split_kernel<128, 256>); 2 = whatever the grid size (tests).
-    // Measured (round 4, tools/lab/time_conv.py, tools/lab/pmc_p256.sh): FETCH_SIZE per launch of the FPN output conv at p2 1.97 -> 0.44 M KiB, L2 misses
-    // 35.7 -> 11.2 M -- and the SAME wall time on random operands (1410-1420 us either way; the chip holds 1.85 GHz under the ring kernel's loop and
-    // 1.97-2.16 GHz under this one, which needs 2230 cycles per K-step against 1970): the layer is limited by the power the MFMAs draw, not by its
-    // traffic; on all-zero operands (2.4 GHz either way) the ring kernel wins by the cycle ratio, 1049 against 1124 us.  And the channel-major sums move
-    // one box of the full-size gate from 0.9e-3 to 1.01e-3 px off the fp32 oracle (bare tolerance 1e-3): not adopted.
-    int patch256 = getenv("AMP_PATCH256") ? atoi(getenv("AMP_PATCH256")) : 0;
-    // EXPERIMENT switch, default OFF (AMP_NLOOP=1): several N tiles per workgroup for the short-K 1x1 layers (conv1x1_nloop_kernel).  Measured (round 4,
-    // tools/lab/time_nloop.py, A/B in one process, bit-identical): the training step's deconv 930-970 -> 856 us, res3.0's stride-2 shortcut 315 -> 291 us at B = 16
-    // and 154 -> 151 at B = 8, res4.0's shortcut 223 -> 240 us (WORSE), an inference step 16.16 against 16.12 ms: what bounds these layers is not the ring's
-    // cold start (that was the mask tail's case: four taps over the SAME pixels and a store-free epilogue) but their bytes; 0.1 ms of a 74-ms training step
-    // does not pay for a second loop structure on the training path.
-    int nloop = getenv("AMP_NLOOP") ? atoi(getenv("AMP_NLOOP")) : 0;
-    int mask_tail_loop = getenv("AMP_NO_MASK_TAIL_LOOP") ? 0 : 1;      // EXPERIMENT switch: 0 = the fused mask-head tail on conv_split_kernel<128, 256, 3> (one tap per workgroup)
-    int patch_conv = getenv("AMP_NO_PATCH_CONV") ? 0 : 1;      // EXPERIMENT switch: 0 = the implicit-GEMM kernels for the 64-channel-window 3x3 layers; 2 = conv3x3_c64_kernel whatever the grid size (tests)
-    int stagger = getenv("AMP_STAGGER") ? atoi(getenv("AMP_STAGGER")) : 1;      // ConvArgs::stagger (tools/stamp_conv.py)
-    int generic_epi = 0;   // tests: force the generic epilogue
-    int ablate = 0;        // tools/bench_conv_ablate.py: timing variants of the register-staged kernel
-};
 static ConvSwitches g_sw;
 extern "C" void amp_debug_set_f16x3_bn256(int v) { g_sw.f16x3_bn256 = v; }
 extern "C" void amp_debug_set_short_k(int v) { g_sw.short_k = v; }
@@ -2898,12 +1997,6 @@ extern "C" void amp_debug_set_mask_tail_loop(int v) { g_sw.mask_tail_loop = v; }
 extern "C" void amp_debug_set_patch_conv(int v) { g_sw.patch_conv = v; }
 extern "C" void amp_debug_set_conv_generic_epilogue(int on) { g_sw.generic_epi = on; }
 extern "C" void amp_debug_set_conv_ablate(int mode) { g_sw.ablate = mode; }
-// Two thresholds that were switches once.  One round of 128 x 256 tiles (192 ... 511 of them) is taken from WIDE_NSTEPS K-steps on.  Round 4 measured the
-// alternative's bound -- two 128 x 128 workgroups per CU move 64 KB per 1536 MFMA cycles through an L2 -> LDS path that gives a CU ~33 B/clk -- and 16 instead
-// of 64: res4's conv1 (M = 32768, K = 1024) 54 -> 49 us, fc2 55 -> 47 us, res4.0 conv1 32 -> 29 us in the per-launch table (bit-identical), 506.3 / 507.7
-// against 509.0 / 506.0 images/s for the step: nothing outside the noise, so the rule stays at 64
-constexpr int WIDE_NSTEPS = 64;
-constexpr int SHORT_K_STEPS = 16;     // the two-buffer 128 x 128 tiles take K <= 512
 #ifdef AMP_STAMP
 extern "C" int amp_debug_read_stamps(unsigned long long* out) {     // 64 values; zeroes the device counters
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamp), sizeof(unsigned long long) * 64) != hipSuccess) return -1;
@@ -3371,202 +2464,6 @@ extern "C" int amp_conv2d_nhwc(amp_ctx* ctx, const amp_conv_desc* d, const float
                                const float* scale, const float* shift, const float* res, float* y) {
     return amp_conv2d_nhwc_ex(ctx, d, x, w, scale, shift, res, nullptr, y);
 }
-
-namespace {
-struct ConvPlanIn {             // what the selection depends on: conv_run's arguments with presence flags for the pointers
-    int mode;                   // amp_ctx::conv_mode
-    amp_conv_desc d;
-    int groups, fmt, in_shift, force_f32;
-    bool res, mask, scale;
-    int fuse;                   // 0: none, 1: PredictFuse, 2: RpnFuse with rpn_ld predictor rows
-    int rpn_ld;
-};
-struct ConvPlan {
-    amp::ConvKernel kernel;
-    int epi;                    // the launch's epilogue template argument (0 generic, 1 rows, 2 scatter / upsampled residual, 3: predict or RPN tail with 16 rows, 4 / 5: 32 / 48 rows)
-    int ntn, nblk, stagger;     // ConvArgs::ntn, ::nblk (the grid), ::stagger
-    int tiles_x, tiles_y;       // the patch kernels' 8 x 16 pixel tiles
-    int nloop_nt;               // N tiles per workgroup of conv1x1_nloop_kernel
-    int rpn_nbp;                // blocks of 16 predictor rows of the fused RPN tail
-    bool dominant;              // a launch of the dominant kernel (amp_prof_rec::variant 0)
-    bool f16x3;                 // the kernel reads the weights in the split layout
-    int Ho, Wo, M, K, nsteps, cin_win, cpg, out_mode, y_split, korder;      // the layer as ConvArgs carries it
-    size_t x_bytes, w_bytes;
-};
-
-// conv3x3_c64_kernel is taken from 512 tiles of 8 x 16 pixels x 64 channels on (patch_conv = 2: whatever the grid size)
-bool c64_patch_fills(const ConvSwitches& sw, long long tiles) { return sw.patch_conv == 2 || tiles >= 512; }
-
-// Which kernel takes the layer, and with which grid: pure host code (no HIP call, nothing of a context but its mode).  AMP_ERR_ARG + amp_last_error
-// on a combination no kernel supports.
-int conv_plan(const ConvPlanIn& in, const ConvSwitches& sw, ConvPlan* plan) {
-    using amp::ConvKernel;
-    const amp_conv_desc* d = &in.d;
-    ConvPlan p = ConvPlan();
-    AMP_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0, "amp_conv2d_nhwc: bad shape");
-    AMP_REQUIRE(d->Cin % 4 == 0, "amp_conv2d_nhwc: Cin=%d must be a multiple of 4 (pad the input)", d->Cin);
-    AMP_REQUIRE(d->KH > 0 && d->KW > 0 && d->stride > 0 && d->pad >= 0, "amp_conv2d_nhwc: bad window");
-    AMP_REQUIRE(d->res_mode >= 0 && d->res_mode <= 2 && d->out_mode >= 0 && d->out_mode <= 2,
-                "amp_conv2d_nhwc: bad res_mode/out_mode");
-    AMP_REQUIRE(d->res_mode == 0 || in.res, "amp_conv2d_nhwc: res_mode=%d needs res", d->res_mode);
-    const int Cin = d->Cin, Cout = d->Cout, KH = d->KH, KW = d->KW;
-    p.Ho = (d->H + 2 * d->pad - KH) / d->stride + 1;
-    p.Wo = (d->W + 2 * d->pad - KW) / d->stride + 1;
-    AMP_REQUIRE(p.Ho > 0 && p.Wo > 0, "amp_conv2d_nhwc: empty output");
-    AMP_REQUIRE(d->res_mode != 2 || (p.Ho % 2 == 0 && p.Wo % 2 == 0),
-                "amp_conv2d_nhwc: res_mode=2 needs even output size, got %dx%d", p.Ho, p.Wo);
-    AMP_REQUIRE(d->out_mode != 1 || Cout % 4 == 0, "amp_conv2d_nhwc: out_mode=1 needs Cout %% 4 == 0");
-    const long long Mll = (long long)d->B * p.Ho * p.Wo;
-    AMP_REQUIRE(Mll < (1ll << 31) / 4 && (long long)d->B * d->H * d->W < (1ll << 31),
-                "amp_conv2d_nhwc: tensor too large for 32-bit pixel indices");
-    p.M = (int)Mll;
-    const bool grouped = in.groups > 1;
-    p.cin_win = p.cpg = Cin;
-    if (grouped) {
-        AMP_REQUIRE(Cin == Cout && Cin % in.groups == 0 && Cout % 64 == 0 && d->out_mode == 0,
-                    "amp_conv2d_grouped_nhwc: needs Cin == Cout, a multiple of 64 and of groups, out_mode 0");
-        p.cpg = Cin / in.groups;
-        AMP_REQUIRE(p.cpg == 8 || p.cpg == 16 || p.cpg == 32 || p.cpg == 64, "amp_conv2d_grouped_nhwc: %d channels per group (8/16/32/64 supported)", p.cpg);
-        p.cin_win = 64;
-    }
-    p.K = KH * KW * p.cin_win;
-    p.nsteps = amp::cdiv(p.K, BK);
-    const int epi = (sw.generic_epi || (Cout & 3) != 0) ? 0 : ((d->res_mode == 2 || d->out_mode != 0) ? 2 : 1);
-    const int ntm = amp::cdiv(p.M, 128);
-    p.x_bytes = (size_t)d->B * d->H * d->W * Cin * sizeof(float);
-    p.w_bytes = (size_t)Cout * p.K * sizeof(float);
-    // LDS-DMA kernel: every layer but the stem (Cin = 4); buffers must stay below the out-of-range marker (2 GiB)
-    const bool small = sw.ablate == 0 && p.x_bytes < (size_t)OOB_VOFF && p.w_bytes < (size_t)OOB_VOFF;
-    const bool glds = (Cin % BK == 0) && small;
-    AMP_REQUIRE(!grouped || glds, "amp_conv2d_grouped_nhwc: operands must stay below 2 GiB");
-    const bool stem = Cin == 4 && KW == 8 && Cout <= 64 && small;   // the padded 7x7 stem
-    const bool x_is_split = (in.fmt & 1) != 0, res_split = (in.fmt & 4) != 0, mask_split = (in.fmt & 8) != 0;
-    p.y_split = (in.fmt & 2) ? 1 : 0;
-    p.korder = (sw.korder && KH * KW > 1) ? 1 : 0;
-    p.out_mode = d->out_mode;
-    p.rpn_nbp = 1;
-    if (in.fuse == 1) {     // the mask head's deconv with ReLU + predictor + sigmoid in its epilogue (conv_epilogue_predict)
-        AMP_REQUIRE(x_is_split && d->out_mode == 1 && Cout == 1024 && KH == 1 && KW == 1 && d->relu && !in.res && !in.mask && !in.scale && sw.split_ring,
-                    "conv: the fused deconv-predict epilogue needs a split input, Cout = 4 x 256, ReLU and the ring kernel");
-        p.out_mode = 3;
-    } else if (in.fuse == 2) {      // the RPN head's predictors in the 3x3 conv's epilogue (conv_epilogue_rpn): one 128 x 256 tile = all hidden channels of 128 pixels
-        AMP_REQUIRE(x_is_split && d->out_mode == 0 && Cout == 256 && d->relu && !in.res && !in.mask && sw.split_ring && in.in_shift == 0,
-                    "conv: the fused RPN epilogue needs a split input, Cout = 256, ReLU and the ring kernel");
-        AMP_REQUIRE(in.rpn_ld == 16 || ((in.rpn_ld == 32 || in.rpn_ld == 48) && !p.korder), "conv: the fused RPN epilogue writes 16, 32 or 48 predictor rows (16 with AMP_KORDER), not %d", in.rpn_ld);
-        p.rpn_nbp = in.rpn_ld / 16;
-        p.out_mode = 4;
-        p.y_split = 0;
-    }
-    AMP_REQUIRE(!mask_split || (in.mask && epi != 0 && Cout % 32 == 0 && p.out_mode == 0), "conv: a split-format mask needs mask, Cout %% 32 == 0, out_mode 0 and a fast epilogue");
-    AMP_REQUIRE(!res_split || (in.res && epi != 0 && Cout % 32 == 0), "conv: a split-format residual needs res, Cout %% 32 == 0 and a fast epilogue");
-    // split output: out_mode 0; or the 2x2 deconv scatter (out_mode 1) straight from the ring kernel's accumulators -- checked again where the kernel is chosen
-    const bool deconv_split = p.y_split && p.out_mode == 1;
-    AMP_REQUIRE(!p.y_split || ((p.out_mode == 0 || p.out_mode == 1) && Cout % 32 == 0 && epi != 0), "conv: split output needs out_mode 0 (or the deconv scatter) and Cout %% 32 == 0");
-    AMP_REQUIRE(!deconv_split || ((Cout / 4) % 64 == 0 && !in.res && !in.mask && x_is_split && sw.split_ring && Cout % 256 == 0),
-                "conv: a split deconv output needs Cout / 4 %% 64 == 0, a split input, no residual / mask and the ring kernel's direct epilogue");
-    AMP_REQUIRE(!x_is_split || (in.mode == AMP_CONV_F16X3 && !in.force_f32 && Cin % 32 == 0 && glds),
-                "conv: a split-format input needs AMP_CONV_F16X3, Cin %% 32 == 0 and operands below 2 GiB");
-    p.epi = epi;
-    p.stagger = sw.stagger;
-    p.tiles_x = amp::cdiv(p.Wo, 16); p.tiles_y = amp::cdiv(p.Ho, 8);
-    auto take = [&](ConvKernel k, int ntn, long long nblk, bool dominant = false) {
-        p.kernel = k; p.ntn = ntn; p.nblk = (int)nblk; p.dominant = dominant;
-        *plan = p;
-        return AMP_OK;
-    };
-    const int nblk128 = ntm * amp::cdiv(Cout, 128);
-    if (in.mode == AMP_CONV_F16X3 && !in.force_f32 && sw.ablate == 0 && (glds || stem)) {
-        p.f16x3 = true;
-        // 256-wide tiles (8 waves, one workgroup per CU) when they fill the chip twice -- or once, if the K loop is long enough to
-        // amortise a single round (fc1: M = 8000, K = 12544: 64-wide tiles re-read the 400 MB activation matrix from HBM)
-        const int nblk256 = (Cout % 256 == 0) ? ntm * (Cout / 256) : 0;
-        const bool wide256 = sw.f16x3_bn256 && !grouped && !stem && (nblk256 >= 512 || (nblk256 >= 192 && p.nsteps >= WIDE_NSTEPS));
-        const int ntm256 = amp::cdiv(p.M, 256);
-        // a split input that carries a 2^in_shift (scaled loss gradients): only the ring kernel undoes it (out_scale in its fold)
-        AMP_REQUIRE(!(x_is_split && in.in_shift != 0) || (sw.split_ring && epi != 0 && wide256 && p.out_mode != 3),
-                    "conv: a scaled split input needs a layer the 128 x 256 ring kernel takes (Cout %% 256 == 0, enough tiles)");
-        // N tiles per workgroup for the short-K 1x1 layers on the ring kernel (0: not such a layer): as many as leave a full round of workgroups
-        int nloop_nt = 0;
-        if (KH == 1 && KW == 1 && d->pad == 0 && !grouped && Cout % 256 == 0 && Cout >= 512 && Cin % BK == 0 && p.nsteps >= 2 && p.nsteps <= 16 && !p.korder &&
-            p.y_split && !in.mask && d->res_mode == 0 && (p.out_mode == 0 || p.out_mode == 1)) {      // (no residual, no mask: see conv_epilogue_direct_rows PLAIN)
-            const int ntn_ = Cout / 256;
-            nloop_nt = ntn_ < 8 ? ntn_ : 8;
-            while (nloop_nt > 1 && (ntn_ % nloop_nt != 0 || (long long)ntm * (ntn_ / nloop_nt) < 256)) --nloop_nt;
-        }
-        const long long tiles = (long long)d->B * p.tiles_y * p.tiles_x;      // 8 x 16 pixel tiles of the patch kernels
-        const long long p256_tiles = tiles * (Cout / 256);
-        const bool plain_3x3 = KH == 3 && KW == 3 && d->stride == 1 && d->pad == 1;
-        const bool patch256_ok = sw.patch256 != 0 && x_is_split && sw.split_ring && epi != 0 && !grouped && plain_3x3 &&
-            Cin % 32 == 0 && Cin >= 64 && Cout % 256 == 0 && p.nsteps == 9 * (Cin / 32) &&
-            (p.out_mode == 4 || (p.out_mode == 0 && p.y_split && (!in.mask || mask_split) && (d->res_mode == 0 || (d->res_mode == 1 && res_split)))) &&
-            (sw.patch256 == 2 || ((p256_tiles >= 512 || (p256_tiles >= 192 && p.nsteps >= 64)) && p256_tiles * 100 <= (long long)nblk256 * 108));
-        const bool ring = x_is_split && sw.split_ring && epi != 0;      // conv_split_kernel's precondition
-        if (sw.patch_conv != 0 && x_is_split && p.y_split && plain_3x3 && p.cin_win == 64 && (grouped || (Cin == 64 && Cout == 64)) &&
-            p.out_mode == 0 && d->res_mode == 0 && epi != 0 && (!in.mask || mask_split) && in.in_shift == 0 && Cout % 64 == 0 && c64_patch_fills(sw, tiles * (Cout / 64)))
-            // res2's dense 64 -> 64 layers and the ResNeXt conv2: a pixel patch staged once, nine taps read out of it (conv3x3_c64_kernel)
-            return take(grouped && p.cpg <= 32 ? ConvKernel::C64_PATCH_DIAG : ConvKernel::C64_PATCH, Cout / 64, tiles * (Cout / 64));
-        if (patch256_ok) {
-            // FPN output / RPN / res4 / res5 3x3: 8 x 16 pixel tiles, the patch of a 32-channel chunk staged once for its nine taps (conv3x3_patch_kernel)
-            p.epi = p.out_mode == 4 ? 2 + p.rpn_nbp : 1;
-            return take(ConvKernel::PATCH256, Cout / 256, p256_tiles, true);
-        }
-        if (p.out_mode == 3 && sw.mask_tail_loop && Cin % BK == 0 && !p.korder && p.Ho * p.Wo >= 128 /* a 128-pixel block spans at most two RoIs */)
-            return take(ConvKernel::MASK_TAIL, 1, ntm);      // fused mask-head tail: the four taps of a pixel block in one workgroup (a kernel of its own: not the dominant one)
-        if (p.out_mode == 3) {                                // ... one (pixel block, tap) tile per workgroup on the 128 x 256 ring kernel
-            p.epi = 3;
-            return take(ConvKernel::SPLIT_128x256, 4, ntm * 4, true);
-        }
-        if (p.out_mode == 4) {                                // fused RPN tail: one N tile
-            p.epi = 2 + p.rpn_nbp;
-            return take(ConvKernel::SPLIT_128x256, 1, ntm, true);
-        }
-        if (ring && sw.short_k && !grouped && p.nsteps <= SHORT_K_STEPS && in.res && d->res_mode == 1 && res_split && p.y_split && !in.mask &&
-            Cout % 128 == 0 && ntm * (Cout / 128) >= 1024) {
-            // the trunk's conv3 + residual (K = 64 ... 256 into 4 K channels: byte-bound): 128 x 128 tiles on TWO buffers -- tile s + 2 goes into
-            // the buffer of tile s once every wave holds its fragments, same prefetch distance as the three-buffer ring -- so that TWO
-            // workgroups fit a CU and one's residual loads and stores overlap the other's staging: res2 -5 %, res3 -8 %, res4 -3 % on these
-            // launches (A/B in one call; bit-identical); without a residual it is 4 % slower
-            p.stagger = 0;
-            return take(ConvKernel::SPLIT_SHORT_128x128, Cout / 128, ntm * (Cout / 128));
-        }
-        if (sw.nloop && nloop_nt >= 2 && ring && (wide256 || deconv_split)) {
-            // short-K 1x1 layers: several N tiles of a pixel block in one workgroup, the ring carried across them (conv1x1_nloop_kernel)
-            p.nloop_nt = nloop_nt;
-            return take(p.out_mode == 1 ? ConvKernel::NLOOP_SCATTER : ConvKernel::NLOOP, Cout / 256, ntm * (Cout / 256 / nloop_nt));
-        }
-        if (ring && (wide256 || deconv_split))                // 128 x 256 tiles, 3-buffer ring
-            // (the K = 256 deconv with its scatter epilogue on two-buffer 128 x 128 tiles, two workgroups per CU: 1009 against 931 us -- measured, not kept)
-            return take(ConvKernel::SPLIT_128x256, Cout / 256, ntm * (Cout / 256), true);
-        if (ring && !grouped && Cout % 128 == 0 && (ntm256 * (Cout / 128) >= 512 || (ntm256 * (Cout / 128) >= 192 && p.nsteps >= 64)))
-            return take(ConvKernel::SPLIT_256x128, Cout / 128, ntm256 * (Cout / 128));      // Cout = 128 (or 384, ...): 256 x 128 tiles
-        if (ring && sw.tall64 && epi == 1 && !grouped && Cout == 64 && in.in_shift == 0 && ntm256 >= 1024) {
-            p.stagger = 0;
-            return take(ConvKernel::SPLIT_TALL64, 1, ntm256);
-        }
-        if (x_is_split) {      // both operands by LDS-DMA
-            if (wide256) return take(ConvKernel::F16X3S_256, Cout / 256, ntm * (Cout / 256));
-            if (!grouped && Cout > 64 && nblk128 >= 512) return take(ConvKernel::F16X3S_128, amp::cdiv(Cout, 128), nblk128);
-            // (grouped: the window of a 64-wide N tile is the tile's own 64 input channels = 256 B of a split row too; <= 32 channels per group: one K-step per tap)
-            return take(grouped && p.cpg <= 32 ? ConvKernel::F16X3S_G32 : ConvKernel::F16X3S_64, amp::cdiv(Cout, 64), ntm * amp::cdiv(Cout, 64));
-        }
-        if (stem) {
-            p.epi = epi == 2 ? 0 : epi;
-            return take(ConvKernel::F16X3_STEM, 1, ntm);
-        }
-        if (grouped) return take(ConvKernel::F16X3_64, Cout / 64, ntm * (Cout / 64));     // the window of a 64-wide N tile is the tile's own 64 input channels
-        if (wide256) return take(ConvKernel::F16X3_256, Cout / 256, ntm * (Cout / 256));
-        if (Cout > 64 && nblk128 >= 512) return take(ConvKernel::F16X3_128, amp::cdiv(Cout, 128), nblk128);
-        return take(ConvKernel::F16X3_64, amp::cdiv(Cout, 64), ntm * amp::cdiv(Cout, 64));
-    }
-    if (stem) return take(ConvKernel::GLDS_STEM, 1, ntm);
-    if (glds) {     // BN = 64 also for wide layers whose 128-wide grid would leave CUs idle (2 workgroups fit per CU)
-        if (!grouped && Cout > 64 && nblk128 >= 512) return take(ConvKernel::GLDS_128, amp::cdiv(Cout, 128), nblk128, true);
-        return take(ConvKernel::GLDS_64, amp::cdiv(Cout, 64), ntm * amp::cdiv(Cout, 64));
-    }
-    if (Cout > 64) return take(ConvKernel::MFMA_128, amp::cdiv(Cout, 128), nblk128);
-    return take(ConvKernel::MFMA_64, 1, ntm);
-}
-}  // namespace
 
 amp::ConvKernel amp::conv_kernel_for(int conv_mode, const amp_conv_desc& d, int groups, int fmt, int in_shift, bool res, bool mask) {
     ConvPlan p;

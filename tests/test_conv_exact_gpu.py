@@ -1,4 +1,4 @@
-"""Every launch family of conv_run (csrc/conv.hip conv_plan) against the float64 reference of tests/gemm_exact_ref.py, BIT FOR BIT: the
+"""Every launch family of conv_run (csrc/conv_plan.h conv_plan) against the float64 reference of tests/gemm_exact_ref.py, BIT FOR BIT: the
 operands are of the classes on which both convolution arithmetics are exact (class I integers; class L with a live low half, AMP_CONV_F16X3 only),
 so there is no tolerance.  Every case names the kernel and the epilogue it is meant to run and the switch state that selects them;
 amp_debug_conv_plan is asked first, so a later rule change cannot make a case vacuous.  Every output lives inside a larger allocation

@@ -773,7 +773,7 @@ def test_patch_staged_wide_3x3_equals_the_channel_major_ring_kernel(gpu_ctx, sha
         L.amp_debug_set_patch256(0)
         L.amp_debug_set_korder(0)
     ntiles, nsteps = (B * H * W + 127) // 128 * (Cout // 256), 9 * Cin // 32
-    if ntiles >= 512 or (ntiles >= 192 and nsteps >= 64):          # the dispatch rule of the ring kernel (conv.hip wide256); smaller shapes: fp64 only
+    if ntiles >= 512 or (ntiles >= 192 and nsteps >= 64):          # the dispatch rule of the ring kernel (conv_plan.h wide256); smaller shapes: fp64 only
         nd = int((outs["patch"].view(torch.int32) != outs["ring_chan"].view(torch.int32)).sum())
         assert nd == 0, f"{nd} words differ from the channel-major ring kernel"
         assert not torch.equal(outs["ring_chan"].view(torch.int32), outs["ring_tap"].view(torch.int32))       # the switch did switch the order

@@ -1,4 +1,4 @@
-"""Which kernel conv_run gives a layer (csrc/conv.hip conv_plan), without a GPU: tests/golden/conv_plan_table.json holds one row per distinct
+"""Which kernel conv_run gives a layer (csrc/conv_plan.h conv_plan), without a GPU: tests/golden/conv_plan_table.json holds one row per distinct
 combination of selection inputs and switch state that the benchmark (default and --full) and tests/test_{conv,conv_modes,x101,backward}_gpu.py
 reach, with the launch the if / else chain of conv_run chose for it BEFORE conv_plan existed (recorded from that commit, not from this code);
 the rows of the cases of tests/test_conv_exact_gpu.py came later and were recorded from the rules current then (the table's "what" field).

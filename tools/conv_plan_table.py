@@ -1,4 +1,4 @@
-"""tests/golden/conv_plan_table.json: which launch conv_run gives each layer (csrc/conv.hip conv_plan), one row per distinct combination of
+"""tests/golden/conv_plan_table.json: which launch conv_run gives each layer (csrc/conv_plan.h conv_plan), one row per distinct combination of
 selection inputs and switch state.
 
 python tools/conv_plan_table.py            rewrite the "chosen" half of every row from its inputs through amp_debug_conv_plan (no GPU)
