@@ -49,6 +49,11 @@ pycocotools:
     `amp_mask_morphology` call changes the shape of every mask of an image by a distance on its run list -- every vertical piece sends a
     grown or shrunk interval to the columns within the radius, and a pixel's class follows from the integer cover of those intervals, found
     by a sort and a scan of +1 / -1 events on the device (csrc/morphology.hip) or by a sweep per column on the host --; no mask is decoded.
+  * `mask_distance_maps`, `inscribed_circles`, `erosion_curve` and the `inscribed_radius` column of `region_properties` (what users do today
+    with scipy.ndimage.distance_transform_edt on one decoded array per mask): ONE `amp_mask_distance` call gives the exact squared distance
+    of every mask pixel to the nearest pixel outside its mask, the deepest pixel, the sums and the erosion curve of every mask of an image
+    from the run lists -- every pixel walks the columns outwards from its own and looks up the vertical piece that holds its row, one wave
+    per 64 rows of a piece on the device (csrc/mask_distance.hip), the same walk in a loop on the host --; no mask is decoded to the image.
 With no prediction at all the detection precision is 0/0: like the reference this raises ZeroDivisionError.
 The independent checker is oracle/matcher.py (a loop-for-loop restatement of the reference, pinned by its known-answer test)."""
 import numpy as np
@@ -209,6 +214,7 @@ RPROPS_DEFAULT_KEYS = ["area", "equivalent_diameter", "major_axis_length", "peri
 RPROPS_KEYS = ("area", "bbox", "bbox_area", "centroid", "convex_area", "eccentricity", "equivalent_diameter", "extent", "major_axis_length",
                "minor_axis_length", "orientation", "perimeter", "solidity")
 RPROPS_TOPOLOGY_KEYS = ("euler_number", "filled_area")            # from mask_topology at connectivity 2: the mask as a shape with pieces
+RPROPS_DISTANCE_KEYS = ("inscribed_radius",)                      # from inscribed_circles at border_value 0: the largest circle inside the mask
 
 
 def region_floats(bbox, vals):
@@ -245,8 +251,9 @@ def _rprops_columns(keys):
     keys = list(RPROPS_DEFAULT_KEYS if keys is None else keys)
     cols = []
     for k in keys:
-        if k not in RPROPS_KEYS and k not in RPROPS_TOPOLOGY_KEYS:
-            raise ValueError(f"region_properties: unsupported key {k!r} (supported: {', '.join(RPROPS_KEYS + RPROPS_TOPOLOGY_KEYS)})")
+        if k not in RPROPS_KEYS and k not in RPROPS_TOPOLOGY_KEYS and k not in RPROPS_DISTANCE_KEYS:
+            raise ValueError(f"region_properties: unsupported key {k!r} (supported: "
+                             f"{', '.join(RPROPS_KEYS + RPROPS_TOPOLOGY_KEYS + RPROPS_DISTANCE_KEYS)})")
         cols += [f"bbox-{i}" for i in range(4)] if k == "bbox" else [f"centroid-{i}" for i in range(2)] if k == "centroid" else [k]
     return cols
 
@@ -256,9 +263,10 @@ def region_properties(masks, keys=None, size=None, device='auto'):
     a dict of column name -> np.ndarray [N], columns named like regionprops_table ('bbox-0' .. 'bbox-3', 'centroid-0', 'centroid-1', the rest by
     key).  A region is ALL set pixels of one mask (holes and disconnected parts included), coordinates are (row, column) of the full image.
 
-    masks: anything masks_to_rle accepts (size=(h, w) for polygons); keys: any of RPROPS_KEYS and RPROPS_TOPOLOGY_KEYS ('euler_number' and
+    masks: anything masks_to_rle accepts (size=(h, w) for polygons); keys: any of RPROPS_KEYS, RPROPS_TOPOLOGY_KEYS ('euler_number' and
     'filled_area', int64, 0 for an empty mask: skimage's -- foreground 8-connected, holes 4-connected -- from mask_topology at connectivity 2 on
-    the same path), None for the reference's default list; device:
+    the same path) and RPROPS_DISTANCE_KEYS ('inscribed_radius', float64, 0 for an empty mask: inscribed_circles' radius at border_value 0
+    on the same path), None for the reference's default list; device:
     'cpu' (host), 'cuda' (HIP device, an error without one) or 'auto' (the device when one is visible).  One amp_mask_region_props call returns
     13 exact integers per mask (csrc/region_props.hip, or mask_analysis_host.hip on the host); region_floats derives the floats from them for both
     paths, so they agree bit for bit.  An empty mask: area, perimeter, convex_area, equivalent_diameter 0, bbox (0, 0, 0, 0), NaN elsewhere.
@@ -277,6 +285,8 @@ def region_properties(masks, keys=None, size=None, device='auto'):
     rows = [region_floats(b, v) for b, v in zip(bbox.tolist(), vals.tolist())]
     ints = ("area", "bbox_area", "convex_area", "bbox-0", "bbox-1", "bbox-2", "bbox-3")
     topo = mask_topology(rles, 2, device=device) if any(c in RPROPS_TOPOLOGY_KEYS for c in cols) else {}
+    if any(c in RPROPS_DISTANCE_KEYS for c in cols):
+        topo = dict(topo, inscribed_radius=inscribed_circles(rles, 0, device=device)["radius"])
     return {c: topo[c] if c in topo else np.array([r[c] for r in rows], dtype=np.int64 if c in ints else np.float64) for c in cols}
 
 
@@ -539,6 +549,84 @@ def near_pairs(masks, gap=1, shape='disk', size=None, device='auto'):
     masks, size = _unwrap_masks(masks, size)
     meets = overlap_matrix(grown, masks_to_rle(masks, size, device), device=device) > 0
     return np.argwhere(np.triu(meets, 1)).astype(np.int64).reshape(-1, 2)
+
+
+# ---- distance inside a mask (scipy.ndimage.distance_transform_edt on one decoded array per mask) ------------------------------------------------
+
+def _mask_distance(who, masks, border_value, ncurve, want_map, size, device):
+    """One rle.mask_distance call for a public function; every argument is checked before anything else happens"""
+    if isinstance(border_value, bool) or border_value not in (0, 1):
+        raise ValueError(f"{who}: border_value = {border_value!r} (0 or 1)")
+    if str(device).lower() not in ("auto", "cpu", "cuda"):
+        raise ValueError(f"{who}: device = {device!r} ('auto', 'cpu' or 'cuda')")
+    masks, size = _unwrap_masks(masks, size)
+    rles = masks_to_rle(masks, size, device)
+    sizes = {tuple(int(v) for v in r["size"]) for r in rles}
+    if len(sizes) > 1:
+        raise ValueError(f"{who}: masks of different sizes {sorted(sizes)}")
+    res = rle.mask_distance(rles, int(border_value), ncurve, want_map, ctx=_device_context(who, device, len(rles)),
+                            size=size if not rles else None)
+    return res + (int(rles[0]["size"][0]) if rles else 1,)            # and the image height: what a position col * h + row is split by
+
+
+def mask_distance_maps(masks, border_value=0, squared=False, size=None, device='auto'):
+    """How far inside its mask every pixel lies: per mask a dict {'bbox': (r0, c0, r1, c1), 'distance': array [r1 - r0, c1 - c0]} with the
+    Euclidean distance of every mask pixel of the tight box (ends exclusive; zeros and an empty array for an empty mask) to the nearest pixel
+    that is not in the mask, 0 outside the mask -- scipy.ndimage.distance_transform_edt on the decoded mask, cut to the box.  border_value 0:
+    the pixels just outside the image are background as well (the mask padded by one zero on every side); 1: only pixels of the image count
+    (scipy on the undecorated array).  squared=True gives the exact uint32 squared distances; otherwise float64, numpy's correctly rounded
+    root of them.  A mask without background (border_value 1 and the full image) has rle.DIST_NONE, or inf, on every pixel: scipy leaves that
+    case undefined.
+
+    masks: anything masks_to_rle accepts (size=(h, w) for polygons), an Instances or an InstanceSet; device: 'cpu' (host), 'cuda' (HIP device,
+    an error without one) or 'auto' (the device when one is visible).  One amp_mask_distance call on the run lists (csrc/mask_distance.hip, or
+    mask_distance_host.hip on the host: identical bytes), no mask is decoded to the image; a pixel costs about as many steps as its distance.
+    ValueError before any device work for a bad border value or device and for masks of different sizes."""
+    _, boxes, _, maps, _ = _mask_distance("mask_distance_maps", masks, border_value, 0, True, size, device)
+    out = []
+    for b, m in zip(boxes.tolist(), maps):
+        if not squared:
+            none = m == rle.DIST_NONE
+            m = np.sqrt(m.astype(np.float64))
+            m[none] = np.inf
+        out.append({"bbox": tuple(int(v) for v in b), "distance": m})
+    return out
+
+
+def inscribed_circles(masks, border_value=0, size=None, device='auto'):
+    """The largest circle that fits into every mask, centred on a pixel: a dict of [N] arrays 'd2' (int64, the largest squared distance of a
+    mask pixel to the nearest pixel outside the mask), 'radius' (float64, its root: the circle of that radius about the pixel's centre reaches
+    the centre of the nearest outside pixel), 'row', 'col' (int64, the pixel that attains it, among equals the first in column-major order)
+    and 'center_xy' ([N, 2] float64, (col + 0.5, row + 0.5) in the corner coordinates of mask_contours).  The particle size that a satellite
+    or a ragged outline does not inflate; 2 * radius across a neck is its width.  An empty mask: d2 0, radius 0, row and col -1, center_xy
+    NaN; a mask without background (border_value 1 and the full image): d2 rle.DIST_NONE, radius inf, pixel (0, 0).  A statistics-only
+    amp_mask_distance call: no map, no curve.  masks, border_value, device and errors as in mask_distance_maps."""
+    stats, _, _, _, h = _mask_distance("inscribed_circles", masks, border_value, 0, False, size, device)
+    return _circles(stats, h)
+
+
+def _circles(stats, h):
+    """inscribed_circles' dict from amp_mask_distance's stats of masks of image height h"""
+    d2, pos, area = stats[:, 0].copy(), stats[:, 1], stats[:, 3]
+    some = area > 0
+    radius = np.sqrt(d2.astype(np.float64))
+    radius[d2 == rle.DIST_NONE] = np.inf
+    row = np.where(some, pos % h, -1).astype(np.int64)
+    col = np.where(some, pos // h, -1).astype(np.int64)
+    xy = np.stack([col + 0.5, row + 0.5], axis=1).astype(np.float64).reshape(-1, 2)
+    xy[~some] = np.nan
+    return {"d2": d2.astype(np.int64), "radius": radius, "row": row, "col": col, "center_xy": xy}
+
+
+def erosion_curve(masks, max_radius, border_value=0, size=None, device='auto'):
+    """How many pixels of every mask lie deeper than r, for every r at once: int64 [N, max_radius + 1], column r = the pixels whose distance
+    to the nearest pixel outside the mask exceeds r.  Column 0 is the area; with border_value 0 column r is the area of
+    erode_masks(masks, 'disk', r, border_value=0) -- a pixel survives the disk of radius r exactly when no outside pixel lies within r of it
+    --, the granulometry that costs one erode_masks call per radius otherwise.  max_radius: an integer 0 .. 1024.  One amp_mask_distance call
+    with a curve, no map.  masks, border_value, device and errors as in mask_distance_maps; ValueError for a bad max_radius as well."""
+    if isinstance(max_radius, bool) or not isinstance(max_radius, (int, np.integer)) or not 0 <= int(max_radius) <= rle.MORPH_MAX_RADIUS:
+        raise ValueError(f"erosion_curve: max_radius = {max_radius!r} (an integer 0 .. {rle.MORPH_MAX_RADIUS})")
+    return _mask_distance("erosion_curve", masks, border_value, int(max_radius) + 1, False, size, device)[2]
 
 
 # ---- overlap-free instances: the owner of every pixel (the labels[mask_i] = i + 1 loop over decoded masks) ---------------------------------------

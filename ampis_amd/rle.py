@@ -579,6 +579,50 @@ def morphology(masks, op, shape='disk', radius=1, border_value=0, ctx=None, size
     return (res, boxes, areas.astype(np.int64)) if return_stats else res
 
 
+DIST_NONE = 0xFFFFFFFF                                              # AMP_DIST_NONE: the squared distance of a pixel of a mask without background
+DIST_MAX_CURVE = MORPH_MAX_RADIUS + 1
+
+
+def mask_distance(masks, border_value=0, ncurve=0, want_map=False, ctx=None, size=None):
+    """Exact squared distance maps of RLE dicts of one image size (amp_mask_distance; with want_map a first call that only asks for the
+    capacity, which the check answers on the host).  For every pixel of a mask the squared Euclidean distance to the nearest pixel outside it
+    -- scipy.ndimage.distance_transform_edt, squared --; border_value 0 counts the pixels just outside the image as background, 1 does not
+    (scipy on the undecorated array).  Returns (stats, boxes, curve, maps): stats int64 [n, 4] = {d2_max, pos, sum_d2, area} with pos = col *
+    h + row of the first pixel in column-major order that attains d2_max (zeros for an empty mask, {DIST_NONE, 0, 0, h * w} for a mask
+    without background); boxes int64 [n, 4] = the tight boxes {r0, c0, r1, c1}, ends exclusive; curve int64 [n, ncurve] = the pixels with
+    d2 > r^2 for r = 0 .. ncurve - 1 (ncurve 0 .. 1025); maps = per mask the uint32 [r1 - r0, c1 - c0] squared distances on its box, 0
+    outside the mask, or None without want_map.  size=(h, w) is needed only when there is no mask.  ValueError for a bad border value or
+    ncurve and masks of different sizes.  ctx: a _lib.Context (computed on its device) or None (on the host): the same bytes."""
+    if isinstance(border_value, bool) or border_value not in (0, 1):
+        raise ValueError(f"mask_distance: border_value = {border_value!r} (0 or 1)")
+    if isinstance(ncurve, bool) or not isinstance(ncurve, (int, np.integer)) or not 0 <= int(ncurve) <= DIST_MAX_CURVE:
+        raise ValueError(f"mask_distance: ncurve = {ncurve!r} (an integer 0 .. {DIST_MAX_CURVE})")
+    n, ncurve = len(masks), int(ncurve)
+    sizes = {tuple(int(v) for v in r["size"]) for r in masks}
+    if size is not None:
+        sizes.add((int(size[0]), int(size[1])))
+    if len(sizes) > 1:
+        raise ValueError(f"mask_distance: masks of different sizes {sorted(sizes)}")
+    stats, boxes, curve = np.zeros((n, 4), dtype=np.uint64), np.zeros((n, 4), dtype=np.int64), np.zeros((n, ncurve), dtype=np.uint64)
+    if n == 0:
+        return stats.astype(np.int64), boxes, curve.astype(np.int64), ([] if want_map else None)
+    h, w = sizes.pop()
+    pool, off, ln = _pool([_counts(x) for x in masks])
+    args = (_handle(ctx), _vp(pool), _vp(off), _vp(ln), n, h, w, int(border_value), _vp(stats), _vp(boxes), _vp(curve) if ncurve else None, ncurve)
+    if not want_map:
+        check(lib().amp_mask_distance(*args, None, 0, None, None), "amp_mask_distance")
+        return stats.astype(np.int64), boxes, curve.astype(np.int64), None
+    map_off, need = np.zeros(n, dtype=np.uint64), np.zeros(1, dtype=np.uint64)
+    buf = np.empty(1, dtype=np.uint32)
+    st = lib().amp_mask_distance(*args, _vp(buf), 0, _vp(map_off), _vp(need))               # the need: refused before any evaluation
+    if st == -3:
+        buf = np.empty(int(need[0]), dtype=np.uint32)
+        st = lib().amp_mask_distance(*args, _vp(buf), int(need[0]), _vp(map_off), _vp(need))
+    check(st, "amp_mask_distance")
+    maps = [buf[int(o): int(o) + int((b[2] - b[0]) * (b[3] - b[1]))].reshape(int(b[2] - b[0]), int(b[3] - b[1])).copy() for o, b in zip(map_off, boxes)]
+    return stats.astype(np.int64), boxes, curve.astype(np.int64), maps
+
+
 def merge(rles, intersect=False):
     assert len(rles) >= 1
     h, w = rles[0]["size"]

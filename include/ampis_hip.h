@@ -747,6 +747,38 @@ int amp_mask_morphology(amp_ctx* ctx, const uint32_t* pool, const unsigned long 
                         int shape, int radius, int border_value, uint32_t* out_pool, unsigned long long out_cap,
                         unsigned long long* out_off /* [n] */, int* out_len /* [n] */, long long* boxes /* [n][4] */,
                         unsigned long long* areas /* [n] */, unsigned long long* need /* [1] */);
+/* Distance maps inside masks: for the n run lists pool[off[i] : off[i] + len[i]] of one h x w image size (1 <= h, w <= 32768, h * w <= 2^30)
+ * the exact squared Euclidean distance d2(p) of every pixel p of mask i to the nearest pixel that is not in mask i -- what
+ * scipy.ndimage.distance_transform_edt gives, squared --, its per-mask statistics and the erosion curve, in one call, without a dense mask.
+ * ALL POINTERS ARE HOST POINTERS.  border_value 0: the pixels just outside the image are background as well, as if the mask were padded by
+ * one zero on every side; 1: only pixels inside the image count (scipy on the undecorated array).  A mask with no background at all
+ * (border_value 1 and the full image) has d2 = AMP_DIST_NONE on every pixel; every real value is below 2^31.
+ * The masks are cut into pieces, maximal vertical runs of ones of one column (amp_mask_parts' items).  For a pixel at row r of piece [s, e)
+ * of its own column the column distance is g = min(r - s + 1, e - r), where with border_value 1 a side that is the image's edge (s == 0 or
+ * e == h) does not count; d2(p) = min over the columns c' of (c - c')^2 + g_c'(r)^2, with g_c'(r) = 0 where (r, c') is not in the mask and
+ * columns -1 and w contributing (c - c')^2 with border_value 0.  The search walks outwards from the pixel's own column and stops as soon as
+ * dx^2 reaches the best value so far, so it is exact and a pixel costs about as many steps as its distance.
+ *   stats[i] = {d2_max, pos, sum_d2, area}: pos = col * h + row of the pixel that attains d2_max, among equals the smallest pos (the first in
+ *              column-major order); zeros for an empty mask, {AMP_DIST_NONE, 0, 0, h * w} for the mask without background;
+ *   boxes[i] = the tight box {r0, c0, r1, c1}, ends exclusive, zeros for an empty mask (amp_mask_morphology's layout);
+ *   curve[i][r], r = 0 .. ncurve - 1 (ncurve 0 .. AMP_MORPH_MAX_RADIUS + 1; curve == NULL requires ncurve == 0) = the pixels of mask i with
+ *              d2 > r^2: curve[i][0] is the area, and with border_value 0 curve[i][r] is the area of the erosion by the disk of radius r;
+ *   map (or NULL, then map_cap must be 0 and map_off and need are not used): mask i's squared distances on its tight box, row-major, 0 outside
+ *              the mask, at map[map_off[i] .. + (r1 - r0) * (c1 - c0)), the crops back to back in mask order.  need[0] = the sum of the box
+ *              areas is always written when map != NULL and the arguments are valid; with map_cap below it the call returns AMP_ERR_NOMEM
+ *              and writes nothing else.
+ * Checked on the host before any device work (AMP_ERR_ARG naming the offender, nothing written): the sizes, n < 0, border_value, ncurve,
+ * NULL pointers that are not optional, map_cap without map, every run list non-empty and summing to h * w.  n == 0, empty masks, full masks
+ * and zero-length runs are valid.
+ * ctx == NULL: computed on the host (mask_distance_host.hip).  Otherwise on ctx's device and stream (mask_distance.hip): upload, one memset
+ * and one kernel whatever the masks hold, download; integer arithmetic and integer atomics only, the bytes do not depend on the device's
+ * scheduling and equal the host's.  Both paths evaluate the one walk of mask_distance.h; its work grows with the distance found:
+ * O(pixels x inscribed radius) in the worst case, and nothing is refused for that reason. */
+#define AMP_DIST_NONE 0xffffffffu
+int amp_mask_distance(amp_ctx* ctx, const uint32_t* pool, const unsigned long long* off, const int* len, int n, int h, int w,
+                      int border_value, unsigned long long* stats /* [n][4] */, long long* boxes /* [n][4] */,
+                      unsigned long long* curve /* [n][ncurve] or NULL */, int ncurve, uint32_t* map /* or NULL */,
+                      unsigned long long map_cap, unsigned long long* map_off /* [n] */, unsigned long long* need /* [1] */);
 
 /* The model: DefaultPredictor(cfg) / predictor(img) ---------------------------------------------- */
 typedef struct amp_model amp_model;
