@@ -178,14 +178,14 @@ namespace amp {
 // internal convolution entry (conv.hip): w_split = weights already in the f16x3 split layout (amp_split_weights) or null;
 // force_f32 = 1 runs the fp32-MFMA kernel whatever the context mode is; in_shift = s: (AMP_CONV_F16X3 only) the input is multiplied
 // by 2^s before the operand split and the sum by 2^-s (data gradients: tiny values would otherwise sit in the f16 subnormals).
-struct PredictFuse {              // the mask head's tail fused into the deconv's epilogue (conv.hip conv_epilogue_predict)
+struct PredictFuse {              // the mask head's tail fused into the deconv's epilogue (conv_predict.h conv_epilogue_predict)
     const float* pred_w;          // [K][256] predictor weights, fp32
     const float* pred_b;          // [K]
     const int* cls;               // [N] class of each RoI
     int K;
     float* prob;                  // [N][28][28]
 };
-struct RpnFuse {                  // the RPN head's 1x1 predictors fused into the 3x3 conv's epilogue (conv.hip conv_epilogue_rpn)
+struct RpnFuse {                  // the RPN head's 1x1 predictors fused into the 3x3 conv's epilogue (conv_predict.h conv_epilogue_rpn)
     const float* w_split;         // [ld][256] objectness + anchor-delta rows (+ zero rows) in the split row format
     const float* bias;            // [ld]
     float* pred;                  // [M][ld]

@@ -12,7 +12,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 typedef _Float16 pp_h4 __attribute__((ext_vector_type(4)));
 // SPLIT: a pixel's 16 bytes are the f16 hi halves of its 4 values, then the lo' halves ((v - hi) * 2^11) -- what the f16x3 stem would make
-// of the fp32 pixel tap by tap (conv.hip split8); stem_pool_f16x3_kernel then stages the halves as they are
+// of the fp32 pixel tap by tap (conv_f16x3.h split8); stem_pool_f16x3_kernel then stages the halves as they are
 template <bool SPLIT>
 __global__ void preprocess_kernel(const uint8_t* __restrict__ img, float* __restrict__ out, int B, int H, int W, int Hp,
                                   int Wp, float m0, float m1, float m2, float s0, float s1, float s2, const int* __restrict__ img_hw) {

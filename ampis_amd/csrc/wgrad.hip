@@ -176,7 +176,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(const WgradArgs a) {
 }
 
 // wgrad_f16x3_kernel (conv mode AMP_CONV_F16X3): the same GEMM on the f16 matrix pipe with the 3-MFMA operand split of
-// conv_f16x3_kernel (conv.hip): x = hi + lo'*2^-11, dW ~= sum hi*hi + (hi*lo' + lo'*hi) * 2^-11, fp32 accumulation.
+// conv_f16x3_kernel (conv_f16x3.h): x = hi + lo'*2^-11, dW ~= sum hi*hi + (hi*lo' + lo'*hi) * 2^-11, fp32 accumulation.
 // v_mfma_f32_32x32x16_f16 wants 8 CONSECUTIVE reduction indices (pixels) per lane, but in memory the pixel is the slow index of
 // both operands.  The transposition happens in the register stage that has to exist anyway for the split: wave w of a step owns
 // pixels 8w..8w+7, a lane two adjacent columns; it loads its 8 x 2 block of each operand (8 coalesced 512-B row loads), splits it
@@ -406,7 +406,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_f16x3_kernel(const WgradArgs a, 
 //   * a K-step is 32 pixels; the 32 x 128-channel slab of dY rows (512 B per pixel) and the 32 x 256-channel slab of X rows (1 KiB per
 //     pixel, through the [tap][pixel] offset table) are copied AS THEY ARE into LDS by LDS-DMA (6 requests per wave and step, zero fill
 //     beyond the tensor / outside the image), through a ring of three 48-KiB tiles with counted vmcnt and bare barriers, and the two
-//     halves of the workgroup ping-pong between loading and multiplying -- conv_split_kernel's loop (conv.hip);
+//     halves of the workgroup ping-pong between loading and multiplying -- conv_split_kernel's loop (conv_split.h);
 //   * the MFMA wants 8 consecutive PIXELS per lane and channel, the rows hold consecutive CHANNELS per pixel: gfx950's transposing LDS read
 //     does the rest -- ds_read_b64_tr_b16 hands lane i of a 16-lane group column i of a 4-row x 16-column block of 16-bit elements, so
 //     two of them are the f16x8 operand of v_mfma_f32_16x16x32_f16 (probed on the GPU: tools/tr_probe.hip);

@@ -1,4 +1,4 @@
-"""Lab: in-kernel phase timing of conv_split_kernel (library built with `make EXTRA=-DAMP_STAMP`, see conv.hip g_stamp).
+"""Lab: in-kernel phase timing of conv_split_kernel (library built with `make EXTRA=-DAMP_STAMP`, see csrc/conv_split.h g_stamp).
 usage (GPU box): AMP_STAGGER=0|1 python tools/stamp_conv.py [layer ...]"""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
