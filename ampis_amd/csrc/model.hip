@@ -69,6 +69,7 @@ struct amp_model {
     std::map<std::string, ConvW> conv;                     // keyed by detectron2 module prefix
     std::map<std::string, std::vector<float>> host_raw;    // raw host copies needed at finalize (BN stats, fused parts)
     std::map<std::string, bool> loaded;
+    std::map<std::string, bool> raw_fresh;                 // halves of the fused predictor matrices loaded since the last amp_model_finalize
     std::vector<std::string> expected;
     bool finalized = false;
     // ---- workspace ----
@@ -886,7 +887,8 @@ int run_train(amp_model* m, const uint8_t* imgs_d, int B, int H, int W, const am
     m->saving = backward;
     // the forward trunk of a training step runs on pre-split operands like inference: refresh the weights' split copies (stale since the
     // last SGD step) once here instead of splitting every layer's weights inside its own launch
-    if (!dry && backward && m->split_stale && m->ctx->conv_mode == AMP_CONV_F16X3 && getenv("AMP_NO_TRAIN_NATIVE") == nullptr) AMP_TRY(refresh_split_weights(m));
+    // (a forward-only call too: the losses of the same weights must not depend on whether an inference came in between)
+    if (!dry && m->split_stale && m->ctx->conv_mode == AMP_CONV_F16X3 && getenv("AMP_NO_TRAIN_NATIVE") == nullptr) AMP_TRY(refresh_split_weights(m));
     static const bool no_dgrad_batch = getenv("AMP_NO_DGRAD_BATCH") != nullptr;      // EXPERIMENT switch: transpose + split in front of every data-gradient conv
     const bool dgrad_batch = !dry && backward && !no_dgrad_batch && m->ctx->conv_mode == AMP_CONV_F16X3;
     if (dgrad_batch) AMP_TRY(refresh_dgrad_weights(m));
@@ -1915,6 +1917,7 @@ int amp_model_load_tensor(amp_model* m, const char* name_c, const float* data, c
         const size_t cols = box ? 1024 : 256;
         AMP_REQUIRE(numel == rows * (is_w ? cols : 1), "%s: unexpected size %zu", name_c, numel);
         m->host_raw[name].assign(data, data + numel);           // fused at finalize
+        m->raw_fresh[name] = true;
     } else if (prefix == "roi_heads.mask_head.deconv") {
         if (is_w) {
             AMP_REQUIRE(ndim == 4 && shape[0] == 256 && shape[1] == 256 && shape[2] == 2 && shape[3] == 2, "%s: expected [256,256,2,2]", name_c);
@@ -2108,17 +2111,31 @@ int amp_model_finalize(amp_model* m) {
     auto fuse = [&](const char* key, const char* a, const char* b, int ra, int rb, int cols, int rows_padded = 0) -> int {
         const int rp = rows_padded ? rows_padded : (ra + rb + 3) / 4 * 4;   // rows padded to a multiple of 4 (zero rows): 16-byte output rows
         std::vector<float> w((size_t)rp * cols, 0.f), bias(rp, 0.f);
-        const auto& wa = m->host_raw.at(std::string(a) + ".weight");
-        const auto& wb = m->host_raw.at(std::string(b) + ".weight");
-        const auto& ba = m->host_raw.at(std::string(a) + ".bias");
-        const auto& bb = m->host_raw.at(std::string(b) + ".bias");
-        memcpy(w.data(), wa.data(), wa.size() * 4);
-        memcpy(w.data() + wa.size(), wb.data(), wb.size() * 4);
-        memcpy(bias.data(), ba.data(), ba.size() * 4);
-        memcpy(bias.data() + ba.size(), bb.data(), bb.size() * 4);
         ConvW& cw = m->conv[key];
-        if (!cw.w) { cw.w = palloc(m, w.size()); cw.shift = palloc(m, bias.size()); }
+        const bool stored = cw.w != nullptr;
+        if (!stored) { cw.w = palloc(m, w.size()); cw.shift = palloc(m, bias.size()); }
         AMP_REQUIRE(cw.w && cw.shift, "amp_model_finalize: parameter arena exhausted");
+        // A finalize after the first one (a partial reload through amp_model_load_tensor): the device rows are the truth -- SGD steps and
+        // broadcasts have moved them past the host copies of the first load -- and only a half loaded since then replaces its rows.
+        auto is_fresh = [&](const std::string& name) { auto f = m->raw_fresh.find(name); return f != m->raw_fresh.end() && f->second; };
+        const bool all_fresh = is_fresh(std::string(a) + ".weight") && is_fresh(std::string(b) + ".weight") && is_fresh(std::string(a) + ".bias") &&
+                               is_fresh(std::string(b) + ".bias");      // a full reload: nothing of the device rows is kept, nothing is read back
+        if (stored && !all_fresh) {
+            AMP_TRY(amp::comm_wait_done(m->ctx));
+            AMP_HIP_CHECK(hipStreamSynchronize(m->ctx->stream));
+            AMP_HIP_CHECK(hipMemcpy(w.data(), cw.w, w.size() * 4, hipMemcpyDeviceToHost));
+            AMP_HIP_CHECK(hipMemcpy(bias.data(), cw.shift, bias.size() * 4, hipMemcpyDeviceToHost));
+        }
+        auto half = [&](const std::string& name, float* dst) {
+            if (stored && !is_fresh(name)) return;
+            const auto& v = m->host_raw.at(name);
+            memcpy(dst, v.data(), v.size() * 4);
+            m->raw_fresh[name] = false;
+        };
+        half(std::string(a) + ".weight", w.data());
+        half(std::string(b) + ".weight", w.data() + (size_t)ra * cols);
+        half(std::string(a) + ".bias", bias.data());
+        half(std::string(b) + ".bias", bias.data() + ra);
         cw.cout = rp; cw.cin = cols; cw.kh = cw.kw = 1;
         cw.w_absmax = 0.f;
         for (float f : w) cw.w_absmax = std::max(cw.w_absmax, std::fabs(f));
