@@ -257,6 +257,7 @@ def _declare(L):
         "amp_mask_contours": ([vp, vp, vp, vp, i, i, i, i, vp, vp, vp, vp, vp, C.c_ulonglong, vp, C.c_ulonglong, vp], i),
         "amp_mask_morphology": ([vp, vp, vp, vp, i, i, i, i, i, i, i, vp, C.c_ulonglong, vp, vp, vp, vp, vp], i),
         "amp_mask_distance": ([vp, vp, vp, vp, i, i, i, i, vp, vp, vp, i, vp, C.c_ulonglong, vp, vp], i),
+        "amp_mask_intensity": ([vp, vp, vp, vp, i, i, i, vp, i, i, i, vp, vp, C.c_ulonglong, vp], i),
         "amp_model_cfg_default": ([C.POINTER(ModelCfg)], i),
         "amp_model_create": ([vp, C.POINTER(ModelCfg), C.POINTER(vp)], i),
         "amp_model_create_anchors": ([vp, C.POINTER(ModelCfg), C.POINTER(AnchorCfg), C.POINTER(vp)], i),

@@ -54,6 +54,11 @@ pycocotools:
     of every mask pixel to the nearest pixel outside its mask, the deepest pixel, the sums and the erosion curve of every mask of an image
     from the run lists -- every pixel walks the columns outwards from its own and looks up the vertical piece that holds its row, one wave
     per 64 rows of a piece on the device (csrc/mask_distance.hip), the same walk in a loop on the host --; no mask is decoded to the image.
+  * `intensity_properties`, `intensity_histograms`, `intensity_quantiles` and the intensity columns of `region_properties` (what users do
+    today with skimage's regionprops(..., intensity_image=img) or img[RLE.decode(m)] per instance): ONE `amp_mask_intensity` call gives the
+    exact integer sums, extremes and histograms of the micrograph's grey levels under every mask of an image from the run lists -- in a
+    column-major plane of the image every run is one contiguous range, so the device transposes the image once and reduces the runs
+    (csrc/mask_intensity.hip), the host cuts the runs at the column ends --; no mask is decoded.
 With no prediction at all the detection precision is 0/0: like the reference this raises ZeroDivisionError.
 The independent checker is oracle/matcher.py (a loop-for-loop restatement of the reference, pinned by its known-answer test)."""
 import numpy as np
@@ -246,19 +251,24 @@ def region_floats(bbox, vals):
     return out
 
 
-def _rprops_columns(keys):
-    """regionprops_table's column names of `keys` (None: the reference's default list); ValueError naming a key this module does not have."""
+def _rprops_columns(keys, channels=0):
+    """regionprops_table's column names of `keys` (None: the reference's default list); ValueError naming a key this module does not have.
+    channels: those of the intensity image (0: none; the intensity keys are then refused by the caller); their columns are
+    _intensity_columns'."""
     keys = list(RPROPS_DEFAULT_KEYS if keys is None else keys)
     cols = []
     for k in keys:
+        if k in RPROPS_INTENSITY_KEYS:
+            cols += [c[0] for c in _intensity_columns("region_properties", [k], max(channels, 1))]
+            continue
         if k not in RPROPS_KEYS and k not in RPROPS_TOPOLOGY_KEYS and k not in RPROPS_DISTANCE_KEYS:
             raise ValueError(f"region_properties: unsupported key {k!r} (supported: "
-                             f"{', '.join(RPROPS_KEYS + RPROPS_TOPOLOGY_KEYS + RPROPS_DISTANCE_KEYS)})")
+                             f"{', '.join(RPROPS_KEYS + RPROPS_TOPOLOGY_KEYS + RPROPS_DISTANCE_KEYS + RPROPS_INTENSITY_KEYS)})")
         cols += [f"bbox-{i}" for i in range(4)] if k == "bbox" else [f"centroid-{i}" for i in range(2)] if k == "centroid" else [k]
     return cols
 
 
-def region_properties(masks, keys=None, size=None, device='auto'):
+def region_properties(masks, keys=None, size=None, device='auto', intensity_image=None):
     """Shape measurements of every mask, the table skimage.measure.regionprops_table gives InstanceSet.compute_rprops (ampis/structures.py:474-514):
     a dict of column name -> np.ndarray [N], columns named like regionprops_table ('bbox-0' .. 'bbox-3', 'centroid-0', 'centroid-1', the rest by
     key).  A region is ALL set pixels of one mask (holes and disconnected parts included), coordinates are (row, column) of the full image.
@@ -274,12 +284,22 @@ def region_properties(masks, keys=None, size=None, device='auto'):
     UNPINNED PARITY: skimage is not part of this environment and the reference stores no region-property output, so no vector of the reference's
     pins this function.  The definitions are skimage's regionprops (rc coordinates, 0.16 and later) restated in DESIGN §7e; the tests hold
     the integers to an independent scipy / brute-force evaluation of those definitions and the floats to their exact-rational value.
-    ValueError for an unknown key (before any device work), a bad `device`, masks of different sizes."""
-    cols = _rprops_columns(keys)
+    ValueError for an unknown key (before any device work), a bad `device`, masks of different sizes.
+
+    intensity_image: the micrograph under the masks, as intensity_properties takes it.  With it the keys of RPROPS_INTENSITY_KEYS
+    ('intensity_mean', 'intensity_min', 'intensity_max', 'intensity_std', 'centroid_weighted' and their older names) are intensity_properties'
+    columns of the same masks on the same path; without it such a key is a ValueError before any device work."""
+    wanted = [k for k in (keys or ()) if k in RPROPS_INTENSITY_KEYS]
+    if wanted and intensity_image is None:
+        raise ValueError(f"region_properties: the key {wanted[0]!r} needs an intensity_image")
+    channels = rle.intensity_image("region_properties", intensity_image)[0].shape[2] if wanted else 0
+    cols = _rprops_columns(keys, channels)
     rles = masks_to_rle(masks, size, device)
     sizes = {tuple(int(v) for v in r["size"]) for r in rles}
     if len(sizes) > 1:
         raise ValueError(f"region_properties: masks of different sizes {sorted(sizes)}")
+    if wanted:
+        grey = intensity_properties(rles, intensity_image, wanted, device=device)      # refuses an image of another size before any device work
     ctx = _device_context("region_properties", device, len(rles))
     bbox, vals = rle.region_props(rles, ctx=ctx)
     rows = [region_floats(b, v) for b, v in zip(bbox.tolist(), vals.tolist())]
@@ -287,17 +307,22 @@ def region_properties(masks, keys=None, size=None, device='auto'):
     topo = mask_topology(rles, 2, device=device) if any(c in RPROPS_TOPOLOGY_KEYS for c in cols) else {}
     if any(c in RPROPS_DISTANCE_KEYS for c in cols):
         topo = dict(topo, inscribed_radius=inscribed_circles(rles, 0, device=device)["radius"])
+    if wanted:
+        topo = dict(topo, **grey)
     return {c: topo[c] if c in topo else np.array([r[c] for r in rows], dtype=np.int64 if c in ints else np.float64) for c in cols}
 
 
-def compute_rprops(iset, keys=None, return_df=False, device='auto'):
+def compute_rprops(iset, keys=None, return_df=False, device='auto', intensity_image=None):
     """InstanceSet.compute_rprops (ampis/structures.py:474-514) as a function: stores in iset.rprops a pandas DataFrame with one row per instance
     -- the region_properties columns of `keys` plus 'class_idx' -- and returns it when return_df.  Duck-typed: iset.instances.masks,
     iset.instances.image_size (for polygon masks), iset.instances.class_idx.  Unlike the reference, whose cells are the one-element arrays of
-    one regionprops_table call per mask, the cells here are scalars."""
+    one regionprops_table call per mask, the cells here are scalars.  intensity_image: the image of the RPROPS_INTENSITY_KEYS; None: iset.img,
+    and a ValueError before any device work when such a key is asked for and there is neither."""
     import pandas as pd
     inst = iset.instances
-    table = region_properties(inst.masks, keys, size=tuple(int(v) for v in inst.image_size), device=device)
+    if intensity_image is None and any(k in RPROPS_INTENSITY_KEYS for k in (keys or ())):
+        intensity_image = getattr(iset, "img", None)
+    table = region_properties(inst.masks, keys, size=tuple(int(v) for v in inst.image_size), device=device, intensity_image=intensity_image)
     df = pd.DataFrame(table)
     df["class_idx"] = np.asarray(inst.class_idx).reshape(-1)
     iset.rprops = df
@@ -627,6 +652,137 @@ def erosion_curve(masks, max_radius, border_value=0, size=None, device='auto'):
     if isinstance(max_radius, bool) or not isinstance(max_radius, (int, np.integer)) or not 0 <= int(max_radius) <= rle.MORPH_MAX_RADIUS:
         raise ValueError(f"erosion_curve: max_radius = {max_radius!r} (an integer 0 .. {rle.MORPH_MAX_RADIUS})")
     return _mask_distance("erosion_curve", masks, border_value, int(max_radius) + 1, False, size, device)[2]
+
+
+# ---- grey levels under a mask (skimage.measure.regionprops(..., intensity_image=img); img[RLE.decode(m)] per instance) ----------------------------
+
+INTENSITY_KEYS = ("intensity_mean", "intensity_min", "intensity_max", "intensity_std", "centroid_weighted")
+INTENSITY_ALIASES = {"mean_intensity": "intensity_mean", "min_intensity": "intensity_min", "max_intensity": "intensity_max",
+                     "weighted_centroid": "centroid_weighted"}          # skimage's names before 0.19
+RPROPS_INTENSITY_KEYS = INTENSITY_KEYS + tuple(INTENSITY_ALIASES)    # what region_properties takes with an intensity_image
+
+
+def intensity_floats(vals):
+    """THE derivation of the intensity columns from the exact integers of amp_mask_intensity (vals: the 8 ints {N, sum v, sum v^2, sum r v,
+    sum c v, min, max, 0} of one mask and channel) -> dict of 'intensity_mean', 'intensity_min', 'intensity_max', 'intensity_std',
+    'centroid_weighted-0', 'centroid_weighted-1'.  Both the device and the host path go through here, so they return identical bytes.  The
+    mean sum v / N and the weighted centroid (sum r v / sum v, sum c v / sum v) are quotients of Python integers, rounded once; the standard
+    deviation is the population's, sqrt((N sum v^2 - (sum v)^2) / N^2), with the difference that cancels formed in Python integers and the
+    quotient rounded once before the root.  min and max stay integers.  An empty mask: NaN, and min / max 0; sum v = 0: a NaN centroid."""
+    import math
+    from fractions import Fraction
+    N, sv, svv, srv, scv, mn, mx = (int(v) for v in vals[:7])
+    nan = float("nan")
+    out = {"intensity_mean": nan, "intensity_min": mn, "intensity_max": mx, "intensity_std": nan, "centroid_weighted-0": nan, "centroid_weighted-1": nan}
+    if N:
+        out["intensity_mean"] = sv / N
+        out["intensity_std"] = math.sqrt(float(Fraction(N * svv - sv * sv, N * N)))
+    if sv:
+        out["centroid_weighted-0"], out["centroid_weighted-1"] = srv / sv, scv / sv
+    return out
+
+
+def _intensity_columns(who, keys, channels):
+    """[(column name, intensity_floats' name, channel)] of `keys` (None: INTENSITY_KEYS) for an image of `channels` channels: named like
+    regionprops_table, a column by the key as it was given, 'centroid_weighted-0', '-1', and with more than one channel a trailing '-ch'"""
+    cols = []
+    for k in (INTENSITY_KEYS if keys is None else keys):
+        if k not in RPROPS_INTENSITY_KEYS:
+            raise ValueError(f"{who}: unsupported key {k!r} (supported: {', '.join(RPROPS_INTENSITY_KEYS)})")
+        base = INTENSITY_ALIASES.get(k, k)
+        parts = [(f"{k}-{i}", f"{base}-{i}") for i in range(2)] if base == "centroid_weighted" else [(k, base)]
+        for col, src in parts:
+            cols += [(col, src, 0)] if channels == 1 else [(f"{col}-{ch}", src, ch) for ch in range(channels)]
+    return cols
+
+
+def _intensity_input(who, masks, img, size, device):
+    """(rles, ctx) of an intensity call on img, the image as rle.intensity_image returns it; the device and the sizes are checked before
+    anything else happens"""
+    if str(device).lower() not in ("auto", "cpu", "cuda"):
+        raise ValueError(f"{who}: device = {device!r} ('auto', 'cpu' or 'cuda')")
+    masks, size = _unwrap_masks(masks, size)
+    rles = masks_to_rle(masks, size if size is not None else img.shape[:2], device)
+    sizes = {tuple(int(v) for v in r["size"]) for r in rles}
+    if sizes - {img.shape[:2]}:
+        raise ValueError(f"{who}: masks of sizes {sorted(sizes)} on an image of size {img.shape[:2]}")
+    return rles, _device_context(who, device, len(rles))
+
+
+def _intensity_table(cols, vals):
+    rows = [[intensity_floats(v) for v in m] for m in vals.tolist()]
+    return {col: np.array([r[ch][src] for r in rows], dtype=np.int64 if src in ("intensity_min", "intensity_max") else np.float64)
+            for col, src, ch in cols}
+
+
+def intensity_properties(masks, image, keys=None, size=None, device='auto'):
+    """The grey levels of the micrograph under every mask, the intensity columns skimage.measure.regionprops_table(..., intensity_image=image)
+    gives: a dict of column name -> np.ndarray [N].  keys: any of INTENSITY_KEYS -- 'intensity_mean', 'intensity_min', 'intensity_max',
+    'intensity_std' (the population's), 'centroid_weighted' (columns '-0' row and '-1' column, in the full image's coordinates) -- or their
+    older names 'mean_intensity', 'min_intensity', 'max_intensity', 'weighted_centroid' (the columns then carry the name that was given); None:
+    all five.  With an image of C > 1 channels every column has a trailing '-ch' as skimage appends it: 'intensity_mean-0',
+    'centroid_weighted-0-2'.  min and max are int64, the rest float64; an empty mask has NaN, and min / max 0; a mask over zeros only has a
+    NaN centroid.  A region is ALL set pixels of one mask; overlapping masks do not see each other.
+
+    masks: anything masks_to_rle accepts, an Instances or an InstanceSet; image: uint8, uint16 or bool (read as uint8) of shape [h, w] or
+    [h, w, C], C <= 4, the masks' size.  A DEPARTURE FROM SKIMAGE: a float or signed image is a ValueError that names the dtype -- every
+    number here derives from exact integer sums; quantise first.  device: 'cpu' (host), 'cuda' (HIP device, an error without one) or 'auto'
+    (the device when one is visible).  One amp_mask_intensity call on the run lists (csrc/mask_intensity.hip, or mask_intensity_host.hip on
+    the host: identical bytes), no mask is decoded; intensity_floats derives the floats for both paths.  UNPINNED PARITY: skimage is not part
+    of this environment; the definitions are restated in DESIGN §7p and the tests hold the integers to NumPy and scipy.ndimage on decoded masks.
+    ValueError before any device work for an unknown key, a bad image or device and an image of another size than the masks."""
+    img, _ = rle.intensity_image("intensity_properties", image)
+    cols = _intensity_columns("intensity_properties", keys, img.shape[2])
+    rles, ctx = _intensity_input("intensity_properties", masks, img, size, device)
+    vals, _ = rle.mask_intensity(rles, img, None, ctx=ctx)
+    return _intensity_table(cols, vals)
+
+
+def intensity_histograms(masks, image, bins=None, size=None, device='auto'):
+    """The grey-level histogram of the micrograph under every mask: (hist, bin_edges) = uint32 [N, bins] (or [N, C, bins] for an image of
+    shape [h, w, C]) counts and the int64 [bins + 1] edges; bin b holds the values bin_edges[b] <= v < bin_edges[b + 1], equal bins over the
+    dtype's whole range.  bins: a power of two, at most 4096 and at most the dtype's levels; None: 256 for uint8, 1024 for uint16.  masks,
+    image, device and errors as in intensity_properties; the same amp_mask_intensity call with a histogram."""
+    img0 = np.asarray(image)
+    img, depth = rle.intensity_image("intensity_histograms", image)
+    bins = (256 if depth == 8 else 1024) if bins is None else bins
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 1 <= int(bins) <= min(rle.INTENSITY_MAX_BINS, 1 << depth) or int(bins) & (int(bins) - 1):
+        raise ValueError(f"intensity_histograms: bins = {bins!r} (a power of two, at most {min(rle.INTENSITY_MAX_BINS, 1 << depth)} for {img.dtype})")
+    rles, ctx = _intensity_input("intensity_histograms", masks, img, size, device)
+    shift = depth - (int(bins).bit_length() - 1)
+    _, hist = rle.mask_intensity(rles, img, shift, ctx=ctx)
+    return (hist[:, 0, :].copy() if img0.ndim == 2 else hist), np.arange(int(bins) + 1, dtype=np.int64) << shift
+
+
+def intensity_quantiles(masks, image, q, size=None, device='auto'):
+    """Quantiles of the grey levels under every mask, from the histogram: float64 [N] for a number q, [N, len(q)] for a sequence, with a
+    trailing C for an image of shape [h, w, C].  The inverted-CDF rule, exact: the value of rank k = max(1, ceil(q N)) among the mask's N
+    sorted values -- np.sort(img[mask])[k - 1] --, with q taken as the exact rational of the float; q = 0.5 is the (lower) median, 0 the
+    minimum, 1 the maximum.  NaN for an empty mask.  uint8 images are resolved fully.  A uint16 image has more levels than the 4096 bins of a
+    call: the result is then THE LOWER EDGE OF THE BIN of 16 levels that holds the quantile, a multiple of 16 at most 15 below the value.
+    masks, image, device and errors as in intensity_properties; ValueError for a q outside [0, 1]."""
+    from fractions import Fraction
+    import math
+    qs = np.asarray(q, dtype=np.float64)
+    if qs.ndim > 1 or not np.all((qs >= 0) & (qs <= 1)):             # a NaN fails the comparison
+        raise ValueError(f"intensity_quantiles: q = {q!r} (a number or a sequence of numbers in [0, 1])")
+    img0 = np.asarray(image)
+    img, depth = rle.intensity_image("intensity_quantiles", image)
+    rles, ctx = _intensity_input("intensity_quantiles", masks, img, size, device)
+    shift = max(depth - 12, 0)
+    _, hist = rle.mask_intensity(rles, img, shift, ctx=ctx)
+    cum = np.cumsum(hist.astype(np.int64), axis=2)
+    out = np.full((len(rles), qs.size, img.shape[2]), np.nan)
+    for j, qv in enumerate(qs.reshape(-1).tolist()):
+        f = Fraction(qv)
+        for i in range(len(rles)):
+            N = int(cum[i, 0, -1])
+            if N:
+                k = max(1, math.ceil(f * N))
+                for ch in range(img.shape[2]):
+                    out[i, j, ch] = int(np.searchsorted(cum[i, ch], k, side="left")) << shift      # the first bin whose cumulated count reaches k
+    out = out if img0.ndim == 3 else out[:, :, 0]
+    return out[:, 0] if qs.ndim == 0 else out
 
 
 # ---- overlap-free instances: the owner of every pixel (the labels[mask_i] = i + 1 loop over decoded masks) ---------------------------------------

@@ -623,6 +623,54 @@ def mask_distance(masks, border_value=0, ncurve=0, want_map=False, ctx=None, siz
     return stats.astype(np.int64), boxes, curve.astype(np.int64), maps
 
 
+INTENSITY_NVALS = 8                                                 # AMP_INTENSITY_NVALS: {N, sum v, sum v^2, sum r v, sum c v, min, max, 0}
+INTENSITY_MAX_BINS = 4096
+INTENSITY_CHUNK = 2048                                              # the pixel ranks of one work item of the device path (csrc/mask_intensity.h)
+
+
+def intensity_image(who, image):
+    """The image of a mask_intensity call as the C-contiguous uint8 or uint16 array [h, w, C] the call reads; (array, depth).  bool is read as
+    uint8.  ValueError naming the dtype for a float or signed image -- exactness is the point: quantise first -- and for a bad shape."""
+    img = np.asarray(image)
+    if img.dtype == np.bool_:
+        img = img.view(np.uint8)
+    if img.dtype not in (np.dtype(np.uint8), np.dtype(np.uint16)):
+        raise ValueError(f"{who}: an image of dtype {img.dtype} (uint8, uint16 or bool; quantise a float or signed image first)")
+    if img.ndim not in (2, 3) or (img.ndim == 3 and not 1 <= img.shape[2] <= 4) or img.shape[0] < 1 or img.shape[1] < 1:
+        raise ValueError(f"{who}: an image of shape {img.shape} ([h, w] or [h, w, C] with 1 <= C <= 4)")
+    return np.ascontiguousarray(img.reshape(img.shape[0], img.shape[1], -1)), 8 * img.dtype.itemsize
+
+
+def mask_intensity(rles, image, hist_shift=None, ctx=None):
+    """The grey levels of `image` under RLE dicts of its size, one C call (amp_mask_intensity): (vals, hist).  vals uint64 [n, C, 8] = per mask
+    and channel the exact integers {N, sum v, sum v^2, sum r v, sum c v, min, max, 0} over the mask's pixels (r, c) (row and column in the full
+    image), zeros for an empty mask; hist uint32 [n, C, nbins], the pixels with v >> hist_shift == b, nbins = 2^(depth - hist_shift) <= 4096,
+    or None without hist_shift.  image: uint8, uint16 or bool (read as uint8), [h, w] or [h, w, C] with C <= 4.  ValueError for a float or
+    signed image (naming the dtype), a bad hist_shift and an image whose size differs from the masks'.  ctx: a _lib.Context (computed on its
+    device) or None (on the host): the same bytes."""
+    img, depth = intensity_image("mask_intensity", image)
+    h, w, ch = img.shape
+    if hist_shift is not None and (isinstance(hist_shift, bool) or not isinstance(hist_shift, (int, np.integer)) or
+                                   not max(depth - 12, 0) <= int(hist_shift) <= depth):
+        raise ValueError(f"mask_intensity: hist_shift = {hist_shift!r} (None, or an integer {max(depth - 12, 0)} .. {depth} at depth {depth}: "
+                         f"at most {INTENSITY_MAX_BINS} bins)")
+    sizes = {tuple(int(v) for v in r["size"]) for r in rles}
+    if sizes - {(h, w)}:
+        raise ValueError(f"mask_intensity: masks of sizes {sorted(sizes)} on an image of size {(h, w)}")
+    n = len(rles)
+    shift = -1 if hist_shift is None else int(hist_shift)
+    nbins = 0 if shift < 0 else 1 << (depth - shift)
+    vals = np.zeros((n, ch, INTENSITY_NVALS), dtype=np.uint64)
+    hist = None if shift < 0 else np.zeros((n, ch, nbins), dtype=np.uint32)
+    if n == 0:
+        return vals, hist
+    pool, off, ln = _pool([_counts(x) for x in rles])
+    need = np.zeros(1, dtype=np.uint64)
+    check(lib().amp_mask_intensity(_handle(ctx), _vp(pool), _vp(off), _vp(ln), n, h, w, _vp(img), ch, depth, shift, _vp(vals),
+                                   None if hist is None else _vp(hist), 0 if hist is None else hist.size, _vp(need)), "amp_mask_intensity")
+    return vals, hist
+
+
 def merge(rles, intersect=False):
     assert len(rles) >= 1
     h, w = rles[0]["size"]

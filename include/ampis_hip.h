@@ -779,6 +779,30 @@ int amp_mask_distance(amp_ctx* ctx, const uint32_t* pool, const unsigned long lo
                       int border_value, unsigned long long* stats /* [n][4] */, long long* boxes /* [n][4] */,
                       unsigned long long* curve /* [n][ncurve] or NULL */, int ncurve, uint32_t* map /* or NULL */,
                       unsigned long long map_cap, unsigned long long* map_off /* [n] */, unsigned long long* need /* [1] */);
+/* Grey levels under masks: for the n run lists pool[off[i] : off[i] + len[i]] of one h x w image size (1 <= h, w <= 32768, h * w <= 2^30) and
+ * one image of that size -- C order [h][w][channels], channels 1 .. 4, uint8 (depth 8) or uint16 (depth 16) -- the exact statistics of the
+ * image's values on the pixels of every mask, per channel, and on request a histogram, in one call, without a dense mask -- the integers
+ * behind skimage's regionprops(..., intensity_image=img) columns.  ALL POINTERS ARE HOST POINTERS.
+ *   vals[i][ch] = {N, sum v, sum v^2, sum r v, sum c v, min, max, 0} over the pixels (r, c) of mask i (row and column in the full image) with
+ *              v = image[r][c][ch]; N is the mask's area; eight zeros for an empty mask.  Overlapping masks do not see each other.  Every
+ *              sum fits 64 bits by the limits above: sum v^2 < 2^30 * 2^32, sum r v and sum c v < 2^30 * 2^15 * 2^16.
+ *   hist_shift -1: no histogram; hist, hist_cap and need are not used.  Otherwise a pixel of value v counts in bin v >> hist_shift of
+ *              nbins = 2^(depth - hist_shift) bins, 1 <= nbins <= 4096 (hist_shift 0 .. 8 at depth 8, 4 .. 16 at depth 16):
+ *              hist[i][ch][b], [n][channels][nbins] words.  need[0] = n * channels * nbins is always written when the arguments are valid;
+ *              with hist_cap below it the call returns AMP_ERR_NOMEM and writes nothing else.
+ * Checked on the host before any device work (AMP_ERR_ARG, every message begins "amp_mask_intensity: ", nothing written): the sizes, n < 0,
+ * channels, depth, hist_shift and the number of bins it asks for, NULL pointers (hist and need only with a histogram), every run list
+ * non-empty and summing to h * w.  n == 0, empty masks, full masks and zero-length runs are valid.
+ * ctx == NULL: computed on the host (mask_intensity_host.hip: the runs cut at the column ends, the image read at stride w * channels).
+ * Otherwise on ctx's device and stream (mask_intensity.hip): upload, a fill, a tile transpose of the image into one column-major plane per
+ * channel -- where every run is one contiguous range --, one segmented reduction whatever the masks hold, download; integer arithmetic and
+ * integer atomics only, the bytes do not depend on the device's scheduling and equal the host's. */
+#define AMP_INTENSITY_NVALS 8
+int amp_mask_intensity(amp_ctx* ctx, const uint32_t* pool, const unsigned long long* off, const int* len, int n, int h, int w,
+                       const void* image /* host, C order [h][w][channels], uint8 or uint16 */, int channels /* 1..4 */, int depth /* 8 | 16 */,
+                       int hist_shift /* -1: no histogram; else bin = v >> hist_shift */, unsigned long long* vals /* [n][channels][8] */,
+                       uint32_t* hist /* [n][channels][nbins] or NULL */, unsigned long long hist_cap /* words */,
+                       unsigned long long* need /* [1]: words hist needs */);
 
 /* The model: DefaultPredictor(cfg) / predictor(img) ---------------------------------------------- */
 typedef struct amp_model amp_model;
