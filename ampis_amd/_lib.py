@@ -317,6 +317,7 @@ def _declare(L):
         "amp_model_sgd_step_ex": ([vp, C.POINTER(SgdOpts)], i),
         "amp_model_clip_stats": ([vp, vp, vp, i, C.POINTER(i)], i),
         "amp_debug_last_sgd_path": ([vp], i),
+        "amp_debug_train_plan": ([vp, vp, vp], i),
         "amp_pipeline_create": ([vp, i, C.POINTER(vp)], i),
         "amp_pipeline_submit": ([vp, vp, i, i, i, i, vp, vp, C.POINTER(C.c_longlong)], i),
         "amp_pipeline_wait": ([vp, C.c_longlong, C.POINTER(Dets)], i),

@@ -161,7 +161,7 @@ int amp::compact_dets_run(amp_ctx* ctx, int B, int D, const int* det_count, cons
     return AMP_OK;
 }
 
-// thresh_img: optional device [B] per-image score floors (model.hip raises them for an image with more than ccap candidates)
+// thresh_img: optional device [B] per-image score floors (model.hip run() raises them for an image with more than ccap candidates)
 int amp::box_candidates_run(amp_ctx* ctx, const float* pred, int ld, const float* proposals, const int* prop_count, int B, int Rcap, int K,
                             const float reg_weights[4], float score_thresh, int img_h, int img_w, const int* img_hw, const float* thresh_img,
                             float* dense_boxes, unsigned long long* keys, int ccap, int* cand_count, int* overflow) {

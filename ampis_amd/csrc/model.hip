@@ -6,158 +6,56 @@
 // the kernels here: conv OIHW -> [Cout][KH][KW][Cin]; stem padded to Cin 4 / KW 8; FrozenBN -> per-channel (scale, shift);
 // fc1 columns permuted from (c,ph,pw) to (ph,pw,c); cls_score+bbox_pred and objectness+anchor_deltas fused row-wise;
 // ConvTranspose IOHW -> [(ky,kx,co)][Cin].
-#include <math.h>
-#include <string.h>
+//
+// model_types.h: the types and helpers below and the training step share; train_plan.h: which path a training step takes (pure);
+// model_train.h: the training step (run_train) in stages.
+#include "model_types.h"
+#include "model_train.h"
 
-#include <map>
-#include <string>
-#include <vector>
-
-#include "common.h"
-
-namespace {
-
-struct ConvW {
-    float* w = nullptr;      // device [Cout][KH][KW][Cin]
-    float* scale = nullptr;  // device [Cout] or null
-    float* shift = nullptr;  // device [Cout] or null
-    int cout = 0, cin = 0, kh = 0, kw = 0;
-    float* w_split = nullptr; // AMP_CONV_F16X3 operand copy of w (amp_split_weights), made at finalize; null: not eligible / out of range
-    float* wt_split = nullptr; // training: split data-gradient form of w (refresh_dgrad_weights, once per step); null: not made
-    float w_absmax = 0.f;    // max |w| seen at load (range check of the split copy)
-    int groups = 1;          // > 1: w is the window layout [Cout][KH][KW][64] of amp_group_expand_weights (ResNeXt conv2)
-};
-
-struct NamedBuf {
-    void* ptr;
-    int dtype;   // 0 f32, 1 i32, 2 u64
-    int ndim;
-    long long shape[5];
-};
-
-struct Bump {
-    char* base = nullptr;
-    size_t cap = 0, off = 0, peak = 0;
-    bool dry = false;
-    void* alloc(size_t bytes) {
-        const size_t a = (off + 255) & ~(size_t)255;
-        off = a + bytes;
-        if (off > peak) peak = off;
-        if (dry) return reinterpret_cast<void*>(a + 256);   // non-null fake
-        return (off <= cap) ? base + a : nullptr;
+// tests: 0 / 1 into the step's switches (g_tsw, model_types.h), -1: what the environment said
+extern "C" void amp_debug_set_split_chain(int on) { g_tsw.split_chain = on < 0 ? g_tsw_env.split_chain : on; }
+extern "C" void amp_debug_set_rpn_train_fuse(int on) { g_tsw.rpn_train_fuse = on < 0 ? g_tsw_env.rpn_train_fuse : on; }
+extern "C" void amp_debug_set_rpn_sparse(int on) { g_tsw.rpn_sparse = on < 0 ? g_tsw_env.rpn_sparse : on; }
+extern "C" void amp_debug_set_mask_tail_split(int on) { g_tsw.mask_tail_split = on < 0 ? g_tsw_env.mask_tail_split : on; }
+extern "C" void amp_debug_set_gx(int on) { g_tsw.gx = on < 0 ? g_tsw_env.gx : on; }      // 0 / 1: ResNeXt blocks on fp32 gradients / on the scaled split chain
+// Host-only view of the step plan for tests/test_train_plan.py and tools/train_step_digest.py: no device, no context, no model.
+// inputs: 36 integers --
+//   0 backward, 1 dry, 2 conv_mode, 3 split_stale, 4 rpn_batch, 5 rpn_ld, 6 pred_cout, 7 pred_cin, 8 pred_scale, 9 conv_cout, 10 conv_cin, 11 conv_kh, 12 conv_kw
+//   (TrainPlanIn, known at entry); 13 acts_split, 14 gs_chain_ok, 15 num_groups, 16 stride_in_1x1, 17 lv_ld, 18 fc1_split (after the trunk); 19 N, 20 Kp, 21 fcn_split,
+//   22 deconv_split, 23 predictor_split (after the counts); then one layer for the per-layer rules: 24 bias, 25 xfmt, 26 cout, 27 cin, 28 kh, 29 kw, 30 rows (its
+//   output pixels: the weight gradient's Mo, the data gradient's B * Hy * Wy, the RPN level's pixels), 31 dys_floats (capacity of the scaled split copy),
+//   32 has_wt_split, 33 same_dy, 34 copy_rows (rows of the copy dys_scratch holds), 35 reserved (0).
+// switches: the 16 of TrainSwitches in declaration order (dy_convert_min_rows as an int), or null for the process's current state.
+// out: 21 integers -- refresh_fwd, dgrad_batch, sr_ok, rpn_train_fused, HS, AS, GSW, GS, GX, last_chain, SR, async_on, MS, MT, DS (TrainPlan in declaration order), then
+//   wgrad_route().convert, .fused, dgrad_takes_wsplit, dy_reuse_allowed, rpn_level_split, gx_dy_pass of the layer.
+extern "C" int amp_debug_train_plan(const int* in, const int* sw, int* out) {
+    AMP_REQUIRE(in && out, "amp_debug_train_plan: null argument");
+    TrainPlanIn pi;
+    pi.backward = in[0] != 0; pi.dry = in[1] != 0; pi.conv_mode = in[2]; pi.split_stale = in[3] != 0; pi.rpn_batch = in[4]; pi.rpn_ld = in[5];
+    pi.pred_cout = in[6]; pi.pred_cin = in[7]; pi.pred_scale = in[8] != 0; pi.conv_cout = in[9]; pi.conv_cin = in[10]; pi.conv_kh = in[11]; pi.conv_kw = in[12];
+    pi.acts_split = in[13] != 0; pi.gs_chain_ok = in[14] != 0; pi.num_groups = in[15]; pi.stride_in_1x1 = in[16] != 0; pi.lv_ld = in[17]; pi.fc1_split = in[18] != 0;
+    pi.N = in[19]; pi.Kp = in[20]; pi.fcn_split = in[21] != 0; pi.deconv_split = in[22] != 0; pi.predictor_split = in[23] != 0;
+    TrainSwitches s = g_tsw;
+    if (sw) {
+        s.train_native = sw[0]; s.dgrad_batch = sw[1]; s.rpn_sparse = sw[2]; s.rpn_train_fuse = sw[3]; s.mask_tail_split = sw[4]; s.deconv_split = sw[5];
+        s.async_reduce = sw[6]; s.split_grads = sw[7]; s.fused_bias = sw[8]; s.dy_convert = sw[9]; s.dy_convert_min_rows = sw[10]; s.dy_reuse = sw[11];
+        s.gx = sw[12]; s.rpn_split = sw[13]; s.gx_dy_inkernel = sw[14]; s.split_chain = sw[15];
     }
-    template <class T>
-    T* get(size_t n) { return reinterpret_cast<T*>(alloc(n * sizeof(T))); }
-};
-
-const char* kStage[4] = {"res2", "res3", "res4", "res5"};
-const int kOut[4] = {256, 512, 1024, 2048};
-const int kStride[4] = {1, 2, 2, 2};
-
-}  // namespace
-
-struct amp_model {
-    amp_ctx* ctx = nullptr;
-    amp_model_cfg cfg;
-    amp_anchor_cfg anchors;              // MODEL.ANCHOR_GENERATOR.{SIZES, ASPECT_RATIOS}; n_sizes 0 = the sizes 32 .. 512 with the ratios 0.5, 1, 2
-    int rpn_A = 3;                       // anchors per location; the predictor tensor holds A logit rows, 4 A delta rows and zero rows up to amp::rpn_ld(A)
-    int nblk[4] = {3, 4, 6, 3};          // RESNETS.DEPTH 50 / 101
-    int mid[4] = {64, 128, 256, 512};     // NUM_GROUPS * WIDTH_PER_GROUP * 2^stage
-    // ---- parameters ----
-    float* parena = nullptr;
-    size_t parena_floats = 0, parena_used = 0;
-    std::map<std::string, ConvW> conv;                     // keyed by detectron2 module prefix
-    std::map<std::string, std::vector<float>> host_raw;    // raw host copies needed at finalize (BN stats, fused parts)
-    std::map<std::string, bool> loaded;
-    std::map<std::string, bool> raw_fresh;                 // halves of the fused predictor matrices loaded since the last amp_model_finalize
-    std::vector<std::string> expected;
-    bool finalized = false;
-    // ---- workspace ----
-    Bump ws;
-    std::map<std::string, NamedBuf> taps;
-    int* d_batch_iota = nullptr;        // [max_batch * post_nms_topk] roi -> image
-    int* d_flags = nullptr;             // [4] overflow flags
-    // pinned host staging
-    int* h_counts = nullptr;            // [max_batch] (pinned)
-    int* h_small = nullptr;             // pinned scratch for small uploads
-    char* h_res = nullptr;              // pinned: the per-detection results of one call (one D2H copy)
-    size_t h_res_bytes = 0;
-    std::vector<char> host_out;         // result storage
-    // host results of the last call
-    std::vector<int> r_n, r_classes, r_rle_len;
-    std::vector<float> r_boxes, r_scores;
-    std::vector<unsigned long long> r_rle_off;
-    std::vector<uint32_t> r_pool;       // (fallback when the pinned pool below could not be allocated)
-    uint32_t* h_pool = nullptr;         // pinned, host-cacheable: the run lengths of one call land here by DMA and are handed out in place
-    size_t h_pool_counts = 0;
-    const uint32_t* r_pool_ptr = nullptr;
-    int rle_mode = 0;                   // amp_model_set_rle_output: 0 run lengths, 1 counts strings (encoded on the device), 2 both
-    char* h_str = nullptr;              // pinned: the counts strings of one call
-    size_t h_str_bytes = 0;
-    hipEvent_t ev_counts = nullptr;     // marks the arrival of the detection counts on the host (run(): the wait that is not a stream sync)
-    size_t str_bytes_last = 0;      // bytes of counts strings the previous inference produced (the size of the speculative read-back)
-    std::vector<unsigned long long> r_str_off;
-    std::vector<int> r_str_len;
-    std::vector<int> r_out_h, r_out_w;
-    float last_stage_ms[8];
-    // ---- training ----
-    float* garena = nullptr;            // gradients, same offsets as parena
-    float* varena = nullptr;            // SGD momentum buffers, same offsets
-    amp_loss_opts loss_opts = {AMP_BOXLOSS_SMOOTH_L1, 0.f, 1.f, 1.f, AMP_BOXLOSS_SMOOTH_L1, 0.f, 1.f};   // amp_model_set_loss_opts (= amp_loss_opts_default)
-    bool saving = false;                // run_trunk keeps every activation the backward pass needs
-    bool acts_split = false;            // ... and kept them in the split row format (training on the native trunk, AMP_CONV_F16X3)
-    int last_rpn_sparse = -1;           // 1: the last backward pass ran the RPN head's gradients over the sampled pixels only (rpn_sparse.hip)
-    int last_chain = -1;                // the last backward pass's backbone chain: 0 fp32 storage, 1 split activations + fp32 gradients, 2 scaled split gradients (R50 / R101), 3 the same for ResNeXt blocks
-    bool gs_chain_ok = false;           // ... and the backbone's backward chain can run on scaled split gradients (dense 3x3, stride in conv1: R50 / R101)
-    bool mask_acts_split = false;       // the mask head's pooled input and fcn1..3 outputs of the last training forward likewise
-    bool deconv_out_split = false;      // ... and the deconv's [N,28,28,256] output (round 4)
-    bool mask_tail_split = false;       // ... and fcn4's output (the deconv's input): the deconv and its three gradient launches on pre-split operands
-    struct BlockAct { std::string key; float *x_in, *t1, *t2, *sc, *out; int in_h, in_w, oh, ow, cin, mid, cout, stride, stage; bool has_sc; };
-    std::vector<BlockAct> blocks;
-    float* lat[4] = {nullptr, nullptr, nullptr, nullptr};
-    float* rpn_t[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    bool rpn_train_fused = false;       // this training step's RPN head ran with the predictors in the conv's epilogue (no hidden tensor saved): the sparse backward recomputes its rows
-    struct Trainable { float* p; size_t n; };
-    std::vector<Trainable> trainable;
-    unsigned long long* sgd_chunks = nullptr;   // device table for amp::sgd_chunks_run, built at the first amp_model_sgd_step
-    int sgd_nchunks = 0;
-    amp::SgdPlan sgd_plan;                      // the general step (amp_model_sgd_step_ex): built at its first call, one tensor per state_dict entry
-    bool sgd_plan_built = false;
-    bool clip_stats_valid = false;              // sgd_plan.ttab holds N / k of a norm-clipped step
-    int last_sgd_path = 0;                      // amp_debug_last_sgd_path: 1 sgd_chunks_kernel, 2 the general kernels
-    struct JobTable { amp::WeightJob* jobs = nullptr; void* chunks = nullptr; int nchunks = 0; };
-    JobTable fwd_jobs, dgrad_jobs;              // refresh_split_weights / refresh_dgrad_weights: every layer's split copy in one launch
-    bool fwd_jobs_dirty = true, dgrad_jobs_dirty = true;
-    float* dgrad_arena = nullptr;               // split data-gradient weights (ConvW::wt_split), AMP_CONV_F16X3 training
-    size_t dgrad_floats = 0;
-    bool grads_valid = false;
-    float* split_arena = nullptr;       // f16x3 operand copies of the weights (inference)
-    size_t split_floats = 0;
-    bool split_stale = false;
-    int f32_reruns = 0;                 // batches re-run in AMP_CONV_F32 after the range flag was raised
-    uint8_t* img_stage = nullptr;       // device copy of host images (amp_model_infer / forward_losses with imgs_on_host), grown on demand
-    size_t img_stage_bytes = 0;
-    std::vector<int> img_hw;            // optional per-image valid sizes for the next batches
-    // ---- gradient exchange (comm.hip): merged arena ranges per bucket, in the order the backward pass completes them ----
-    std::vector<int> gb_bucket;
-    std::vector<size_t> gb_off, gb_n;
-    int grad_overlap = -1;              // -1: on when the context has a communicator; 0 / 1: amp_model_set_grad_overlap
-    unsigned int* bm_scratch = nullptr; // window bit maps of amp_mask_targets_bitmask (bitmask ground truth), grown on demand
-    size_t bm_words = 0;
-    int* bm_flag = nullptr;
-    unsigned issued_mask = 0;           // buckets of the current gradients already handed to RCCL (bit b); all set = exchanged
-};
-
-static int g_split_chain = -1;   // -1: from the environment (AMP_NO_SPLIT_CHAIN), 0 / 1: set by amp_debug_set_split_chain (tests)
-extern "C" void amp_debug_set_split_chain(int on) { g_split_chain = on; }
-static int g_rpn_train_fuse = -1;    // -1: from the environment (AMP_NO_RPN_TRAIN_FUSE), 0 / 1: set by amp_debug_set_rpn_train_fuse (tests)
-extern "C" void amp_debug_set_rpn_train_fuse(int on) { g_rpn_train_fuse = on; }
-static int g_rpn_sparse = -1;        // -1: from the environment (AMP_NO_RPN_SPARSE), 0 / 1: set by amp_debug_set_rpn_sparse (tests)
-extern "C" void amp_debug_set_rpn_sparse(int on) { g_rpn_sparse = on; }
-static int g_mask_tail_split = -1;   // -1: from the environment (AMP_NO_MASK_TAIL_SPLIT), 0 / 1: set by amp_debug_set_mask_tail_split (tests)
-extern "C" void amp_debug_set_mask_tail_split(int on) { g_mask_tail_split = on; }
-static int g_gx = -1;                // -1: from the environment (AMP_NO_GX), 0 / 1: ResNeXt blocks on fp32 gradients / on the scaled split chain (tests)
-extern "C" void amp_debug_set_gx(int on) { g_gx = on; }
+    TrainPlan p;
+    train_plan_entry(pi, s, &p);
+    train_plan_trunk(pi, s, &p);
+    train_plan_counts(pi, s, &p);
+    const bool bias = in[24] != 0;
+    const int xfmt = in[25], cout = in[26], cin = in[27], kh = in[28], kw = in[29];
+    const long long rows = in[30];
+    const unsigned long long dys_floats = (unsigned long long)in[31];
+    const WgradRoute wr = wgrad_route(s, pi.conv_mode, p.GSW, bias, xfmt, cout, cin, kh, kw, rows, dys_floats);
+    const int o[21] = {p.refresh_fwd, p.dgrad_batch, p.sr_ok, p.rpn_train_fused, p.HS, p.AS, p.GSW, p.GS, p.GX, p.last_chain, p.SR, p.async_on, p.MS, p.MT, p.DS,
+                       wr.convert, wr.fused, dgrad_takes_wsplit(p.dgrad_batch, in[32] != 0, rows, cout, kh, kw, cin), dy_reuse_allowed(s, in[33] != 0, in[34], rows),
+                       rpn_level_split(s, p.GSW, rows, dys_floats, pi.pred_scale, pi.lv_ld, pi.pred_cout, pi.conv_cout), gx_dy_pass(s)};
+    memcpy(out, o, sizeof(o));
+    return AMP_OK;
+}
 extern "C" int amp_debug_last_backward_chain(amp_model* m) { return m ? m->last_chain : -1; }
 extern "C" int amp_debug_last_rpn_sparse(amp_model* m) { return m ? m->last_rpn_sparse : -1; }
 
@@ -218,74 +116,6 @@ std::vector<float> oihw_to_ohwi(const float* w, int O, int I, int KH, int KW, in
     return out;
 }
 
-int launch_conv(amp_model* m, const ConvW& cw, const float* x, int B, int H, int W, int stride, int pad, bool relu,
-                int res_mode, const float* res, int out_mode, float* y, int fmt = 0) {
-    amp_conv_desc d;
-    d.B = B; d.H = H; d.W = W; d.Cin = cw.cin; d.Cout = cw.cout; d.KH = cw.kh; d.KW = cw.kw;
-    d.stride = stride; d.pad = pad; d.relu = relu ? 1 : 0; d.res_mode = res_mode; d.out_mode = out_mode;
-    // pre-split weights when the layer has them; a layer whose weights exceed the fp16 range of the split copy stays on fp32 MFMA
-    const bool eligible = cw.cin % 32 == 0 || (cw.cin == 4 && cw.kw == 8);   // dense and grouped layers, the padded stem
-    // (after an SGD step the split copies are stale until the next inference refreshes them: split per call then)
-    return amp::conv_run(m->ctx, &d, cw.groups, x, cw.w, m->split_stale ? nullptr : cw.w_split, (eligible && !cw.w_split) ? 1 : 0, cw.scale, cw.shift, res,
-                         nullptr, y, 0, fmt);
-}
-
-// Inference in AMP_CONV_F16X3: tensors that only feed convolutions travel in the split operand format (written by the producer's
-// epilogue / by RoIAlign, same bytes as fp32), so their consumers stage both operands by LDS-DMA and split nothing.
-bool split_chain(amp_model* m, std::initializer_list<const char*> keys) {
-    static const bool env_off = getenv("AMP_NO_SPLIT_CHAIN") != nullptr;
-    const bool off = g_split_chain < 0 ? env_off : g_split_chain == 0;
-    if (off || m->ws.dry || m->ctx->conv_mode != AMP_CONV_F16X3 || m->split_stale) return false;
-    for (const char* k : keys) {
-        auto it = m->conv.find(k);
-        if (it == m->conv.end() || !it->second.w_split) return false;
-    }
-    return true;
-}
-
-void tap(amp_model* m, const char* name, void* p, int dtype, std::initializer_list<long long> shape) {
-    NamedBuf nb;
-    nb.ptr = p; nb.dtype = dtype; nb.ndim = (int)shape.size();
-    int i = 0;
-    for (long long s : shape) nb.shape[i++] = s;
-    m->taps[name] = nb;
-}
-
-#define AMP_TRY(expr) do { int _s = (expr); if (_s != AMP_OK) return _s; } while (0)
-#define AMP_ALLOC(var, T, n)                                                                  \
-    T* var = ws.get<T>((size_t)(n));                                                          \
-    if (!var) { amp::set_error("amp_model: workspace exhausted allocating %s (%zu bytes, cap %zu)", #var, \
-                               (size_t)(n) * sizeof(T), ws.cap); return AMP_ERR_NOMEM; }
-
-// Hand bucket b of the gradient arena to RCCL: everything the backward pass has launched so far is ordered before it, everything
-// it launches from here on overlaps it.  No-op without a communicator or with the overlap switched off.
-int issue_bucket(amp_model* m, int b) {
-    amp_ctx* ctx = m->ctx;
-    if (m->ws.dry || !ctx->comm || m->grad_overlap == 0) return AMP_OK;
-    AMP_TRY(amp::wgrad_async_join(ctx));      // the bucket's last reductions may still be on the side stream
-    // every range of the bucket, in groups of at most 64 per grouped RCCL call (a fragmented arena may hold more than 64)
-    size_t off[64], n[64];
-    int nr = 0;
-    for (size_t i = 0; i < m->gb_bucket.size(); ++i) {
-        if (m->gb_bucket[i] != b) continue;
-        off[nr] = m->gb_off[i]; n[nr] = m->gb_n[i];
-        if (++nr == 64) { AMP_TRY(amp::comm_allreduce_ranges(ctx, m->garena, off, n, nr, b)); nr = 0; }
-    }
-    AMP_TRY(amp::comm_allreduce_ranges(ctx, m->garena, off, n, nr, b));
-    m->issued_mask |= 1u << b;
-    return AMP_OK;
-}
-
-struct Trunk {
-    float* feat[5];
-    int fh[5], fw[5];
-    amp_rpn_levels lv;
-    amp_fpn_feats ff;
-    int max_n;
-    const int* img_hw;    // device [B][2] per-image sizes (amp_model_set_image_sizes) or null: clip / rescale with these, not the frame
-    bool feat_split;      // p2..p6 are in the split row format (the trunk's native activation format in AMP_CONV_F16X3 inference)
-};
-
 // Shared by inference and training: preprocess -> ResNet-50 -> FPN -> RPN head. With ws.dry nothing is launched.
 int run_trunk(amp_model* m, const uint8_t* imgs_d, int B, int H, int W, Trunk& T) {
     Bump& ws = m->ws;
@@ -326,8 +156,7 @@ int run_trunk(amp_model* m, const uint8_t* imgs_d, int B, int H, int W, Trunk& T
     // backward kernels read them.
     // Training (m->saving): the saved activations stay in the format too when EVERY trunk conv reads it (R50 / R101) -- the backward
     // kernels take them as they are (wgrad x_split, AMP_FMT_MASK_SPLIT, amp_relu_mask_split) -- otherwise the trunk keeps fp32.
-    static const bool train_native = getenv("AMP_NO_TRAIN_NATIVE") == nullptr;      // EXPERIMENT switch
-    bool native = !dry && split_chain(m, {}) && (!m->saving || train_native);
+    bool native = !dry && split_chain(m, {}) && (!m->saving || g_tsw.train_native != 0);
     auto reads_split = [&](const std::string& key) {
         if (!native) return false;
         auto it = m->conv.find(key);
@@ -515,14 +344,6 @@ int run_trunk(amp_model* m, const uint8_t* imgs_d, int B, int H, int W, Trunk& T
     for (int l = 0; l < 4; ++l) { T.ff.feat[l] = feat[l]; T.ff.h[l] = fh[l]; T.ff.w[l] = fw[l]; T.ff.stride[l] = fstride[l]; }
     return AMP_OK;
 }
-
-struct Proposals {
-    float* boxes;    // [B][Rcap][4]
-    float* logits;   // [B][Rcap]
-    int* count;      // [B]
-    int* anchor;     // [B][Rcap] global anchor index each proposal was decoded from
-    int Rcap;
-};
 
 // find_top_rpn_proposals: per-level top-k, decode, sort, NMS, first post_nms_topk.
 int run_proposals(amp_model* m, const Trunk& T, int B, int H, int W, int k, int Rcap, Proposals& P) {
@@ -867,793 +688,6 @@ int run(amp_model* m, const uint8_t* imgs_d, int B, int H, int W, const int* out
             ++n;
         }
         m->r_n[b] = n;
-    }
-    return AMP_OK;
-}
-
-int refresh_split_weights(amp_model* m);
-int refresh_dgrad_weights(amp_model* m);
-
-// Training-mode forward + losses. With ws.dry nothing is launched (workspace sizing only).
-int run_train(amp_model* m, const uint8_t* imgs_d, int B, int H, int W, const amp_gt* gt, unsigned int seed, float losses[5], bool backward) {
-    Bump& ws = m->ws;
-    const bool dry = ws.dry;
-    const amp_model_cfg& c = m->cfg;
-    amp_ctx* ctx = m->ctx;
-    const int K = c.num_classes;
-    auto CONV = [&](const char* key) -> const ConvW& { return m->conv.at(key); };
-    Trunk T;
-    struct ModeGuard { amp_ctx* c; int mode; ~ModeGuard() { c->conv_mode = mode; } } mode_guard{m->ctx, m->ctx->conv_mode};
-    m->saving = backward;
-    // the forward trunk of a training step runs on pre-split operands like inference: refresh the weights' split copies (stale since the
-    // last SGD step) once here instead of splitting every layer's weights inside its own launch
-    // (a forward-only call too: the losses of the same weights must not depend on whether an inference came in between)
-    if (!dry && m->split_stale && m->ctx->conv_mode == AMP_CONV_F16X3 && getenv("AMP_NO_TRAIN_NATIVE") == nullptr) AMP_TRY(refresh_split_weights(m));
-    static const bool no_dgrad_batch = getenv("AMP_NO_DGRAD_BATCH") != nullptr;      // EXPERIMENT switch: transpose + split in front of every data-gradient conv
-    const bool dgrad_batch = !dry && backward && !no_dgrad_batch && m->ctx->conv_mode == AMP_CONV_F16X3;
-    if (dgrad_batch) AMP_TRY(refresh_dgrad_weights(m));
-    // the RPN head's backward pass runs over the sampled anchors' pixels only (rpn_sparse.hip) -- and then the forward pass need not save the head's hidden
-    // tensor: the predictors run in the conv's epilogue as in inference, the backward pass recomputes the rows it needs from the gathered patches
-    bool sr_ok = false;
-    if (!dry) {      // (the plan run comes before the parameters: no layer table yet)
-        static const bool no_rpn_sparse = getenv("AMP_NO_RPN_SPARSE") != nullptr;          // EXPERIMENT switch: the dense backward of the RPN head
-        static const bool no_rpn_train_fuse = getenv("AMP_NO_RPN_TRAIN_FUSE") != nullptr;  // EXPERIMENT switch: the head's hidden tensor saved by the forward pass
-        const ConvW& cpred = CONV("proposal_generator.rpn_head.pred");
-        const ConvW& cconv = CONV("proposal_generator.rpn_head.conv");
-        const int T_ld = amp::rpn_ld(m->rpn_A);
-        sr_ok = backward && (g_rpn_sparse < 0 ? !no_rpn_sparse : g_rpn_sparse != 0) && cpred.cout == T_ld && cpred.cin == 256 && cpred.scale == nullptr && c.rpn_batch <= 512 &&
-                cconv.cout == 256 && cconv.cin == 256 && cconv.kh == 3 && cconv.kw == 3;
-        m->rpn_train_fused = !dry && sr_ok && (g_rpn_train_fuse < 0 ? !no_rpn_train_fuse : g_rpn_train_fuse != 0) && m->ctx->conv_mode == AMP_CONV_F16X3;
-    }
-    const int trunk_status = run_trunk(m, imgs_d, B, H, W, T);
-    m->saving = false;
-    m->rpn_train_fused = false;
-    AMP_TRY(trunk_status);
-    const int total_gt = dry ? c.max_gt : gt->gt_off[B];
-    const int npoly = dry ? c.max_poly_doubles : gt->poly_off[gt->inst_poly_off ? gt->inst_poly_off[total_gt] : total_gt];
-    AMP_REQUIRE(total_gt <= c.max_gt && npoly <= c.max_poly_doubles, "amp_model_forward_losses: %d instances / %d polygon doubles exceed cfg.max_gt / max_poly_doubles", total_gt, npoly);
-    int A = 0;
-    for (int l = 0; l < 5; ++l) A += T.fh[l] * T.fw[l] * m->rpn_A;
-
-    AMP_ALLOC(d_gt_boxes, float, (size_t)std::max(total_gt, 1) * 4);
-    AMP_ALLOC(d_gt_cls, int, (size_t)std::max(total_gt, 1));
-    AMP_ALLOC(d_gt_off, int, (size_t)B + 1);
-    // polygons: one per instance (gt->inst_poly_off == NULL) or a range of polygons per instance; bitmask instances carry run lengths
-    const int n_polys = dry ? c.max_gt : (gt->inst_poly_off ? gt->inst_poly_off[total_gt] : total_gt);
-    const size_t n_runs = (dry || !gt->rle_off) ? 0 : (size_t)gt->rle_off[total_gt];
-    AMP_REQUIRE(dry || n_polys <= c.max_gt, "amp_model_forward_losses: %d polygons exceed cfg.max_gt", n_polys);
-    AMP_ALLOC(d_poly_off, int, (size_t)std::max(n_polys, total_gt) + 1);
-    AMP_ALLOC(d_inst_poly_off, int, (size_t)total_gt + 1);
-    AMP_ALLOC(d_poly_xy, double, (size_t)std::max(npoly, 1));
-    AMP_ALLOC(d_rle_off, unsigned long long, (size_t)total_gt + 1);
-    AMP_ALLOC(d_rle_hw, int, (size_t)std::max(total_gt, 1) * 2);
-    AMP_ALLOC(match_val, float, (size_t)B * A);
-    AMP_ALLOC(match_idx, int, (size_t)B * A);
-    AMP_ALLOC(gt_best, unsigned int, (size_t)std::max(total_gt, 1));
-    AMP_ALLOC(label, signed char, (size_t)B * A);
-    AMP_ALLOC(keys, uint32_t, (size_t)B * A);
-    AMP_ALLOC(rpn_sampled, int, (size_t)B * c.rpn_batch);
-    AMP_ALLOC(rpn_counts, int, (size_t)B * 2);
-    AMP_ALLOC(rpn_partial, float, (size_t)B * 2);
-    float* d_rpn_pred[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (backward) {
-        for (int l = 0; l < 5; ++l) {
-            AMP_ALLOC(dp, float, (size_t)B * T.fh[l] * T.fw[l] * T.lv.ld);
-            d_rpn_pred[l] = dp;
-            if (!dry) AMP_HIP_CHECK(hipMemsetAsync(dp, 0, (size_t)B * T.fh[l] * T.fw[l] * T.lv.ld * 4, ctx->stream));
-        }
-    }
-    if (!dry) {
-        AMP_HIP_CHECK(hipMemcpyAsync(d_gt_off, gt->gt_off, (size_t)(B + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-        AMP_HIP_CHECK(hipMemcpyAsync(d_poly_off, gt->poly_off, (size_t)(n_polys + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-        if (gt->inst_poly_off) AMP_HIP_CHECK(hipMemcpyAsync(d_inst_poly_off, gt->inst_poly_off, (size_t)(total_gt + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-        if (gt->rle_off) {
-            AMP_REQUIRE(gt->rle_counts && gt->rle_hw, "amp_model_forward_losses: amp_gt.rle_off without rle_counts / rle_hw");
-            AMP_HIP_CHECK(hipMemcpyAsync(d_rle_off, gt->rle_off, (size_t)(total_gt + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-            if (total_gt) AMP_HIP_CHECK(hipMemcpyAsync(d_rle_hw, gt->rle_hw, (size_t)total_gt * 8, hipMemcpyHostToDevice, ctx->stream));
-        }
-        if (total_gt) {
-            AMP_HIP_CHECK(hipMemcpyAsync(d_gt_boxes, gt->boxes, (size_t)total_gt * 16, hipMemcpyHostToDevice, ctx->stream));
-            AMP_HIP_CHECK(hipMemcpyAsync(d_gt_cls, gt->classes, (size_t)total_gt * 4, hipMemcpyHostToDevice, ctx->stream));
-        }
-        if (npoly) AMP_HIP_CHECK(hipMemcpyAsync(d_poly_xy, gt->poly_xy, (size_t)npoly * 8, hipMemcpyHostToDevice, ctx->stream));
-        AMP_TRY(amp_anchor_labels(ctx, &T.lv, B, d_gt_boxes, d_gt_off, total_gt, c.rpn_iou_lo, c.rpn_iou_hi, match_val, match_idx, gt_best, label));
-        AMP_TRY(amp_rpn_sample_loss_ex(ctx, &T.lv, backward ? d_rpn_pred : nullptr, B, d_gt_boxes, d_gt_off, label, match_idx, keys, c.rpn_batch, c.rpn_pos_max, seed,
-                                       rpn_sampled, rpn_counts, rpn_partial, &m->loss_opts));
-        tap(m, "rpn_label", label, 3, {B, A});
-        tap(m, "rpn_match_idx", match_idx, 1, {B, A});
-        tap(m, "rpn_sampled", rpn_sampled, 1, {B, c.rpn_batch});
-        tap(m, "rpn_counts", rpn_counts, 1, {B, 2});
-    }
-    // proposals (training top-k), GT appended, matched and sampled
-    Proposals PR;
-    AMP_TRY(run_proposals(m, T, B, H, W, c.pre_nms_topk_train, c.post_nms_topk_train, PR));
-    const int RB = c.roi_batch;
-    const int ncap = c.post_nms_topk_train + c.max_gt;
-    AMP_ALLOC(rkeys, uint32_t, (size_t)B * ncap);
-    AMP_ALLOC(rcls_s, int, (size_t)B * ncap);
-    AMP_ALLOC(rgti_s, int, (size_t)B * ncap);
-    AMP_ALLOC(rois, float, (size_t)B * RB * 4);
-    AMP_ALLOC(roi_cls, int, (size_t)B * RB);
-    AMP_ALLOC(roi_gti, int, (size_t)B * RB);
-    AMP_ALLOC(roi_counts, int, (size_t)B * 2);
-    const int R = B * RB;
-    const int ld_box = (5 * K + 1 + 3) / 4 * 4;
-    AMP_ALLOC(roi_batch_idx, int, (size_t)R);
-    AMP_ALLOC(pooled, float, (size_t)R * 49 * 256);
-    AMP_ALLOC(fc1, float, (size_t)R * 1024);
-    AMP_ALLOC(fc2, float, (size_t)R * 1024);
-    AMP_ALLOC(box_pred, float, (size_t)R * ld_box);
-    AMP_ALLOC(box_partial, float, (size_t)B * 2);
-    float* d_box_pred = nullptr;
-    if (backward) { AMP_ALLOC(dbp, float, (size_t)R * ld_box); d_box_pred = dbp; }
-    std::vector<int> h_counts(2 * B, 0), h_cls, h_gti;
-    if (!dry) {
-        AMP_TRY(amp_roi_sample(ctx, B, PR.boxes, PR.count, PR.Rcap, d_gt_boxes, d_gt_cls, d_gt_off, K, RB, c.roi_fg_max, c.roi_iou, seed, rkeys,
-                               rcls_s, rgti_s, ncap, rois, roi_cls, roi_gti, roi_counts, PR.anchor, A));
-        std::vector<int> iota(R);
-        for (int i = 0; i < R; ++i) iota[i] = i / RB;
-        AMP_HIP_CHECK(hipMemcpyAsync(roi_batch_idx, iota.data(), (size_t)R * 4, hipMemcpyHostToDevice, ctx->stream));
-        AMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));   // iota is a temporary
-        // heads of a training step on the native trunk (HS): the pooled tensors and the mask head's hidden activations are stored in the
-        // split row format as well (their convolutions stage pre-split operands; wgrad / the ReLU masks of the backward pass read the format)
-        const bool HS = backward && m->acts_split && CONV("roi_heads.box_head.fc1").w_split != nullptr;
-        AMP_TRY(amp::roi_align_run(ctx, &T.ff, rois, roi_batch_idx, nullptr, R, 7, pooled, nullptr, HS ? 1 : 0, T.feat_split ? 1 : 0));
-        AMP_TRY(launch_conv(m, CONV("roi_heads.box_head.fc1"), pooled, 1, 1, R, 1, 0, true, 0, nullptr, 0, fc1, HS ? 1 : 0));
-        AMP_TRY(launch_conv(m, CONV("roi_heads.box_head.fc2"), fc1, 1, 1, R, 1, 0, true, 0, nullptr, 0, fc2));
-        AMP_TRY(launch_conv(m, CONV("roi_heads.box_predictor"), fc2, 1, 1, R, 1, 0, false, 0, nullptr, 0, box_pred));
-        // counts decide the normalisers and the mask-branch sizes
-        h_cls.resize(R); h_gti.resize(R);
-        AMP_HIP_CHECK(hipMemcpyAsync(h_counts.data(), roi_counts, (size_t)2 * B * 4, hipMemcpyDeviceToHost, ctx->stream));
-        AMP_HIP_CHECK(hipMemcpyAsync(h_cls.data(), roi_cls, (size_t)R * 4, hipMemcpyDeviceToHost, ctx->stream));
-        AMP_HIP_CHECK(hipMemcpyAsync(h_gti.data(), roi_gti, (size_t)R * 4, hipMemcpyDeviceToHost, ctx->stream));
-        AMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        tap(m, "train_rois", rois, 0, {B, RB, 4});
-        tap(m, "train_roi_cls", roi_cls, 1, {B, RB});
-        tap(m, "train_roi_gti", roi_gti, 1, {B, RB});
-        tap(m, "train_roi_counts", roi_counts, 1, {B, 2});
-        tap(m, "train_box_pred", box_pred, 0, {R, ld_box});
-    }
-    int total_rois = 0, N = dry ? B * c.roi_fg_max : 0;       // the plan sizes the mask rows with the sampler's own cap
-    std::vector<int> fg_off(B + 1, 0);
-    if (!dry) {
-        for (int b = 0; b < B; ++b) { total_rois += h_counts[2 * b] + h_counts[2 * b + 1]; fg_off[b + 1] = fg_off[b] + h_counts[2 * b]; }
-        N = fg_off[B];
-        AMP_TRY(amp_box_loss_ex(ctx, B, RB, K, box_pred, ld_box, d_box_pred, rois, roi_cls, roi_gti, d_gt_boxes, d_gt_off, c.bbox_reg_weights, total_rois,
-                                box_partial, &m->loss_opts));
-    }
-    // mask branch on the foreground RoIs (the first nfg of every image's sample)
-    const int Nc = std::max(N, 1);
-    AMP_ALLOC(m_rois, float, (size_t)Nc * 4);
-    AMP_ALLOC(m_batch, int, (size_t)Nc);
-    AMP_ALLOC(m_cls, int, (size_t)Nc);
-    AMP_ALLOC(m_poly, int, (size_t)Nc);
-    AMP_ALLOC(mpooled, float, (size_t)Nc * 196 * 256);
-    AMP_ALLOC(mt_a, float, (size_t)Nc * 196 * 256);
-    AMP_ALLOC(mt_b, float, (size_t)Nc * 784 * 256);
-    const int Kp = (K + 3) / 4 * 4;
-    AMP_ALLOC(mlogits, float, (size_t)Nc * 784 * Kp);
-    AMP_ALLOC(m_partial, float, (size_t)Nc);
-    AMP_ALLOC(m_targets, unsigned char, (size_t)Nc * 784);
-    float *macts[5] = {mpooled, mt_a, mpooled, mt_a, mpooled};   // input, fcn1..fcn4 outputs (ping-pong in eval mode)
-    float* d_mlogits = nullptr;
-    if (backward) {
-        for (int i = 1; i <= 4; ++i) { AMP_ALLOC(ma, float, (size_t)Nc * 196 * 256); macts[i] = ma; }
-        AMP_ALLOC(dml, float, (size_t)Nc * 784 * Kp);
-        d_mlogits = dml;
-    }
-    if (dry && !backward) return AMP_OK;
-    std::vector<float> h_mpart(N);
-    int bm_overflow = 0;
-    if (N > 0 && !dry) {
-        std::vector<int> hb(N), hc(N), hp(N);
-        for (int b = 0; b < B; ++b) {
-            const int nb = fg_off[b + 1] - fg_off[b];
-            if (!nb) continue;
-            AMP_HIP_CHECK(hipMemcpyAsync(m_rois + (size_t)fg_off[b] * 4, rois + (size_t)b * RB * 4, (size_t)nb * 16, hipMemcpyDeviceToDevice, ctx->stream));
-            for (int i = 0; i < nb; ++i) {
-                hb[fg_off[b] + i] = b;
-                hc[fg_off[b] + i] = h_cls[b * RB + i];
-                hp[fg_off[b] + i] = gt->gt_off[b] + h_gti[b * RB + i];
-            }
-        }
-        AMP_HIP_CHECK(hipMemcpyAsync(m_batch, hb.data(), (size_t)N * 4, hipMemcpyHostToDevice, ctx->stream));
-        AMP_HIP_CHECK(hipMemcpyAsync(m_cls, hc.data(), (size_t)N * 4, hipMemcpyHostToDevice, ctx->stream));
-        AMP_HIP_CHECK(hipMemcpyAsync(m_poly, hp.data(), (size_t)N * 4, hipMemcpyHostToDevice, ctx->stream));
-        AMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));   // hb/hc/hp are temporaries
-        const bool MS = backward && m->acts_split && split_chain(m, {"roi_heads.mask_head.mask_fcn1", "roi_heads.mask_head.mask_fcn2",
-                                                                      "roi_heads.mask_head.mask_fcn3", "roi_heads.mask_head.mask_fcn4"});
-        m->mask_acts_split = MS;          // macts[0..3] split
-        // macts[4] (the deconv's input, the 'dy' operand of ITS weight gradient and the mask of its data gradient) split as well: the deconv runs on
-        // the ring kernel, the predictor's data gradient leaves d(deconv out) * 2^16 as split rows with the deconv's bias sums on the side, and the
-        // deconv's weight- and data-gradient launches stage both operands as they are (AMP_NO_MASK_TAIL_SPLIT: fp32 macts[4] and d_mtb as before)
-        static const bool no_mt = getenv("AMP_NO_MASK_TAIL_SPLIT") != nullptr;      // EXPERIMENT switch
-        const bool MT = MS && (g_mask_tail_split < 0 ? !no_mt : g_mask_tail_split != 0) && Kp <= 16 && (size_t)N * 784 * 256 * 4 < 0x80000000ull && ((long long)N * 196 + 127) / 128 >= 512 /* the ring kernel takes the deconv's data gradient */ && split_chain(m, {"roi_heads.mask_head.deconv"});
-        m->mask_tail_split = MT;
-        AMP_TRY(amp::roi_align_run(ctx, &T.ff, m_rois, m_batch, nullptr, N, 14, mpooled, nullptr, MS ? 1 : 0, T.feat_split ? 1 : 0));
-        for (int i = 1; i <= 4; ++i) {
-            const std::string key = "roi_heads.mask_head.mask_fcn" + std::to_string(i);
-            AMP_TRY(launch_conv(m, CONV(key.c_str()), macts[i - 1], N, 14, 14, 1, 1, true, 0, nullptr, 0, macts[i], MS ? ((i < 4 || MT) ? 3 : 1) : 0));
-        }
-        // MT: the deconv's OUTPUT stays in the split row format too (round 4): the ring kernel scatters split rows straight from its accumulators
-        // (conv_epilogue_direct, out_mode 1) instead of sending 1.6 GB of fp32 through the staged epilogue; the predictor reads it as a split
-        // operand, its weight gradient takes x split, its data gradient the split activation as the ReLU mask (AMP_NO_DECONV_SPLIT: fp32 as before)
-        static const bool no_ds = getenv("AMP_NO_DECONV_SPLIT") != nullptr;      // EXPERIMENT switch
-        const bool DS = MT && !no_ds && split_chain(m, {"roi_heads.mask_head.predictor"});
-        m->deconv_out_split = DS;
-        AMP_TRY(launch_conv(m, CONV("roi_heads.mask_head.deconv"), macts[4], N, 14, 14, 1, 0, true, 0, nullptr, 1, mt_b, MT ? (DS ? 3 : 1) : 0));
-        AMP_TRY(launch_conv(m, CONV("roi_heads.mask_head.predictor"), mt_b, N, 28, 28, 1, 0, false, 0, nullptr, 0, mlogits, DS ? 1 : 0));
-        if (n_runs) {
-            // bitmask ground truth: BitMasks.crop_and_resize from the run lengths.  The runs travel in a buffer of their own (their
-            // size is data-dependent: not part of the workspace plan), the window bit maps in a scratch of <= 256 frame-sized slots.
-            const int Hp = (H + 31) / 32 * 32, Wp = (W + 31) / 32 * 32;
-            for (int i = 0; i < total_gt; ++i)
-                AMP_REQUIRE(gt->rle_off[i + 1] == gt->rle_off[i] || (gt->rle_hw[2 * i] >= 1 && gt->rle_hw[2 * i] <= Hp && gt->rle_hw[2 * i + 1] >= 1 && gt->rle_hw[2 * i + 1] <= Wp),
-                            "amp_model_forward_losses: the bitmask of instance %d is %dx%d, the frame %dx%d", i, gt->rle_hw[2 * i], gt->rle_hw[2 * i + 1], Hp, Wp);
-            const size_t slot = (size_t)Wp * (Hp / 32 + 1);
-            const int nslots = std::min(N, 256);
-            const size_t need = slot * nslots + (n_runs + 63) / 64 * 64;
-            if (m->bm_words < need) {
-                AMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-                if (m->bm_scratch) AMP_HIP_CHECK(hipFree(m->bm_scratch));
-                m->bm_scratch = nullptr; m->bm_words = 0;
-                AMP_HIP_CHECK(hipMalloc(&m->bm_scratch, need * sizeof(unsigned int)));
-                m->bm_words = need;
-            }
-            if (!m->bm_flag) { AMP_HIP_CHECK(hipMalloc(&m->bm_flag, sizeof(int))); AMP_HIP_CHECK(hipMemsetAsync(m->bm_flag, 0, sizeof(int), ctx->stream)); }
-            unsigned int* d_runs = m->bm_scratch + slot * nslots;
-            AMP_HIP_CHECK(hipMemcpyAsync(d_runs, gt->rle_counts, n_runs * sizeof(unsigned int), hipMemcpyHostToDevice, ctx->stream));
-            AMP_TRY(amp_mask_targets_bitmask(ctx, N, m_rois, m_poly, d_rle_off, d_runs, d_rle_hw, m->bm_scratch, slot, nslots, m_targets, m->bm_flag));
-        }
-        AMP_TRY(amp_mask_target_loss_fmt(ctx, N, Kp, mlogits, d_mlogits, m_rois, m_cls, m_poly, d_poly_xy, d_poly_off, gt->inst_poly_off ? d_inst_poly_off : nullptr,
-                                         n_runs ? d_rle_off : nullptr, m_targets, m_partial, m_targets));
-        AMP_HIP_CHECK(hipMemcpyAsync(h_mpart.data(), m_partial, (size_t)N * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (n_runs) AMP_HIP_CHECK(hipMemcpyAsync(&bm_overflow, m->bm_flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        tap(m, "train_mask_targets", m_targets, 4, {N, 28, 28});
-        tap(m, "train_mask_logits", mlogits, 0, {N, 28, 28, Kp});
-    }
-    if (!dry) {
-        std::vector<float> h_rpn(2 * B), h_box(2 * B);
-        AMP_HIP_CHECK(hipMemcpyAsync(h_rpn.data(), rpn_partial, (size_t)2 * B * 4, hipMemcpyDeviceToHost, ctx->stream));
-        AMP_HIP_CHECK(hipMemcpyAsync(h_box.data(), box_partial, (size_t)2 * B * 4, hipMemcpyDeviceToHost, ctx->stream));
-        AMP_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        AMP_REQUIRE(!bm_overflow, "amp_model_forward_losses: a bitmask window did not fit its scratch slot (internal sizing error)");
-        float s_bce = 0.f, s_loc = 0.f, s_ce = 0.f, s_l1 = 0.f, s_mask = 0.f;
-        for (int b = 0; b < B; ++b) { s_bce += h_rpn[2 * b]; s_loc += h_rpn[2 * b + 1]; s_ce += h_box[2 * b]; s_l1 += h_box[2 * b + 1]; }
-        for (int i = 0; i < N; ++i) s_mask += h_mpart[i];
-        const float rpn_norm = (float)(c.rpn_batch * B);
-        losses[0] = total_rois ? s_ce / (float)total_rois : 0.f;
-        const amp_loss_opts& lo = m->loss_opts;      // the weights as detectron2 applies them (x 1.0f by default: the same bits)
-        losses[1] = s_l1 / (float)std::max(total_rois, 1) * lo.box_bbox_reg_loss_weight;
-        losses[2] = N ? s_mask / ((float)N * 784.f) : 0.f;
-        losses[3] = s_bce / rpn_norm * lo.rpn_loss_weight;
-        losses[4] = s_loc / rpn_norm * (lo.rpn_loss_weight * lo.rpn_bbox_reg_loss_weight);
-    }
-    if (!backward) return AMP_OK;
-
-    // =============================================== backward ===============================================
-    // Gradients of the five losses (weighted as amp_model_set_loss_opts says: the loss kernels' gradients carry the weights) w.r.t. every
-    // trainable parameter, into m->garena (same offsets as the parameters).  Stem and res2 are frozen (FREEZE_AT = 2), FrozenBN has no parameters; its scale is folded into the weight
-    // transforms (data gradients) and the wgrad reduce (weight gradients).
-    if (!dry) AMP_TRY(amp::comm_wait_done(ctx));    // a previous exchange of this arena (a step without sgd_step, a re-run) must have finished
-    if (!dry) { m->issued_mask = 0; m->grads_valid = false; }
-    const size_t WG_SCRATCH = (size_t)64 << 20;     // floats: split-K slabs of the largest layer
-    const size_t WT_SCRATCH = (size_t)13 << 20;     // floats: transformed weights of the largest layer (fc1: 12.85 M)
-    AMP_ALLOC(wg_scratch, float, WG_SCRATCH);
-    AMP_ALLOC(wt_scratch, float, WT_SCRATCH);
-    // The slab reductions (69 launches of ~20 us between MFMA kernels) run on a second stream behind an event (amp::wgrad_async_*), with
-    // a second scratch so that the next layer's kernel does not wait for the previous layer's reduction.  AMP_ASYNC_REDUCE=0: on the main stream.
-    static const bool async_on = getenv("AMP_ASYNC_REDUCE") ? atoi(getenv("AMP_ASYNC_REDUCE")) != 0 : true;
-    AMP_ALLOC(wg_scratch1, float, async_on ? WG_SCRATCH : 64);
-    struct AsyncScope {          // every exit from the backward pass joins the side stream and leaves the context in the plain mode
-        amp_ctx* c; bool on;
-        ~AsyncScope() { if (on) (void)amp::wgrad_async_end(c); }
-    } async_scope{ctx, false};
-    if (!dry && async_on) { AMP_TRY(amp::wgrad_async_begin(ctx, wg_scratch1)); async_scope.on = true; }
-    AMP_ALLOC(cs_scratch, float, (size_t)4 << 20);   // ceil(M/512) * N floats of the largest bias-gradient reduction
-    const size_t DYS_SCRATCH = (size_t)B * T.fh[0] * T.fw[0] * 256;      // floats: the largest dy converted to a scaled split operand (p2 level)
-    AMP_ALLOC(dys_scratch, float, DYS_SCRATCH);
-    const bool GSW = m->acts_split && getenv("AMP_NO_SPLIT_GRADS") == nullptr && ctx->conv_mode == AMP_CONV_F16X3;
-    const float* dys_of = nullptr;       // the dy tensor whose scaled split copy dys_scratch currently holds
-    long long dys_rows = 0;
-    auto GW = [&](const ConvW& cw) { return m->garena + (cw.w - m->parena); };
-    auto GB = [&](const ConvW& cw) { return m->garena + (cw.shift - m->parena); };
-    auto bgrad = [&](const ConvW& cw, const float* dy, long long M_, bool acc) -> int {
-        return amp_colsum(ctx, dy, (int)M_, cw.cout, cs_scratch, GB(cw), acc ? 1 : 0);
-    };
-    // weight gradient; bias = true: the bias gradient (column sums of dy) as well -- summed on the side by the AMP_CONV_F16X3 kernel from the
-    // dy tiles it stages anyway, by a separate amp_colsum pass over dy on the fp32 MFMA
-    const bool AS = m->acts_split;      // the trunk's saved activations are in the split row format
-    auto wgrad = [&](const ConvW& cw, const float* x, int B_, int H_, int W_, int stride, int pad, const float* dy, bool acc, bool bias = false, int xfmt = 0) -> int {   // xfmt: 1 = x split, 2 = dy split and scaled by 2^16
-        amp_conv_desc d;
-        d.B = B_; d.H = H_; d.W = W_; d.Cin = cw.cin; d.Cout = cw.cout; d.KH = cw.kh; d.KW = cw.kw; d.stride = stride; d.pad = pad;
-        d.relu = 0; d.res_mode = 0; d.out_mode = 0;
-        AMP_REQUIRE(amp_conv_wgrad_scratch_floats(&d) <= WG_SCRATCH, "backward: wgrad scratch too small");
-        static const bool no_fused_bias = getenv("AMP_NO_FUSED_BIAS") != nullptr;      // EXPERIMENT switch
-        dys_of = nullptr;                          // a scaled split copy is only trusted right after the weight gradient that made it
-        const bool fused = bias && ctx->conv_mode == AMP_CONV_F16X3 && !no_fused_bias && !(xfmt & 2);
-        // a big biased layer whose activation is already split (FPN output / RPN conv at p2, p3; the mask head): one pass over dy gives the bias
-        // gradient AND dy * 2^16 in the split format, and the weight gradient runs on wgrad_split_kernel (+35-45 % on these shapes)
-        static const bool no_conv = getenv("AMP_NO_DY_CONVERT") != nullptr;      // EXPERIMENT switch
-        static const long long dyc_min_rows = getenv("AMP_DY_CONVERT_MIN_ROWS") ? atoll(getenv("AMP_DY_CONVERT_MIN_ROWS")) : 200000;      // EXPERIMENT switch
-        const long long Mo = (long long)B_ * ((H_ + 2 * pad - cw.kh) / stride + 1) * ((W_ + 2 * pad - cw.kw) / stride + 1);
-        if (bias && xfmt == 1 && GSW && !no_conv && cw.cout % 128 == 0 && cw.cin % 128 == 0 && cw.kh * cw.kw * cw.cin >= 256 && (Mo >= dyc_min_rows || (cw.kh * cw.kw * cw.cin >= 4096 && Mo >= 4096)) &&
-            (size_t)Mo * cw.cout <= DYS_SCRATCH) {
-            AMP_TRY(amp_colsum_split(ctx, dy, (int)Mo, cw.cout, cs_scratch, GB(cw), acc ? 1 : 0, dys_scratch, 16));
-            dys_of = dy; dys_rows = Mo;                 // the data-gradient convolution of the same dy can stage this copy (dgrad below)
-            return amp_conv2d_wgrad_fmt(ctx, &d, x, dys_scratch, cw.scale, wg_scratch, GW(cw), acc ? 1 : 0, 16, 0, 3, nullptr, 0);
-        }
-        // AMP_CONV_F16X3 splits dy * 2^16 like the data gradients below (ignored on the fp32 MFMA)
-        AMP_TRY(amp_conv2d_wgrad_fmt(ctx, &d, x, dy, cw.scale, wg_scratch, GW(cw), acc ? 1 : 0, 16, 0, xfmt, fused ? GB(cw) : nullptr, acc ? 1 : 0));
-        if (bias && !fused) {
-            const int Ho_ = (H_ + 2 * pad - cw.kh) / stride + 1, Wo_ = (W_ + 2 * pad - cw.kw) / stride + 1;
-            return bgrad(cw, dy, (long long)B_ * Ho_ * Wo_, acc);
-        }
-        return AMP_OK;
-    };
-    // the split data-gradient weights of this step (refresh_dgrad_weights) where conv_run would take a split copy: its LDS-DMA kernels,
-    // i.e. operands below 2 GiB (cout % 32 == 0 by construction); null: transpose and split in front of the launch as before
-    auto dgrad_wsplit = [&](const ConvW& cw, int B_, int Hy, int Wy) -> const float* {
-        if (!dgrad_batch || !cw.wt_split) return nullptr;
-        const size_t xb = (size_t)B_ * Hy * Wy * cw.cout * 4, wb = (size_t)cw.cout * cw.kh * cw.kw * cw.cin * 4;
-        return (xb < 0x80000000ull && wb < 0x80000000ull) ? cw.wt_split : nullptr;
-    };
-    // dx = conv(dy, flipped/transposed/scaled w) (+ res) (* mask>0); dy is [B_,Hy,Wy,cw.cout]
-    auto dgrad = [&](const ConvW& cw, const float* dy, int B_, int Hy, int Wy, int fwd_pad, const float* res, const float* mask, float* dx, bool mask_split = false) -> int {
-        AMP_REQUIRE((size_t)cw.cout * cw.kh * cw.kw * cw.cin <= WT_SCRATCH, "backward: weight-transform scratch too small");
-        const float* wsp = dgrad_wsplit(cw, B_, Hy, Wy);
-        const float* wt = wsp ? cw.w : wt_scratch;        // with a split copy the fp32 pointer is not read
-        if (!wsp) AMP_TRY(amp_dgrad_weights(ctx, cw.w, cw.scale, cw.cout, cw.kh, cw.kw, cw.cin, wt_scratch));
-        amp_conv_desc d;
-        d.B = B_; d.H = Hy; d.W = Wy; d.Cin = cw.cout; d.Cout = cw.cin; d.KH = cw.kh; d.KW = cw.kw; d.stride = 1; d.pad = cw.kh - 1 - fwd_pad;
-        d.relu = 0; d.res_mode = res ? 1 : 0; d.out_mode = 0;
-        // data gradient on the context's arithmetic; AMP_CONV_F16X3 splits dy * 2^16 (gradients of 1e-9..1e-4 would sit in the f16
-        // subnormals) -- unless the weight gradient of the same dy has just left that very tensor in dys_scratch: then the ring kernel stages
-        // it as it is and undoes the 2^16 in its fold
-        static const bool no_reuse = getenv("AMP_NO_DY_REUSE") != nullptr;      // EXPERIMENT switch
-        const int fmt = (mask && mask_split) ? 8 : 0;
-        if (dy == dys_of && !no_reuse && dys_rows == (long long)B_ * Hy * Wy &&
-            amp::conv_kernel_for(ctx->conv_mode, d, 1, 1 | fmt, 16, res != nullptr, mask != nullptr) == amp::ConvKernel::SPLIT_128x256)      // only the ring kernel undoes the 2^16
-            return amp::conv_run(ctx, &d, 1, dys_scratch, wt, wsp, 0, nullptr, nullptr, res, mask, dx, 16, 1 | fmt);
-        return amp::conv_run(ctx, &d, 1, dy, wt, wsp, 0, nullptr, nullptr, res, mask, dx, 16, fmt);
-    };
-    // The backbone's chain on SCALED SPLIT gradients (GS): a gradient tensor is kept as the split rows of d * 2^16, so its data-gradient
-    // convolution stages both operands by LDS-DMA on the ring kernel (no split, no scaling: the scale rides through the linear chain),
-    // residual and ReLU mask come in the split format, and the weight-gradient kernel passes the halves through (xfmt 3).
-    static const bool no_gs = getenv("AMP_NO_SPLIT_GRADS") != nullptr;      // EXPERIMENT switch
-    const bool GS = AS && !no_gs && ctx->conv_mode == AMP_CONV_F16X3 && m->gs_chain_ok;
-    static const bool no_gx = getenv("AMP_NO_GX") != nullptr;      // EXPERIMENT switch: ResNeXt blocks on fp32 gradients (split activations only)
-    const bool GX = AS && !GS && !no_gs && (g_gx < 0 ? !no_gx : g_gx != 0) && ctx->conv_mode == AMP_CONV_F16X3 && c.num_groups > 1 && !c.stride_in_1x1;
-    if (!dry) m->last_chain = !AS ? 0 : (GS ? 2 : (GX ? 3 : 1));      // which backbone chain ran (amp_debug_last_backward_chain)
-    auto dgrad_s = [&](const ConvW& cw, const float* dy_s, int B_, int Hy, int Wy, int fwd_pad, const float* res_s, const float* mask_s, float* dx_s) -> int {
-        AMP_REQUIRE((size_t)cw.cout * cw.kh * cw.kw * cw.cin <= WT_SCRATCH, "backward: weight-transform scratch too small");
-        const float* wsp = dgrad_wsplit(cw, B_, Hy, Wy);
-        if (!wsp) AMP_TRY(amp_dgrad_weights(ctx, cw.w, cw.scale, cw.cout, cw.kh, cw.kw, cw.cin, wt_scratch));
-        amp_conv_desc d;
-        d.B = B_; d.H = Hy; d.W = Wy; d.Cin = cw.cout; d.Cout = cw.cin; d.KH = cw.kh; d.KW = cw.kw; d.stride = 1; d.pad = cw.kh - 1 - fwd_pad;
-        d.relu = 0; d.res_mode = res_s ? 1 : 0; d.out_mode = 0;
-        return amp::conv_run(ctx, &d, 1, dy_s, wsp ? cw.w : wt_scratch, wsp, 0, nullptr, nullptr, res_s, mask_s, dx_s, 0, 1 | 2 | (res_s ? 4 : 0) | (mask_s ? 8 : 0));
-    };
-
-    // ---- gradient buffers of the FPN outputs p2..p6 ----
-    float* d_feat[5];
-    for (int l = 0; l < 5; ++l) {
-        AMP_ALLOC(df, float, (size_t)B * T.fh[l] * T.fw[l] * 256);
-        d_feat[l] = df;
-        // p2..p5: the first RoIAlign backward below writes every cell (amp::roi_align_bwd_run, init): no zero fill of 1.3 GB at B = 16; p6 has no pooler
-        if (!dry && l == 4) AMP_HIP_CHECK(hipMemsetAsync(df, 0, (size_t)B * T.fh[l] * T.fw[l] * 256 * 4, ctx->stream));
-    }
-    int dfeat_init = 1;      // handed to the first RoIAlign backward, 0 afterwards
-    int fstr[4] = {4, 8, 16, 32};
-
-    // ---- mask head ----
-    AMP_ALLOC(d_mtb, float, (size_t)Nc * 784 * 256);
-    AMP_ALLOC(d_ma, float, (size_t)Nc * 196 * 256);
-    AMP_ALLOC(d_mb, float, (size_t)Nc * 196 * 256);
-    AMP_ALLOC(dwd_t, float, (size_t)256 * 4 * 256);
-    AMP_ALLOC(dbd_t, float, 256);
-    if (!dry && N > 0) {
-        const ConvW& cp = CONV("roi_heads.mask_head.predictor");
-        const bool MT = m->mask_tail_split && ctx->conv_mode == AMP_CONV_F16X3;
-        const bool DS = MT && m->deconv_out_split;
-        AMP_TRY(wgrad(cp, mt_b, N, 28, 28, 1, 0, d_mlogits, false, true, DS ? 1 : 0));
-        if (DS) AMP_TRY(amp_small_k_dgrad_split_ld(ctx, d_mlogits, Kp, K, cp.w, 256, mt_b, d_mtb, N * 784, 16, cs_scratch, dbd_t, 0));    // + the deconv's bias sums
-        else if (MT) AMP_TRY(amp_small_k_dgrad_split_f32act(ctx, d_mlogits, Kp, K, cp.w, 256, mt_b, d_mtb, N * 784, 16, cs_scratch, dbd_t, 0));
-        else AMP_TRY(amp_small_k_dgrad(ctx, d_mlogits, Kp, K, cp.w, 256, mt_b, d_mtb, (size_t)N * 784));
-        const ConvW& cd = CONV("roi_heads.mask_head.deconv");
-        {   // weight gradient in [ci][tap][co] form, then transposed into the forward layout [(tap,co)][ci]
-            amp_conv_desc d;
-            d.B = N; d.H = 28; d.W = 28; d.Cin = 256; d.Cout = 256; d.KH = 2; d.KW = 2; d.stride = 2; d.pad = 0; d.relu = 0; d.res_mode = 0; d.out_mode = 0;
-            AMP_REQUIRE(amp_conv_wgrad_scratch_floats(&d) <= WG_SCRATCH, "backward: wgrad scratch too small");
-            // here the gradient is the 'x' operand (MT: both operands split rows, the 2^16 sits in x and is undone like a dy shift)
-            if (MT) AMP_TRY(amp_conv2d_wgrad_fmt(ctx, &d, d_mtb, macts[4], nullptr, wg_scratch, dwd_t, 0, 16, 0, 3, nullptr, 0));
-            else AMP_TRY(amp_conv2d_wgrad_scaled(ctx, &d, d_mtb, macts[4], nullptr, wg_scratch, dwd_t, 0, 0, 16));
-            AMP_TRY(amp::wgrad_async_join(ctx));      // dwd_t is read right away
-            AMP_TRY(amp_deconv_grad_transpose(ctx, dwd_t, GW(cd), 256, 4, 256, 0));
-            if (!MT) AMP_TRY(amp_colsum(ctx, d_mtb, N * 784, 256, cs_scratch, dbd_t, 0));
-            for (int q = 0; q < 4; ++q) AMP_HIP_CHECK(hipMemcpyAsync(GB(cd) + q * 256, dbd_t, 256 * 4, hipMemcpyDeviceToDevice, ctx->stream));
-            // data gradient: a 2x2 stride-2 convolution of d_mtb with w[ci][ky][kx][co], masked by fcn4's ReLU
-            const float* wsp = (cd.scale == nullptr && cd.cout == 1024 && cd.cin == 256) ? dgrad_wsplit(cd, N, 28, 28) : nullptr;   // [ci][(tap, co)] = the 2x2 window rows
-            if (!wsp) AMP_TRY(amp_dgrad_weights(ctx, cd.w, nullptr, 1024, 1, 1, 256, wt_scratch));
-            amp_conv_desc g;
-            g.B = N; g.H = 28; g.W = 28; g.Cin = 256; g.Cout = 256; g.KH = 2; g.KW = 2; g.stride = 2; g.pad = 0; g.relu = 0; g.res_mode = 0; g.out_mode = 0;
-            // MT: the data gradient leaves the mask head's chain in the scaled split domain (the 2^16 rides on): fcn4..fcn1 below take d * 2^16 as
-            // split rows straight from the producing convolution's epilogue -- no fp32 tensor, no conversion pass
-            if (MT) AMP_TRY(amp::conv_run(ctx, &g, 1, d_mtb, wsp ? cd.w : wt_scratch, wsp, 0, nullptr, nullptr, nullptr, macts[4], d_ma, 0, 1 | 2 | 8));
-            else AMP_TRY(amp::conv_run(ctx, &g, 1, d_mtb, wsp ? cd.w : wt_scratch, wsp, 0, nullptr, nullptr, nullptr, macts[4], d_ma, 16, 0));
-        }
-        float* dcur = d_ma;
-        float* dnext = d_mb;
-        for (int i = 4; i >= 1; --i) {
-            const std::string key = "roi_heads.mask_head.mask_fcn" + std::to_string(i);
-            const ConvW& cf = CONV(key.c_str());
-            if (MT) {
-                // bias gradient: column sums of the split rows (read-only: half the bytes of the converting pass); weight gradient on both split
-                // operands; data gradient split -> split with fcn(i-1)'s split rows as the ReLU mask, the last one (no mask) back to fp32 for RoIAlign
-                AMP_TRY(amp_colsum_of_split(ctx, dcur, N * 196, 256, cs_scratch, GB(cf), 0, 16));
-                AMP_TRY(wgrad(cf, macts[i - 1], N, 14, 14, 1, 1, dcur, false, false, 3));
-                if (i > 1) {
-                    AMP_TRY(dgrad_s(cf, dcur, N, 14, 14, 1, nullptr, macts[i - 1], dnext));
-                } else {
-                    AMP_REQUIRE((size_t)cf.cout * cf.kh * cf.kw * cf.cin <= WT_SCRATCH, "backward: weight-transform scratch too small");
-                    const float* wsp1 = dgrad_wsplit(cf, N, 14, 14);
-                    if (!wsp1) AMP_TRY(amp_dgrad_weights(ctx, cf.w, cf.scale, cf.cout, cf.kh, cf.kw, cf.cin, wt_scratch));
-                    amp_conv_desc d1;
-                    d1.B = N; d1.H = 14; d1.W = 14; d1.Cin = cf.cout; d1.Cout = cf.cin; d1.KH = cf.kh; d1.KW = cf.kw; d1.stride = 1; d1.pad = cf.kh - 1 - 1;
-                    d1.relu = 0; d1.res_mode = 0; d1.out_mode = 0;
-                    AMP_TRY(amp::conv_run(ctx, &d1, 1, dcur, wsp1 ? cf.w : wt_scratch, wsp1, 0, nullptr, nullptr, nullptr, nullptr, dnext, 16, 1));
-                }
-            } else {
-                AMP_TRY(wgrad(cf, macts[i - 1], N, 14, 14, 1, 1, dcur, false, true, m->mask_acts_split));
-                AMP_TRY(dgrad(cf, dcur, N, 14, 14, 1, nullptr, i > 1 ? macts[i - 1] : nullptr, dnext, m->mask_acts_split));
-            }
-            std::swap(dcur, dnext);
-        }
-        AMP_TRY(amp::roi_align_bwd_run(ctx, d_feat, T.fh, T.fw, fstr, 256, m_rois, m_batch, N, 14, dcur, B, dfeat_init));
-        dfeat_init = 0;
-    } else if (!dry) {
-        for (const char* key : {"roi_heads.mask_head.predictor", "roi_heads.mask_head.deconv", "roi_heads.mask_head.mask_fcn1", "roi_heads.mask_head.mask_fcn2",
-                                "roi_heads.mask_head.mask_fcn3", "roi_heads.mask_head.mask_fcn4"}) {
-            const ConvW& cw = CONV(key);
-            AMP_HIP_CHECK(hipMemsetAsync(GW(cw), 0, (size_t)cw.cout * cw.kh * cw.kw * cw.cin * 4, ctx->stream));
-            AMP_HIP_CHECK(hipMemsetAsync(GB(cw), 0, (size_t)cw.cout * 4, ctx->stream));
-        }
-    }
-    AMP_TRY(issue_bucket(m, 0));
-
-    // ---- box head ----
-    AMP_ALLOC(d_fc2, float, (size_t)R * 1024);
-    AMP_ALLOC(d_fc1, float, (size_t)R * 1024);
-    AMP_ALLOC(d_pooled, float, (size_t)R * 49 * 256);
-    if (!dry) {
-        const ConvW& cb = CONV("roi_heads.box_predictor");
-        AMP_TRY(wgrad(cb, fc2, 1, 1, R, 1, 0, d_box_pred, false, true));
-        AMP_TRY(dgrad(cb, d_box_pred, 1, 1, R, 0, nullptr, fc2, d_fc2));
-        const ConvW& c2 = CONV("roi_heads.box_head.fc2");
-        AMP_TRY(wgrad(c2, fc1, 1, 1, R, 1, 0, d_fc2, false, true));
-        AMP_TRY(dgrad(c2, d_fc2, 1, 1, R, 0, nullptr, fc1, d_fc1));
-        const ConvW& c1 = CONV("roi_heads.box_head.fc1");
-        AMP_TRY(wgrad(c1, pooled, 1, 1, R, 1, 0, d_fc1, false, true, AS && c1.w_split != nullptr));
-        AMP_TRY(dgrad(c1, d_fc1, 1, 1, R, 0, nullptr, nullptr, d_pooled));
-        AMP_TRY(amp::roi_align_bwd_run(ctx, d_feat, T.fh, T.fw, fstr, 256, rois, roi_batch_idx, R, 7, d_pooled, B, dfeat_init));
-        dfeat_init = 0;
-    }
-    AMP_TRY(issue_bucket(m, 1));
-
-    // ---- RPN head (shared weights: gradients accumulate over the 5 levels) ----
-    // The losses touch <= RPN.BATCH_SIZE_PER_IMAGE anchors per image: the head's gradients over those pixels only (rpn_sparse.hip), all levels in one list
-    const int SRR = B * c.rpn_batch;
-    AMP_ALLOC(sr_rows, unsigned int, (size_t)SRR);
-    AMP_ALLOC(sr_nrows, int, (size_t)B);
-    AMP_ALLOC(sr_dpred, float, (size_t)SRR * amp::rpn_ld(m->rpn_A));
-    AMP_ALLOC(sr_act, float, (size_t)SRR * 256);
-    AMP_ALLOC(sr_dt, float, (size_t)SRR * 256);
-    AMP_ALLOC(sr_xg, float, (size_t)SRR * 2304);
-    const size_t sr_G_floats = std::max((size_t)SRR * 2304, amp::rpn_sparse_sums_floats(amp::rpn_ld(m->rpn_A)));      // G, and the head sums' partials before it
-    AMP_ALLOC(sr_G, float, sr_G_floats);
-    AMP_ALLOC(sr_wt, float, (size_t)2304 * 256);
-    bool SR = false;
-    if (!dry) {
-        const ConvW& cpred = CONV("proposal_generator.rpn_head.pred");
-        const ConvW& cconv = CONV("proposal_generator.rpn_head.conv");
-        SR = sr_ok && T.lv.ld == cpred.cout;
-        bool rpn_fused_lvl = false;
-        for (int l = 0; l < 5; ++l) rpn_fused_lvl = rpn_fused_lvl || m->rpn_t[l] == nullptr;
-        AMP_REQUIRE(SR || !rpn_fused_lvl, "%s", "backward: the RPN head's hidden tensor was not saved and the sparse backward pass does not apply");
-        if (SR) {
-            amp::RpnSparseArgs sa;
-            sa.B = B; sa.batch = c.rpn_batch; sa.ld = T.lv.ld; sa.K = cpred.cout; sa.C = 256; sa.A = T.lv.A;
-            for (int l = 0; l < 5; ++l) {
-                sa.fh[l] = T.fh[l]; sa.fw[l] = T.fw[l];
-                sa.dpred[l] = d_rpn_pred[l]; sa.t[l] = m->rpn_t[l]; sa.feat[l] = T.feat[l]; sa.dfeat[l] = d_feat[l];
-            }
-            sa.sampled = rpn_sampled; sa.counts = rpn_counts;
-            sa.t_split = AS ? 1 : 0; sa.feat_split = AS ? 1 : 0;
-            // recompute the hidden rows only when run_trunk really fused the head (it saved no t for some level), from split weights only while they
-            // are fresh (AMP_NO_TRAIN_NATIVE does not refresh them after an SGD step: null = split per call)
-            sa.recompute_t = rpn_fused_lvl ? 1 : 0; sa.w_conv_split = m->split_stale ? nullptr : cconv.w_split; sa.conv_shift = cconv.shift;
-            sa.w_pred = cpred.w; sa.w_conv = cconv.w; sa.conv_scale = cconv.scale;
-            sa.gw_pred = GW(cpred); sa.gb_pred = GB(cpred); sa.gw_conv = GW(cconv); sa.gb_conv = GB(cconv);
-            sa.rows = sr_rows; sa.nrows = sr_nrows; sa.dpred_rows = sr_dpred; sa.act_rows = sr_act; sa.dt_rows = sr_dt; sa.xg = sr_xg; sa.G = sr_G; sa.G_floats = sr_G_floats; sa.wt = sr_wt;
-            sa.wg_scratch = wg_scratch; sa.wg_scratch_floats = WG_SCRATCH;
-            AMP_TRY(amp::rpn_sparse_backward(ctx, sa));
-            dys_of = nullptr;
-        }
-        m->last_rpn_sparse = SR ? 1 : 0;
-    }
-    for (int l = 0; l < 5; ++l) {
-        AMP_ALLOC(d_t, float, (size_t)B * T.fh[l] * T.fw[l] * 256);
-        if (dry || SR) continue;
-        const ConvW& cpred = CONV("proposal_generator.rpn_head.pred");
-        const ConvW& cconv = CONV("proposal_generator.rpn_head.conv");
-        AMP_TRY(wgrad(cpred, m->rpn_t[l], B, T.fh[l], T.fw[l], 1, 0, d_rpn_pred[l], l > 0, true, AS));
-        const long long Ml = (long long)B * T.fh[l] * T.fw[l];
-        static const bool no_rpn_split = getenv("AMP_NO_RPN_SPLIT") != nullptr;      // EXPERIMENT switch
-        if (GSW && !no_rpn_split && Ml >= 200000 && (size_t)Ml * 256 <= DYS_SCRATCH && cpred.scale == nullptr && T.lv.ld == 16 && cpred.cout <= 16 && cconv.cout == 256) {
-            // big levels on the native trunk: the predictor's data gradient (K = 15) is one bandwidth-bound pass that writes d_t * 2^16 as split
-            // rows and sums the conv's bias gradient on the side; both gradients of the conv then stage that copy on the ring kernels
-            AMP_TRY(amp_small_k_dgrad_split(ctx, d_rpn_pred[l], cpred.cout, cpred.w, 256, m->rpn_t[l], dys_scratch, (int)Ml, 16, cs_scratch, GB(cconv), l > 0 ? 1 : 0));
-            amp_conv_desc dd;
-            dd.B = B; dd.H = T.fh[l]; dd.W = T.fw[l]; dd.Cin = cconv.cin; dd.Cout = cconv.cout; dd.KH = cconv.kh; dd.KW = cconv.kw; dd.stride = 1; dd.pad = 1;
-            dd.relu = 0; dd.res_mode = 0; dd.out_mode = 0;
-            AMP_REQUIRE(amp_conv_wgrad_scratch_floats(&dd) <= WG_SCRATCH, "backward: wgrad scratch too small");
-            AMP_TRY(amp_conv2d_wgrad_fmt(ctx, &dd, T.feat[l], dys_scratch, cconv.scale, wg_scratch, GW(cconv), l > 0 ? 1 : 0, 16, 0, 3, nullptr, 0));
-            dys_of = d_t; dys_rows = Ml;             // (d_t itself stays unwritten: its only reader below takes the split copy)
-        } else {
-            AMP_TRY(dgrad(cpred, d_rpn_pred[l], B, T.fh[l], T.fw[l], 0, nullptr, m->rpn_t[l], d_t, AS));
-            AMP_TRY(wgrad(cconv, T.feat[l], B, T.fh[l], T.fw[l], 1, 1, d_t, l > 0, true, AS));
-        }
-        AMP_TRY(dgrad(cconv, d_t, B, T.fh[l], T.fw[l], 1, d_feat[l], nullptr, d_feat[l]));   // accumulate in place
-    }
-    AMP_TRY(issue_bucket(m, 2));
-
-    // ---- FPN ----
-    if (!dry) AMP_TRY(amp_subsample2_bwd(ctx, d_feat[4], d_feat[3], B, T.fh[3], T.fw[3], 256));    // p6 = p5[::2, ::2]
-    float* d_res[4] = {nullptr, nullptr, nullptr, nullptr};   // gradients w.r.t. res3..res5 outputs (index = stage)
-    float* d_lat_prev = nullptr;                              // 2x2 sums of the finer level's lateral gradient
-    for (int l = 2; l <= 5; ++l) {
-        const int s_ = l - 2;
-        const int fh_ = T.fh[s_], fw_ = T.fw[s_];
-        AMP_ALLOC(d_lat, float, (size_t)B * fh_ * fw_ * 256);
-        float* d_lat_next = nullptr;
-        if (l < 5) { AMP_ALLOC(dln, float, (size_t)B * T.fh[s_ + 1] * T.fw[s_ + 1] * 256); d_lat_next = dln; }
-        if (l >= 3) { AMP_ALLOC(dr, float, (size_t)B * fh_ * fw_ * kOut[s_]); d_res[s_] = dr; }
-        if (dry) { d_lat_prev = d_lat_next; continue; }
-        const std::string ln = "backbone.fpn_lateral" + std::to_string(l), on = "backbone.fpn_output" + std::to_string(l);
-        const ConvW& co = CONV(on.c_str());
-        const ConvW& cl = CONV(ln.c_str());
-        AMP_TRY(wgrad(co, m->lat[s_], B, fh_, fw_, 1, 1, d_feat[s_], false, true, AS));
-        AMP_TRY(dgrad(co, d_feat[s_], B, fh_, fw_, 1, d_lat_prev, nullptr, d_lat));      // + top-down share from the finer level
-        if (l < 5) {
-            AMP_TRY(amp::upsample2_bwd_run(ctx, d_lat, d_lat_next, B, T.fh[s_ + 1], T.fw[s_ + 1], 256, 1));      // first writer: no zero fill
-        }
-        const float* res_in = nullptr;   // input of the lateral conv = output of stage s_
-        for (auto& ba : m->blocks) if (ba.stage == s_) res_in = ba.out;
-        AMP_TRY(wgrad(cl, res_in, B, fh_, fw_, 1, 0, d_lat, false, true, AS));
-        if (l >= 3) AMP_TRY(dgrad(cl, d_lat, B, fh_, fw_, 0, nullptr, nullptr, d_res[s_]));
-        d_lat_prev = d_lat_next;
-    }
-    AMP_TRY(issue_bucket(m, 3));
-
-    // ---- ResNet res5 .. res3 (reverse block order) ----
-    float* dcur = nullptr;
-    bool dcur_masked = false;
-    const int nblk = dry ? 0 : (int)m->blocks.size();
-    // dry run: reserve the worst-case gradient buffers of every trainable block
-    if (dry) {
-        int hh = ((H + 31) / 32 * 32) / 4, ww = ((W + 31) / 32 * 32) / 4;
-        for (int s_ = 1; s_ < 4; ++s_) {
-            hh = (hh - 1) / 2 + 1; ww = (ww - 1) / 2 + 1;
-            { AMP_ALLOC(r0, float, (size_t)B * hh * ww * kOut[s_]); (void)r0; }     // the stage's entry gradient as a scaled split tensor
-            for (int b_ = 0; b_ < m->nblk[s_]; ++b_) {
-                AMP_ALLOC(r1, float, (size_t)B * hh * ww * m->mid[s_]);
-                AMP_ALLOC(r2, float, (size_t)B * hh * ww * m->mid[s_]);
-                AMP_ALLOC(r3, float, (size_t)B * hh * ww * kOut[s_]);
-                AMP_ALLOC(r4, float, (size_t)B * hh * ww * kOut[s_]);
-                (void)r1; (void)r2; (void)r3; (void)r4;
-                if (m->cfg.num_groups > 1) {     // ResNeXt on the split trunk: conv2's input decoded to fp32 for the grouped weight gradient (at the block's INPUT resolution in its first block)
-                    const int up = (b_ == 0 && !c.stride_in_1x1) ? 2 : 1;
-                    AMP_ALLOC(r5, float, (size_t)B * (hh * up) * (ww * up) * m->mid[s_]);
-                    AMP_ALLOC(r6, float, (size_t)B * hh * ww * m->mid[s_]);          // ... and its output gradient (the scaled split chain)
-                    (void)r5; (void)r6;
-                }
-            }
-        }
-    }
-    for (int bi = nblk - 1; bi >= 0; --bi) {
-        const amp_model::BlockAct& ba = m->blocks[bi];
-        if (ba.stage == 0) break;                               // res2 is frozen
-        const bool last_of_stage = (bi + 1 == nblk) || m->blocks[bi + 1].stage != ba.stage;
-        if (last_of_stage) {
-            // gradient from the FPN lateral; the next stage's first block (if any) has already added its share into d_res
-            dcur = d_res[ba.stage];
-            dcur_masked = false;
-        }
-        const size_t out_elems = (size_t)B * ba.oh * ba.ow * ba.cout;
-        const ConvW& c3 = CONV((ba.key + ".conv3").c_str());
-        const ConvW& c2 = CONV((ba.key + ".conv2").c_str());
-        const ConvW& c1 = CONV((ba.key + ".conv1").c_str());
-        // RESNETS.STRIDE_IN_1X1: the block's stride sits in conv1 (MSRA R50 / R101) or in the 3x3 conv2 (ResNeXt); t1 is conv1's output
-        const int st1 = c.stride_in_1x1 ? ba.stride : 1, st2 = c.stride_in_1x1 ? 1 : ba.stride;
-        const int h1 = (ba.in_h - 1) / st1 + 1, w1 = (ba.in_w - 1) / st1 + 1;
-        AMP_ALLOC(d_t2, float, (size_t)B * ba.oh * ba.ow * ba.mid);
-        AMP_ALLOC(d_t1, float, (size_t)B * h1 * w1 * ba.mid);
-        float* d_t2_up = nullptr;            // stride-2 conv2: dy spread over the even positions of a zeroed map, then a stride-1 data gradient
-        if (st2 == 2) { AMP_ALLOC(up, float, (size_t)B * h1 * w1 * ba.mid); d_t2_up = up; }
-        // conv2's two gradients: dense, or grouped (ResNeXt: window layout, grouped_bwd.hip)
-        auto c2_backward = [&]() -> int {
-            const float* dy2 = d_t2;
-            if (st2 == 2) {
-                AMP_HIP_CHECK(hipMemsetAsync(d_t2_up, 0, (size_t)B * h1 * w1 * ba.mid * 4, ctx->stream));
-                AMP_TRY(amp_subsample2_bwd(ctx, d_t2, d_t2_up, B, h1, w1, ba.mid));
-                dy2 = d_t2_up;
-            } else {
-                AMP_REQUIRE(st2 == 1, "backward: conv2 with stride %d", st2);
-            }
-            if (c2.groups > 1) {
-                amp_conv_desc dw;
-                dw.B = B; dw.H = h1; dw.W = w1; dw.Cin = ba.mid; dw.Cout = ba.mid; dw.KH = 3; dw.KW = 3; dw.stride = st2; dw.pad = 1; dw.relu = 0; dw.res_mode = 0; dw.out_mode = 0;
-                AMP_REQUIRE(amp_grouped_wgrad_scratch_floats(&dw) <= WG_SCRATCH && (size_t)ba.mid * 9 * 64 <= WT_SCRATCH, "backward: grouped scratch too small");
-                AMP_TRY(amp::wgrad_async_join(ctx));      // the grouped kernels use wg_scratch on the main stream: no reduction may still be reading it
-                // t1 is split on the native trunk.  grouped_wgrad_kernel can decode it on the load (amp_conv2d_grouped_wgrad_fmt, fmt 1), but its
-                // loop is bound by load issue and the two 2-byte loads + converts per value DOUBLE its time (6.6 -> 13.0 ms per X-101 step at
-                // B = 4 / 1024^2, measured); one decoding pass into a scratch (read 4 B, write 4 B per value: ~0.05 ms per layer) and the fp32 form is cheaper
-                const float* t1f = ba.t1;
-                if (AS) {
-                    AMP_ALLOC(t1_dec, float, (size_t)B * h1 * w1 * ba.mid);
-                    AMP_TRY(amp_unsplit_rows(ctx, ba.t1, (long long)B * h1 * w1, ba.mid, t1_dec));
-                    t1f = t1_dec;
-                }
-                AMP_TRY(amp_conv2d_grouped_wgrad(ctx, &dw, c2.groups, t1f, d_t2, c2.scale, wg_scratch, GW(c2)));
-                AMP_TRY(amp_group_dgrad_weights(ctx, c2.w, c2.scale, ba.mid, 3, 3, wt_scratch));
-                amp_conv_desc dd = dw;
-                dd.stride = 1;
-                dys_of = nullptr;
-                return amp::conv_run(ctx, &dd, c2.groups, dy2, wt_scratch, nullptr, 0, nullptr, nullptr, nullptr, ba.t1, d_t1, 16, AS ? 8 : 0);      // (the ReLU mask t1 likewise)
-            }
-            AMP_TRY(wgrad(c2, ba.t1, B, h1, w1, st2, 1, d_t2, false, false, AS));
-            return dgrad(c2, dy2, B, h1, w1, 1, nullptr, ba.t1, d_t1, AS);
-        };
-        const bool need_dx = !(ba.stage == 1 && ba.has_sc);   // the input of res3.0 is the frozen res2 output
-        if (GS) {
-            // every gradient of the chain below is a scaled split tensor (see dgrad_s)
-            if (last_of_stage) {
-                AMP_ALLOC(dcur_s, float, out_elems);
-                AMP_TRY(amp_relu_mask_to_split(ctx, dcur, ba.out, dcur_s, out_elems, ba.cout, 16));
-                dcur = dcur_s;
-            } else if (!dcur_masked) {
-                amp::set_error("backward: a block whose input is not the previous block's output is not expected inside a stage");
-                return AMP_ERR_STATE;
-            }
-            dcur_masked = false;
-            AMP_TRY(wgrad(c3, ba.t2, B, ba.oh, ba.ow, 1, 0, dcur, false, false, 3));
-            AMP_TRY(dgrad_s(c3, dcur, B, ba.oh, ba.ow, 0, nullptr, ba.t2, d_t2));
-            AMP_TRY(wgrad(c2, ba.t1, B, ba.oh, ba.ow, 1, 1, d_t2, false, false, 3));
-            AMP_TRY(dgrad_s(c2, d_t2, B, ba.oh, ba.ow, 1, nullptr, ba.t1, d_t1));
-            AMP_TRY(wgrad(c1, ba.x_in, B, ba.in_h, ba.in_w, ba.stride, 0, d_t1, false, false, 3));
-            if (ba.has_sc) {
-                const ConvW& cs = CONV((ba.key + ".shortcut").c_str());
-                AMP_TRY(wgrad(cs, ba.x_in, B, ba.in_h, ba.in_w, ba.stride, 0, dcur, false, false, 3));
-                if (need_dx) {
-                    AMP_ALLOC(tmp_sc, float, (size_t)B * ba.oh * ba.ow * ba.cin);
-                    AMP_ALLOC(tmp_in, float, (size_t)B * ba.oh * ba.ow * ba.cin);
-                    AMP_TRY(dgrad_s(cs, dcur, B, ba.oh, ba.ow, 0, nullptr, nullptr, tmp_sc));
-                    AMP_TRY(dgrad_s(c1, d_t1, B, ba.oh, ba.ow, 0, tmp_sc, nullptr, tmp_in));
-                    float* dprev = d_res[ba.stage - 1];             // fp32: already holds the FPN lateral's share
-                    if (ba.stride == 2) AMP_TRY(amp_subsample2_bwd_split(ctx, tmp_in, dprev, B, ba.in_h, ba.in_w, ba.cin, 16));
-                    else { amp::set_error("backward: stride-1 projection block is not expected here"); return AMP_ERR_STATE; }
-                }
-            } else {
-                AMP_ALLOC(d_in, float, out_elems);
-                const bool fuse = bi > 0 && m->blocks[bi - 1].out == ba.x_in;
-                AMP_TRY(dgrad_s(c1, d_t1, B, ba.oh, ba.ow, 0, dcur, fuse ? ba.x_in : nullptr, d_in));
-                dcur = d_in;
-                dcur_masked = fuse;
-            }
-        } else if (GX) {
-            // ResNeXt (grouped conv2, the block's stride in it) on the scaled split gradient chain: conv3 / conv1 / shortcut exactly as above;
-            // conv2's weight gradient on decoded operands (the 2^16 undone by its reduce pass), its data gradient = the grouped FORWARD kernel on
-            // transposed windows, split in / split out with t1 as the ReLU mask (a stride-2 layer: dy's rows scattered into a zeroed map first);
-            // in a stage's first block conv1's data gradient lives at the INPUT resolution and joins the fp32 stage-exit map there
-            if (last_of_stage) {
-                AMP_ALLOC(dcur_s, float, out_elems);
-                AMP_TRY(amp_relu_mask_to_split(ctx, dcur, ba.out, dcur_s, out_elems, ba.cout, 16));
-                dcur = dcur_s;
-            } else if (!dcur_masked) {
-                amp::set_error("backward: a block whose input is not the previous block's output is not expected inside a stage");
-                return AMP_ERR_STATE;
-            }
-            dcur_masked = false;
-            AMP_TRY(wgrad(c3, ba.t2, B, ba.oh, ba.ow, 1, 0, dcur, false, false, 3));
-            AMP_TRY(dgrad_s(c3, dcur, B, ba.oh, ba.ow, 0, nullptr, ba.t2, d_t2));
-            {
-                amp_conv_desc dw;
-                dw.B = B; dw.H = h1; dw.W = w1; dw.Cin = ba.mid; dw.Cout = ba.mid; dw.KH = 3; dw.KW = 3; dw.stride = st2; dw.pad = 1; dw.relu = 0; dw.res_mode = 0; dw.out_mode = 0;
-                AMP_REQUIRE(amp_grouped_wgrad_scratch_floats(&dw) <= WG_SCRATCH && (size_t)ba.mid * 9 * 64 <= WT_SCRATCH, "backward: grouped scratch too small");
-                AMP_REQUIRE(st2 == 1 || st2 == 2, "backward: conv2 with stride %d", st2);
-                AMP_ALLOC(t1_dec, float, (size_t)B * h1 * w1 * ba.mid);
-                AMP_TRY(amp_unsplit_rows(ctx, ba.t1, (long long)B * h1 * w1, ba.mid, t1_dec));      // x is read nine times per pixel: decoded once; dy once: decoded on the load
-                AMP_TRY(amp::wgrad_async_join(ctx));      // the grouped kernels use wg_scratch on the main stream
-                // dy too is decoded by a pass of its own: decoding it on the load (fmt 2) costs the kernel more than the pass (55.1 against 52.8 ms
-                // per X-101 step, A/B in one call; AMP_GX_DY_INKERNEL=1 for the other)
-                static const bool dy_pass = getenv("AMP_GX_DY_INKERNEL") == nullptr;
-                if (dy_pass) {
-                    AMP_ALLOC(dt2_dec, float, (size_t)B * ba.oh * ba.ow * ba.mid);
-                    AMP_TRY(amp_unsplit_rows(ctx, d_t2, (long long)B * ba.oh * ba.ow, ba.mid, dt2_dec));
-                    AMP_TRY(amp_conv2d_grouped_wgrad_fmt(ctx, &dw, c2.groups, t1_dec, dt2_dec, c2.scale, wg_scratch, GW(c2), 0, 16));
-                } else
-                AMP_TRY(amp_conv2d_grouped_wgrad_fmt(ctx, &dw, c2.groups, t1_dec, d_t2, c2.scale, wg_scratch, GW(c2), 2, 16));
-                AMP_TRY(amp_group_dgrad_weights(ctx, c2.w, c2.scale, ba.mid, 3, 3, wt_scratch));
-                const float* dy2 = d_t2;
-                if (st2 == 2) { AMP_TRY(amp_scatter2_rows(ctx, d_t2, d_t2_up, B, h1, w1, ba.mid)); dy2 = d_t2_up; }
-                amp_conv_desc dd = dw;
-                dd.stride = 1;
-                dys_of = nullptr;
-                AMP_TRY(amp::conv_run(ctx, &dd, c2.groups, dy2, wt_scratch, nullptr, 0, nullptr, nullptr, nullptr, ba.t1, d_t1, 0, 1 | 2 | 8));
-            }
-            AMP_TRY(wgrad(c1, ba.x_in, B, ba.in_h, ba.in_w, st1, 0, d_t1, false, false, 3));
-            if (ba.has_sc) {
-                const ConvW& cs = CONV((ba.key + ".shortcut").c_str());
-                AMP_TRY(wgrad(cs, ba.x_in, B, ba.in_h, ba.in_w, ba.stride, 0, dcur, false, false, 3));
-                if (need_dx) {
-                    if (ba.stride != 2 || st1 != 1) { amp::set_error("backward: a ResNeXt projection block with stride %d / %d is not expected here", ba.stride, st1); return AMP_ERR_STATE; }
-                    float* dprev = d_res[ba.stage - 1];             // fp32, input resolution: already holds the FPN lateral's share
-                    AMP_ALLOC(tmp_sc, float, (size_t)B * ba.oh * ba.ow * ba.cin);
-                    AMP_ALLOC(tmp_full, float, (size_t)B * ba.in_h * ba.in_w * ba.cin);
-                    AMP_TRY(dgrad_s(cs, dcur, B, ba.oh, ba.ow, 0, nullptr, nullptr, tmp_sc));
-                    AMP_TRY(dgrad_s(c1, d_t1, B, h1, w1, 0, nullptr, nullptr, tmp_full));
-                    AMP_TRY(amp_accumulate_split(ctx, tmp_full, dprev, (long long)B * ba.in_h * ba.in_w, ba.cin, 16));
-                    AMP_TRY(amp_subsample2_bwd_split(ctx, tmp_sc, dprev, B, ba.in_h, ba.in_w, ba.cin, 16));
-                }
-            } else {
-                AMP_ALLOC(d_in, float, out_elems);
-                const bool fuse = bi > 0 && m->blocks[bi - 1].out == ba.x_in;
-                AMP_TRY(dgrad_s(c1, d_t1, B, ba.oh, ba.ow, 0, dcur, fuse ? ba.x_in : nullptr, d_in));
-                dcur = d_in;
-                dcur_masked = fuse;
-            }
-        } else {
-        // d(pre-activation) = d(out) * (out > 0); inside a stage the previous iteration's input-gradient conv has applied it already
-        if (!dcur_masked) AMP_TRY(AS ? amp_relu_mask_split(ctx, dcur, ba.out, out_elems, ba.cout) : amp_relu_mask(ctx, dcur, ba.out, out_elems));
-        dcur_masked = false;
-        AMP_TRY(wgrad(c3, ba.t2, B, ba.oh, ba.ow, 1, 0, dcur, false, false, AS));
-        AMP_TRY(dgrad(c3, dcur, B, ba.oh, ba.ow, 0, nullptr, ba.t2, d_t2, AS));
-        AMP_TRY(c2_backward());
-        AMP_TRY(wgrad(c1, ba.x_in, B, ba.in_h, ba.in_w, st1, 0, d_t1, false, false, AS));
-        if (ba.has_sc) {
-            const ConvW& cs = CONV((ba.key + ".shortcut").c_str());
-            AMP_TRY(wgrad(cs, ba.x_in, B, ba.in_h, ba.in_w, ba.stride, 0, dcur, false, false, AS));
-            if (need_dx) {
-                float* dprev = d_res[ba.stage - 1];             // already holds the FPN lateral's share
-                AMP_ALLOC(tmp_sc, float, (size_t)B * ba.oh * ba.ow * ba.cin);
-                AMP_TRY(dgrad(cs, dcur, B, ba.oh, ba.ow, 0, nullptr, nullptr, tmp_sc));
-                if (ba.stride != 2) { amp::set_error("backward: stride-1 projection block is not expected here"); return AMP_ERR_STATE; }
-                if (st1 == 2) {     // both branches at the block's output resolution: add, then spread over the input map
-                    AMP_ALLOC(tmp_in, float, (size_t)B * ba.oh * ba.ow * ba.cin);
-                    AMP_TRY(dgrad(c1, d_t1, B, ba.oh, ba.ow, 0, tmp_sc, nullptr, tmp_in));
-                    AMP_TRY(amp_subsample2_bwd(ctx, tmp_in, dprev, B, ba.in_h, ba.in_w, ba.cin));
-                } else {            // conv1 ran at the input resolution: its data gradient joins dprev there; the strided shortcut's is spread
-                    AMP_ALLOC(tmp_full, float, (size_t)B * ba.in_h * ba.in_w * ba.cin);
-                    AMP_TRY(dgrad(c1, d_t1, B, h1, w1, 0, dprev, nullptr, tmp_full));
-                    AMP_HIP_CHECK(hipMemcpyAsync(dprev, tmp_full, (size_t)B * ba.in_h * ba.in_w * ba.cin * 4, hipMemcpyDeviceToDevice, ctx->stream));
-                    AMP_TRY(amp_subsample2_bwd(ctx, tmp_sc, dprev, B, ba.in_h, ba.in_w, ba.cin));
-                }
-            }
-        } else {
-            AMP_ALLOC(d_in, float, out_elems);
-            // + identity shortcut, times the ReLU mask of the block below (its output IS this block's input)
-            const bool fuse = bi > 0 && m->blocks[bi - 1].out == ba.x_in;
-            AMP_TRY(dgrad(c1, d_t1, B, ba.oh, ba.ow, 0, dcur, fuse ? ba.x_in : nullptr, d_in, AS));
-            dcur = d_in;
-            dcur_masked = fuse;
-        }
-        }
-        if (bi == 0 || m->blocks[bi - 1].stage != ba.stage) AMP_TRY(issue_bucket(m, 7 - ba.stage));   // res5 -> 4, res4 -> 5, res3 -> 6
-    }
-    if (async_scope.on) { async_scope.on = false; AMP_TRY(amp::wgrad_async_end(ctx)); }
-    if (!dry) {
-        if (m->grad_overlap != 0) AMP_TRY(amp::comm_mark_producer_end(ctx));
-        m->grads_valid = true;
     }
     return AMP_OK;
 }

@@ -371,7 +371,7 @@ __global__ void relu_mask_split_kernel(float* __restrict__ g, const float* __res
     }
 }
 
-// Scaled split gradients (the backbone's backward pass on the ring kernel, model.hip): a gradient tensor d is kept as the split rows of
+// Scaled split gradients (the backbone's backward pass on the ring kernel, model_train.h Backward::block): a gradient tensor d is kept as the split rows of
 // d * scale (scale = 2^16: loss gradients of 1e-9..1e-4 would sit in the f16 subnormals), so that data-gradient convolutions stage it by
 // LDS-DMA like an activation and the weight-gradient kernel passes its halves through.
 // out = split(scale * (act > 0 ? g : 0)): the entry of a stage's chain (g fp32 from the FPN lateral, act = the stage output, split rows)

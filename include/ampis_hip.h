@@ -937,6 +937,10 @@ int  amp_model_set_momentum_tensor(amp_model* m, const char* name, const float* 
 int  amp_model_set_image_sizes(amp_model* m, const int* hw_h, int B);
 /* Device buffer of an intermediate stage of the last infer call (parity tests): dtype 0 f32, 1 i32, 2 u64. */
 int  amp_model_get_tap(amp_model* m, const char* name, void** ptr, int* dtype, int* ndim, long long shape[5]);
+/* Which path a training step takes (csrc/train_plan.h), host only: no context, no model, no GPU.  inputs: 36 integers (the step's shape and
+ * state, then one layer for the per-layer rules), switches: the 16 A/B switches or NULL for the process's current state, out: 21 integers;
+ * the order of all three is documented at the definition in csrc/model.hip and named in tests/test_train_plan.py. */
+int  amp_debug_train_plan(const int* inputs, const int* switches, int* out);
 
 /* Several batches in flight on one GPU (serving throughput) -------------------------------------------------------------
  * An amp_pipeline runs `depth` lanes -- models the caller created on contexts of their own (own stream, workspace and result buffers),

@@ -369,7 +369,7 @@ def test_training_trajectories_agree_between_modes(gpu_ctx):
 
 
 def test_native_split_trunk_against_fp32_activations(gpu_ctx):
-    """AMP_CONV_F16X3 inference keeps every trunk and head activation in the split row format (model.hip run_trunk); with the
+    """AMP_CONV_F16X3 inference keeps every trunk and head activation in the split row format (model.hip run_trunk, split_chain of model_types.h); with the
     switch off the same kernels exchange fp32 tensors and split them in the consumer.  Conv inputs are identical either way (the
     stage test below proves the convolutions bit-identical); what differs is that residual / FPN top-down adds and RoIAlign read the
     stored value hi + lo' * 2^-11 instead of the fp32 one: a 2^-23 relative rounding of the stored activation.  So: taps agree to a
